@@ -6,7 +6,7 @@ already resident in HBM: frame index (major-sync scan, size-chain walk, prefix
 sums) + fused segment decode (parse, FIR/IIR, rematrix, output shift, RIFF order)
 into int32 PCM, also in HBM.
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload c3|c4]
+    python bench.py [--gpus N --steps K --warmup W] [--workload c3|c4] [--dump-outputs DIR] [--full]
 
 Workloads (BASELINE.json `configs`):
   c3 (default, the headline): configs[2] -- synthetic 6-ch / 96 kHz / 24-bit MLP, 2 decorrelation
@@ -20,9 +20,16 @@ torch.distributed.run, decided before anything touches the GPU); under torchrun 
 in the environment) it is one of the ranks.  The title list is sharded, no data-path collective; one
 tiny RCCL all-reduce sums the per-rank totals and takes the slowest rank's time.
 
-At N = 1 the JSON line also carries: the CPU baseline on 1 core and on all host cores (the compiled
-reference when oracle/_ref travelled with the repo), a bit-exact comparison of EVERY unique title of
-the batch against that CPU decode, and sub-records for other shapes of the path ("sub").
+A plain run sets up, warms up, times the K steps, checks that every title decoded without an error and
+prints the JSON line (value, ms_per_step, the k_decode roofline from the timed steps' own kernel times).
+--dump-outputs DIR then writes a seeded sample of the last timed step's PCM and every title's stream
+info as float64 .npy files (write_outputs); the inputs are the same from run to run.
+
+--full adds what the headline does not need.  At N = 1: the CPU baseline on 1 core and on all host
+cores (the compiled reference when oracle/_ref travelled with the repo), a bit-exact comparison of
+EVERY unique title of the batch against that CPU decode, and sub-records for other shapes of the path
+("sub"); else (and with --no-cpu) a sample of titles against the oracle; with --pipeline > 1 the serial
+step, for c4 the single-batch latency.
 """
 import argparse
 import json
@@ -54,6 +61,11 @@ def parse_args(argv=None):
     ap.add_argument("--aus", type=int, default=512, help="access units per title (c3)")
     ap.add_argument("--replicas", type=int, default=4,
                     help="device-side copies of the unique title set (distinct addresses; c3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks and records the headline does not need: CPU baseline and bit-exact "
+                         "comparison, oracle sample, serial step, c4 latency, sub-records (the options below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of the last timed step's outputs to DIR/<name>.npy (float64)")
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="CPU baseline budget per leg")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline and the full-size check")
     ap.add_argument("--no-sub", action="store_true", help="skip the sub-records (other shapes of the path)")
@@ -73,7 +85,10 @@ def parse_args(argv=None):
                     help="PCM layout written by the decode: interleaved = frame-major, the order the "
                          "reference's dvda_read() hands out (default); planar = the order its decode_packet "
                          "appends to `samples`")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ----------------------------------------------------------------------------- launcher (N > 1)
@@ -346,6 +361,46 @@ class Batch:
         for c in self.ctxs:
             c.close()
         del self.d_pcm, self.d_pcms, self.d_bytes
+
+
+DUMP_SEED = 20240611
+DUMP_BYTES = 48 << 20       # all ranks together; the files are float64
+
+
+def write_outputs(b, out_dir, prefix="", budget=DUMP_BYTES):
+    """What a caller of the timed path receives from its last step, as float64 (exact for int32 PCM and the uint32
+    status words) in out_dir/<prefix><name>.npy:
+      status, pcm_frames  every title's dvda_mlp_stream_info
+      pcm_titles          the PCM of whole titles, in the layout the decode wrote, concatenated in title order: titles
+                          drawn by a seeded permutation while they fit in 2/3 of the budget
+      pcm_sample          single samples at seeded positions drawn uniformly over the PCM of all titles, in order
+    The draws depend only on the batch's shape, so runs with the same arguments dump the same positions."""
+    torch, n = b.torch, b.n_streams
+    k = (b._turn - 1) % b.depth                          # the slot the last step decoded into
+    d_pcm = b.d_pcms[k]
+    infos = b.ctxs[k].stream_info(n, stream=b.streams[k])
+    per_title = b.all_frames * b.all_nch                 # int32 words (interleaved / planar: one per sample)
+    rng = np.random.default_rng(DUMP_SEED)
+    words = budget // 8
+    picked, room = [], words * 2 // 3
+    for i in rng.permutation(n):
+        if per_title[i] > room:
+            break
+        picked.append(int(i))
+        room -= int(per_title[i])
+    picked = sorted(picked) or [int(np.argmin(per_title))]
+    titles = np.concatenate([d_pcm[int(b.out_off[i]):int(b.out_off[i] + per_title[i])][:words * 2 // 3].cpu().numpy()
+                             for i in picked])
+    starts = np.concatenate([[0], np.cumsum(per_title)])
+    m = int(min(words - len(titles), starts[-1]))
+    r = np.sort(rng.integers(0, starts[-1], size=m))
+    t = np.searchsorted(starts, r, side="right") - 1
+    pos = torch.from_numpy(b.out_off[t] + (r - starts[t])).to(b.dev)
+    sample = d_pcm[pos].cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("status", [inf.status for inf in infos]), ("pcm_frames", [inf.pcm_frames for inf in infos]),
+                    ("pcm_titles", titles), ("pcm_sample", sample)):
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), np.asarray(a, np.float64))
 
 
 def roofline_record(b, kms, launches, traffic, valu_per_sample=None):
@@ -1172,9 +1227,11 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     kernel_ms, launches = b.kernel_time()
+    if args.dump_outputs:
+        write_outputs(b, args.dump_outputs, "" if world == 1 else "rank%d_" % rank, DUMP_BYTES // world)
     # ---- the same step with nothing in flight beside it: one slot, the blocking decode call, waited for every time
     serial = None
-    if args.pipeline > 1 and world == 1:
+    if args.full and args.pipeline > 1 and world == 1:
         ks = max(3, min(10, args.steps))
         b.sync()
         t1 = time.perf_counter()
@@ -1193,7 +1250,7 @@ def main():
     b.check_status()
     # ---- single-batch latency (c4): one step at a time, host clock around index + decode + sync
     latency = None
-    if args.workload == "c4":
+    if args.full and args.workload == "c4":
         lat = []
         for _ in range(50):
             b.sync()
@@ -1206,13 +1263,13 @@ def main():
                    "p90_ms": round(lat[int(len(lat) * 0.9)] * 1e3, 4), "batches": len(lat),
                    "what": "one batch: index + decode enqueued and waited for, host clock"}
 
-    # ---- ... and match the CPU decode bit for bit: every unique title against the all-core CPU leg
+    # ---- ... and (--full) match the CPU decode bit for bit: every unique title against the all-core CPU leg
     #      (rank 0 at N = 1), the replicas against each other on the device; else a sample vs the oracle
     cpu = None
     bit_exact = None
     checked = 0
-    full = (not args.no_cpu) and world == 1 and args.workload == "c3"
-    if full:
+    cpu_check = args.full and (not args.no_cpu) and world == 1 and args.workload == "c3"
+    if cpu_check:
         n_threads, logical_cpus, cpu_quota = usable_cpus()
         cpu, ref_pcm = cpu_legs(flat, offs, sizes, frames.astype(np.int64), assignment, rate_code, nch,
                                 args.cpu_seconds, n_threads)
@@ -1228,7 +1285,7 @@ def main():
         bit_exact = bit_exact and b.replicas_equal() and b.slots_equal()
         if not bit_exact:
             raise SystemExit("HIP decode differs from the CPU decoder (%s)" % cpu[0]["kind"])
-    elif args.verify or args.workload == "c4":
+    elif args.full and (args.verify or args.workload == "c4"):
         picks = np.arange(b.n_streams) if args.workload == "c4" else \
             np.linspace(0, b.n_streams - 1, num=min(args.verify, b.n_streams), dtype=np.int64)
         bit_exact = b.verify_sample(flat, offs, sizes, picks)
@@ -1296,7 +1353,7 @@ def main():
                 "bit_exact": bit_exact,
                 "bit_exact_titles_checked": checked,
                 "bit_exact_against": (cpu[0]["kind"] + " CPU decode of every unique title; replicas compared on the device")
-                if full else "oracle (sample)",
+                if cpu_check else "oracle (sample)" if checked else "not checked (bench.py --full checks)",
             },
             "roofline": roofline_record(b, kernel_ms, launches, prof["hbm_bytes_per_launch"] if prof else None, issue),
         }
@@ -1336,7 +1393,8 @@ def main():
                 out["speedup_vs_cpu"]["vs_all_%d_host_cpus_extrapolated" % logical_cpus] = round(
                     value / (per_thread * logical_cpus), 1)
         out["host"] = {"gen_seconds": round(t_gen, 2), "cpus": os.cpu_count()}
-        if world == 1 and not args.no_sub and args.workload == "c3" and args.substreams == 1 and assignment == 12:
+        if args.full and world == 1 and not args.no_sub and args.workload == "c3" and args.substreams == 1 \
+                and assignment == 12:
             sub_steps = max(5, min(args.steps, 20))
             # (the host-path records first: behind the other sub-records -- dozens of contexts and streams opened and
             #  closed -- the same passes ran 26 ms where they take 18-21 in a fresh process, copies-only unchanged.  The

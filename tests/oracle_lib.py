@@ -5,6 +5,8 @@ TEST INFRASTRUCTURE: only tests/, __graft_entry__.smoke() and bench.py's
 cpu_baseline leg import this.
 """
 import ctypes
+import hashlib
+import json
 import os
 import subprocess
 
@@ -14,6 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 ORACLE_SO = os.path.join(ORACLE_DIR, "libmlp_oracle.so")
 REF_SO = os.path.join(ORACLE_DIR, "_ref", "libdvda_ref.so")
+REF_DIGESTS = os.path.join(ROOT, "tests", "golden", "reference_digests.json")
 
 CHANNELS = [1, 2, 3, 4, 3, 4, 5, 3, 4, 5, 4, 5, 6, 4, 5, 4, 5, 6, 5, 5, 6]
 
@@ -81,3 +84,31 @@ class Reference:
         if r < 0:
             raise RuntimeError("reference output capacity too small")
         return out[:, :r].copy(), int(r)
+
+
+def _digest(values):
+    h = hashlib.sha256()
+    for v in values:
+        a = np.ascontiguousarray(v)
+        h.update(("%s%s;" % (a.dtype.str, a.shape)).encode())
+        h.update(a.tobytes())
+    return h.hexdigest()
+
+
+def same_as_reference(key, got, reference_output):
+    """True when `got` (a tuple of arrays / numbers) equals what the compiled reference returns for the same input.
+    Where oracle/_ref has been built, reference_output() runs the reference and the digest of its result must also be
+    the one stored under `key` in tests/golden/reference_digests.json (DVDA_RECORD_REFERENCE=1 stores it instead);
+    elsewhere that stored digest stands in for the reference."""
+    table = json.load(open(REF_DIGESTS)) if os.path.exists(REF_DIGESTS) else {}
+    if Reference.available():
+        want = reference_output()
+        if os.environ.get("DVDA_RECORD_REFERENCE") == "1":
+            table[key] = _digest(want)
+            with open(REF_DIGESTS, "w") as f:
+                json.dump(table, f, indent=0, sort_keys=True)
+                f.write("\n")
+        assert table.get(key) == _digest(want), "stored reference digest of %s is missing or stale" % key
+        return len(got) == len(want) and all(np.array_equal(g, w) for g, w in zip(got, want))
+    assert key in table, "no stored reference digest for %s" % key
+    return _digest(got) == table[key]

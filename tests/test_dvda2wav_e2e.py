@@ -4,13 +4,16 @@ oracle/_ref/dvda2wav_ref = the reference utility, all reference sources.
 oracle/_ref/dvda2wav_hip = the same reference sources with src/mlp.c replaced by our binding
                            (integration/mlp_hip_shim.c -> libdvda_mlp_hip.so).
 Both are built in the dev container by `make -C oracle ref_tools` and travel to the GPU box as
-prebuilt binaries; the tests skip where they are absent."""
+prebuilt binaries; the tests skip where they are absent, except the two CPU tests, which compare with the stored
+digests of the reference tool's output (tests/golden/reference_digests.json) instead."""
 import os
 import subprocess
 import tempfile
 
 import numpy as np
 import pytest
+
+from tests import oracle_lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_TOOL = os.path.join(ROOT, "oracle", "_ref", "dvda2wav_ref")
@@ -48,29 +51,34 @@ def _mlp_disc(pkg, oracle, tmp, layouts):
     return disc.write_disc(tmp, tracks), want
 
 
-@pytest.mark.skipif(not os.path.exists(REF_TOOL), reason="reference tools not built (dev container only)")
 def test_pcm_disc_through_reference_dvda2wav(pkg):
-    """configs[0]: 2-ch / 48 kHz / 16-bit uncompressed PCM AOB, reference CPU path (plumbing)."""
+    """configs[0]: 2-ch / 48 kHz / 16-bit uncompressed PCM AOB, reference CPU path (plumbing).  Without the reference
+    tools, the digest of what the reference's tool wrote (tests/golden/reference_digests.json) stands in for it."""
     disc = pkg.disc
     rng = np.random.RandomState(5)
     samples = rng.randint(-32768, 32768, size=(5020, 2))
     with tempfile.TemporaryDirectory() as tmp:
         ats = disc.write_disc(tmp, [{"sectors": disc.pcm_track_sectors(samples, 0, 0, 1),
                                      "pcm_frames": len(samples), "rate_code": 0}])
-        wavs = _run(REF_TOOL, ats, os.path.join(tmp, "out"))
-        assert len(wavs) == 1
-        got = _wav_pcm(wavs[0], 2, 16)
-        assert np.array_equal(got, samples.T)
+
+        def reference():
+            wavs = _run(REF_TOOL, ats, os.path.join(tmp, "out"))
+            assert len(wavs) == 1
+            return (_wav_pcm(wavs[0], 2, 16),)
+
+        assert oracle_lib.same_as_reference("dvda2wav_pcm_disc", (samples.T.astype(np.int32),), reference)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_TOOL), reason="reference tools not built (dev container only)")
 def test_mlp_disc_reference_equals_oracle(pkg, oracle):
     with tempfile.TemporaryDirectory() as tmp:
         ats, want = _mlp_disc(pkg, oracle, tmp, [(1, 1, 1, 64, 0), (12, 1, 2, 48, 0)])
-        wavs = _run(REF_TOOL, ats, os.path.join(tmp, "out"))
-        assert len(wavs) == 2
-        for w, pcm in zip(wavs, want):
-            assert np.array_equal(_wav_pcm(w, pcm.shape[0], 24), pcm)
+
+        def reference():
+            wavs = _run(REF_TOOL, ats, os.path.join(tmp, "out"))
+            assert len(wavs) == 2
+            return tuple(_wav_pcm(w, pcm.shape[0], 24) for w, pcm in zip(wavs, want))
+
+        assert oracle_lib.same_as_reference("dvda2wav_mlp_disc", tuple(want), reference)
 
 
 @pytest.mark.gpu

@@ -1,6 +1,7 @@
 """CPU tests of the oracle: pinned against the committed golden vectors (produced by the
 real reference, tests/golden/make_golden.py), the reference's own bit-reader known answers,
-and -- where oracle/_ref exists -- the compiled reference on fresh fuzz streams."""
+and the compiled reference on fuzz streams (where oracle/_ref is not built, the digests of its output stored in
+tests/golden/reference_digests.json)."""
 import ctypes
 import glob
 import os
@@ -91,10 +92,8 @@ def test_codebook_lut(oracle, book):
             assert peek in (0, 0x80)
 
 
-@pytest.mark.skipif(not oracle_lib.Reference.available(), reason="compiled reference not present")
 def test_oracle_vs_compiled_reference(oracle, pkg):
     syn = pkg.synth
-    ref = oracle_lib.Reference()
     n = 0
     for asg, S in ((12, 1), (12, 2), (1, 1), (0x14, 2), (0, 1)):
         for rate in (0, 1, 2):
@@ -104,20 +103,19 @@ def test_oracle_vs_compiled_reference(oracle, pkg):
                                        profile=1 if feat else 0, features=feat,
                                        restart_interval=[8, 3][seed])
                     data, frames = syn.stream(cfg, 1000 + n)
-                    want, r = ref.decode(data, asg, rate, cfg.bps_code, frames)
                     got, r2, st = oracle.decode(data, syn.channels(asg), frames, chunk=[0, 777][seed])
-                    assert st == 0 and r == r2 == frames
-                    assert np.array_equal(got, want)
+                    assert st == 0 and r2 == frames
+                    assert oracle_lib.same_as_reference(
+                        "oracle_vs_reference_%d" % n, (got, r2),
+                        lambda: oracle_lib.Reference().decode(data, asg, rate, cfg.bps_code, frames))
                     n += 1
     assert n == 90
 
 
-@pytest.mark.skipif(not oracle_lib.Reference.available(), reason="compiled reference not present")
 def test_oracle_vs_reference_on_major_syncs_without_restart_headers(oracle, pkg):
     """reference src/mlp.c:449-460, 748-753: a major sync in front of an access unit whose blocks carry no restart
     header (generator feature SYNCONLY) -- the parameters are compared, the decode goes on with the state it has."""
     syn = pkg.synth
-    ref = oracle_lib.Reference()
     n = 0
     for asg, S in ((12, 1), (12, 2), (1, 1), (0x14, 2)):
         for feat in (0, syn.SF_ALL, syn.SF_FAST, syn.SF["CHAINED"] | syn.SF["FIRRAND"]):
@@ -128,10 +126,11 @@ def test_oracle_vs_reference_on_major_syncs_without_restart_headers(oracle, pkg)
                 v = data[:len(data) - len(data) % 2].reshape(-1, 2)
                 syncs = int(np.count_nonzero((v[:-1, 0] == 0xF8) & (v[:-1, 1] == 0x72) & (v[1:, 0] == 0x6F) & (v[1:, 1] == 0xBB)))
                 assert syncs > (32 + [8, 3][seed] - 1) // [8, 3][seed]          # more syncs than restart points
-                want, r = ref.decode(data, asg, 1, cfg.bps_code, frames)
                 got, r2, st = oracle.decode(data, syn.channels(asg), frames, chunk=[0, 777][seed])
-                assert st == 0 and r == r2 == frames
-                assert np.array_equal(got, want)
+                assert st == 0 and r2 == frames
+                assert oracle_lib.same_as_reference(
+                    "syncs_without_restart_%d" % n, (got, r2),
+                    lambda: oracle_lib.Reference().decode(data, asg, 1, cfg.bps_code, frames))
                 n += 1
     assert n == 32
 
@@ -153,7 +152,6 @@ def test_oracle_flags_corruption(oracle, pkg):
     assert r == 0 and st == 0
 
 
-@pytest.mark.skipif(not oracle_lib.Reference.available(), reason="compiled reference not present")
 @pytest.mark.parametrize("S", [1, 2])
 def test_oracle_vs_reference_on_changed_major_syncs(oracle, pkg, S):
     """reference src/mlp.c:449-460: an access unit whose major sync announces other stream parameters
@@ -169,21 +167,24 @@ def test_oracle_vs_reference_on_changed_major_syncs(oracle, pkg, S):
     data, frames = syn.stream(cfg, 4040 + S)
     changed, _ = stream_tools.change_sync_params(data, (1, 4, 5, 6, 9), g1_bps=0, assignment=None)
     want_frames = frames - 5 * 80
-    with tempfile.TemporaryDirectory() as tmp:
-        np.save(os.path.join(tmp, "in.npy"), changed)
-        code = ("import sys, numpy as np; sys.path.insert(0, %r); from tests import oracle_lib; "
-                "d = np.load(%r); pcm, r = oracle_lib.Reference().decode(d, 12, 1, 2, %d, chunk=1999); "
-                "np.save(%r, pcm)" % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                                      os.path.join(tmp, "in.npy"), frames, os.path.join(tmp, "out.npy")))
-        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        want = np.load(os.path.join(tmp, "out.npy"))
-    assert want.shape == (6, want_frames)
+
+    def reference():
+        with tempfile.TemporaryDirectory() as tmp:
+            np.save(os.path.join(tmp, "in.npy"), changed)
+            code = ("import sys, numpy as np; sys.path.insert(0, %r); from tests import oracle_lib; "
+                    "d = np.load(%r); pcm, r = oracle_lib.Reference().decode(d, 12, 1, 2, %d, chunk=1999); "
+                    "np.save(%r, pcm)" % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                          os.path.join(tmp, "in.npy"), frames, os.path.join(tmp, "out.npy")))
+            r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+            assert r.returncode == 0, r.stderr[-2000:]
+            want = np.load(os.path.join(tmp, "out.npy"))
+        assert want.shape == (6, want_frames)
+        return (want,)
+
     got, r2, st = oracle.decode(changed, 6, frames)
-    assert st == 2 and r2 == want_frames and np.array_equal(got, want)
+    assert st == 2 and r2 == want_frames and oracle_lib.same_as_reference("changed_major_syncs_%dss" % S, (got,), reference)
 
 
-@pytest.mark.skipif(not oracle_lib.Reference.available(), reason="compiled reference not present")
 def test_oracle_vs_reference_on_a_long_run_of_changed_major_syncs(oracle, pkg):
     """src/mlp.c:449-460 drops ANY number of consecutive access units whose major sync announces other parameters.
     The HIP index walks through at most 64 in a row (csrc/mlp_index.h MAX_DROP) and reports a longer run
@@ -198,18 +199,22 @@ def test_oracle_vs_reference_on_a_long_run_of_changed_major_syncs(oracle, pkg):
     which = tuple(range(2, 68))
     changed, _ = stream_tools.change_sync_params(data, which, g1_bps=0, assignment=None)
     want_frames = frames - len(which) * 80
-    with tempfile.TemporaryDirectory() as tmp:
-        np.save(os.path.join(tmp, "in.npy"), changed)
-        code = ("import sys, numpy as np; sys.path.insert(0, %r); from tests import oracle_lib; "
-                "d = np.load(%r); pcm, r = oracle_lib.Reference().decode(d, 12, 1, 2, %d, chunk=1999); "
-                "np.save(%r, pcm)" % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                                      os.path.join(tmp, "in.npy"), frames, os.path.join(tmp, "out.npy")))
-        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        want = np.load(os.path.join(tmp, "out.npy"))
-    assert want.shape == (6, want_frames)
+
+    def reference():
+        with tempfile.TemporaryDirectory() as tmp:
+            np.save(os.path.join(tmp, "in.npy"), changed)
+            code = ("import sys, numpy as np; sys.path.insert(0, %r); from tests import oracle_lib; "
+                    "d = np.load(%r); pcm, r = oracle_lib.Reference().decode(d, 12, 1, 2, %d, chunk=1999); "
+                    "np.save(%r, pcm)" % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                          os.path.join(tmp, "in.npy"), frames, os.path.join(tmp, "out.npy")))
+            r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+            assert r.returncode == 0, r.stderr[-2000:]
+            want = np.load(os.path.join(tmp, "out.npy"))
+        assert want.shape == (6, want_frames)
+        return (want,)
+
     got, r2, st = oracle.decode(changed, 6, frames)
-    assert st == 2 and r2 == want_frames and np.array_equal(got, want)
+    assert st == 2 and r2 == want_frames and oracle_lib.same_as_reference("long_run_of_changed_major_syncs", (got,), reference)
 
 
 def test_oracle_reports_substreams_of_different_access_unit_length():

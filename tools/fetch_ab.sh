@@ -8,7 +8,7 @@ for v in "$@"; do
   for c in FETCH_SIZE WRITE_SIZE; do
     OUT=$ROOT/gpurun_out/fetch_ab/$v/$c
     mkdir -p "$OUT"
-    timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$OUT" -- python3 "$ROOT/bench.py" --steps 2 --warmup 1 --no-cpu --verify 0 ${BENCH_ARGS} > "$OUT.log" 2>&1
+    timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$OUT" -- python3 "$ROOT/bench.py" --full --steps 2 --warmup 1 --no-cpu --verify 0 ${BENCH_ARGS} > "$OUT.log" 2>&1
     python3 - "$OUT" "$v" "$c" <<'PY'
 import csv, glob, sys
 tot, n = 0.0, 0

@@ -11,9 +11,9 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for S in $(echo "$SUBS" | tr ',' ' '); do
   mkdir -p "$OUT/$S"
-  ARGS="--steps 3 --warmup 1 --no-cpu --verify 0 --only-sub $S"
+  ARGS="--full --steps 3 --warmup 1 --no-cpu --verify 0 --only-sub $S"
   rm -rf "$OUT/$S/trace" "$OUT/$S/fetch" "$OUT/$S/write" "$OUT/$S/bench.json"      # (no summary from an earlier run's files)
-  timeout 600 python3 "$ROOT/bench.py" --steps 10 --warmup 2 --no-cpu --verify 4 --only-sub $S > "$OUT/$S/bench.json" 2> "$OUT/$S/bench.err" \
+  timeout 600 python3 "$ROOT/bench.py" --full --steps 10 --warmup 2 --no-cpu --verify 4 --only-sub $S > "$OUT/$S/bench.json" 2> "$OUT/$S/bench.err" \
     || { echo "$S: bench failed (rc $?), sub-record skipped"; rm -f "$OUT/$S/bench.json"; continue; }
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$S/trace" -- python3 "$ROOT/bench.py" $ARGS > "$OUT/$S/trace.log" 2>&1 \
     || { echo "$S: kernel-trace run failed (rc $?), sub-record skipped"; rm -rf "$OUT/$S/trace" "$OUT/$S/bench.json"; continue; }

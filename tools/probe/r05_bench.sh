@@ -1,10 +1,10 @@
 #!/bin/bash
 # tools/probe/r05_bench.sh [TAG] -- the whole bench (no CPU leg) with all sub-records, one line per record.  Diagnostic.
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
-cd "$ROOT"; mkdir -p gpurun_out/r05
+cd "$ROOT"; OUT=${OUT:-$(mktemp -d)}; mkdir -p "$OUT"; echo "bench line and stderr in $OUT"
 TAG=${1:-a}
-timeout 1200 python3 bench.py --steps 20 --warmup 5 --no-cpu 2>gpurun_out/r05/bench_$TAG.err | tail -1 > gpurun_out/r05/bench_$TAG.json
-python3 - gpurun_out/r05/bench_$TAG.json <<'PY'
+timeout 1200 python3 bench.py --full --steps 20 --warmup 5 --no-cpu 2>"$OUT/bench_$TAG.err" | tail -1 > "$OUT/bench_$TAG.json"
+python3 - "$OUT/bench_$TAG.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
 print('headline %.0f Msamples/s  %.4f ms/step  k_decode %.4f ms  frac %.4f' % (d['value'], d['ms_per_step'], d['roofline']['kernel_ms'], d['roofline']['frac']))

@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for F in 2 3; do
   for FREE in 0 1; do
-    DVDA_BENCH_FREE_OVERLAP=$FREE python3 "$ROOT/bench.py" --steps 20 --warmup 3 --no-cpu --no-disc --only-sub chained_two_substreams --chain-flight $F \
+    DVDA_BENCH_FREE_OVERLAP=$FREE python3 "$ROOT/bench.py" --full --steps 20 --warmup 3 --no-cpu --no-disc --only-sub chained_two_substreams --chain-flight $F \
       > "$OUT/bench_f${F}_free${FREE}.json" 2> "$OUT/bench_f${F}_free${FREE}.err"
     python3 - "$OUT/bench_f${F}_free${FREE}.json" $F $FREE <<'PY'
 import json, sys
@@ -22,7 +22,7 @@ PY
 done
 for FREE in 0 1; do
   DVDA_BENCH_FREE_OVERLAP=$FREE timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_free$FREE" -- \
-    python3 "$ROOT/bench.py" --steps 6 --warmup 2 --no-cpu --no-disc --verify 0 --only-sub chained_two_substreams --chain-flight 2 > "$OUT/trace_free$FREE.log" 2>&1
+    python3 "$ROOT/bench.py" --full --steps 6 --warmup 2 --no-cpu --no-disc --verify 0 --only-sub chained_two_substreams --chain-flight 2 > "$OUT/trace_free$FREE.log" 2>&1
   echo "== kernel trace, 2 contexts in flight, free=$FREE"
   find "$OUT/trace_free$FREE" -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} "$OUT/kernel_stats_free$FREE.csv"
   python3 - "$OUT/kernel_stats_free$FREE.csv" <<'PY'

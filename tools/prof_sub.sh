@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/sub_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 "$ROOT/bench.py" --steps 3 --warmup 1 --no-cpu --verify 0 --only-sub "$SUBS" > "$OUT/trace.log" 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 "$ROOT/bench.py" --full --steps 3 --warmup 1 --no-cpu --verify 0 --only-sub "$SUBS" > "$OUT/trace.log" 2>&1
 echo "rc=$?"
 find "$OUT/trace" -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} "$OUT/kernel_stats.csv"
 python3 - "$OUT/kernel_stats.csv" <<'PY'
