@@ -92,6 +92,10 @@ extern "C" {
 #define DVDA_ST_DEVICE       (1u << 29)  /* streaming tier only: a HIP runtime call failed inside a step -- not a
                                             property of the stream; the decoder stops (it does not fall back to the
                                             batch tier on the same device without a word)                     */
+#define DVDA_ST_CONCEALED    (1u << 30)  /* conceal mode only (dvda_mlp_hip_set_conceal): the stream was damaged and
+                                            comes out as kept PCM, silence and PCM of a fresh decoder; the damage
+                                            bits moved into its spans (dvda_mlp_hip_conceal_spans).  NOT in
+                                            DVDA_ST_BENIGN: a caller has to ask for silence to accept it      */
 /* DVDA_ST_CHAINED, _MIDFRAME, _COLD, _YIELD, _TIMING and _SEQ are raised by the fast pass and then decoded exactly by
  * the passes behind it (chain passes: parse in parallel, the filter recursion alone per channel, rematrix
  * in parallel; or the sequential pass); they stay set as information.  Bits that do not invalidate the PCM: */
@@ -164,6 +168,51 @@ int dvda_mlp_hip_decode(dvda_mlp_hip_ctx *ctx, int32_t *d_pcm, const uint64_t *d
  * workspaces on first use) and the *_info / *_count calls. */
 int dvda_mlp_hip_decode_async(dvda_mlp_hip_ctx *ctx, int32_t *d_pcm, const uint64_t *d_out_off,
                               const uint64_t *d_out_stride, void *stream);
+/* (On a context in conceal mode dvda_mlp_hip_decode_async returns DVDA_HIP_EINVAL: concealing reads the damage back.) */
+
+/* Conceal mode (default off; off = every output, status bit, launch and allocation as without it).  With it on,
+ * dvda_mlp_hip_decode hands out a damaged stream as
+ *     kept PCM ++ silence ++ PCM decoded by a fresh decoder ++ ...
+ * instead of a non-benign status:
+ *   damage   an access unit whose parity / CRC-8 fails or that cannot be framed; when no unit check locates it, the
+ *            whole segment whose decode reported a non-benign status (always so for streams without check data)
+ *   kept     every access unit in front of the first damaged one, exactly as without conceal mode (a range that starts at
+ *            the stream's first byte is decoded with the FIR history dvda_mlp_hip_set_initial_fir gave the stream)
+ *   resume   the first major sync behind the damage at which every substream opens with a restart header; from there
+ *            a fresh decoder (zero FIR / IIR history, no parameters carried) -- the PCM the reference returns for the
+ *            bytes from that sync on.  Damage behind it: the same again (at most 4 decode rounds; what is still
+ *            damaged after the last is concealed whole)
+ *   silence  g = (t_r - t_k - n_k) mod 65536 PCM frames between the last kept unit (16-bit input timing t_k, n_k
+ *            frames) and the resume unit (t_r), plus 65536 w, w >= 0 the integer that brings the span's bytes per
+ *            frame closest to the stream's mean over its kept ranges; 0 frames in front of the first usable major
+ *            sync and behind the last kept unit.  Zeros in every layout.
+ *            (t_k + n_k is taken as the input timing of the kept range's first unit + the PCM frames the range decodes
+ *            to: the last unit's own frame count, standard or not, without a second parse; input timing that does not
+ *            advance by the units' PCM frames inside a kept range gives a gap off by the difference)
+ * A concealed stream's status is DVDA_ST_CONCEALED | the benign bits of its kept ranges (| DVDA_ST_OVERFLOW when the
+ * composed stream does not fit: pcm_frames = the capacity needed, and the stream's region holds no concealed output --
+ * what the ordinary decode wrote there is left as it is); mlp_frames counts the kept access units.  These are what
+ * dvda_mlp_hip_stream_info reports; the index's own records stay as the decode left them, so a second decode of the same
+ * index (after DVDA_ST_OVERFLOW) starts from the index's findings, conceal mode on or off.  A stream without damage
+ * decodes exactly as without conceal mode.  The call blocks a little longer for a batch with damage (a second index and
+ * decode of the ranges); a clean batch costs one read of the stream records. */
+int dvda_mlp_hip_set_conceal(dvda_mlp_hip_ctx *ctx, int on);
+
+/* One concealed span of a stream: PCM frames [first_frame, first_frame + frames) of the output are silence, standing
+ * for bytes [byte_off, byte_end) of the stream (offsets from the stream's first byte); cause = the DVDA_ST_* bits of the
+ * damage.  flags: */
+#define DVDA_CONCEAL_LEADING  1u    /* in front of the first usable major sync (frames = 0)           */
+#define DVDA_CONCEAL_TRAILING 2u    /* behind the last kept access unit (frames = 0)                  */
+#define DVDA_CONCEAL_ROUNDS   4u    /* holds a range still damaged after the last decode round        */
+typedef struct dvda_mlp_conceal_span {
+    uint64_t first_frame, frames;
+    uint64_t byte_off, byte_end;
+    uint32_t cause, flags;
+} dvda_mlp_conceal_span;
+/* The spans of `stream` from the last dvda_mlp_hip_decode in conceal mode (blocks on `stream_`): up to cap of them into
+ * spans, *n = how many there are (0 for a clean stream). */
+int dvda_mlp_hip_conceal_spans(dvda_mlp_hip_ctx *ctx, uint32_t stream, dvda_mlp_conceal_span *spans, uint32_t cap,
+                               uint32_t *n, void *stream_);
 
 /* Sizes the workspaces of the passes behind the fast pass ahead of time (they only ever grow): chain passes for
  * `chain_segments` deferred segments holding `chain_pcm_frames` PCM frames in all (for titles whose restart points

@@ -12,6 +12,7 @@
 // pass (a 32-byte summary decides what else is launched); a batch with chained segments grows the
 // chain workspace on first use.
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -27,6 +28,7 @@
 #include "mlp_check.h"
 #include "mlp_coop.h"
 #include "mlp_index.h"
+#include "mlp_conceal.h"
 #include "pcm_unswizzle.h"
 #include "wav_pack.h"
 
@@ -55,6 +57,12 @@ static hipError_t ws_malloc(void **p, size_t bytes)
         e = hipMemset(*p, poison & 0xFF, bytes);
     return e;
 }
+
+// conceal mode: the composed record of a concealed stream, what dvda_mlp_hip_stream_info reports for it
+struct ConcealInfo {
+    uint32_t valid, status;
+    uint64_t rows, frames;
+};
 
 struct dvda_mlp_hip_ctx {
     int device;
@@ -140,6 +148,23 @@ struct dvda_mlp_hip_ctx {
     uint32_t ev_end_made;
     uint32_t ev_made;          // events created
     uint64_t ev_count;         // decode calls recorded since the last dvda_mlp_hip_kernel_time
+    // conceal mode (mlp_conceal.h): nothing of it is allocated before a batch with damage needs it
+    bool conceal;
+    dvda_mlp_hip_ctx *cc_child;        // the second index: the kept ranges, each a stream of its own, fresh state
+    ConcealPlan *d_cc_plan;
+    uint64_t cc_plan_cap;              // plans
+    uint8_t *d_cc_bytes;               // the ranges gathered 16-byte aligned (+ 64 readable bytes)
+    uint64_t cc_bytes_cap;
+    uint64_t *d_cc_tab;                // gather table [3 * pieces], then the child's ranges and outputs [4 * pieces]
+    uint64_t cc_tab_cap;
+    int32_t *d_cc_scr[CONCEAL_ROUNDS]; // per round: the ranges' PCM, each laid out as the stream it belongs to
+    uint64_t cc_scr_cap[CONCEAL_ROUNDS];
+    ConcealOp *d_cc_ops;
+    uint64_t cc_ops_cap;
+    int32_t *d_cc_fir;                 // zero FIR history of the ranges' fresh decoders [pieces][2][48]
+    uint64_t cc_fir_cap;
+    std::vector<std::vector<dvda_mlp_conceal_span>> cc_spans;  // per stream of the last decode
+    std::vector<ConcealInfo> cc_info;                           // per stream of the last decode: the concealed ones
 };
 
 // what the workspaces hold right now (mlp_bounds.h)
@@ -227,6 +252,15 @@ static void free_ws(dvda_mlp_hip_ctx *c)
         (void)hipEventDestroy(c->ev_end[i]);
     if (c->idx_graph)
         (void)hipGraphExecDestroy(c->idx_graph);
+    if (c->cc_child)
+        dvda_mlp_hip_destroy(c->cc_child);
+    (void)hipFree(c->d_cc_plan);
+    (void)hipFree(c->d_cc_bytes);
+    (void)hipFree(c->d_cc_tab);
+    for (uint32_t r = 0; r < CONCEAL_ROUNDS; r++)
+        (void)hipFree(c->d_cc_scr[r]);
+    (void)hipFree(c->d_cc_ops);
+    (void)hipFree(c->d_cc_fir);
 }
 
 extern "C" const char *dvda_mlp_hip_version(void) { return "dvda-mlp-hip 0.1 (gfx950)"; }
@@ -610,6 +644,8 @@ extern "C" int dvda_mlp_hip_index(dvda_mlp_hip_ctx *c, const uint8_t *d_bytes, u
         return DVDA_HIP_EINVAL;
     hipStream_t st = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(c->device));
+    c->cc_spans.clear();
+    c->cc_info.clear();
     int rc = ensure_byte_ws(c, total_bytes);
     if (rc)
         return rc;
@@ -748,15 +784,27 @@ extern "C" int dvda_mlp_hip_reserve(dvda_mlp_hip_ctx *c, uint64_t chain_pcm_fram
 static int decode_impl(dvda_mlp_hip_ctx *c, int32_t *d_pcm, const uint64_t *d_out_off, const uint64_t *d_out_stride,
                        void *stream_, bool blocking);
 
+static int conceal_run(dvda_mlp_hip_ctx *c, int32_t *d_pcm, const uint64_t *d_out_off, const uint64_t *d_out_stride,
+                       hipStream_t st);
+
 extern "C" int dvda_mlp_hip_decode(dvda_mlp_hip_ctx *c, int32_t *d_pcm, const uint64_t *d_out_off,
                                    const uint64_t *d_out_stride, void *stream_)
 {
-    return decode_impl(c, d_pcm, d_out_off, d_out_stride, stream_, true);
+    if (c) {
+        c->cc_spans.clear();
+        c->cc_info.clear();
+    }
+    const int rc = decode_impl(c, d_pcm, d_out_off, d_out_stride, stream_, true);
+    if (rc != DVDA_HIP_OK || !c->conceal)
+        return rc;
+    return conceal_run(c, d_pcm, d_out_off, d_out_stride, (hipStream_t)stream_);
 }
 
 extern "C" int dvda_mlp_hip_decode_async(dvda_mlp_hip_ctx *c, int32_t *d_pcm, const uint64_t *d_out_off,
                                          const uint64_t *d_out_stride, void *stream_)
 {
+    if (c && c->conceal)
+        return DVDA_HIP_EINVAL;     // concealing reads the damage back: the blocking call only
     return decode_impl(c, d_pcm, d_out_off, d_out_stride, stream_, false);
 }
 
@@ -1074,6 +1122,12 @@ extern "C" int dvda_mlp_hip_stream_info(dvda_mlp_hip_ctx *c, dvda_mlp_stream_inf
         o.group0_rate = (h[i].sync >> 8) & 0xF;
         o.group1_rate = (h[i].sync >> 12) & 0xF;
         o.segments = h[i].n_seg;
+        if (i < c->cc_info.size() && c->cc_info[i].valid) {
+            // conceal mode: the stream as it was handed out (kept + silence + resumed)
+            o.status = c->cc_info[i].status;
+            o.pcm_frames = c->cc_info[i].rows;
+            o.mlp_frames = c->cc_info[i].frames;
+        }
     }
     return DVDA_HIP_OK;
 }
@@ -1260,6 +1314,396 @@ extern "C" int dvda_mlp_hip_segment_fir(dvda_mlp_hip_ctx *c, uint32_t segment, i
 
 // ------------------------------------------------------------------ streaming tier: the decoder state stays on the device
 // (mlp_step.h; host side: mlp_stream.c)
+// ------------------------------------------------------------------ conceal mode (mlp_conceal.h)
+
+extern "C" int dvda_mlp_hip_set_conceal(dvda_mlp_hip_ctx *c, int on)
+{
+    if (!c)
+        return DVDA_HIP_EINVAL;
+    c->conceal = on != 0;
+    c->cc_spans.clear();
+    c->cc_info.clear();
+    return DVDA_HIP_OK;
+}
+
+extern "C" int dvda_mlp_hip_conceal_spans(dvda_mlp_hip_ctx *c, uint32_t stream, dvda_mlp_conceal_span *spans,
+                                          uint32_t cap, uint32_t *n, void *stream_)
+{
+    if (!c || !n || (cap && !spans))
+        return DVDA_HIP_EINVAL;
+    if (!c->indexed)
+        return DVDA_HIP_ESTATE;
+    if (stream >= c->n_streams)
+        return DVDA_HIP_EINVAL;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream_));
+    *n = 0;
+    if (stream >= c->cc_spans.size())
+        return DVDA_HIP_OK;
+    const std::vector<dvda_mlp_conceal_span> &v = c->cc_spans[stream];
+    *n = (uint32_t)v.size();
+    for (uint32_t k = 0; k < cap && k < v.size(); k++)
+        spans[k] = v[k];
+    return DVDA_HIP_OK;
+}
+
+namespace {
+struct CcItem {                 // a kept byte range of a damaged stream
+    uint64_t a, b;              // absolute offsets in the caller's buffer
+    uint32_t t_first;           // input timing at a (t_first + frames: behind its last unit)
+    uint32_t cause, flags;      // the span in front of it: DVDA_ST_* bits, DVDA_CONCEAL_* flags
+    uint32_t state;             // 0: to decode (fresh), 1: decoded clean
+    uint32_t round, piece;      // decoded by that round as that piece
+    uint64_t scr_off, cap;      // its PCM in the round's scratch (int32 units), capacity / channel stride there (frames)
+    uint64_t frames, units;
+    uint32_t status, stream;
+};
+struct CcStream {
+    uint32_t id;
+    std::vector<CcItem> items;
+    uint32_t tail_cause, tail_flags;
+};
+} // namespace
+
+// frames of silence for a span of B bytes whose timing says g (mod 65536): g + 65536 w, w >= 0 the integer whose bytes per
+// frame come closest to m, the stream's mean over its kept ranges (no mean: g)
+static uint64_t conceal_gap(uint64_t B, uint32_t g, double m)
+{
+    if (!(m > 0.0))
+        return g;
+    double w0 = floor(((double)B / m - (double)g) / 65536.0);
+    if (w0 < 0.0)
+        w0 = 0.0;
+    uint64_t best = 0;
+    double bd = 0.0;
+    for (int k = 0; k < 2; k++) {
+        const uint64_t G = (uint64_t)g + 65536ull * ((uint64_t)w0 + (uint64_t)k);
+        const double d = G ? fabs((double)B / (double)G - m) : INFINITY;
+        if (k == 0 || d < bd) {
+            best = G;
+            bd = d;
+        }
+    }
+    return best;
+}
+
+// The blocking decode is through; conceal mode: the damaged streams are planned, their kept ranges decoded again in
+// rounds by a second context (fresh state, each range a stream of its own), and the result laid out in the caller's
+// buffer with zeros between the ranges.  A batch without damage returns after one read of the stream records.
+static int conceal_run(dvda_mlp_hip_ctx *c, int32_t *d_pcm, const uint64_t *d_out_off, const uint64_t *d_out_stride,
+                       hipStream_t st)
+{
+    const uint32_t ns = c->n_streams;
+    c->cc_spans.assign(ns, std::vector<dvda_mlp_conceal_span>());
+    c->cc_info.assign(ns, ConcealInfo());
+    std::vector<StreamRec> h(ns);
+    HIP_TRY(hipMemcpyAsync(h.data(), c->d_streams, (size_t)ns * sizeof(StreamRec), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<uint32_t> dam;
+    for (uint32_t i = 0; i < ns; i++)
+        if (h[i].status & CONCEAL_DAMAGE)
+            dam.push_back(i);
+    if (dam.empty())
+        return DVDA_HIP_OK;
+    std::vector<uint64_t> soff(ns), slen(ns), oo(ns), os(ns);
+    HIP_TRY(hipMemcpyAsync(soff.data(), c->d_soff, (size_t)ns * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(slen.data(), c->d_slen, (size_t)ns * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(oo.data(), d_out_off, (size_t)ns * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(os.data(), d_out_stride, (size_t)ns * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+
+    int rc;
+    std::vector<ConcealPlan> plans;
+    auto run_plan = [&](dvda_mlp_hip_ctx *x, uint32_t n) -> int {
+        int r = grow(&c->d_cc_plan, &c->cc_plan_cap, n);
+        if (r)
+            return r;
+        hipLaunchKernelGGL(k_conceal_plan, dim3((n + 63) / 64), dim3(64), 0, st, x->d_bytes, x->d_soff, x->d_slen, x->d_seg,
+                           x->d_seg_status, x->d_n_cand, x->max_segments, x->d_streams, n, c->d_cc_plan);
+        HIP_TRY(hipGetLastError());
+        plans.resize(n);
+        HIP_TRY(hipMemcpyAsync(plans.data(), c->d_cc_plan, (size_t)n * sizeof(ConcealPlan), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return DVDA_HIP_OK;
+    };
+    // a plan's ranges (relative to `base`, the piece `len` bytes long) -> items; `in` = the span in front of the piece
+    auto items_of = [](const ConcealPlan &P, uint64_t base, uint32_t cause_in, uint32_t flags_in, std::vector<CcItem> &out,
+                       uint32_t &tail) {
+        const uint32_t n = P.n <= CONCEAL_MAX_RANGES ? P.n : 0u;       // (0xFFFFFFFF: not planned -- nothing kept)
+        for (uint32_t k = 0; k < n; k++) {
+            CcItem it;
+            memset(&it, 0, sizeof(it));
+            it.a = base + P.r[k].a;
+            it.b = base + P.r[k].b;
+            it.t_first = P.r[k].t_first;
+            it.cause = P.r[k].cause | (k == 0 ? cause_in : 0u);
+            it.flags = k == 0 ? flags_in : 0u;
+            out.push_back(it);
+        }
+        tail = (P.n <= CONCEAL_MAX_RANGES ? P.tail_cause : DVDA_ST_ENVELOPE) | (n == 0 ? cause_in : 0u);
+    };
+
+    // ---- round 0: the caller's index
+    if ((rc = run_plan(c, ns)) != 0)
+        return rc;
+    std::vector<CcStream> S;
+    for (uint32_t i : dam) {
+        CcStream cs;
+        cs.id = i;
+        cs.tail_flags = 0;
+        items_of(plans[i], soff[i], 0u, 0u, cs.items, cs.tail_cause);
+        S.push_back(cs);
+    }
+    const uint32_t layout = c->pcm_layout;
+    const uint64_t vb = layout == DVDA_PCM_WAV24 ? 3 : layout == DVDA_PCM_WAV16 ? 2 : 4;
+    auto chans = [&](uint32_t i) { return (uint64_t)channel_count((h[i].sync >> 16) & 0x1Fu); };
+
+    // ---- rounds 1 .. CONCEAL_ROUNDS - 1: every range not yet decoded clean, fresh
+    for (uint32_t round = 1; round < CONCEAL_ROUNDS; round++) {
+        uint32_t np = 0;
+        for (CcStream &cs : S)
+            for (CcItem &it : cs.items)
+                if (it.state == 0) {
+                    it.stream = cs.id;
+                    it.piece = np++;
+                }
+        if (np == 0)
+            break;
+        // gather table [3 np], then the second index's ranges and outputs [4 np]
+        std::vector<uint64_t> up(7 * (size_t)np);
+        std::vector<CcItem *> pc(np);
+        uint64_t pos = 0;
+        for (CcStream &cs : S) {
+            for (CcItem &it : cs.items) {
+                if (it.state != 0)
+                    continue;
+                const uint32_t q = it.piece;
+                const uint64_t len = it.b - it.a;
+                pc[q] = &it;
+                up[3 * (size_t)q] = it.a;
+                up[3 * (size_t)q + 1] = pos;
+                up[3 * (size_t)q + 2] = len;
+                up[3 * (size_t)np + q] = pos;
+                up[4 * (size_t)np + q] = len;
+                pos += (len + 15) & ~(uint64_t)15;
+            }
+        }
+        if ((rc = grow(&c->d_cc_bytes, &c->cc_bytes_cap, pos + 64)) != 0 ||
+            (rc = grow(&c->d_cc_tab, &c->cc_tab_cap, 7 * (uint64_t)np)) != 0 ||
+            (rc = grow(&c->d_cc_fir, &c->cc_fir_cap, 2 * 48 * (uint64_t)np)) != 0)
+            return rc;
+        HIP_TRY(hipMemcpyAsync(c->d_cc_tab, up.data(), up.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(c->d_cc_bytes, 0, pos + 64, st));
+        hipLaunchKernelGGL(k_conceal_gather, dim3(16, np < 65535u ? np : 65535u), dim3(256), 0, st, c->d_bytes, c->d_cc_bytes,
+                           c->d_cc_tab, np);
+        HIP_TRY(hipGetLastError());
+        // FIR history of the ranges' decoders: a range that starts at its stream's first byte starts with what the caller's
+        // decode started that stream with (dvda_mlp_hip_set_initial_fir: its kept PCM is then exactly the output without
+        // conceal mode); every other range with zeros, given explicitly -- a range that starts at a major sync whose first
+        // block continues the history (DVDA_ST_CHAINED) is decoded with zero history there, as the oracle decodes it, not
+        // refused
+        HIP_TRY(hipMemsetAsync(c->d_cc_fir, 0, 2 * 48 * (size_t)np * sizeof(int32_t), st));
+        if (c->d_init_fir)
+            for (uint32_t q = 0; q < np; q++)
+                if (pc[q]->a == soff[pc[q]->stream])
+                    HIP_TRY(hipMemcpyAsync(c->d_cc_fir + 2 * 48 * (size_t)q, c->d_init_fir + 2 * 48 * (size_t)pc[q]->stream,
+                                           2 * 48 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        // the second context: as large as the caller's in segments (the ranges hold a part of its candidates)
+        if (!c->cc_child || c->cc_child->max_streams < np) {
+            if (c->cc_child)
+                dvda_mlp_hip_destroy(c->cc_child);
+            c->cc_child = nullptr;
+            HIP_TRY(hipStreamSynchronize(st));
+            if ((rc = dvda_mlp_hip_create(&c->cc_child, c->device, np < 64 ? 64 : np, c->max_segments)) != 0)
+                return rc;
+            c->cc_child->idx_graph_state = -1;
+        }
+        dvda_mlp_hip_ctx *x = c->cc_child;
+        x->pcm_layout = c->pcm_layout;
+        x->lanes_per_seg = c->lanes_per_seg;
+        x->chain_form = c->chain_form;
+        x->conceal = false;
+        x->d_init_fir = c->d_cc_fir;
+        const uint64_t *d_x = c->d_cc_tab + 3 * (size_t)np;
+        if ((rc = dvda_mlp_hip_index(x, c->d_cc_bytes, pos, d_x, d_x + np, np, st)) != 0)
+            return rc;
+        std::vector<StreamRec> xh(np);
+        HIP_TRY(hipMemcpyAsync(xh.data(), x->d_streams, (size_t)np * sizeof(StreamRec), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        // each range's scratch holds what its access units decode to at the standard timing (not the stream's capacity:
+        // the memory follows the damage); a range that needs more (DVDA_ST_OVERFLOW, non-standard timing) is decoded
+        // once more with the size it reported, up to its stream's capacity
+        for (uint32_t q = 0; q < np; q++) {
+            const uint64_t std_rows = xh[q].frames * rows_per_au((xh[q].sync >> 8) & 0xFu);
+            pc[q]->cap = std_rows < os[pc[q]->stream] ? std_rows : os[pc[q]->stream];
+        }
+        for (int attempt = 0; attempt < 2; attempt++) {
+            uint64_t scr = 0;
+            for (uint32_t q = 0; q < np; q++) {
+                const uint64_t C = chans(pc[q]->stream), cap = pc[q]->cap;
+                pc[q]->scr_off = scr;
+                up[5 * (size_t)np + q] = scr;
+                up[6 * (size_t)np + q] = cap;
+                scr += vb == 4 ? C * cap : (cap * C * vb + 3) / 4 + 4;
+            }
+            if ((rc = grow(&c->d_cc_scr[round], &c->cc_scr_cap[round], scr + 16)) != 0)
+                return rc;
+            HIP_TRY(hipMemcpyAsync(c->d_cc_tab + 5 * (size_t)np, up.data() + 5 * (size_t)np, 2 * (size_t)np * sizeof(uint64_t),
+                                   hipMemcpyHostToDevice, st));
+            if ((rc = dvda_mlp_hip_decode(x, c->d_cc_scr[round], d_x + 2 * (size_t)np, d_x + 3 * (size_t)np, st)) != 0)
+                return rc;
+            HIP_TRY(hipMemcpyAsync(xh.data(), x->d_streams, (size_t)np * sizeof(StreamRec), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            bool redo = false;
+            for (uint32_t q = 0; q < np; q++)
+                if ((xh[q].status & DVDA_ST_OVERFLOW) && xh[q].rows > pc[q]->cap && pc[q]->cap < os[pc[q]->stream]) {
+                    pc[q]->cap = xh[q].rows < os[pc[q]->stream] ? xh[q].rows : os[pc[q]->stream];
+                    redo = true;
+                }
+            if (!redo)
+                break;
+        }
+        const bool last = round + 1 == CONCEAL_ROUNDS;
+        bool again = false;
+        // (a range whose decode reports DVDA_ST_ENVELOPE is not trusted either: the caller's streams may carry it, a range
+        //  decoded again must come out inside the envelope)
+        for (uint32_t q = 0; q < np; q++)
+            again |= (xh[q].status & (CONCEAL_DAMAGE | DVDA_ST_ENVELOPE)) != 0;
+        if (again && !last && (rc = run_plan(x, np)) != 0)
+            return rc;
+        for (CcStream &cs : S) {
+            std::vector<CcItem> nv;
+            uint32_t carry = 0, carry_flags = 0;        // a span behind a range: in front of the next one
+            for (CcItem &it : cs.items) {
+                it.cause |= carry;
+                it.flags |= carry_flags;
+                carry = carry_flags = 0;
+                if (it.state != 0) {
+                    nv.push_back(it);
+                    continue;
+                }
+                const StreamRec &r = xh[it.piece];
+                if (!(r.status & (CONCEAL_DAMAGE | DVDA_ST_ENVELOPE))) {
+                    it.state = 1;
+                    it.round = round;
+                    it.frames = r.rows;
+                    it.units = r.frames;
+                    it.status = r.status;
+                    nv.push_back(it);
+                } else if (last) {
+                    // still damaged after the last round: concealed whole
+                    carry = it.cause | (r.status & (CONCEAL_DAMAGE | DVDA_ST_ENVELOPE));
+                    carry_flags = it.flags | DVDA_CONCEAL_ROUNDS;
+                } else {
+                    items_of(plans[it.piece], it.a, it.cause, it.flags, nv, carry);
+                }
+            }
+            cs.tail_cause |= carry;
+            cs.tail_flags |= carry_flags;
+            cs.items.swap(nv);
+        }
+    }
+
+    // ---- layout: kept ranges in order, silence between them
+    std::vector<ConcealOp> moves, fills;
+    for (CcStream &cs : S) {
+        const uint32_t i = cs.id;
+        const uint64_t C = chans(i);
+        uint64_t K = 0, F = 0, units = 0;
+        uint32_t benign = 0;
+        bool ovf = false;                       // a range whose own decode did not fit
+        for (const CcItem &it : cs.items) {
+            ovf |= (it.status & DVDA_ST_OVERFLOW) != 0;
+            K += it.b - it.a;
+            F += it.frames;
+            units += it.units;
+            benign |= it.status & DVDA_ST_BENIGN;
+        }
+        const double m = K && F ? (double)K / (double)F : 0.0;
+        std::vector<dvda_mlp_conceal_span> sp;
+        std::vector<ConcealOp> mv, fl;
+        uint64_t pos = 0;
+        const CcItem *prev = nullptr;
+        for (const CcItem &it : cs.items) {
+            dvda_mlp_conceal_span s;
+            memset(&s, 0, sizeof(s));
+            s.cause = it.cause;
+            s.flags = it.flags;
+            s.byte_end = it.a - soff[i];
+            if (!prev) {
+                if (it.a > soff[i]) {
+                    s.flags |= DVDA_CONCEAL_LEADING;
+                    sp.push_back(s);
+                }
+            } else {
+                const uint32_t g = (it.t_first - (uint32_t)(prev->t_first + prev->frames)) & 0xFFFFu;
+                const uint64_t G = conceal_gap(it.a - prev->b, g, m);
+                s.first_frame = pos;
+                s.frames = G;
+                s.byte_off = prev->b - soff[i];
+                sp.push_back(s);
+                if (G) {
+                    ConcealOp o = {oo[i], 0, pos, G, os[i], 0, (uint32_t)C, 0};
+                    fl.push_back(o);
+                }
+                pos += G;
+            }
+            if (it.frames) {
+                ConcealOp o = {oo[i], it.scr_off, pos, it.frames, os[i], it.cap, (uint32_t)C, it.round};
+                mv.push_back(o);
+            }
+            pos += it.frames;
+            prev = &it;
+        }
+        const uint64_t end = soff[i] + slen[i];
+        if (!prev || prev->b < end) {
+            dvda_mlp_conceal_span s;
+            memset(&s, 0, sizeof(s));
+            s.first_frame = pos;
+            s.byte_off = prev ? prev->b - soff[i] : 0;
+            s.byte_end = slen[i];
+            s.cause = cs.tail_cause;
+            s.flags = cs.tail_flags | DVDA_CONCEAL_TRAILING | (prev ? 0u : DVDA_CONCEAL_LEADING);
+            sp.push_back(s);
+        }
+        uint32_t status = DVDA_ST_CONCEALED | benign;
+        if (pos > os[i] || ovf)
+            status |= DVDA_ST_OVERFLOW;         // pcm_frames = the capacity needed; the region holds no concealed output
+        else {
+            moves.insert(moves.end(), mv.begin(), mv.end());
+            fills.insert(fills.end(), fl.begin(), fl.end());
+        }
+        // (the composed record is the host's: the index's own record stays as the decode left it, so that a second decode of
+        //  the same index -- after DVDA_ST_OVERFLOW -- starts from what the index found, conceal mode on or off)
+        c->cc_info[i].valid = 1;
+        c->cc_info[i].status = status;
+        c->cc_info[i].rows = pos;
+        c->cc_info[i].frames = units;
+        c->cc_spans[i].swap(sp);
+    }
+    const uint32_t nm = (uint32_t)moves.size(), nf = (uint32_t)fills.size();
+    if (nm + nf) {
+        if ((rc = grow(&c->d_cc_ops, &c->cc_ops_cap, (uint64_t)nm + nf)) != 0)
+            return rc;
+        std::vector<ConcealOp> ops(moves);
+        ops.insert(ops.end(), fills.begin(), fills.end());
+        HIP_TRY(hipMemcpyAsync(c->d_cc_ops, ops.data(), ops.size() * sizeof(ConcealOp), hipMemcpyHostToDevice, st));
+        ConcealSrc srcs;
+        memset(&srcs, 0, sizeof(srcs));
+        for (uint32_t r = 0; r < CONCEAL_ROUNDS; r++)
+            srcs.p[r] = c->d_cc_scr[r];
+        if (nm)
+            hipLaunchKernelGGL(k_conceal_move, dim3(64, nm < 65535u ? nm : 65535u), dim3(256), 0, st, c->d_cc_ops, nm,
+                               layout, d_pcm, srcs);
+        if (nf)
+            hipLaunchKernelGGL(k_conceal_fill, dim3(64, nf < 65535u ? nf : 65535u), dim3(256), 0, st, c->d_cc_ops + nm, nf,
+                               layout, d_pcm);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return DVDA_HIP_OK;
+}
+
 struct StepDesc {           // what the host writes in front of the packet's bytes: a one-segment index made by hand
     SegRec seg;
     StreamRec streams;

@@ -58,7 +58,21 @@ EXPORTS = ("dvda_mlp_hip_create", "dvda_mlp_hip_destroy", "dvda_mlp_hip_index", 
            "dvda_pcm_hip_workspace_words", "dvda_pcm_hip_decode_sectors", "dvda_pcm_hip_result",
            "dvda_mlp_hip_demux_sectors", "dvda_mlp_hip_pack_wav",
            "dvda_mlp_hip_shard", "dvda_mlp_hip_create_multi", "dvda_mlp_hip_destroy_multi",
-           "dvda_mlp_hip_multi_devices", "dvda_mlp_hip_decode_multi", "dvda_mlp_hip_multi_device_time")
+           "dvda_mlp_hip_multi_devices", "dvda_mlp_hip_decode_multi", "dvda_mlp_hip_multi_device_time",
+           "dvda_mlp_hip_set_conceal", "dvda_mlp_hip_conceal_spans")
+
+ST_CONCEALED = 1 << 30          # DVDA_ST_CONCEALED: conceal mode, the stream was damaged (not in ST_BENIGN)
+CONCEAL_LEADING, CONCEAL_TRAILING, CONCEAL_ROUNDS = 1, 2, 4     # DVDA_CONCEAL_* span flags
+
+
+class ConcealSpan(ctypes.Structure):
+    """dvda_mlp_conceal_span of include/dvda_mlp_hip.h"""
+    _fields_ = [("first_frame", ctypes.c_uint64), ("frames", ctypes.c_uint64), ("byte_off", ctypes.c_uint64),
+                ("byte_end", ctypes.c_uint64), ("cause", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+    def as_tuple(self):
+        return (int(self.first_frame), int(self.frames), int(self.byte_off), int(self.byte_end), int(self.cause),
+                int(self.flags))
 
 
 def lib():
@@ -119,6 +133,10 @@ def lib():
         L.dvda_mlp_hip_multi_device_time.argtypes = [vp, u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)]
         L.dvda_mlp_hip_decode_multi.argtypes = [vp, vp, vp, u32, u32, vp, vp, ctypes.POINTER(StreamInfo),
                                                 ctypes.POINTER(MultiSummary)]
+        L.dvda_mlp_hip_set_conceal.argtypes = [vp, ctypes.c_int]
+        L.dvda_mlp_hip_set_initial_fir.argtypes = [vp, vp]
+        L.dvda_mlp_hip_segment_fir.argtypes = [vp, u32, vp, vp]
+        L.dvda_mlp_hip_conceal_spans.argtypes = [vp, u32, ctypes.POINTER(ConcealSpan), u32, ctypes.POINTER(u32), vp]
         _lib = L
     return _lib
 
@@ -303,6 +321,78 @@ def decode_streams(streams, device=0, max_segments=None, lanes_per_segment=0, la
     finally:
         if own:
             ctx.close()
+
+
+def decode_streams_concealed(streams, device=0, max_segments=None, lanes_per_segment=0, layout=PCM_PLANAR, init_fir=None):
+    """decode_streams in conceal mode (dvda_mlp_hip_set_conceal): a damaged stream comes out as kept PCM ++ silence ++
+    PCM of a fresh decoder ++ ... instead of a non-benign status (include/dvda_mlp_hip.h states the rule).
+
+    -> (pcm, infos, spans).  pcm[i] as decode_streams gives it (int32 [channels, pcm_frames]) for PCM_PLANAR /
+    PCM_INTERLEAVED, the payload bytes (uint8) for PCM_WAV24 / PCM_WAV16; spans[i] = list of
+    (first_frame, frames, byte_off, byte_end, cause, flags), empty for a stream without damage.
+    init_fir: optional int32 [n_streams, 2, 48], the FIR history the streams start with (dvda_mlp_hip_set_initial_fir)."""
+    import torch
+    if not torch.cuda.is_available():
+        raise HipError("no GPU visible to torch: the MLP decode path is HIP-only")
+    dev = torch.device("cuda", device)
+    flat, offs, lens = pack_streams(streams)
+    total = int(len(flat) - 64)
+    if max_segments is None:
+        max_segments = max(64, total // 64)
+    nb = {PCM_WAV24: 3, PCM_WAV16: 2}.get(layout, 4)
+    ctx = Context(device, len(streams), max_segments, lanes_per_segment, layout)
+    try:
+        _check(lib().dvda_mlp_hip_set_conceal(ctx._h, 1), "dvda_mlp_hip_set_conceal")
+        d_fir = None
+        if init_fir is not None:
+            d_fir = torch.from_numpy(np.ascontiguousarray(init_fir, np.int32).reshape(len(streams), 2, 48)).to(dev)
+            _check(lib().dvda_mlp_hip_set_initial_fir(ctx._h, d_fir.data_ptr()), "dvda_mlp_hip_set_initial_fir")
+        d_bytes = torch.from_numpy(flat).to(dev)
+        d_off = torch.from_numpy(offs.astype(np.int64)).to(dev)
+        d_len = torch.from_numpy(lens.astype(np.int64)).to(dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        ctx.index(d_bytes.data_ptr(), total, d_off.data_ptr(), d_len.data_ptr(), len(streams), st)
+        infos = ctx.stream_info(stream=st)
+        rows = [int(inf.mlp_frames) * ROWS_PER_AU.get(int(inf.group0_rate), 0) for inf in infos]
+        nch = [int(inf.channels) for inf in infos]
+        for attempt in range(3):
+            out_off, pos = [], 0
+            for r, c in zip(rows, nch):
+                out_off.append(pos)
+                pos += r * c if nb == 4 else (r * c * nb + 3) // 4 + 4
+            d_pcm = torch.zeros(max(pos, 1), dtype=torch.int32, device=dev)
+            d_out_off = torch.tensor(out_off, dtype=torch.int64, device=dev)
+            d_stride = torch.tensor(rows, dtype=torch.int64, device=dev)
+            if attempt:
+                ctx.index(d_bytes.data_ptr(), total, d_off.data_ptr(), d_len.data_ptr(), len(streams), st)
+            ctx.decode(d_pcm.data_ptr(), d_out_off.data_ptr(), d_stride.data_ptr(), st)
+            infos = ctx.stream_info(stream=st)
+            if not any(inf.status & ST["OVERFLOW"] for inf in infos):
+                break
+            # silence and a fresh decoder's access units can need more than the index's count: the size needed
+            rows = [max(r, int(inf.pcm_frames)) for r, inf in zip(rows, infos)]
+        spans = []
+        for i in range(len(streams)):
+            n = ctypes.c_uint32()
+            _check(lib().dvda_mlp_hip_conceal_spans(ctx._h, i, None, 0, ctypes.byref(n), st), "conceal_spans")
+            arr = (ConcealSpan * max(int(n.value), 1))()
+            _check(lib().dvda_mlp_hip_conceal_spans(ctx._h, i, arr, int(n.value), ctypes.byref(n), st), "conceal_spans")
+            spans.append([arr[k].as_tuple() for k in range(int(n.value))])
+        host = d_pcm.cpu().numpy()
+        pcm = []
+        for i, inf in enumerate(infos):
+            r, c, f = rows[i], nch[i], min(int(inf.pcm_frames), rows[i])
+            if nb != 4:
+                pcm.append(host.view(np.uint8)[4 * out_off[i]:4 * out_off[i] + f * c * nb].copy())
+            elif not r * c:
+                pcm.append(np.zeros((c, 0), np.int32))
+            elif layout == PCM_INTERLEAVED:
+                pcm.append(np.ascontiguousarray(host[out_off[i]:out_off[i] + r * c].reshape(r, c).T[:, :f]))
+            else:
+                pcm.append(np.ascontiguousarray(host[out_off[i]:out_off[i] + r * c].reshape(c, r)[:, :f]))
+        return pcm, list(infos), spans
+    finally:
+        ctx.close()
 
 
 def shard_c(sizes, parts):

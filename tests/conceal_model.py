@@ -1,0 +1,230 @@
+"""The conceal-mode rule (include/dvda_mlp_hip.h, dvda_mlp_hip_set_conceal) restated on the host with the CPU oracle:
+what a damaged stream must come out as, composed from oracle calls on byte ranges of it --
+
+    oracle.decode(D[a0:b0]) ++ zeros(G1) ++ oracle.decode(D[a1:b1]) ++ ...
+
+Kept ranges: a fresh decoder starts at the first major sync (of the stream's parameters) whose every substream opens
+with a restart header and whose access unit verifies; the range ends in front of the first damaged access unit the
+oracle stops at -- that unit itself when its framing / parity / CRC-8 fails, else the major sync that starts its
+segment (the whole segment is damaged).  Silence between two ranges: the input-timing gap, wrapped by 65536 frames
+to the stream's mean bytes per frame.
+"""
+import math
+
+import numpy as np
+
+ORA_DAMAGE = 0x1FD          # oracle status bits that mark damage (all but SYNC_CHANGE and ENVELOPE: a fresh decoder at a
+                            # major sync that continues the FIR history is outside the reference's envelope, not damaged)
+LEADING, TRAILING = 1, 2    # DVDA_CONCEAL_* span flags
+SYNC_PARAMS = 0x00FFFFFF
+
+
+def u8(D, p):
+    return int(D[p])
+
+
+def au_size(D, p):
+    return 2 * (((u8(D, p) & 0xF) << 8) | u8(D, p + 1))
+
+
+def au_timing(D, p):
+    return (u8(D, p + 2) << 8) | u8(D, p + 3)
+
+
+def is_sync(D, p, lim=None):
+    lim = len(D) if lim is None else lim
+    if p + 32 > lim or au_size(D, p) < 32:
+        return False
+    return bytes(D[p + 4:p + 8]) == b"\xF8\x72\x6F\xBB" and (u8(D, p + 20) >> 4) in (1, 2)
+
+
+def packed_sync(D, p):
+    """SegRec.sync layout of csrc/mlp_index.h"""
+    return ((u8(D, p + 8) >> 4) | ((u8(D, p + 8) & 0xF) << 4) | ((u8(D, p + 9) >> 4) << 8) |
+            ((u8(D, p + 9) & 0xF) << 12) | ((u8(D, p + 11) & 0x1F) << 16) | ((u8(D, p + 20) >> 4) << 24))
+
+
+def unit_check(D, p, S, lim=None):
+    """0 when the access unit at p is framed and its substreams verify (reference src/mlp.c:656-712), else a bit"""
+    lim = len(D) if lim is None else lim
+    if p + 4 > lim:
+        return 1 << 4
+    size = au_size(D, p)
+    if size < 4 or p + size > lim:
+        return 1 << 4
+    fe = p + size
+    q = p + 32 if is_sync(D, p, fe) else p + 4
+    ends, check = [], 0
+    for s in range(S):
+        if q + 2 > fe:
+            return 1 << 4
+        w = (u8(D, q) << 8) | u8(D, q + 1)
+        if s == 0:
+            check = (w >> 13) & 1
+        ends.append((w & 0xFFF) * 2)
+        q += 4 if w & 0x8000 else 2
+    if q > fe:
+        return 1 << 4
+    prev = 0
+    for e in ends:
+        if e < prev or q + e > fe or (check and e - prev < 2):
+            return 1 << 4
+        if check:
+            parity, crc, fin = 0, 0x3C, 0
+            for k in range(q + prev, q + e - 2):
+                v = u8(D, k)
+                parity ^= v
+                fin = crc ^ v
+                crc = fin
+                for _ in range(8):
+                    crc = ((crc << 1) ^ 0x63) & 0xFF if crc & 0x80 else (crc << 1) & 0xFF
+            if (u8(D, q + e - 2) ^ parity) != 0xA9:
+                return 1 << 2
+            if fin != u8(D, q + e - 1):
+                return 1 << 3
+        prev = e
+    return 0
+
+
+def can_resume(D, p, want):
+    """a fresh decoder may start at p: major sync of the stream's parameters, every substream opens with a restart
+    header (decode_block src/mlp.c:748-753), the unit verifies"""
+    if not is_sync(D, p) or (packed_sync(D, p) ^ want) & SYNC_PARAMS:
+        return False
+    S = u8(D, p + 20) >> 4
+    fe = p + au_size(D, p)
+    if fe > len(D):
+        return False
+    q, end0 = p + 32, 0
+    for s in range(S):
+        if q + 2 > fe:
+            return False
+        w = (u8(D, q) << 8) | u8(D, q + 1)
+        if s == 0:
+            end0 = (w & 0xFFF) * 2
+        q += 4 if w & 0x8000 else 2
+    if q >= fe or (u8(D, q) & 0xC0) != 0xC0:
+        return False
+    if S == 2 and (q + end0 >= fe or (u8(D, q + end0) & 0xC0) != 0xC0):
+        return False
+    return unit_check(D, p, S) == 0
+
+
+def sync_offsets(D):
+    """every even offset that holds a major-sync access unit (what the index's pattern scan finds)"""
+    b = np.asarray(D, np.uint8)
+    hits = np.nonzero((b[4:-3] == 0xF8) & (b[5:-2] == 0x72) & (b[6:-1] == 0x6F) & (b[7:] == 0xBB))[0] if len(b) > 8 else []
+    return [int(p) for p in hits if p % 2 == 0 and is_sync(D, int(p))]
+
+
+def chain(D, a):
+    """offsets of the access units the size chain from a frames (the walk stops where a unit cannot be framed)"""
+    out, p = [], a
+    while p + 4 <= len(D):
+        size = au_size(D, p)
+        if size < 4 or p + size > len(D):
+            break
+        out.append(p)
+        p += size
+    return out, p
+
+
+def kept_ranges(D, nch, rows_per_au, oracle, cap=None):
+    """-> list of (a, b, frames, t_first, t_end): the kept byte ranges of D under the rule"""
+    D = np.asarray(D, np.uint8)
+    cap = cap or (len(D) + 4096) * 2
+    syncs = sync_offsets(D)
+    if not syncs:
+        return []
+    want = packed_sync(D, syncs[0])
+    out, bound = [], 0
+    while True:
+        r = next((p for p in syncs if p >= bound and can_resume(D, p, want)), None)
+        if r is None:
+            return out
+        offs, chain_end = chain(D, r)
+        S = u8(D, r + 20) >> 4
+
+        def bad(e):
+            return oracle.decode(D[r:e], nch, cap)[2] & ORA_DAMAGE
+
+        unframed = chain_end + 4 <= len(D) and au_size(D, chain_end) < 4     # not a cut tail: a broken header
+        if not unframed and not bad(chain_end):
+            # (the oracle verifies every unit's check data: nothing to look for unit by unit)
+            u_c = None
+        else:
+            # the first unit whose own framing / check data fails
+            u_c = next((k for k, o in enumerate(offs) if unit_check(D, o, S)), None)
+        if u_c is None and unframed:
+            u_c = len(offs)
+            offs = offs + [chain_end]
+        ends = offs[1:u_c + 1] if u_c is not None else offs[1:] + [chain_end]
+        # the first unit the oracle's decode fails on in front of it (the oracle drops a failing unit and goes on:
+        # the shortest failing prefix says which one)
+        u_d = None
+        if ends and bad(ends[-1]):
+            lo, hi = 0, len(ends) - 1
+            while lo < hi:
+                mid = (lo + hi) // 2
+                if bad(ends[mid]):
+                    hi = mid
+                else:
+                    lo = mid + 1
+            u_d = lo
+        if u_d is not None and (u_c is None or u_d < u_c):
+            # nothing the unit says: its segment (from the major sync in front of it) is damaged whole
+            kept_end = max(o for o in offs[:u_d + 1] if is_sync(D, o))
+        elif u_c is not None:
+            kept_end = offs[u_c]                    # the unit itself is damaged
+        else:
+            kept_end = len(D)
+        if kept_end > r:
+            # behind the range's last unit: its first unit's input timing + the PCM frames the range decodes to
+            _, frames, _ = oracle.decode(D[r:kept_end], nch, cap)
+            out.append((r, kept_end, frames, au_timing(D, r), (au_timing(D, r) + frames) & 0xFFFF))
+        if kept_end >= len(D):
+            return out
+        bound = kept_end + 2
+
+
+def gap_frames(B, g, m):
+    """g + 65536 w, w >= 0 bringing B bytes per frame closest to m (no mean: g)"""
+    if not m > 0:
+        return g
+    w0 = max(math.floor((B / m - g) / 65536.0), 0)
+    best = None
+    for k in (0, 1):
+        G = g + 65536 * (w0 + k)
+        d = abs(B / G - m) if G else math.inf
+        if best is None or d < best[1]:
+            best = (G, d)
+    return best[0]
+
+
+def conceal(D, nch, rows_per_au, oracle, cap=None):
+    """-> (pcm int32 [nch, frames], spans [(first_frame, frames, byte_off, byte_end, flags)]) under the rule"""
+    D = np.asarray(D, np.uint8)
+    cap = cap or (len(D) + 4096) * 2
+    R = kept_ranges(D, nch, rows_per_au, oracle, cap)
+    if not R:
+        return np.zeros((nch, 0), np.int32), [(0, 0, 0, len(D), LEADING | TRAILING)]
+    K = sum(b - a for a, b, _, _, _ in R)
+    F = sum(f for _, _, f, _, _ in R)
+    m = K / F if K and F else 0.0
+    parts, spans, pos = [], [], 0
+    for k, (a, b, f, t_first, _) in enumerate(R):
+        if k == 0:
+            if a > 0:
+                spans.append((0, 0, 0, a, LEADING))
+        else:
+            pb, pt_end = R[k - 1][1], R[k - 1][4]
+            G = gap_frames(a - pb, (t_first - pt_end) & 0xFFFF, m)
+            spans.append((pos, G, pb, a, 0))
+            parts.append(np.zeros((nch, G), np.int32))
+            pos += G
+        pcm, _, _ = oracle.decode(D[a:b], nch, cap)
+        parts.append(pcm)
+        pos += f
+    if R[-1][1] < len(D):
+        spans.append((pos, 0, R[-1][1], len(D), TRAILING))
+    return np.concatenate(parts, axis=1), spans
