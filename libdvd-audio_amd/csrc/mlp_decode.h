@@ -486,22 +486,27 @@ struct BitReaderT {
     // small ring: everything there is room for at once -- after a seek that is the whole ring, one memory round trip
     // instead of one per granule.  Issue and commit apart, so that a lane with two rings has both rings' loads in
     // flight together.  -> granules asked for (0: no room)
-    __device__ __forceinline__ int32_t fill_issue(uint4 (&q)[4]) const
+    // (MAXG: at most so many granules a call, as many registers as that takes: the row phase's top-up has few to spare)
+    template <int MAXG = 4>
+    __device__ __forceinline__ int32_t fill_issue(uint4 (&q)[MAXG]) const
     {
         static_assert(G == CHUNK_DWORDS || (G == 4 && RD == 16), "the small ring is 16 dwords filled by 16-byte granules");
-        const int32_t n = room() ? (RD - ahead()) >> 2 : 0;     // 0 .. 4 granules
+        int32_t n = room() ? (RD - ahead()) >> 2 : 0;           // 0 .. 4 granules
+        if (MAXG < 4 && n > MAXG)
+            n = MAXG;
 #pragma unroll
-        for (int g = 0; g < 4; g++)
+        for (int g = 0; g < MAXG; g++)
             if (g < n) {
                 const uint32_t f = fillpos + 4u * g, last = max_chunk + (uint32_t)(CHUNK_DWORDS - G);
                 q[g] = gsrc[(f < last ? f : last) >> 2];
             }
         return n;
     }
-    __device__ __forceinline__ void fill_commit(const uint4 (&q)[4], int32_t n)
+    template <int MAXG = 4>
+    __device__ __forceinline__ void fill_commit(const uint4 (&q)[MAXG], int32_t n)
     {
 #pragma unroll
-        for (int g = 0; g < 4; g++)
+        for (int g = 0; g < MAXG; g++)
             if (g < n) {
                 ring_store4<RD>(slot(fillpos), q[g], (fillpos & (RD - 1)) == 0);
                 filled();
@@ -596,37 +601,72 @@ using BitReader = BitReaderT<RING_DWORDS, CHUNK_DWORDS>;
 // the one 32-dword ring is 8.25)
 constexpr int DUO_RING = 16, DUO_GRAN = 4;
 
-// Arithmetic, branch-free decode of the three code books (mlp_tables.h: huff_entry) from a 9-bit
-// peek t: returns value | length << 8, value 0xFF for the two invalid codes of a book, and 0 (no
-// bits, value 0) for "book" 0 = no code.  Checked exhaustively against the table by
-// dvda_mlp_hip_selftest_huff (tests/test_gpu_parity.py).
-// m_esc: wave mask of "t & 0x100" (escape form), compared by the caller well ahead of here so that the
-// select at the end needs no wait-state padding (tools/hazard_check.py); bmask: all ones when there is
-// a code book (cb != 0), else 0 -- the caller keeps that as bit 31 of the packed slot parameters
-__device__ __forceinline__ uint32_t huff_decode_m(uint32_t cb, uint32_t t, uint64_t m_esc, uint32_t bmask)
+// ---- the row loop's packed slot parameters ("hot word"), laid out for the instructions that read them.
+// profiles/r05_valu_issue_rates.txt: at this kernel's two waves per SIMD v_lshrrev_b32 / v_ashrrev_i32 / v_and_b32 /
+// v_add_u32 / v_bitop3_b32 issue at twice the rate of v_bfe_u32, v_lshlrev_b32, every v_cmp and v_cndmask_b32_e64.  A
+// field that is only ever a shift count therefore sits where the hardware's own masking of the count (low 5 bits of a
+// 32-bit shift, low 6 of a 64-bit one) cuts it out of `hw >> position`, and what the row loop used to derive from the
+// code book per symbol is stored at block-header time:
+//   [4:0]   lsb_bits                    count of `msb << hw`, `~hw` = 31 - lsb_bits, `hw & 31` for the position
+//   [9:5]   quant step size (<= 15: bit 9 is 0)                      count of `x << (hw >> 5)`
+//   [15:10] filter shift + quant step size (<= 30: bit 15 is 0)      count of the 64-bit `acc >> (hw >> 10)`
+//   [18:16] [25:24]  A = (4 - cb) << 8 | (7 - (8 >> cb))             `(hw >> 16) & 0x307`: escape code = (top >> E) + A
+//   [23:20] B = base - 2 (9, 7, 6 for books 1, 2, 3); with bit 28    `(hw >> 20) & 0x10F` = B + 0x100
+//   [30:26] E = 28 + cb (its low two bits are the code book)         count of `top >> (hw >> 26)`
+//   [31]    the slot has a code book
+// [31:16] are zero without a code book.  The fields only the header parser reads (filter orders and shifts) are the
+// cold word's (COLD_*), kept in LDS: it is read and written at block headers only.
+__host__ __device__ constexpr uint32_t hot_word(uint32_t cb, uint32_t lb, uint32_t q, uint32_t shift)
 {
-    // "1" + (3 - cb) bits -> 7 + bits, length 4 - cb: the bits are the top of the low byte
-    const uint32_t a = (((t & 0xFFu) >> (5u + cb)) + 7u) | ((4u - cb) << 8);
-    // "0"^z "1" (z = 2..8) -> 8 - z ; "01" "0"^k "1" -> base + k : both are z' = leading zeros of
-    // the low 7 bits, length z' + 3
-    // (the low 7 bits moved to the top of a word with a sentinel 1 behind them: clz is 0..7 at once)
-    const uint32_t z = (uint32_t)__clz((int)((t << 25) | 0x01000000u));   // 7 if the low 7 bits are 0
-    const uint32_t base = __builtin_amdgcn_ubfe(0x08090B08u, 8u * cb, 8u); // 11, 9, 8 for books 1, 2, 3
-    // both arms computed, one select: left to itself the compiler branches around them per lane
-    uint32_t up = base + z, dn = 6u - z;
-    asm volatile("" : "+v"(up), "+v"(dn));
-    uint32_t val = (t & 0x80u) ? up : dn;
-    val = z > 6u ? 0xFFu : val;
-    uint32_t e = val | (((z > 6u ? 6u : z) + 3u) << 8);
-    asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(e) : "v"(a), "s"(m_esc));
-    return e & bmask;
+    return lb | (q << 5) | ((shift + q) << 10) |
+           (cb ? ((7u - (8u >> cb)) << 16) | ((cb == 1 ? 9u : cb == 2 ? 7u : 6u) << 20) | ((4u - cb) << 24) |
+                 ((28u + cb) << 26) | (1u << 31)
+               : 0u);
+}
+__device__ __forceinline__ uint32_t hot_cb(uint32_t hw) { return (hw >> 26) & 3u; }
+__device__ __forceinline__ uint32_t hot_lb(uint32_t hw) { return hw & 31u; }
+__device__ __forceinline__ uint32_t hot_q(uint32_t hw) { return (hw >> 5) & 15u; }
+__host__ __device__ constexpr uint32_t cold_word(uint32_t iir_order, uint32_t fir_order, uint32_t fir_shift, uint32_t iir_shift)
+{
+    return iir_order | (fir_order << 4) | (fir_shift << 8) | (iir_shift << 12);
 }
 
+// Arithmetic, branch-free decode of the three code books (mlp_tables.h: huff_entry) from the 32 bits at the reading
+// position (the code is the top 9 of them) and the slot's hot word: returns value | length << 8, value 0xFF for the
+// two invalid codes of a book, and 0 (no bits, value 0) for "book" 0 = no code.  Checked exhaustively against the
+// table by dvda_mlp_hip_selftest_huff (tests/test_gpu_parity.py).  Written against the two issue classes: no left
+// shift but the one that packs the length, no v_bfe, the escape form chosen by the sign of `top` (one v_ashrrev, one
+// v_bitop3) instead of a wave mask and a select on it.
+__device__ __forceinline__ uint32_t huff_decode_top(uint32_t top, uint32_t hw)
+{
+    // "1" + (3 - cb) bits -> 7 + bits, length 4 - cb: top >> E is the leading 1 and the bits, A takes the 1 out again
+    const uint32_t a = (top >> ((hw >> 26) & 31u)) + ((hw >> 16) & 0x307u);
+    // "0"^z "1" (z = 2..8) -> 8 - z ; "01" "0"^k "1" -> base + k : both are z' = leading zeros of the seven bits
+    // behind the first two, length z' + 3.  Those seven bits with a sentinel 1 behind them, the two in front cleared
+    // (the first is 0 here): n = z' + 2 = 2..9 at once, 9 for the two invalid codes
+    const uint32_t n = (uint32_t)__clz((int)((top & 0x3F800000u) | 0x00400000u));
+    // both arms (each with the 0x100 that makes the length n + 1) and a bitwise select between them; the masks are
+    // made by arithmetic and fenced: told that they are all ones or all zeros the compiler turns each back into
+    // v_cmp + wait states + v_cndmask, or branches around the arms per lane.
+    // The second form ("01...") when bit 30 is set AND one of the seven bits is: for the two invalid codes the first
+    // form's arm is 0x108 - 9 = 0xFF with length 9 by itself -- the table's entry for them, no compare of its own
+    const uint32_t up = ((hw >> 20) & 0x10Fu) + n, dn = 0x108u - n;
+    uint32_t d = 0x40000000u - (top & 0x7F800000u);
+    asm("" : "+v"(d));
+    uint32_t ms = (uint32_t)((int32_t)d >> 31);
+    asm("" : "+v"(ms));
+    uint32_t val = (up & ms) | (dn & ~ms);
+    asm("" : "+v"(val));
+    const uint32_t e = (n << 8) + val;
+    uint32_t m = (uint32_t)((int32_t)top >> 31);                 // the escape form: the code's first bit
+    asm("" : "+v"(m));
+    return ((a & m) | (e & ~m)) & (uint32_t)((int32_t)hw >> 31);
+}
+
+// the same from a 9-bit peek and the code book's number (the cooperative kernel, the self-test)
 __device__ __forceinline__ uint32_t huff_decode(uint32_t cb, uint32_t t)
 {
-    uint64_t m_esc = __builtin_amdgcn_ballot_w64((t & 0x100u) != 0);
-    asm volatile("" : "+s"(m_esc));
-    return huff_decode_m(cb, t, m_esc, cb ? 0xFFFFFFFFu : 0u);
+    return huff_decode_top(t << 23, hot_word(cb, 0u, 0u, 0u));
 }
 
 // DUO lanes: what the header parser and the block bookkeeping keep per substream, for the substream that is not the
@@ -691,6 +731,9 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
     constexpr bool XCH = PAIRED;
     __shared__ int32_t s_xch[XCH ? WAVES : 1][MAXCH][XCH ? 64 : 1];
     __shared__ uint32_t s_nchained[WAVES];          // fast pass: lanes of the wave that stopped on ST_CHAINED
+    // per lane and slot, what only the header parser reads of a slot's parameters (cold_word(): filter orders and
+    // shifts).  A lane reads and writes its own column only, at block headers: 1.5 KB that leave pk[] to the row loop
+    __shared__ uint16_t s_cold[WAVES][NS][64];
 
     if (threadIdx.x < WAVES)
         s_nchained[threadIdx.x] = 0;
@@ -929,8 +972,7 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
     constexpr bool CFU = !PARSE && !GENERAL && !DUO;                  // (nor has the two-substream lane: its parked substream takes them)     // (the sequential pass has no registers to spare)
     constexpr int CFW = CFU ? 8 : 4;
     int32_t cf[NS][CFW];
-    uint32_t pk[NS];                  // codebook | lsb_bits<<2 | qss<<7 | shift<<11 | iir_order<<15 |
-                                      // fir_order<<19 | fir_shift<<23 | iir_shift<<27 | (codebook != 0)<<31
+    uint32_t pk[NS];                  // the row loop's packed parameters: hot_word()
     int32_t sho[NS];                  // signed huffman offset (src/mlp.c:1152-1176)
     uint32_t mreg[2][4];              // channel coefficients of matrices 0 and 1 (int16 pairs), zero
                                       // beyond max_matrix_channel
@@ -955,7 +997,8 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
 #pragma unroll
         for (int j = 0; j < CFW; j++)
             cf[k][j] = 0;
-        pk[k] = 24u << 2;                         // codebook 0, 24 LSBs
+        pk[k] = hot_word(0u, 24u, 0u, 0u);        // codebook 0, 24 LSBs
+        s_cold[wv][k][lane] = (uint16_t)cold_word(0u, 0u, 0u, 0u);
         sho[k] = -(1 << 23);
     }
 #pragma unroll
@@ -1535,10 +1578,12 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                                                                 ((uint32_t)cf[kk][CFU ? 2 * j + 1 : 0] << 16));
                                     }
                                 }
-                            uint32_t codebook = pk_old & 3u;
-                            const uint32_t lb_old = (pk_old >> 2) & 31u, q_old = (pk_old >> 7) & 15u;
-                            uint32_t iir_order = (pk_old >> 15) & 0xFu, fir_order = (pk_old >> 19) & 0xFu;
-                            uint32_t fir_shift = (pk_old >> 23) & 0xFu, iir_shift = (pk_old >> 27) & 0xFu;
+                            uint32_t codebook = hot_cb(pk_old);
+                            const uint32_t lb_old = hot_lb(pk_old), q_old = hot_q(pk_old);
+                            uint16_t *const cold = &s_cold[wv][kr < (uint32_t)NS ? kr : 0u][lane];
+                            const uint32_t cold_old = kr < (uint32_t)NS ? *cold : 0u;
+                            uint32_t iir_order = cold_old & 0xFu, fir_order = (cold_old >> 4) & 0xFu;
+                            uint32_t fir_shift = (cold_old >> 8) & 0xFu, iir_shift = (cold_old >> 12) & 0xFu;
                             uint32_t lsbs = lb_old + q_old;
                             int32_t hoff = sho_old + huff_center(codebook, lb_old);
                             bool touched = qss_changed;
@@ -1671,10 +1716,9 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                                     if (fir_order && frames_done == 0 && blocks_in_frame == 0)
                                         status |= ST_CHAINED;      // needs the previous segment's history
                                     const int32_t nsho = hoff - huff_center(codebook, lb);
-                                    const uint32_t npk = codebook | (lb << 2) | (q << 7) | (shift << 11) |
-                                                         (iir_order << 15) | (fir_order << 19) |
-                                                         (fir_shift << 23) | (iir_shift << 27) |
-                                                         (codebook ? 1u << 31 : 0u);
+                                    const uint32_t npk = hot_word(codebook, lb, q, shift);
+                                    if (kr < (uint32_t)NS)
+                                        *cold = (uint16_t)cold_word(iir_order, fir_order, fir_shift, iir_shift);
 #pragma unroll
                                     for (int kk = 0; kk < NS; kk++)
                                         if ((uint32_t)kk == kr) {
@@ -1833,15 +1877,19 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
         // so that it lands in the ring while this row is being decoded.
         // (DUO: a substream of a two-substream stream has at most five channels: 5 x 33 + 6 bits behind an offset of at
         //  most 31 are seven dwords and one more for the last window -- eight resident in each of the two rings; both
-        //  rings' top-ups in flight together)
+        //  rings topped up granule by granule: this is the cold path, the row's own request is below)
         if (active) {
             if constexpr (DUO) {
                 while (__builtin_expect(__any(rd.ahead() < 8 || rx.ahead() < 8), 0)) {
                     DVDA_COV(14);
-                    uint4 q0[4], q1[4];
-                    const int32_t n0 = rx.fill_issue(q0), n1 = rd.fill_issue(q1);
-                    rx.fill_commit(q0, n0);
-                    rd.fill_commit(q1, n1);
+                    // one granule at a time, ring after ring: four registers.  Everything a lane keeps is live here, and
+                    // with both rings' granules in flight together (up to eight, 32 registers) the allocator parked them
+                    // in scratch inside the row loop -- a store behind every load, a wait for each (tests/test_isa_budget.py)
+                    uint4 q[1];
+                    const int32_t n0 = rx.template fill_issue<1>(q);
+                    rx.template fill_commit<1>(q, n0);
+                    const int32_t n1 = rd.template fill_issue<1>(q);
+                    rd.template fill_commit<1>(q, n1);
                 }
             } else {
             if (rd.ahead() < 12)
@@ -1924,8 +1972,10 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
             // 0's until the slot where the lane's substream 1 begins (its channel count is the lane's own: the switch is
             // a masked block at every slot where some lane of the wave has it)
             uint32_t cpos = DUO ? rx.pos : rd.pos;
-            uint32_t cbase = (uint32_t)(uintptr_t)(DUO ? rx.ring : rd.ring);
-            auto cur_window_lds = [&]() -> uint32_t { return cbase + ((~(cpos >> 5) & (uint32_t)(RD - 1)) << 8); };
+            uint32_t cbase = (uint32_t)(uintptr_t)(DUO ? rx.ring : rd.ring) + (uint32_t)((RD - 1) << 8);
+            // plane (RD - 1) - (dword index & (RD - 1)), 256 bytes a plane: counted down from the last plane's address
+            // (shift, mask, subtract where complementing the index first takes four instructions)
+            auto cur_window_lds = [&]() -> uint32_t { return cbase - ((cpos << 3) & (uint32_t)((RD - 1) << 8)); };
             // the row's first window (read here and waited for; a window carried over from the row before was measured
             // and dropped: three more registers through the whole loop cost more than the one LDS round trip they hide)
             uint64_t win = DUO ? rx.window() : rd.window();
@@ -1948,7 +1998,7 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                             if (sw) {
                                 rx.pos = cpos;                  // substream 0's row is read
                                 cpos = rd.pos;
-                                cbase = (uint32_t)(uintptr_t)rd.ring;
+                                cbase = (uint32_t)(uintptr_t)rd.ring + (uint32_t)((RD - 1) << 8);
                                 win = rd.window();
                             }
                         }
@@ -1958,17 +2008,15 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                 if (k >= 2 && !__any(in))
                     continue;
                 if (in) {
-                const uint32_t pkk = pk[k];
-                const uint32_t cb = pkk & 3u, lb = (pkk >> 2) & 31u, q = (pkk >> 7) & 15u,
-                               shift = (pkk >> 11) & 15u;
-                const uint32_t bmask = (uint32_t)((int32_t)pkk >> 31);     // bit 31: the slot has a code book
+                // the slot's hot word (hot_word() above): every field is cut out by one v_lshrrev / v_and / v_not, or by
+                // the masking of a shift count alone
+                const uint32_t hw = pk[k];
+                const uint32_t lb = hw & 31u;
                 // the symbol is cut from the 64 bits at the reading position (a code of at most 9 bits and at most 24
                 // LSBs behind an offset of at most 31)
                 const uint32_t ofs = cpos & 31u;
                 const uint32_t top = (uint32_t)((win << ofs) >> 32);
-                uint64_t m_esc = __builtin_amdgcn_ballot_w64((int32_t)top < 0);      // bit 8 of the 9-bit peek
-                asm volatile("" : "+s"(m_esc));
-                const uint32_t e = huff_decode_m(cb, top >> 23, m_esc, bmask);
+                const uint32_t e = huff_decode_top(top, hw);
                 const uint32_t msb = e & 0xFFu;
                 const uint32_t len = e >> 8;
                 msb_or |= msb;                            // valid values are < 0x20
@@ -1986,17 +2034,22 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                 //  compiler placed, rightly by all it can know, in front of the wait: of registers whose data had not
                 //  arrived.  tests/test_gpu_parity.py::test_fuzz_fast_features found it.)
                 const uint32_t top2 = (uint32_t)((win << o2) >> 32);
-                const uint32_t lsbv = (top2 >> 1) >> (31u - lb);          // lb == 0 -> 0
+                const uint32_t lsbv = (top2 >> 1) >> (~hw & 31u);         // 31 - lb; lb == 0 -> 0
                 if (k + 1 < NS)
                     // (the slot's newest history pair rides through the asm: the filter below starts from it, so the
                     //  scheduler cannot put the multiply-adds in front of the read)
                     asm volatile("ds_read2st64_b32 %0, %2 offset1:1" : "+v"(win), "+v"(sp[k][0]) : "v"(cur_window_lds()));
-                const int32_t residual = (int32_t)(((msb << lb) + lsbv + (uint32_t)sho[k]) << q);
+                // the residual is resq << q
+                // (fenced between the two sums: v_lshl_add_u32 and a plain add, where the compiler's own pick is a
+                //  v_lshlrev_b32 and a v_add3_u32 -- both of the slow class)
+                uint32_t ml = (msb << (hw & 31u)) + lsbv;
+                asm("" : "+v"(ml));
+                const uint32_t resq = ml + (uint32_t)sho[k];
+                const uint32_t q5 = (hw >> 5) & 31u;
                 int32_t value;
                 if constexpr (PARSE) {
                     // chain parse pass: the residual itself is the product (the filter pass runs the recurrence)
-                    value = residual;
-                    (void)shift;
+                    value = (int32_t)(resq << q5);
                     (void)wave_iir;
                 } else {
                 // ---- FIR/IIR reconstruction (src/mlp.c:1278-1300)
@@ -2023,8 +2076,10 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                     if (iir_on)
                         acc += iir_mac(a.iir_ws + (size_t)(k * 16) * a.total_lanes + gl, a.total_lanes);
                 }
-                const int32_t ssum = (int32_t)(acc >> shift);
-                value = mask_q((int32_t)((uint32_t)ssum + (uint32_t)residual), q);
+                // mask_q((acc >> shift) + (resq << q), q) == (((acc >> shift) >> q) + resq) << q: the residual's low q bits
+                // are zero, the sum's are shifted out and in again as zeros -- one 64-bit shift by the stored shift + q and
+                // one add-and-shift, no mask to build
+                value = (int32_t)(((uint32_t)(acc >> ((hw >> 10) & 63u)) + resq) << q5);
                 // the history moves up by one value: pair j takes the odd half of pair j - 1 and its own even half
                 // (v_pk_mov_b32: low result = the half of source 0 that op_sel[0] names, high result = the half of
                 //  source 1 that op_sel[1] names), pair 0 the new value and its own even half -- every pair in place.
@@ -2033,16 +2088,22 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                 //  every slot's whole history back to where the loop keeps it, sixty moves per PCM frame.  The lanes that
                 //  do not carry the slot are masked out of the same four instructions instead.)
                 {
-                    const uint64_t vpair = (uint64_t)(uint32_t)value;
+                    // (only the low half of the last move's second operand is read: its high half is left undefined
+                    //  on purpose -- some register, no instruction -- where a 64-bit zero extension cost a v_mov per slot)
+                    uint32_t vhi;
+                    asm("" : "=v"(vhi));
+                    const uint64_t vpair = (uint64_t)(uint32_t)value | ((uint64_t)vhi << 32);
                     asm("v_pk_mov_b32 %0, %1, %0 op_sel:[1,0]" : "+v"(sp[k][3]) : "v"(sp[k][2]));
                     asm("v_pk_mov_b32 %0, %1, %0 op_sel:[1,0]" : "+v"(sp[k][2]) : "v"(sp[k][1]));
                     asm("v_pk_mov_b32 %0, %1, %0 op_sel:[1,0]" : "+v"(sp[k][1]) : "v"(sp[k][0]));
                     asm("v_pk_mov_b32 %0, %1, %0 op_sel:[0,0]" : "+v"(sp[k][0]) : "v"(vpair));
                 }
                 if (__builtin_expect(wave_iir, 0)) {
-                    if (iir_on)
+                    if (iir_on) {
+                        const int32_t ssum = (int32_t)(acc >> (((hw >> 10) & 63u) - hot_q(hw)));
                         iir_push(a.iir_ws + (size_t)(k * 16) * a.total_lanes + gl, a.total_lanes,
                                  (int32_t)((uint32_t)value - (uint32_t)ssum));
+                    }
                 }
                 }
                 val[k] = value;

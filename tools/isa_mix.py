@@ -1,0 +1,301 @@
+#!/usr/bin/env python3
+"""tools/isa_mix.py [file.s] -- instruction mix of the k_decode row loops, priced by issue class.
+
+At two waves per SIMD (what k_decode runs at) the VALU instructions of gfx950 fall into two issue classes,
+measured by tools/valu_rate.hip and recorded in profiles/r05_valu_issue_rates.txt: about 0.9 ns and about
+1.8 ns per instruction and wave.  This script compiles csrc/mlp_hip.hip to assembly the way
+tools/hazard_check.py does (or reads the given .s), finds every k_decode instance's row loop -- the innermost
+loop that holds the filter's v_mad_i64_i32 chain, or, for the instance that parses only, the code-book
+decode's v_ffbh_u32 -- and prints per instance and per region of the loop the instruction histogram, the
+split into the two classes and the class-weighted cycles.
+
+The class table is read from the rates file (its 2-waves-per-SIMD section), not typed in: an opcode's class
+is its measured time against the threshold halfway between the two clusters, a class's price is its cluster's
+mean.  An opcode the file does not list is reported as "unclassified" and priced as slow.
+
+Regions, by what a basic block of the loop contains (static counts, cold branches included):
+    slot k         the block with the k-th code-book decode (v_ffbh_u32): symbol, filter, history shift
+    slot masks     the small blocks between two slots: which lanes carry the next slot
+    chunk request  blocks that load from global memory
+    commit         blocks with the ring's byte swap (v_perm_b32)
+    flush          blocks that store to global memory
+    rematrix + staging   what is left behind the last slot (LDS writes of the staging tile among it)
+    other          the rest: row bookkeeping, the header parser and every cold branch inside the loop
+
+tests/test_isa_budget.py imports this module and holds every build to what profiles/isa_mix_after.txt records."""
+import collections
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RATES = os.path.join(ROOT, "profiles", "r05_valu_issue_rates.txt")
+HEADLINE = "k_decode<6,false,false,true,false,false,false>"
+
+
+def compile_asm(out=None):
+    out = out or tempfile.NamedTemporaryFile(suffix=".s", delete=False).name
+    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
+                    "-o", out, os.path.join(ROOT, "libdvd-audio_amd", "csrc", "mlp_hip.hip")], check=True,
+                   stderr=subprocess.DEVNULL)
+    return out
+
+
+def compiler_version():
+    try:
+        out = subprocess.run(["/opt/rocm/bin/hipcc", "--version"], capture_output=True, text=True).stdout
+    except OSError:
+        return "unknown"
+    hip = re.search(r"HIP version:\s*(\S+)", out)
+    clang = re.search(r"clang version\s*(\S+)", out)
+    return "HIP %s, clang %s" % (hip.group(1) if hip else "?", clang.group(1) if clang else "?")
+
+
+class Rates:
+    """The two issue classes, from the 2-waves-per-SIMD section of the rates file."""
+
+    def __init__(self, path=RATES):
+        rows, section, self.clock_ghz = {}, False, 2.4
+        for line in open(path):
+            m = re.match(r"device .* clock (\d+) kHz", line)
+            if m:
+                self.clock_ghz = int(m.group(1)) / 1e6
+            if line.startswith("--"):
+                section = line.startswith("-- 2 wave")
+                continue
+            m = re.match(r"(.+?)\s+[\d.]+ ms\s+([\d.]+) ns/instr/wave", line)
+            if section and m:
+                rows[m.group(1).strip()] = float(m.group(2))
+        base = rows["v_add_u32 (independent)"]
+        self.ns = {}
+        for name, ns in rows.items():
+            # "A + N v_add (per instr)": A's own time is what the group takes less N adds
+            m = re.match(r"(\S+ vcc) \+ (\d) v_add \(per instr\)$", name)
+            if m and m.group(2) == "1":
+                self.ns[m.group(1)] = ns * 2 - base
+            elif re.match(r"[vs]_\w+( imm| vgpr| literal| \(vcc\)| \(sgpr pair\)| \((in)?dependent\))?$", name):
+                self.ns[name] = ns
+        self.ns.pop("v_cndmask_b32", None)       # back to back on one vcc: the pathological case, not the opcode's price
+        v = sorted(x for x in self.ns.values())
+        gap, k = max((v[i + 1] - v[i], i) for i in range(len(v) - 1))
+        self.threshold = (v[k] + v[k + 1]) / 2
+        fast = [x for x in v if x < self.threshold]
+        slow = [x for x in v if x >= self.threshold]
+        self.fast_cycles = sum(fast) / len(fast) * self.clock_ghz
+        self.slow_cycles = sum(slow) / len(slow) * self.clock_ghz
+
+    def key(self, op, operands):
+        base = re.sub(r"_(e32|e64)$", "", op)
+        if base.endswith("_sdwa") or base.endswith("_dpp"):
+            return "v_add_u32_sdwa" if base.endswith("_sdwa") else "v_mov_b32_dpp row_shr"
+        if base.startswith("v_cmp"):
+            return "v_cmp (vcc)" if operands.startswith("vcc") else "v_cmp (sgpr pair)"
+        if base == "v_cndmask_b32":
+            return "v_cndmask vcc" if op.endswith("_e32") else "v_cndmask (sgpr pair)"
+        args = [a.strip() for a in operands.split(",")]
+        if base in ("v_lshlrev_b32", "v_lshrrev_b32") and len(args) > 1:
+            return base + (" vgpr" if args[1].startswith("v") else " imm")
+        if base == "v_and_b32" and any(re.match(r"0x[0-9a-f]+$", a) for a in args):
+            return "v_and_b32 literal"
+        if base in ("v_add_u32", "v_pk_mov_b32"):
+            return base + " (independent)"
+        return base
+
+    def classify(self, op, operands):
+        """'fast', 'slow' or 'unclassified' (priced as slow)"""
+        ns = self.ns.get(self.key(op, operands))
+        if ns is None:
+            return "unclassified"
+        return "fast" if ns < self.threshold else "slow"
+
+    def cycles(self, cls):
+        return self.fast_cycles if cls == "fast" else self.slow_cycles
+
+
+def demangle_name(sym):
+    m = re.match(r"_ZN3mlp8k_decodeI((?:L[ib]\d+E)+)EEvNS_10DecodeArgsE$", sym)
+    if not m:
+        return sym
+    vals = re.findall(r"L([ib])(\d+)E", m.group(1))
+    return "k_decode<%s>" % ",".join(v if t == "i" else ("true" if v == "1" else "false") for t, v in vals)
+
+
+Block = collections.namedtuple("Block", "name loop ins")        # ins: [(opcode, operands, from_inline_asm)]
+
+
+def _b(op):
+    """the opcode without its encoding suffix"""
+    return re.sub(r"_(e32|e64)$", "", op)
+
+
+def kernels(path):
+    """-> [(name, info dict, [Block])] for every k_decode instance in the assembly"""
+    L = open(path).read().split("\n")
+    out, i = [], 0
+    while i < len(L):
+        m = re.match(r"(_ZN3mlp8k_decodeI\w+):", L[i])
+        if not m:
+            i += 1
+            continue
+        sym, i = m.group(1), i + 1
+        blocks, parents, in_asm = [Block("entry", None, [])], {}, False
+        while not L[i].startswith(".Lfunc_end"):
+            t = L[i].strip()
+            i += 1
+            m = re.match(r"(?:\.L(BB\d+_\d+):|; %(bb\.\d+):)\s*(?:;\s*(.*))?$", t)
+            if m:
+                name, note = m.group(1) or m.group(2), m.group(3) or ""
+                notes = [note]
+                while L[i].strip().startswith(";") and not L[i].strip().startswith("; %bb"):
+                    notes.append(L[i].strip().lstrip("; "))
+                    i += 1
+                loop = None
+                for n in notes:
+                    mm = re.search(r"in Loop: Header=(BB\d+_\d+)", n)
+                    if mm:
+                        loop = mm.group(1)
+                    if "Loop Header" in n:
+                        loop = name
+                    mm = re.match(r"=*>?\s*Parent Loop (BB\d+_\d+)", n)
+                    if mm:
+                        parents.setdefault(name, []).append(mm.group(1))
+                blocks.append(Block(name, loop, []))
+                continue
+            if "ASMSTART" in t:
+                in_asm = True
+            if "ASMEND" in t:
+                in_asm = False
+            if not t or t[0] in ".;":
+                continue
+            mm = re.match(r"([a-z_0-9]+)\s*(.*?)\s*(?:;.*)?$", t)
+            if mm:
+                blocks[-1].ins.append((mm.group(1), mm.group(2), in_asm))
+        info = {}
+        for t in L[i:i + 120]:                   # the "; Kernel info:" comment block behind the function
+            mm = re.match(r";\s*(NumVgprs|ScratchSize|Occupancy|LDSByteSize|TotalNumSgprs):\s*(\d+)", t.strip())
+            if mm:
+                info.setdefault(mm.group(1), int(mm.group(2)))
+            if t.startswith("; Occupancy"):
+                break
+        out.append((demangle_name(sym), info, blocks, parents))
+    return out
+
+
+def row_loop(blocks, parents):
+    """-> (header label, the row loop's blocks in layout order).
+
+    The loop is the innermost one that holds the filter chain.  The compiler lays its hot path out in one piece --
+    header, chunk request, slots, rematrix, commit, flush, the branch back -- and puts what the loop also contains but
+    rarely runs (the block-header parser with its own loops, error exits) behind it.  The row loop's labels are the
+    ends of that piece: from the header to the last branch back, in front of the first inner loop behind the slots."""
+    def holds(b, op):
+        return any(_b(o) == op for o, _, _ in b.ins)
+    marks = [j for j, b in enumerate(blocks) if holds(b, "v_ffbh_u32") and holds(b, "v_lshlrev_b64") and b.loop]
+    if not marks:
+        return None, []
+    head = collections.Counter(blocks[j].loop for j in marks).most_common(1)[0][0]
+    marks = [j for j in marks if blocks[j].loop == head]
+    order = {b.name: j for j, b in enumerate(blocks)}
+    start = order[head]
+    stop = next((j for j in range(marks[-1] + 1, len(blocks)) if blocks[j].loop != head), len(blocks))
+    end = stop - 1
+    for j in range(stop - 1, marks[-1], -1):
+        tail = [a for o, a, _ in blocks[j].ins if o == "s_branch" or o.startswith("s_cbranch")]
+        if tail and order.get(tail[-1].strip().lstrip(".L"), len(blocks)) <= start:
+            end = j
+            break
+    return head, blocks[start:end + 1]
+
+
+def regions(loop_blocks):
+    """-> ordered {region name: [Block]}"""
+    def holds(b, pred):
+        return any(pred(_b(o)) for o, _, _ in b.ins)
+    slot_at = [j for j, b in enumerate(loop_blocks) if holds(b, lambda o: o == "v_ffbh_u32") and
+               holds(b, lambda o: o == "v_lshlrev_b64")]
+    out = collections.OrderedDict()
+    for j, b in enumerate(loop_blocks):
+        if j in slot_at:
+            n = sum(1 for o, _, _ in b.ins if _b(o) == "v_ffbh_u32")
+            k = sum(sum(1 for o, _, _ in loop_blocks[x].ins if _b(o) == "v_ffbh_u32") for x in slot_at if x < j)
+            name = "slot %d" % k if n == 1 else "slots %d-%d" % (k, k + n - 1)
+        elif slot_at and slot_at[0] < j < slot_at[-1] and len(b.ins) <= 16:
+            name = "slot masks"
+        elif holds(b, lambda o: o == "v_perm_b32"):
+            name = "commit"
+        elif holds(b, lambda o: o.startswith("global_store") or o.startswith("flat_store")):
+            name = "flush"
+        elif holds(b, lambda o: o.startswith("global_load") or o.startswith("flat_load")):
+            name = "chunk request" if not slot_at or j < slot_at[0] else "other"
+        elif slot_at and j > slot_at[-1] and j <= slot_at[-1] + 4 and holds(b, lambda o: o.startswith("ds_write")):
+            name = "rematrix + staging"
+        else:
+            name = "other"
+        out.setdefault(name, []).append(b)
+    return out
+
+
+def mix(blocks_, rates):
+    """-> dict(total, valu, fast, slow, unclassified, cycles, hist, scratch, lane_moves)"""
+    h, cls, unc = collections.Counter(), collections.Counter(), set()
+    for b in blocks_:
+        for op, operands, _ in b.ins:
+            h[_b(op)] += 1
+            if op.startswith("v_"):
+                cls[rates.classify(op, operands)] += 1
+                if rates.classify(op, operands) == "unclassified":
+                    unc.add(_b(op))
+    valu = sum(cls.values())
+    return dict(total=sum(h.values()), valu=valu, fast=cls["fast"], slow=cls["slow"], unclassified=cls["unclassified"],
+                cycles=cls["fast"] * rates.fast_cycles + (cls["slow"] + cls["unclassified"]) * rates.slow_cycles,
+                hist=h, unclassified_ops=unc, scratch=sum(n for o, n in h.items() if o.startswith("scratch_")),
+                lane_moves=h["v_readlane_b32"] + h["v_writelane_b32"])
+
+
+def analyse(path, rates=None):
+    """-> [(instance name, info, row-loop header, OrderedDict region -> mix, whole-loop mix)]"""
+    rates = rates or Rates()
+    res = []
+    for name, info, blocks, parents in kernels(path):
+        head, lb = row_loop(blocks, parents)
+        if head is None:
+            continue
+        reg = regions(lb)
+        res.append((name, info, head, collections.OrderedDict((r, mix(bs, rates)) for r, bs in reg.items()), mix(lb, rates)))
+    return res
+
+
+def report(path, out=sys.stdout):
+    rates = Rates()
+    w = out.write
+    w("compiler: %s\n" % compiler_version())
+    w("classes from profiles/r05_valu_issue_rates.txt, 2 waves per SIMD: threshold %.2f ns; fast %.2f cycles, slow %.2f cycles"
+      " at %.1f GHz; unclassified opcodes are priced as slow\n" % (rates.threshold, rates.fast_cycles, rates.slow_cycles,
+                                                                     rates.clock_ghz))
+    for name, info, head, reg, whole in analyse(path, rates):
+        w("\n== %s%s\n" % (name, "   (the headline instance)" if name == HEADLINE else ""))
+        w("   VGPRs %s, occupancy %s, scratch %s B (whole kernel), LDS %s B; row loop at %s: %d instructions, "
+          "scratch_ in the loop %d, v_readlane/v_writelane in the loop %d\n" %
+          (info.get("NumVgprs"), info.get("Occupancy"), info.get("ScratchSize"), info.get("LDSByteSize"), head,
+           whole["total"], whole["scratch"], whole["lane_moves"]))
+        w("   %-20s %6s %6s %6s %6s %7s %10s\n" % ("region", "instr", "VALU", "fast", "slow", "unclass", "w.cycles"))
+        for r, m in list(reg.items()) + [("whole row loop", whole)]:
+            w("   %-20s %6d %6d %6d %6d %7d %10.0f\n" % (r, m["total"], m["valu"], m["fast"], m["slow"], m["unclassified"],
+                                                        m["cycles"]))
+        for r, m in reg.items():
+            if r.startswith("slot 1") or r == "slots 0-1" or (r == "slot 0" and "slot 1" not in reg):
+                w("   %s: %s\n" % (r, ", ".join("%s %d" % (o, n) for o, n in m["hist"].most_common())))
+        w("   whole row loop, VALU: %s\n" % ", ".join("%s %d" % (o, n) for o, n in whole["hist"].most_common() if o.startswith("v_")))
+        w("   unclassified: %s\n" % (", ".join(sorted(whole["unclassified_ops"])) or "none"))
+
+
+def main():
+    path = sys.argv[1] if len(sys.argv) > 1 else compile_asm()
+    report(path)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
