@@ -89,6 +89,16 @@ void dvda_hip_set_wav_output(int on);
  * The per-reader form: opens the track on HIP device `device`, as a WAV-payload-only reader if wav_output != 0,
  * whatever the thread's defaults are, and leaves those alone. */
 DVDA_Track_Reader *dvda_hip_open_track_reader_on(const DVDA_Track *track, int device, int wav_output);
+/* presentation = 1: MLP track readers opened afterwards (per calling thread, like dvda_hip_set_wav_output) decode the
+ * 2-channel presentation of a two-substream title -- substream 0 alone, DVDA_PRESENT_SUBSTREAM0 of dvda_mlp_hip.h, where
+ * the rule is stated: what a 2-channel player plays from a multichannel disc, not channels 0 and 1 of the full decode.
+ * dvda_channel_count() then returns k (substream 0's channels; 2 on such discs), dvda_riff_wave_channel_mask() the mask of
+ * the identity assignment of k channels (0x3 for k = 2), and dvda_read() / dvda_hip_reader_wav_payload() /
+ * dvda_hip_reader_wav_next() deliver k-channel frames.  One-substream MLP tracks and raw-PCM tracks are read as always.
+ * 0 (default): the full decode. */
+void dvda_hip_set_presentation(int presentation);
+/* dvda_hip_open_track_reader_on with the presentation named too; the thread's defaults stay as they are */
+DVDA_Track_Reader *dvda_hip_open_track_reader_with(const DVDA_Track *track, int device, int wav_output, int presentation);
 /* != 0: the reader holds the WAV payload only (opened with wav_output): dvda_read() on it returns 0 frames -- NOT
  * because the track is empty; take the payload with dvda_hip_reader_wav_payload() */
 int dvda_hip_reader_wav_only(const DVDA_Track_Reader *reader);

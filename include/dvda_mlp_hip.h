@@ -214,6 +214,55 @@ typedef struct dvda_mlp_conceal_span {
 int dvda_mlp_hip_conceal_spans(dvda_mlp_hip_ctx *ctx, uint32_t stream, dvda_mlp_conceal_span *spans, uint32_t cap,
                                uint32_t *n, void *stream_);
 
+/* Presentation (default DVDA_PRESENT_FULL; with it every output, status bit, launch and allocation is as without this
+ * call, also after DVDA_PRESENT_SUBSTREAM0 was set and taken back).
+ *
+ * A two-substream MLP stream carries two presentations: substream 0 alone is the 2-channel one (k channels in general:
+ * its own restart headers, filters, matrices and output shifts -- what a 2-channel decoder plays from a multichannel
+ * disc), both substreams together the full one.  The reference, and DVDA_PRESENT_FULL, parse substream 0's matrices
+ * and never apply them for such a stream (src/mlp.c:539-609): channels 0 and 1 of the full decode are front left and
+ * right, not the stereo mix.  DVDA_PRESENT_SUBSTREAM0 decodes the *presentation stream* of every stream instead:
+ *
+ *   one substream    the stream itself, byte for byte
+ *   two substreams   per complete access unit of the frame chain, in order:
+ *     frame header   the 4 check bits and the 16-bit input timing kept; the 12-bit length = the new unit's 16-bit words
+ *     major sync     (when the unit has one) its 28 bytes with the substream count set to 1 and the 5-bit channel
+ *                    assignment set to the identity assignment of k channels -- k = 1: 0x00, 2: 0x01, 3: 0x02, 4: 0x03,
+ *                    5: 0x06, which map MLP channel c to RIFF channel c (src/mlp.c:416-438).  k = substream 0's
+ *                    max_matrix_channel + 1 from the restart header of the stream's FIRST unit (bits 40-43 of substream
+ *                    0's bytes when both leading flags are set, src/mlp.c:748-753, 822-826); a first unit whose
+ *                    substream 0 opens with no restart header, or a k above 5: DVDA_ST_ENVELOPE, nothing decoded
+ *     directory      substream 0's word (and its extra word) kept, substream 1's dropped
+ *     body           bytes [0, 2 * substream_end_0) of the substream area, the rest dropped; a range that does not fit
+ *                    in the unit is clamped to it (the decode's own checks then report the damage)
+ *
+ * which is an ordinary one-substream stream (src/mlp.c:504-538; substream 0's parity and CRC-8 cover its own bytes
+ * only and stay valid).  PCM, status, pcm_frames, mlp_frames and segments are those of that stream: damage confined to
+ * substream 1's bytes does not touch the presentation, and a later restart header whose max_matrix_channel disagrees
+ * with k is judged as in any one-substream stream.
+ *
+ * With it set, dvda_mlp_hip_index indexes the source, strips it on the device into a workspace that only grows
+ * (csrc/mlp_present.h; no host wait) and indexes the presentation streams with a second, inner context.
+ * dvda_mlp_hip_decode / _decode_async / _reserve / _set_pcm_layout / _set_initial_fir (substream 0's history is
+ * [stream][0][..]) / _set_lanes_per_segment / _set_chain_form / _kernel_time / _decode_time / _segment_count /
+ * _segment_fir act on that context, so every pass and all four layouts work as for any one-substream stream.
+ *   dvda_mlp_hip_stream_info   channels = k (right after the index), pcm_frames, mlp_frames, segments and status are
+ *                              the presentation's; substreams, assignment and the group codes stay the source's;
+ *                              bytes_consumed counts source bytes.  A source stream the index could not frame
+ *                              (DVDA_ST_NO_SYNC, _IRREGULAR, _CAPACITY) keeps that status and decodes nothing.
+ *   dvda_mlp_hip_segment_info  segments are the presentation streams'; offset and end are positions in the caller's
+ *                              SOURCE buffer (the start of the source segment whose stripped bytes begin there).
+ * Scope: conceal mode and DVDA_PRESENT_SUBSTREAM0 on one context give DVDA_HIP_EINVAL, whichever is set second; the
+ * streaming tier and dvda_mlp_hip_decode_multi decode the full presentation only; a batch of 4 GiB or more is
+ * DVDA_HIP_ECAPACITY under DVDA_PRESENT_SUBSTREAM0 (offsets in the workspace are 32-bit).  A change of the setting
+ * asks for a new dvda_mlp_hip_index. */
+#define DVDA_PRESENT_FULL        0u
+#define DVDA_PRESENT_SUBSTREAM0  1u
+int dvda_mlp_hip_set_presentation(dvda_mlp_hip_ctx *ctx, uint32_t presentation);
+/* Device time (ms) of the strip kernels of the last dvda_mlp_hip_index under DVDA_PRESENT_SUBSTREAM0, the source bytes
+ * they walked and the bytes of the presentation streams they wrote (blocks until they have run). */
+int dvda_mlp_hip_present_time(dvda_mlp_hip_ctx *ctx, double *ms, uint64_t *bytes_in, uint64_t *bytes_out);
+
 /* Sizes the workspaces of the passes behind the fast pass ahead of time (they only ever grow): chain passes for
  * `chain_segments` deferred segments holding `chain_pcm_frames` PCM frames in all (for titles whose restart points
  * carry FIR taps -- what encoders write -- that is every segment and every frame of the batch), the sequential pass

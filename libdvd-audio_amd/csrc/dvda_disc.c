@@ -48,6 +48,19 @@ static _Thread_local int g_device = 0;
 static _Thread_local int g_wav_output = 0;
 void dvda_hip_set_device(int device) { g_device = device; }
 void dvda_hip_set_wav_output(int on) { g_wav_output = on != 0; }
+/* 1: MLP track readers opened afterwards decode the presentation substream 0 carries (DVDA_PRESENT_SUBSTREAM0) */
+static _Thread_local int g_present = 0;
+void dvda_hip_set_presentation(int presentation) { g_present = presentation == 1; }
+
+/* the channel assignment a reader answers with: under the presentation a two-substream stream has k channels in the
+ * identity assignment of k (MLP channel c = RIFF channel c, src/mlp.c:416-438), whatever its major sync names */
+static unsigned reader_assignment(const dvda_mlp_stream_info *info, int present)
+{
+    static const unsigned ident[6] = {0, 0x00, 0x01, 0x02, 0x03, 0x06};
+    if (present && info->substreams == 2 && info->channels >= 1 && info->channels <= 5)
+        return ident[info->channels];
+    return info->assignment;
+}
 
 /* ------------------------------------------------------------------ records */
 struct ifo_title {
@@ -654,7 +667,8 @@ static DVDA_Track_Reader *open_mlp(struct aob_set *aobs, const DVDA_Track *k)
         d_sec = d_mlp = NULL;
         for (int attempt = 0; attempt < 2; attempt++) {
             if (dvda_mlp_hip_create(&ctx, g_device, 1, segs) != DVDA_HIP_OK ||
-                dvda_mlp_hip_set_pcm_layout(ctx, DVDA_PCM_INTERLEAVED) != DVDA_HIP_OK)
+                dvda_mlp_hip_set_pcm_layout(ctx, DVDA_PCM_INTERLEAVED) != DVDA_HIP_OK ||
+                dvda_mlp_hip_set_presentation(ctx, g_present ? DVDA_PRESENT_SUBSTREAM0 : DVDA_PRESENT_FULL) != DVDA_HIP_OK)
                 goto fail;
             if (dvda_mlp_hip_index(ctx, d_stream, padded, d_meta + 0, d_meta + 1, 1, NULL) != DVDA_HIP_OK)
                 goto fail;
@@ -714,8 +728,8 @@ static DVDA_Track_Reader *open_mlp(struct aob_set *aobs, const DVDA_Track *k)
         r->bps_code[1] = info.group1_bps;
         r->rate_code[0] = info.group0_rate;
         r->rate_code[1] = info.group1_rate;
-        r->assignment = info.assignment;
-        r->channels = channels_of(info.assignment);
+        r->assignment = reader_assignment(&info, g_present);
+        r->channels = channels_of(r->assignment);
         r->status = info.status;
         r->frames = info.pcm_frames;
         r->stride = stride;
@@ -795,6 +809,7 @@ struct mlp_windows {
     int device, wav_bits;       /* wav_bits != 0: the decode writes the payload (DVDA_PCM_WAV24 / WAV16) */
     int wav_request, wav_decided;   /* the opener asked for the payload; decided (from the first window's major sync:
                                        only a 16- or 24-bit stream is decoded straight into it) */
+    int present;                /* 1: every window decodes the presentation of substream 0 (dvda_hip_set_presentation) */
     int started, finished, failed;
     /* a raw-PCM track read in windows (round 6): sectors decode independently of each other (src/pcm.c:149: whole chunks
        per packet), so a window is a run of sectors and nothing crosses a cut but the count of frames delivered so far */
@@ -1054,6 +1069,9 @@ static int win_index(struct mlp_windows *w, uint64_t len, uint32_t *n_seg)
             if (dvda_mlp_hip_create(&w->ctx, w->device, 1, w->ctx_segs) != DVDA_HIP_OK)
                 return 0;
         }
+        /* (a context kept from the thread's last reader may have served the other presentation) */
+        if (dvda_mlp_hip_set_presentation(w->ctx, w->present ? DVDA_PRESENT_SUBSTREAM0 : DVDA_PRESENT_FULL) != DVDA_HIP_OK)
+            return 0;
         if (dvda_mlp_hip_index(w->ctx, w->d_stream, padded, w->d_meta + 0, w->d_meta + 1, 1, NULL) != DVDA_HIP_OK)
             return 0;
         const int rc = dvda_mlp_hip_segment_count(w->ctx, n_seg, NULL);
@@ -1530,6 +1548,7 @@ static DVDA_Track_Reader *open_mlp_windowed(const DVDA_Track *k)
        layout with them: win_produce decides it from the first window's index) */
     w->wav_bits = 0;
     w->wav_request = g_wav_output ? 1 : 0;
+    w->present = g_present;
     {
         struct win_slot *out = &w->slot[0];
         for (;;) {
@@ -1551,8 +1570,8 @@ static DVDA_Track_Reader *open_mlp_windowed(const DVDA_Track *k)
     r->bps_code[1] = w->info.group1_bps;
     r->rate_code[0] = w->info.group0_rate;
     r->rate_code[1] = w->info.group1_rate;
-    r->assignment = w->info.assignment;
-    r->channels = channels_of(w->info.assignment);
+    r->assignment = reader_assignment(&w->info, w->present);
+    r->channels = channels_of(r->assignment);
     r->status = w->status;
     r->interleaved = 1;
     if (r->channels == 0 || r->channels != w->info.channels)
@@ -1775,6 +1794,15 @@ DVDA_Track_Reader *dvda_hip_open_track_reader_on(const DVDA_Track *k, int device
     DVDA_Track_Reader *r = dvda_open_track_reader(k);
     g_device = keep_device;
     g_wav_output = keep_wav;
+    return r;
+}
+
+DVDA_Track_Reader *dvda_hip_open_track_reader_with(const DVDA_Track *k, int device, int wav_output, int presentation)
+{
+    const int keep = g_present;
+    g_present = presentation == 1;
+    DVDA_Track_Reader *r = dvda_hip_open_track_reader_on(k, device, wav_output);
+    g_present = keep;
     return r;
 }
 

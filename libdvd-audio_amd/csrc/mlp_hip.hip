@@ -29,6 +29,7 @@
 #include "mlp_coop.h"
 #include "mlp_index.h"
 #include "mlp_conceal.h"
+#include "mlp_present.h"
 #include "pcm_unswizzle.h"
 #include "wav_pack.h"
 
@@ -165,6 +166,26 @@ struct dvda_mlp_hip_ctx {
     uint64_t cc_fir_cap;
     std::vector<std::vector<dvda_mlp_conceal_span>> cc_spans;  // per stream of the last decode
     std::vector<ConcealInfo> cc_info;                           // per stream of the last decode: the concealed ones
+    // presentation (mlp_present.h): nothing of it exists before dvda_mlp_hip_set_presentation asks for substream 0
+    uint32_t present;                  // DVDA_PRESENT_*
+    dvda_mlp_hip_ctx *pp_child;        // the second index and every decode pass: the presentation streams
+    uint8_t *d_pp_bytes;               // the presentation streams, each 16-byte aligned (+ 64 readable bytes); only grows
+    uint64_t pp_bytes_cap;
+    uint64_t pp_bound;                 // bytes of it the second index scans
+    uint32_t *d_pp_info;               // [max_streams]: k / why there is no presentation (PP_*)
+    uint32_t *d_pp_size;               // [max_segments + 1]: stripped bytes per source segment
+    uint32_t *d_pp_sbase;              // [max_segments + 1]: their exclusive prefix sum
+    uint32_t *d_pp_len;                // [max_streams + 1]: the streams' lengths, padded to 16
+    uint32_t *d_pp_base;               // [max_streams + 1]: the streams' offsets; last = bytes in use
+    uint64_t *d_pp_off64, *d_pp_len64; // [max_streams]: the ranges as the second index reads them
+    hipEvent_t pp_ev[2];               // around the strip kernels of the last index call
+    bool pp_ev_made, pp_ev_set;
+    // host copies for the getters, fetched on first use after an index call
+    bool pp_map_valid;
+    uint32_t pp_h_nseg;
+    std::vector<SegRec> pp_h_seg;
+    std::vector<uint32_t> pp_h_sbase, pp_h_base, pp_h_info;
+    std::vector<StreamRec> pp_h_streams;
 };
 
 // what the workspaces hold right now (mlp_bounds.h)
@@ -261,6 +282,20 @@ static void free_ws(dvda_mlp_hip_ctx *c)
         (void)hipFree(c->d_cc_scr[r]);
     (void)hipFree(c->d_cc_ops);
     (void)hipFree(c->d_cc_fir);
+    if (c->pp_child)
+        dvda_mlp_hip_destroy(c->pp_child);
+    (void)hipFree(c->d_pp_bytes);
+    (void)hipFree(c->d_pp_info);
+    (void)hipFree(c->d_pp_size);
+    (void)hipFree(c->d_pp_sbase);
+    (void)hipFree(c->d_pp_len);
+    (void)hipFree(c->d_pp_base);
+    (void)hipFree(c->d_pp_off64);
+    (void)hipFree(c->d_pp_len64);
+    if (c->pp_ev_made) {
+        (void)hipEventDestroy(c->pp_ev[0]);
+        (void)hipEventDestroy(c->pp_ev[1]);
+    }
 }
 
 extern "C" const char *dvda_mlp_hip_version(void) { return "dvda-mlp-hip 0.1 (gfx950)"; }
@@ -632,9 +667,23 @@ static void enqueue_index(dvda_mlp_hip_ctx *c, hipStream_t st, const uint8_t *d_
     }
 }
 
+static int present_index(dvda_mlp_hip_ctx *c, hipStream_t st);
+static int index_source(dvda_mlp_hip_ctx *c, const uint8_t *d_bytes, uint64_t total_bytes,
+                        const uint64_t *d_stream_off, const uint64_t *d_stream_len, uint32_t n_streams, void *stream_);
+
 extern "C" int dvda_mlp_hip_index(dvda_mlp_hip_ctx *c, const uint8_t *d_bytes, uint64_t total_bytes,
                                   const uint64_t *d_stream_off, const uint64_t *d_stream_len,
                                   uint32_t n_streams, void *stream_)
+{
+    const int rc = index_source(c, d_bytes, total_bytes, d_stream_off, d_stream_len, n_streams, stream_);
+    if (rc != DVDA_HIP_OK || c->present != DVDA_PRESENT_SUBSTREAM0)
+        return rc;
+    // presentation: the source's index is there; strip, and index what is left (mlp_present.h)
+    return present_index(c, (hipStream_t)stream_);
+}
+
+static int index_source(dvda_mlp_hip_ctx *c, const uint8_t *d_bytes, uint64_t total_bytes,
+                        const uint64_t *d_stream_off, const uint64_t *d_stream_len, uint32_t n_streams, void *stream_)
 {
     if (!c || !d_bytes || !d_stream_off || !d_stream_len || n_streams == 0 || total_bytes == 0)
         return DVDA_HIP_EINVAL;
@@ -752,11 +801,16 @@ __global__ void k_chain_guard(uint4 *plan, const uint32_t *n_seg_ptr, uint32_t m
         plan[n] = make_uint4(t.x, 0, 0, 0);
 }
 
+// presentation: the decode passes, their settings and their timers are the inner context's
+#define PP_INNER(c) ((c) && (c)->present == DVDA_PRESENT_SUBSTREAM0 && (c)->pp_child)
+
 extern "C" int dvda_mlp_hip_reserve(dvda_mlp_hip_ctx *c, uint64_t chain_pcm_frames, uint32_t chain_segments,
                                     uint32_t seq_streams)
 {
     if (!c)
         return DVDA_HIP_EINVAL;
+    if (PP_INNER(c))
+        return dvda_mlp_hip_reserve(c->pp_child, chain_pcm_frames, chain_segments, seq_streams);
     HIP_TRY(hipSetDevice(c->device));
     if (chain_pcm_frames >> 32)
         return DVDA_HIP_ECAPACITY;
@@ -790,6 +844,8 @@ static int conceal_run(dvda_mlp_hip_ctx *c, int32_t *d_pcm, const uint64_t *d_ou
 extern "C" int dvda_mlp_hip_decode(dvda_mlp_hip_ctx *c, int32_t *d_pcm, const uint64_t *d_out_off,
                                    const uint64_t *d_out_stride, void *stream_)
 {
+    if (PP_INNER(c))
+        return c->indexed ? dvda_mlp_hip_decode(c->pp_child, d_pcm, d_out_off, d_out_stride, stream_) : DVDA_HIP_ESTATE;
     if (c) {
         c->cc_spans.clear();
         c->cc_info.clear();
@@ -803,6 +859,8 @@ extern "C" int dvda_mlp_hip_decode(dvda_mlp_hip_ctx *c, int32_t *d_pcm, const ui
 extern "C" int dvda_mlp_hip_decode_async(dvda_mlp_hip_ctx *c, int32_t *d_pcm, const uint64_t *d_out_off,
                                          const uint64_t *d_out_stride, void *stream_)
 {
+    if (PP_INNER(c))
+        return c->indexed ? dvda_mlp_hip_decode_async(c->pp_child, d_pcm, d_out_off, d_out_stride, stream_) : DVDA_HIP_ESTATE;
     if (c && c->conceal)
         return DVDA_HIP_EINVAL;     // concealing reads the damage back: the blocking call only
     return decode_impl(c, d_pcm, d_out_off, d_out_stride, stream_, false);
@@ -1075,6 +1133,8 @@ extern "C" int dvda_mlp_hip_set_pcm_layout(dvda_mlp_hip_ctx *c, uint32_t layout)
     if (!c || layout > DVDA_PCM_WAV16)
         return DVDA_HIP_EINVAL;
     c->pcm_layout = layout;
+    if (c->pp_child)
+        c->pp_child->pcm_layout = layout;
     return DVDA_HIP_OK;
 }
 
@@ -1083,6 +1143,8 @@ extern "C" int dvda_mlp_hip_set_chain_form(dvda_mlp_hip_ctx *c, uint32_t form)
     if (!c || form > 2)
         return DVDA_HIP_EINVAL;
     c->chain_form = form;
+    if (c->pp_child)
+        c->pp_child->chain_form = form;
     return DVDA_HIP_OK;
 }
 
@@ -1091,8 +1153,13 @@ extern "C" int dvda_mlp_hip_set_lanes_per_segment(dvda_mlp_hip_ctx *c, uint32_t 
     if (!c || (lanes > 3 && lanes != 64))
         return DVDA_HIP_EINVAL;
     c->lanes_per_seg = lanes;
+    if (c->pp_child)
+        c->pp_child->lanes_per_seg = lanes;
     return DVDA_HIP_OK;
 }
+
+static int present_stream_info(dvda_mlp_hip_ctx *c, dvda_mlp_stream_info *infos, uint32_t n, void *stream_);
+static int present_segment_info(dvda_mlp_hip_ctx *c, uint32_t segment, dvda_mlp_segment_info *info, void *stream_);
 
 extern "C" int dvda_mlp_hip_stream_info(dvda_mlp_hip_ctx *c, dvda_mlp_stream_info *infos, uint32_t n,
                                         void *stream_)
@@ -1101,6 +1168,8 @@ extern "C" int dvda_mlp_hip_stream_info(dvda_mlp_hip_ctx *c, dvda_mlp_stream_inf
         return DVDA_HIP_EINVAL;
     if (!c->indexed)
         return DVDA_HIP_ESTATE;
+    if (PP_INNER(c))
+        return present_stream_info(c, infos, n, stream_);
     if (n > c->n_streams)
         n = c->n_streams;
     HIP_TRY(hipSetDevice(c->device));
@@ -1138,6 +1207,16 @@ extern "C" int dvda_mlp_hip_segment_count(dvda_mlp_hip_ctx *c, uint32_t *n_segme
         return DVDA_HIP_EINVAL;
     if (!c->indexed)
         return DVDA_HIP_ESTATE;
+    if (PP_INNER(c)) {
+        // (a source with more major syncs than the context holds was indexed in part: the caller's cue to come back
+        //  with a larger context, as without the presentation)
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipStreamSynchronize((hipStream_t)stream_));
+        HIP_TRY(hipMemcpy(n_segments, c->d_n_cand, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (*n_segments > c->max_segments)
+            return DVDA_HIP_ECAPACITY;
+        return dvda_mlp_hip_segment_count(c->pp_child, n_segments, stream_);
+    }
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream_));
     HIP_TRY(hipMemcpy(n_segments, c->d_n_cand, sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -1148,6 +1227,8 @@ extern "C" int dvda_mlp_hip_kernel_time(dvda_mlp_hip_ctx *c, double *avg_ms, uin
 {
     if (!c || !avg_ms)
         return DVDA_HIP_EINVAL;
+    if (PP_INNER(c))
+        return dvda_mlp_hip_kernel_time(c->pp_child, avg_ms, launches);
     HIP_TRY(hipSetDevice(c->device));
     double total = 0;
     // the ring holds the newest EV_RING decode calls
@@ -1172,6 +1253,8 @@ extern "C" int dvda_mlp_hip_decode_time(dvda_mlp_hip_ctx *c, double *avg_ms, uin
 {
     if (!c || !avg_ms)
         return DVDA_HIP_EINVAL;
+    if (PP_INNER(c))
+        return dvda_mlp_hip_decode_time(c->pp_child, avg_ms, calls);
     HIP_TRY(hipSetDevice(c->device));
     double total = 0;
     const uint32_t n = c->ev_count < EV_RING ? (uint32_t)c->ev_count : EV_RING;
@@ -1263,6 +1346,8 @@ extern "C" int dvda_mlp_hip_set_initial_fir(dvda_mlp_hip_ctx *c, const int32_t *
     if (!c)
         return DVDA_HIP_EINVAL;
     c->d_init_fir = d_init_fir;
+    if (c->pp_child)
+        c->pp_child->d_init_fir = d_init_fir;
     return DVDA_HIP_OK;
 }
 
@@ -1273,6 +1358,8 @@ extern "C" int dvda_mlp_hip_segment_info(dvda_mlp_hip_ctx *c, uint32_t segment, 
         return DVDA_HIP_EINVAL;
     if (!c->indexed)
         return DVDA_HIP_ESTATE;
+    if (PP_INNER(c))
+        return present_segment_info(c, segment, info, stream_);
     if (segment >= c->max_segments)
         return DVDA_HIP_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
@@ -1297,6 +1384,8 @@ extern "C" int dvda_mlp_hip_segment_fir(dvda_mlp_hip_ctx *c, uint32_t segment, i
         return DVDA_HIP_EINVAL;
     if (!c->indexed)
         return DVDA_HIP_ESTATE;
+    if (PP_INNER(c))
+        return dvda_mlp_hip_segment_fir(c->pp_child, segment, host_fir, stream_);
     const uint32_t L = 2;       // workspace lane = segment * 2 + substream in every pass
     if ((uint64_t)segment * L + L > c->iir_lanes)
         return DVDA_HIP_EINVAL;
@@ -1316,10 +1405,235 @@ extern "C" int dvda_mlp_hip_segment_fir(dvda_mlp_hip_ctx *c, uint32_t segment, i
 // (mlp_step.h; host side: mlp_stream.c)
 // ------------------------------------------------------------------ conceal mode (mlp_conceal.h)
 
+// ------------------------------------------------------------------ presentation (mlp_present.h)
+
+extern "C" int dvda_mlp_hip_set_presentation(dvda_mlp_hip_ctx *c, uint32_t presentation)
+{
+    if (!c || presentation > DVDA_PRESENT_SUBSTREAM0 || (presentation != DVDA_PRESENT_FULL && c->conceal))
+        return DVDA_HIP_EINVAL;
+    if (presentation == c->present)
+        return DVDA_HIP_OK;
+    if (presentation == DVDA_PRESENT_SUBSTREAM0 && !c->pp_child) {
+        HIP_TRY(hipSetDevice(c->device));
+        int rc = dvda_mlp_hip_create(&c->pp_child, c->device, c->max_streams, c->max_segments);
+        if (rc)
+            return rc;
+        const size_t ns = c->max_segments, nt = c->max_streams;
+        hipError_t e = hipSuccess;
+        auto alloc = [&](void **p, size_t bytes) {
+            if (e == hipSuccess)
+                e = ws_malloc(p, bytes);
+        };
+        alloc((void **)&c->d_pp_info, nt * sizeof(uint32_t));
+        alloc((void **)&c->d_pp_size, (ns + 1) * sizeof(uint32_t));
+        alloc((void **)&c->d_pp_sbase, (ns + 1) * sizeof(uint32_t));
+        alloc((void **)&c->d_pp_len, (nt + 1) * sizeof(uint32_t));
+        alloc((void **)&c->d_pp_base, (nt + 1) * sizeof(uint32_t));
+        alloc((void **)&c->d_pp_off64, nt * sizeof(uint64_t));
+        alloc((void **)&c->d_pp_len64, nt * sizeof(uint64_t));
+        if (e == hipSuccess && (e = hipEventCreate(&c->pp_ev[0])) == hipSuccess) {
+            if ((e = hipEventCreate(&c->pp_ev[1])) == hipSuccess)
+                c->pp_ev_made = true;
+            else
+                (void)hipEventDestroy(c->pp_ev[0]);
+        }
+        if (e != hipSuccess) {
+            // (what was allocated stays with the context and is freed with it; the mode stays as it was)
+            dvda_mlp_hip_destroy(c->pp_child);
+            c->pp_child = nullptr;
+            return DVDA_HIP_ENOMEM;
+        }
+    }
+    if (c->pp_child) {
+        c->pp_child->pcm_layout = c->pcm_layout;
+        c->pp_child->lanes_per_seg = c->lanes_per_seg;
+        c->pp_child->chain_form = c->chain_form;
+        c->pp_child->d_init_fir = c->d_init_fir;
+    }
+    c->present = presentation;
+    c->indexed = false;             // an index made under the other setting is not this setting's
+    c->pp_map_valid = false;
+    return DVDA_HIP_OK;
+}
+
+// the strip kernels and the second index, enqueued behind the source's index on `st`: no host wait
+static int present_index(dvda_mlp_hip_ctx *c, hipStream_t st)
+{
+    const uint32_t n = c->n_streams, ms = c->max_segments;
+    // offsets in the presentation buffer are 32-bit (the scans are)
+    const uint64_t bound = ((c->total_bytes + 15) & ~(uint64_t)15) + 16ull * n;
+    if (bound + 128 >= (1ull << 32))
+        return DVDA_HIP_ECAPACITY;
+    c->indexed = false;
+    c->pp_map_valid = false;
+    if (bound + 128 > c->pp_bytes_cap) {
+        // (the stream's work so far may still read the old buffer: a second index of an earlier call)
+        HIP_TRY(hipStreamSynchronize(st));
+        int rc = grow(&c->d_pp_bytes, &c->pp_bytes_cap, bound + 128);
+        if (rc)
+            return rc;
+    }
+    c->pp_bound = bound;
+    HIP_TRY(hipEventRecord(c->pp_ev[0], st));
+    hipLaunchKernelGGL(k_pp_streams, dim3((n + 255) / 256), dim3(256), 0, st, c->d_bytes, c->d_seg, c->d_streams, n, ms,
+                       c->d_pp_info);
+    hipLaunchKernelGGL(k_pp_size, dim3((ms + 255) / 256), dim3(256), 0, st, c->d_bytes, c->d_seg, c->d_n_cand, ms,
+                       c->d_pp_info, c->d_pp_size);
+    exscan(c, st, c->d_pp_size, c->d_pp_sbase, 0u, c->d_n_cand, ms);
+    hipLaunchKernelGGL(k_pp_len, dim3((n + 255) / 256), dim3(256), 0, st, c->d_streams, n, c->d_n_cand, ms, c->d_pp_info,
+                       c->d_pp_sbase, c->d_pp_len, c->d_pp_len64);
+    exscan(c, st, c->d_pp_len, c->d_pp_base, n, nullptr, n);
+    {
+        const uint64_t out_bytes = bound + 64, chunks = out_bytes / 16;
+        const uint64_t threads = chunks > n ? chunks : n;
+        hipLaunchKernelGGL(k_pp_fill, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, c->d_pp_bytes, out_bytes,
+                           n, c->d_pp_base, c->d_pp_len64, c->d_pp_off64);
+    }
+    {
+        // one wave per source segment, at most a few waves per SIMD of the device
+        uint64_t blocks = ((uint64_t)ms + PP_THREADS / 64 - 1) / (PP_THREADS / 64);
+        if (blocks > 4096)
+            blocks = 4096;
+        hipLaunchKernelGGL(k_pp_copy, dim3((unsigned)blocks), dim3(PP_THREADS), 0, st, c->d_bytes, c->d_seg, c->d_n_cand,
+                           ms, c->d_streams, c->d_pp_info, c->d_pp_size, c->d_pp_sbase, c->d_pp_base, c->d_pp_bytes);
+    }
+    HIP_TRY(hipEventRecord(c->pp_ev[1], st));
+    c->pp_ev_set = true;
+    HIP_TRY(hipGetLastError());
+    const int rc = dvda_mlp_hip_index(c->pp_child, c->d_pp_bytes, bound, c->d_pp_off64, c->d_pp_len64, n, (void *)st);
+    if (rc)
+        return rc;
+    c->indexed = true;
+    return DVDA_HIP_OK;
+}
+
+extern "C" int dvda_mlp_hip_present_time(dvda_mlp_hip_ctx *c, double *ms, uint64_t *bytes_in, uint64_t *bytes_out)
+{
+    if (!c || !ms)
+        return DVDA_HIP_EINVAL;
+    if (!PP_INNER(c) || !c->indexed || !c->pp_ev_set)
+        return DVDA_HIP_ESTATE;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipEventSynchronize(c->pp_ev[1]));
+    float t = 0;
+    HIP_TRY(hipEventElapsedTime(&t, c->pp_ev[0], c->pp_ev[1]));
+    *ms = t;
+    if (bytes_in)
+        *bytes_in = c->total_bytes;
+    if (bytes_out) {
+        uint32_t used = 0;
+        HIP_TRY(hipMemcpy(&used, c->d_pp_base + c->n_streams, sizeof(used), hipMemcpyDeviceToHost));
+        *bytes_out = used;
+    }
+    return DVDA_HIP_OK;
+}
+
+// host copies of what the getters map with (once per index call; the caller has waited for `stream`)
+static int present_map(dvda_mlp_hip_ctx *c)
+{
+    if (c->pp_map_valid)
+        return DVDA_HIP_OK;
+    const uint32_t n = c->n_streams;
+    uint32_t nseg = 0;
+    HIP_TRY(hipMemcpy(&nseg, c->d_n_cand, sizeof(nseg), hipMemcpyDeviceToHost));
+    if (nseg > c->max_segments)
+        nseg = c->max_segments;
+    c->pp_h_nseg = nseg;
+    c->pp_h_seg.resize(nseg);
+    c->pp_h_sbase.resize((size_t)nseg + 1);
+    c->pp_h_base.resize((size_t)n + 1);
+    c->pp_h_info.resize(n);
+    c->pp_h_streams.resize(n);
+    if (nseg)
+        HIP_TRY(hipMemcpy(c->pp_h_seg.data(), c->d_seg, (size_t)nseg * sizeof(SegRec), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(c->pp_h_sbase.data(), c->d_pp_sbase, ((size_t)nseg + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(c->pp_h_base.data(), c->d_pp_base, ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(c->pp_h_info.data(), c->d_pp_info, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(c->pp_h_streams.data(), c->d_streams, (size_t)n * sizeof(StreamRec), hipMemcpyDeviceToHost));
+    c->pp_map_valid = true;
+    return DVDA_HIP_OK;
+}
+
+static int present_stream_info(dvda_mlp_hip_ctx *c, dvda_mlp_stream_info *infos, uint32_t n, void *stream_)
+{
+    if (n > c->n_streams)
+        n = c->n_streams;
+    int rc = dvda_mlp_hip_stream_info(c->pp_child, infos, n, stream_);      // (waits for `stream`)
+    if (rc || (rc = present_map(c)) != 0)
+        return rc;
+    for (uint32_t i = 0; i < n; i++) {
+        dvda_mlp_stream_info &o = infos[i];
+        const StreamRec &h = c->pp_h_streams[i];
+        const uint32_t v = c->pp_h_info[i];
+        // what the source says of itself stays the source's
+        o.assignment = (h.sync >> 16) & 0x1F;
+        o.substreams = (h.sync >> 24) & 0xF;
+        o.group0_bps = h.sync & 0xF;
+        o.group1_bps = (h.sync >> 4) & 0xF;
+        o.group0_rate = (h.sync >> 8) & 0xF;
+        o.group1_rate = (h.sync >> 12) & 0xF;
+        o.bytes_consumed = h.consumed;
+        if (v & (PP_NONE | PP_ENVELOPE)) {
+            // no presentation: the source's own finding (or "no k"), nothing decoded
+            o.status = h.status | (h.first_seg == 0xFFFFFFFFu ? DVDA_ST_NO_SYNC : 0u) | ((v & PP_ENVELOPE) ? DVDA_ST_ENVELOPE : 0u);
+            o.mlp_frames = o.pcm_frames = 0;
+            o.segments = 0;
+            o.channels = (v & PP_ENVELOPE) ? 0u : channel_count(o.assignment);
+        } else {
+            o.channels = (v & PP_K_MASK) ? (v & PP_K_MASK) : channel_count(o.assignment);
+            o.status |= h.status & (DVDA_ST_TRUNCATED | DVDA_ST_EOF);       // a cut or unframed tail is the source's
+        }
+    }
+    return DVDA_HIP_OK;
+}
+
+// a presentation segment's range in the caller's source buffer: its start is the start of the source segment whose
+// stripped bytes begin there, its end the end of the source segment its last stripped byte belongs to
+static int present_segment_info(dvda_mlp_hip_ctx *c, uint32_t segment, dvda_mlp_segment_info *info, void *stream_)
+{
+    int rc = dvda_mlp_hip_segment_info(c->pp_child, segment, info, stream_);
+    if (rc || (rc = present_map(c)) != 0)
+        return rc;
+    const uint32_t s = info->stream;
+    if (s >= c->n_streams || c->pp_h_streams[s].first_seg >= c->pp_h_nseg)
+        return DVDA_HIP_OK;         // (bytes of no stream: the positions stay the presentation buffer's)
+    const StreamRec &h = c->pp_h_streams[s];
+    const uint32_t lo = h.first_seg, hi = lo + h.n_seg <= c->pp_h_nseg ? lo + h.n_seg : c->pp_h_nseg;
+    const uint32_t *sb = c->pp_h_sbase.data();
+    if (info->offset < c->pp_h_base[s] || hi <= lo)
+        return DVDA_HIP_OK;
+    const uint64_t t0 = sb[lo] + (info->offset - c->pp_h_base[s]), t1 = sb[lo] + (info->end - c->pp_h_base[s]);
+    // last source segment of the stream that starts at or before t0 (dead ones have no bytes and sort in front of the
+    // live one that starts at the same place)
+    uint32_t a = lo;
+    for (uint32_t l = lo, r = hi; l < r;) {
+        const uint32_t m = l + (r - l) / 2;
+        if (sb[m] <= t0) {
+            a = m;
+            l = m + 1;
+        } else
+            r = m;
+    }
+    // last one that starts before t1
+    uint32_t b = a;
+    for (uint32_t l = a, r = hi; l < r;) {
+        const uint32_t m = l + (r - l) / 2;
+        if (sb[m] < t1) {
+            b = m;
+            l = m + 1;
+        } else
+            r = m;
+    }
+    const bool empty = info->end <= info->offset;
+    info->offset = c->pp_h_seg[a].off;
+    info->end = empty ? info->offset : c->pp_h_seg[b].end;
+    return DVDA_HIP_OK;
+}
+
 extern "C" int dvda_mlp_hip_set_conceal(dvda_mlp_hip_ctx *c, int on)
 {
-    if (!c)
-        return DVDA_HIP_EINVAL;
+    if (!c || (on && c->present != DVDA_PRESENT_FULL))
+        return DVDA_HIP_EINVAL;     // (conceal mode of a presentation: not built)
     c->conceal = on != 0;
     c->cc_spans.clear();
     c->cc_info.clear();

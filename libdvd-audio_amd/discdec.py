@@ -24,7 +24,7 @@ EXPORTS = [
     "dvda_hip_set_device", "dvda_hip_set_wav_output", "dvda_hip_reader_status", "dvda_hip_reader_total_frames",
     "dvda_hip_reader_wav_payload", "dvda_hip_open_track_reader_on", "dvda_hip_reader_wav_only",
     "dvda_hip_reader_wav_next", "dvda_hip_reader_windowed", "dvda_hip_reader_memory", "dvda_hip_reader_failed",
-    "dvda_hip_release_cached_buffers",
+    "dvda_hip_release_cached_buffers", "dvda_hip_set_presentation", "dvda_hip_open_track_reader_with",
 ]
 
 _lib = None
@@ -67,6 +67,10 @@ def lib():
         L.dvda_hip_set_wav_output.argtypes = [ctypes.c_int]
         L.dvda_hip_open_track_reader_on.restype = ctypes.c_void_p
         L.dvda_hip_open_track_reader_on.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+        L.dvda_hip_open_track_reader_with.restype = ctypes.c_void_p
+        L.dvda_hip_open_track_reader_with.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        L.dvda_hip_set_presentation.restype = None
+        L.dvda_hip_set_presentation.argtypes = [ctypes.c_int]
         L.dvda_hip_reader_wav_only.restype = ctypes.c_int
         L.dvda_hip_reader_wav_only.argtypes = [ctypes.c_void_p]
         L.dvda_hip_reader_total_frames.restype = ctypes.c_ulonglong
@@ -111,7 +115,8 @@ def layout(audio_ts, titleset=1):
     return out
 
 
-def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0, fused=False, pieces=False):
+def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0, fused=False, pieces=False,
+               presentation=0):
     """Decodes one track on the GPU.  Returns a dict: codec ("PCM"/"MLP"), bits, rate, channels,
     mask, status, and pcm = int32 [frames, channels] (interleaved, RIFF-WAVE order) read with
     dvda_read() in `chunk`-frame calls -- or, with wav=True, payload = the WAV data bytes packed
@@ -119,7 +124,9 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
     MLP tracks are decoded straight into that payload, no int32 PCM and no packing pass.  Device and output form are
     the READER's: no process-wide switch is left behind.  pieces=True (with wav=True) takes the payload piece by piece
     (dvda_hip_reader_wav_next: a long track's windows).  A track read in windows (info["windowed"]) reports the peaks of
-    what it held in info["host_peak"] / info["device_peak"]; info["frames"] is then the count at the END of the read."""
+    what it held in info["host_peak"] / info["device_peak"]; info["frames"] is then the count at the END of the read.
+    presentation=1: the 2-channel presentation of a two-substream MLP track (dvda_hip_open_track_reader_with: substream 0
+    alone; info["channels"] is then k and the frames have k channels)."""
     L = lib()
     d = L.dvda_open(audio_ts.encode(), None)
     if not d:
@@ -129,7 +136,7 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
         ts = L.dvda_open_titleset(d, titleset)
         t = L.dvda_open_title(ts, title) if ts else None
         k = L.dvda_open_track(t, track) if t else None
-        r = L.dvda_hip_open_track_reader_on(k, device, 1 if (fused and wav) else 0) if k else None
+        r = L.dvda_hip_open_track_reader_with(k, device, 1 if (fused and wav) else 0, presentation) if k else None
         if not r:
             raise RuntimeError("track %d/%d/%d cannot be opened for reading" % (titleset, title, track))
         ch = L.dvda_channel_count(r)

@@ -31,6 +31,12 @@ class StreamInfo(ctypes.Structure):
                 ("reserved", ctypes.c_uint32)]
 
 
+class SegmentInfo(ctypes.Structure):
+    """dvda_mlp_segment_info of include/dvda_mlp_hip.h"""
+    _fields_ = [("offset", ctypes.c_uint64), ("end", ctypes.c_uint64), ("stream", ctypes.c_uint32),
+                ("mlp_frames", ctypes.c_uint32), ("pcm_frames", ctypes.c_uint32), ("status", ctypes.c_uint32)]
+
+
 class MultiSummary(ctypes.Structure):
     """dvda_mlp_multi_summary of include/dvda_mlp_hip.h"""
     _fields_ = [("pcm_frames", ctypes.c_uint64), ("samples", ctypes.c_uint64), ("compressed_bytes", ctypes.c_uint64),
@@ -59,7 +65,8 @@ EXPORTS = ("dvda_mlp_hip_create", "dvda_mlp_hip_destroy", "dvda_mlp_hip_index", 
            "dvda_mlp_hip_demux_sectors", "dvda_mlp_hip_pack_wav",
            "dvda_mlp_hip_shard", "dvda_mlp_hip_create_multi", "dvda_mlp_hip_destroy_multi",
            "dvda_mlp_hip_multi_devices", "dvda_mlp_hip_decode_multi", "dvda_mlp_hip_multi_device_time",
-           "dvda_mlp_hip_set_conceal", "dvda_mlp_hip_conceal_spans")
+           "dvda_mlp_hip_set_conceal", "dvda_mlp_hip_conceal_spans",
+           "dvda_mlp_hip_set_presentation", "dvda_mlp_hip_present_time")
 
 ST_CONCEALED = 1 << 30          # DVDA_ST_CONCEALED: conceal mode, the stream was damaged (not in ST_BENIGN)
 CONCEAL_LEADING, CONCEAL_TRAILING, CONCEAL_ROUNDS = 1, 2, 4     # DVDA_CONCEAL_* span flags
@@ -134,6 +141,10 @@ def lib():
         L.dvda_mlp_hip_decode_multi.argtypes = [vp, vp, vp, u32, u32, vp, vp, ctypes.POINTER(StreamInfo),
                                                 ctypes.POINTER(MultiSummary)]
         L.dvda_mlp_hip_set_conceal.argtypes = [vp, ctypes.c_int]
+        L.dvda_mlp_hip_set_presentation.argtypes = [vp, u32]
+        L.dvda_mlp_hip_segment_info.argtypes = [vp, u32, ctypes.POINTER(SegmentInfo), vp]
+        L.dvda_mlp_hip_present_time.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(u64),
+                                                ctypes.POINTER(u64)]
         L.dvda_mlp_hip_set_initial_fir.argtypes = [vp, vp]
         L.dvda_mlp_hip_segment_fir.argtypes = [vp, u32, vp, vp]
         L.dvda_mlp_hip_conceal_spans.argtypes = [vp, u32, ctypes.POINTER(ConcealSpan), u32, ctypes.POINTER(u32), vp]
@@ -148,6 +159,7 @@ def _check(rc, what):
 
 
 PCM_PLANAR, PCM_INTERLEAVED, PCM_WAV24, PCM_WAV16 = 0, 1, 2, 3      # DVDA_PCM_* of include/dvda_mlp_hip.h
+PRESENT_FULL, PRESENT_SUBSTREAM0 = 0, 1     # DVDA_PRESENT_*: the full decode / substream 0 alone, the 2-channel presentation
 CHAIN_FORM = 0      # tests: 1 / 2 force the fused / two-pass form of the chain passes on every Context made afterwards
 
 
@@ -176,6 +188,18 @@ class Context:
         except Exception:
             pass
 
+    def set_presentation(self, presentation):
+        """dvda_mlp_hip_set_presentation: PRESENT_FULL (default) or PRESENT_SUBSTREAM0 -- two-substream streams decode
+        to the k-channel presentation substream 0 carries; asks for a new index()"""
+        _check(lib().dvda_mlp_hip_set_presentation(self._h, presentation), "dvda_mlp_hip_set_presentation")
+
+    def present_time(self):
+        """-> (device ms of the strip kernels of the last index, source bytes, presentation bytes)"""
+        ms, a, b = ctypes.c_double(), ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().dvda_mlp_hip_present_time(self._h, ctypes.byref(ms), ctypes.byref(a), ctypes.byref(b)),
+               "dvda_mlp_hip_present_time")
+        return float(ms.value), int(a.value), int(b.value)
+
     def index(self, d_bytes_ptr, total_bytes, d_off_ptr, d_len_ptr, n_streams, stream=0):
         self.n_streams = n_streams
         _check(lib().dvda_mlp_hip_index(self._h, d_bytes_ptr, total_bytes, d_off_ptr, d_len_ptr,
@@ -203,6 +227,17 @@ class Context:
         v = ctypes.c_uint32()
         _check(lib().dvda_mlp_hip_segment_count(self._h, ctypes.byref(v), stream), "segment_count")
         return int(v.value)
+
+    def segment_info(self, segment, stream=0):
+        info = SegmentInfo()
+        _check(lib().dvda_mlp_hip_segment_info(self._h, segment, ctypes.byref(info), stream), "segment_info")
+        return info
+
+    def segment_fir(self, segment, stream=0):
+        """FIR history [2][48] at the end of `segment` (dvda_mlp_hip_segment_fir)"""
+        fir = np.zeros((2, 48), np.int32)
+        _check(lib().dvda_mlp_hip_segment_fir(self._h, segment, fir.ctypes.data, stream), "segment_fir")
+        return fir
 
     def decode_time(self):
         """mean device ms of a whole decode call (all passes); call before kernel_time(), which resets the ring"""
@@ -234,7 +269,8 @@ def pack_streams(streams):
     return flat, np.asarray(offs, np.uint64), np.asarray(lens, np.uint64)
 
 
-def decode_streams(streams, device=0, max_segments=None, lanes_per_segment=0, layout=PCM_PLANAR, ctx=None):
+def decode_streams(streams, device=0, max_segments=None, lanes_per_segment=0, layout=PCM_PLANAR, ctx=None,
+                   presentation=PRESENT_FULL):
     """Decodes a list of complete MLP byte streams on the GPU.
 
     Returns (pcm, infos): pcm[i] is an int32 array [channels, pcm_frames] in RIFF-WAVE
@@ -245,6 +281,8 @@ def decode_streams(streams, device=0, max_segments=None, lanes_per_segment=0, la
     HipError if the HIP path is unavailable; never falls back to a CPU decoder.
     `ctx`: a caller's Context to run on (it stays open and keeps its size: a batch it cannot hold raises); its lane
     and layout settings are set to this call's.
+    presentation=PRESENT_SUBSTREAM0: two-substream streams come out as the k-channel presentation of substream 0
+    (pcm[i] is [k, pcm_frames], infos[i].channels == k); one-substream streams as always.
     """
     import torch
     if not torch.cuda.is_available():
@@ -260,6 +298,8 @@ def decode_streams(streams, device=0, max_segments=None, lanes_per_segment=0, la
     else:
         _check(lib().dvda_mlp_hip_set_lanes_per_segment(ctx._h, lanes_per_segment), "set_lanes")
         _check(lib().dvda_mlp_hip_set_pcm_layout(ctx._h, layout), "set_pcm_layout")
+    if presentation != PRESENT_FULL or not own:
+        ctx.set_presentation(presentation)
     try:
         d_bytes = torch.from_numpy(flat).to(dev)
         d_off = torch.from_numpy(offs.astype(np.int64)).to(dev)
@@ -276,6 +316,8 @@ def decode_streams(streams, device=0, max_segments=None, lanes_per_segment=0, la
             lib().dvda_mlp_hip_segment_count(ctx._h, ctypes.byref(v), st)
             ctx.close()
             ctx = Context(device, len(streams), int(v.value) + 64, lanes_per_segment, layout)
+            if presentation != PRESENT_FULL:
+                ctx.set_presentation(presentation)
             ctx.index(d_bytes.data_ptr(), total, d_off.data_ptr(), d_len.data_ptr(), len(streams), st)
         infos = ctx.stream_info(stream=st)
         rows, nch = [], []
@@ -442,7 +484,7 @@ def decode_streams_multi(streams, devices, layout=PCM_PLANAR, max_segments=None)
         lib().dvda_mlp_hip_destroy_multi(h)
 
 
-def decode_streams_wav(streams, bits, device=0, lanes_per_segment=0):
+def decode_streams_wav(streams, bits, device=0, lanes_per_segment=0, presentation=PRESENT_FULL):
     """Decodes complete MLP byte streams straight into the interleaved little-endian WAV payload dvda2wav
     writes (DVDA_PCM_WAV24 / DVDA_PCM_WAV16: the output stage fused into the decode kernels).
     -> (list of uint8 arrays, infos)."""
@@ -456,6 +498,8 @@ def decode_streams_wav(streams, bits, device=0, lanes_per_segment=0):
     total = int(len(flat) - 64)
     ctx = Context(device, len(streams), max(64, total // 64), lanes_per_segment, PCM_WAV24 if bits == 24 else PCM_WAV16)
     try:
+        if presentation != PRESENT_FULL:
+            ctx.set_presentation(presentation)
         d_bytes = torch.from_numpy(flat).to(dev)
         d_off = torch.from_numpy(offs.astype(np.int64)).to(dev)
         d_len = torch.from_numpy(lens.astype(np.int64)).to(dev)

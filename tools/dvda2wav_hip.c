@@ -56,7 +56,7 @@ static double now_s(void)
     return ts.tv_sec + ts.tv_nsec * 1e-9;
 }
 
-static int extract(DVDA_Title *title, unsigned track_num, const char *dir, int device, int fused_wav)
+static int extract(DVDA_Title *title, unsigned track_num, const char *dir, int device, int fused_wav, int stereo)
 {
     const int timing = getenv("DVDA_TOOL_TIMING") != NULL;       /* diagnostic: where a track's wall-clock time goes */
     const double t_begin = now_s();
@@ -67,7 +67,8 @@ static int extract(DVDA_Title *title, unsigned track_num, const char *dir, int d
         return 0;
     }
     /* this tool only ever writes WAV files: MLP tracks are decoded straight into the payload */
-    DVDA_Track_Reader *r = dvda_hip_open_track_reader_on(track, device, fused_wav);
+    /* --stereo: a two-substream MLP track comes out as the 2-channel presentation its substream 0 carries */
+    DVDA_Track_Reader *r = dvda_hip_open_track_reader_with(track, device, fused_wav, stereo);
     if (!r) {
         fprintf(stderr, "*** Error: unable to open track %u for reading\n", track_num);
         dvda_close_track(track);
@@ -145,6 +146,7 @@ struct pool {
     atomic_uint next, failed, done;     /* done: workers through with the job list */
     const char *dir;
     int fused_wav;
+    int stereo;                         /* --stereo: the 2-channel presentation of two-substream MLP tracks */
     int park;                           /* a worker that is through parks instead of ending (the fast way out) */
 };
 struct worker {
@@ -160,7 +162,7 @@ static void *work(void *arg)
         const unsigned i = atomic_fetch_add(&w->pool->next, 1);
         if (i >= w->pool->n_jobs)
             break;
-        if (!extract(w->pool->jobs[i].title, w->pool->jobs[i].track, w->pool->dir, w->device, w->pool->fused_wav))
+        if (!extract(w->pool->jobs[i].title, w->pool->jobs[i].track, w->pool->dir, w->device, w->pool->fused_wav, w->pool->stereo))
             atomic_fetch_add(&w->pool->failed, 1);
     }
     /* (what this thread's last windowed reader left for a next one would be freed when the thread ends -- 30 ms a worker.
@@ -184,6 +186,8 @@ static void usage(const char *prog)
            "  -T TITLE, --title=TITLE   title number to extract (default: all)\n"
            "  -t TRACK, --track=TRACK   track number to extract (default: all)\n"
            "  -d DIR, --dir=DIR         output directory (default: the working directory)\n"
+           "  -2, --stereo              write the 2-channel presentation of multichannel MLP tracks (substream 0\n"
+           "                            alone: the stereo mix a 2-channel player plays), not all channels\n"
            "  -g N, --gpu=N             HIP device (default 0)\n"
            "  -D LIST, --devices=LIST   comma-separated HIP devices: one worker thread per entry takes tracks in turn\n"
            "                            (default: up to four workers on the device of -g)\n"
@@ -196,15 +200,15 @@ int main(int argc, char *argv[])
                                        {"titleset", required_argument, 0, 'S'}, {"title", required_argument, 0, 'T'},
                                        {"track", required_argument, 0, 't'},    {"dir", required_argument, 0, 'd'},
                                        {"gpu", required_argument, 0, 'g'},      {"help", no_argument, 0, 'h'},
-                                       {"devices", required_argument, 0, 'D'},
+                                       {"devices", required_argument, 0, 'D'},  {"stereo", no_argument, 0, '2'},
                                        {0, 0, 0, 0}};
     const char *audio_ts = NULL, *dir = ".", *cdrom = NULL;
     unsigned titleset_num = 1, title_num = 0, track_num = 0;
-    int devices[64], n_devices = 0, one_device = 0;
+    int devices[64], n_devices = 0, one_device = 0, stereo = 0;
     int c;
     if (getenv("DVDA_TOOL_TIMING"))
         fprintf(stderr, "timing: main at %.1f ms\n", now_s() * 1e3);
-    while ((c = getopt_long(argc, argv, "A:c:S:T:t:d:g:D:h", longopts, NULL)) != -1) {
+    while ((c = getopt_long(argc, argv, "A:c:S:T:t:d:g:D:h2", longopts, NULL)) != -1) {
         switch (c) {
         case 'A': audio_ts = optarg; break;
         case 'c': cdrom = optarg; break;
@@ -217,6 +221,7 @@ int main(int argc, char *argv[])
             for (char *tok = strtok(optarg, ","); tok && n_devices < 64; tok = strtok(NULL, ","))
                 devices[n_devices++] = atoi(tok);
             break;
+        case '2': stereo = 1; break;
         case 'h': usage(argv[0]); return 0;
         default: return 1;
         }
@@ -268,7 +273,7 @@ int main(int argc, char *argv[])
         for (unsigned i = 0; i < w; i++)
             devices[n_devices++] = one_device;
     }
-    struct pool pool = {jobs, n_jobs, 0, 0, 0, dir, fused_wav, getenv("DVDA_TOOL_FULL_TEARDOWN") == NULL};
+    struct pool pool = {jobs, n_jobs, 0, 0, 0, dir, fused_wav, stereo, getenv("DVDA_TOOL_FULL_TEARDOWN") == NULL};
     struct worker workers[64];
     pthread_t th[64];
     int started[64];
