@@ -23,6 +23,18 @@ struct WsCaps {
     uint32_t pad;
 };
 
+constexpr int FREC_WORDS = 36;     // per access unit: 4 header words + 6 matrices x 5 + pad
+
+// What the chain passes need of their workspaces (elements, as in WsCaps) for `segs` deferred segments of `rows` PCM
+// frames in all.  The one statement of it: the host sizes and reserves by it, k_chain_guard refuses by it.
+struct ChainNeed {
+    uint64_t res, brec, frec;
+};
+__host__ __device__ inline ChainNeed chain_need(uint64_t rows, uint64_t segs)
+{
+    return {rows * 8 + 64, 16 * rows + 256 * segs + 64, (rows / 40 + segs + 1) * FREC_WORDS};
+}
+
 #if defined(DVDA_BOUNDS)
 __device__ unsigned long long g_bounds[4];      // violations, then the first one's tag / index / capacity
 __device__ uint32_t g_sink[64];

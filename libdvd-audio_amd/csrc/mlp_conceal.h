@@ -6,7 +6,7 @@
 //   k_conceal_gather the ranges to decode again, copied into a 16-byte aligned workspace (a second index)
 //   k_conceal_move   decoded ranges from their scratch to their place in the caller's buffer
 //   k_conceal_fill   zeros for the concealed spans
-// The host (mlp_hip.hip, conceal_run) decodes the ranges in rounds, each range a stream of its own with fresh state,
+// The host (mlp_conceal_run.h, conceal_run) decodes the ranges in rounds, each range a stream of its own with fresh state,
 // and lays the result out; DESIGN.md section "Conceal mode" states the rule.
 #pragma once
 #include <hip/hip_runtime.h>

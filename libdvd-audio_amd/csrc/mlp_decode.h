@@ -206,7 +206,7 @@ constexpr uint32_t HDR_FIR = 7;             // a channel's first bit + FIR param
 constexpr uint32_t HDR_IIR = 7;             // IIR parameters up to the taps: 145 bits
 constexpr uint32_t HDR_IIR_STATE = 7;       // IIR state (129 bits) + Huffman offset, code book, LSB count (23)
 constexpr uint32_t SUMMARY_PARTS = 64;      // the fast pass adds into summary[1 + block % 64]; k_finalize folds them into summary[0]
-constexpr int FREC_WORDS = 36;     // per access unit: 4 header words + 6 matrices x 5 + pad
+// (FREC_WORDS, the dwords of an access-unit record: mlp_bounds.h, beside the workspace sizes that follow from it)
 // Block records (round 4: fixed places, so that the pass that reads them can ask for a record before it knows
 // what the record before it holds).  Record r of a (segment, substream) -- its r-th block that sets filter
 // parameters -- is six slots of eight dwords at r * BREC_STRIDE; slot k:

@@ -1,4 +1,4 @@
-/* mlp_step.h -- between mlp_stream.c (tier B, the mlp.h mirror: plain C) and mlp_hip.hip: a decoder whose state stays
+/* mlp_step.h -- between mlp_stream.c (tier B, the mlp.h mirror: plain C) and mlp_stepper.h (a part of mlp_hip.hip): a decoder whose state stays
  * on the device from one packet to the next.  Internal to the library (tier B is the public face:
  * include/dvda_mlp_hip.h, dvda_hip_mlpdecoder_decode_packet).
  *
