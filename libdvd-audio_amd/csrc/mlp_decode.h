@@ -427,8 +427,9 @@ __device__ __attribute__((noinline)) void iir_push(int32_t *ws, uint32_t stride,
 // code from a nearby reference (tell_near); dword indices are 32-bit: a batch buffer is limited to 16 GiB
 // (checked by dvda_mlp_hip_index).
 // RD: dwords the ring holds (a power of two; planes 1 .. RD and the mirror, plane 0); G: dwords a fill brings (16: a
-// 64-byte chunk, four loads -- the one-substream kernels; 4: one 16-byte load -- the two small rings of a lane that reads
-// both substreams of its segment, DUO)
+// 64-byte chunk, four loads -- the sequential pass; 4: 16-byte granules, up to four a fill -- the 32-dword ring of the
+// one-substream lane kernels, whose wave refills together, and the two small rings of a lane that reads both
+// substreams of its segment, DUO)
 template <int RD, int G>
 struct BitReaderT {
     const uint4 *gsrc;      // global bytes as 16-byte units
@@ -477,6 +478,26 @@ struct BitReaderT {
         if constexpr (G == CHUNK_DWORDS) {
             ring_fill_sync(gsrc + (fill_src() >> 2), slot(fillpos), (fillpos & (RD - 1)) == 0);
             filled();
+        } else if constexpr (RD > 16) {
+            // the 32-dword ring by granules: the four loads unconditional (clamped to the buffer's last granule, so in
+            // bounds whatever the ring has room for) and in flight together, the commit for the granules there is room
+            // for.  Under the commit's own `g < n` the compiler joined each load to its commit -- load, wait, swap, four
+            // times: four memory round trips for the whole wave where the chunk fill took one.
+            uint4 q[4];
+            const int32_t r = (RD - ahead()) >> 2;
+            const int32_t n = r < 4 ? r : 4;
+            // (the clamp against the buffer's END, the bound the row loop's request already keeps in a scalar register:
+            //  one more bound was one more spilled scalar, read back by v_readlane inside the row loop's top-up)
+            const uint32_t end = max_chunk + (uint32_t)CHUNK_DWORDS;
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const uint32_t e = fillpos + 4u * g + 4u;
+                q[g] = gsrc[((e < end ? e : end) >> 2) - 1u];
+            }
+            // all four have landed before anything else happens, the ones no commit reads among them: a load the
+            // compiler still counts as on its way when the row loop is reached costs a vmcnt(0) at the top of every row
+            __builtin_amdgcn_s_waitcnt(0x0F70);
+            fill_commit(q, n);
         } else {
             uint4 q[4];
             const int32_t n = fill_issue(q);
@@ -490,9 +511,10 @@ struct BitReaderT {
     template <int MAXG = 4>
     __device__ __forceinline__ int32_t fill_issue(uint4 (&q)[MAXG]) const
     {
-        static_assert(G == CHUNK_DWORDS || (G == 4 && RD == 16), "the small ring is 16 dwords filled by 16-byte granules");
-        int32_t n = room() ? (RD - ahead()) >> 2 : 0;           // 0 .. 4 granules
-        if (MAXG < 4 && n > MAXG)
+        static_assert(G == CHUNK_DWORDS || (G == 4 && (RD == 16 || RD == 32)),
+                      "granule fills: the two small rings of a two-substream lane, or the 32-dword ring");
+        int32_t n = room() ? (RD - ahead()) >> 2 : 0;           // 0 .. 4 granules (the 32-dword ring has room for up to 8)
+        if ((MAXG < 4 || RD > 16) && n > MAXG)
             n = MAXG;
 #pragma unroll
         for (int g = 0; g < MAXG; g++)
@@ -723,7 +745,10 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                                                                   // a row's bypassed LSBs and noise seed in registers: with two
                                                                   // more planes its workgroup was 34 KB of LDS and only three fit a CU)
     constexpr int RD = DUO ? DUO_RING : RING_DWORDS;            // dwords a ring holds
-    constexpr int RG = DUO ? DUO_GRAN : CHUNK_DWORDS;           // dwords a fill brings
+    // the one-substream lane instances (fast pass and chain parse pass) refill by granules, the whole wave in the
+    // same row (WAVE_FILL below); the sequential pass keeps the 64-byte chunk a lane asks for by itself
+    constexpr bool WAVE_FILL = !DUO && !PAIRED;
+    constexpr int RG = DUO ? DUO_GRAN : WAVE_FILL ? 4 : CHUNK_DWORDS;   // dwords a fill brings
     using Reader = BitReaderT<RD, RG>;
     __shared__ uint32_t s_ring[WAVES][DUO ? 2 : 1][RD + 1][64];     // + the mirror of plane 0 (DUO: a ring per substream)
     __shared__ int32_t s_out[GENERAL ? 1 : WAVES][TP][OUT_ROWS][GENERAL ? 1 : 64];   // PCM staging
@@ -1901,8 +1926,15 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
         // both 64-byte halves of a 128-byte line are requested in consecutive rows, while the line
         // is still in L2 (one HBM fetch per line); a new line is started when half the ring is free
         // (DUO: sixteen bytes per ring and row, whenever the ring has room for them)
-        const bool pf = active && rd.room();
+        // (WAVE_FILL: the request is the WAVE's.  A lane of its own asks every fifth row, at its own phase, and the wave
+        //  then runs the request, the wait's commit and its sixteen byte swaps in practically every row for a fifth of
+        //  its lanes.  When ANY lane is down to FILL_TURN dwords -- where it asked by itself, so none is served later --
+        //  EVERY lane takes the 16-byte granules its ring has room for, up to four, and the rows in between run none of
+        //  this: one row of three or four.  `fn`: the granules this lane takes this row; 0 in a row without a turn)
+        constexpr int32_t FILL_TURN = 16;
+        const bool pf = !WAVE_FILL && active && rd.room();
         const bool pfx = DUO && active && rx.room();
+        int32_t fn = 0;
         // Four registers each, written by the loads below and read under the same `pf`.  They must hold a DEFINED
         // value on the lanes that do not load.  Zero-filling them with instructions made the compiler wait for
         // every outstanding memory operation -- the previous row's PCM stores included -- before it could
@@ -1922,6 +1954,23 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                 p0 = rx.gsrc[rx.fill_src() >> 2];
             if (pf)
                 p1 = rd.gsrc[rd.fill_src() >> 2];
+        } else if constexpr (WAVE_FILL) {
+            if (__any(active && rd.ahead() <= FILL_TURN)) {
+                const int32_t r = (RD - rd.ahead()) >> 2;
+                fn = active ? (r < 4 ? r : 4) : 0;
+                // past the buffer's end the granules come from its last ones (the spare bytes), as many as are asked for
+                const uint32_t end = rd.max_chunk + (uint32_t)CHUNK_DWORDS;
+                const uint32_t last = end - 4u * (uint32_t)fn;
+                const uint4 *src = rd.gsrc + ((rd.fillpos < last ? rd.fillpos : last) >> 2);
+                if (fn > 0)
+                    p0 = src[0];
+                if (fn > 1)
+                    p1 = src[1];
+                if (fn > 2)
+                    p2 = src[2];
+                if (fn > 3)
+                    p3 = src[3];
+            }
         } else {
         if (pf) {
             const uint32_t c = rd.fillpos < rd.max_chunk ? rd.fillpos : rd.max_chunk;
@@ -2409,6 +2458,25 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
             if (pf) {
                 ring_store4<RD>(rd.slot(rd.fillpos), p1, (rd.fillpos & (RD - 1)) == 0);
                 rd.filled();
+            }
+        } else if constexpr (WAVE_FILL) {
+            // behind a branch of the wave's: a row without a turn runs none of it
+            if (__any(fn > 0)) {
+                const uint32_t f = rd.fillpos;
+                if (fn > 0) {
+                    ring_store4<RD>(rd.slot(f), p0, (f & (RD - 1)) == 0);
+                    if (fn > 1) {
+                        ring_store4<RD>(rd.slot(f + 4u), p1, ((f + 4u) & (RD - 1)) == 0);
+                        if (fn > 2) {
+                            ring_store4<RD>(rd.slot(f + 8u), p2, ((f + 8u) & (RD - 1)) == 0);
+                            if (fn > 3)
+                                ring_store4<RD>(rd.slot(f + 12u), p3, ((f + 12u) & (RD - 1)) == 0);
+                        }
+                    }
+                    rd.fillpos = f + 4u * (uint32_t)fn;
+                    if (rd.fillpos - rd.lo_valid > (uint32_t)RD)
+                        rd.lo_valid = rd.fillpos - RD;                  // the oldest granules were overwritten
+                }
             }
         } else {
         if (pf) {
