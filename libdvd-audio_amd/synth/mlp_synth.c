@@ -39,6 +39,14 @@ static inline int rnd_chance(rng_t *r, unsigned percent)
 {
     return rnd_below(r, 100) < percent;
 }
+/* lo..hi with both ends favoured (extended modes) */
+static int rnd_rail(rng_t *r, int lo, int hi)
+{
+    const uint32_t k = rnd_below(r, 10);
+    if (k == 0) return lo;
+    if (k == 1) return hi;
+    return rnd_range(r, lo, hi);
+}
 
 /* ----------------------------------------------------------- bit writer */
 typedef struct {
@@ -147,6 +155,11 @@ typedef struct {
     filt_t fir, iir;
     int huff_off;
     unsigned codebook, lsbs;
+    /* extended modes only (see "extended modes" below) */
+    int64_t fir_sum, iir_sum; /* sum of |coefficient| of the taps in force                    */
+    unsigned iir_eref;        /* smallest filter shift the IIR taps can meet                  */
+    int64_t sbound;           /* bound on |IIR state entry| since the state was last loaded   */
+    int rail, rail_used;      /* FIR is the rail template now / has been once in this stream  */
 } chan_t;
 
 typedef struct {
@@ -158,6 +171,10 @@ typedef struct {
     unsigned qss[MAXCH];
     chan_t ch[MAXCH];
     int have_restart;
+    /* extended modes only */
+    unsigned noise_shift;
+    unsigned oshift[MAXCH];
+    int64_t mat_bound[MAXCH]; /* bound on |channel value| after the matrices in force */
 } ss_t;
 
 typedef struct {
@@ -167,6 +184,11 @@ typedef struct {
     unsigned rows_per_au;
     ss_t ss[2];
     unsigned leadin; /* current block must use order-0 filters */
+    unsigned f;      /* feature bits in force (0 for the recipe) */
+    /* extended modes only */
+    int full, wide;  /* MLP_SF_FULLSCALE / MLP_SF_WIDEPARAMS */
+    int64_t vn;      /* the stream's bound on a filtered value outside the rail template (2 * vn with it) */
+    int fail;        /* the bookkeeping found no parameters that fit: the stream is not written */
 } gen_t;
 
 static const int RECIPE_FIR[8] = {8192, -4096, 2048, -1024, 512, -256, 128, -64};
@@ -183,7 +205,7 @@ static unsigned bits_for_signed(int maxabs_pos, int minneg)
 /* ---- restart header: reference src/mlp.c:822-851 */
 static void put_restart_header(gen_t *g, bw_t *w, ss_t *s, unsigned au_index)
 {
-    const unsigned f = g->cfg->profile ? g->cfg->features : 0;
+    const unsigned f = g->f;
     unsigned c;
     unsigned noise_shift = (f & MLP_SF_NOISE) ? rnd_below(&g->rng, 8) : rnd_below(&g->rng, 3);
     bw_put(w, 13, 0x18F5);
@@ -192,6 +214,9 @@ static void put_restart_header(gen_t *g, bw_t *w, ss_t *s, unsigned au_index)
     bw_put(w, 4, s->min_ch);
     bw_put(w, 4, s->max_ch);
     bw_put(w, 4, s->max_matrix_ch);
+    if (g->wide)
+        noise_shift = (unsigned)rnd_rail(&g->rng, 0, 15); /* 4-bit field, reference src/mlp.c:827; used at src/mlp.c:1330-1332 */
+    s->noise_shift = noise_shift;
     bw_put(w, 4, noise_shift);
     bw_put(w, 23, rnd(&g->rng) & 0x7FFFFF);            /* noise_gen_seed */
     bw_put(w, 19, rnd(&g->rng) & 0x7FFFF);             /* unknown */
@@ -212,7 +237,7 @@ static void put_restart_header(gen_t *g, bw_t *w, ss_t *s, unsigned au_index)
 static void put_matrices(gen_t *g, bw_t *w, ss_t *s, unsigned maxlen)
 {
     const mlp_synth_cfg *cfg = g->cfg;
-    const unsigned f = cfg->profile ? cfg->features : 0;
+    const unsigned f = g->f;
     const unsigned ncoef = s->max_matrix_ch + 3;
     unsigned m, c;
     unsigned len = cfg->n_matrices;
@@ -271,7 +296,7 @@ static void put_fir(gen_t *g, bw_t *w, chan_t *ch, unsigned order_limit, int all
                     unsigned forced_shift)
 {
     const mlp_synth_cfg *cfg = g->cfg;
-    const unsigned f = cfg->profile ? cfg->features : 0;
+    const unsigned f = g->f;
     unsigned order, i;
     int coef[8];
     unsigned shift;
@@ -388,6 +413,373 @@ static void put_iir(gen_t *g, bw_t *w, chan_t *ch, int allow)
     ch->iir.shift = shift;
 }
 
+/* ------------------------------------------------------- extended modes */
+/* MLP_SF_FULLSCALE and MLP_SF_WIDEPARAMS leave the low corner of the arithmetic that the other features stay in, so
+ * the envelope of SURVEY.md A.4 -- no int32 overflow in shifted_sum + residual and value - shifted_sum (reference
+ * src/mlp.c:1293-1299), in the matrix result (src/mlp.c:1342-1355) or in value << output_shift (src/mlp.c:522, 592)
+ * -- is kept by bookkeeping, never by decoding the stream and looking:
+ *
+ *   vn        drawn once per stream.  Every filtered value stays within vn (2 * vn on a channel that has used the
+ *             rail template), so the matrices may take 2 * vn for every input channel whatever block it comes from
+ *             (the reference rematrixes a whole frame with the parameters its last block leaves).
+ *   residual  rb = the largest |residual| the channel's code book / huffman_lsbs / offset / quant_step_size can code,
+ *             plus 2^qss for mask() (src/mlp.c:246-253).  An IIR state entry is value - shifted_sum, within rb too.
+ *   taps      with A = sum|FIR coeff| / 2^shift, B = sum|IIR coeff| / 2^shift and S the bound on the IIR state, a
+ *             history within v gives |value| <= A v + B S + rb + 2; chan_fits() demands that this is <= v.  A <= 3/4
+ *             as before; the taps are drawn with rb counted as at least vn / 8, and offsets and step sizes are kept
+ *             so small that the narrowest coding ((|offset| + 2) << qss) stays below vn / 64: whatever a later block
+ *             changes and whichever fields its flags let it send, some huffman_lsbs fits.  huffman_lsbs is lowered
+ *             until the channel fits; the stream fails (returns 0) should nothing fit.
+ *   rails     a FIR tap of -32768 (or +32767) at shift 15 cannot satisfy A < 1.  It comes as the template
+ *             {-32768 | +32767, -8192, 0...}: poles of modulus 1/2, sum|impulse response| <= 4, and a history within
+ *             vn rings within 1.5 vn.  A channel uses it once per stream and only while 4 (B S + rb + 2) <= vn / 2,
+ *             which keeps the channel within 2 vn from then on.  IIR and matrix rails need no template.
+ *   matrices  each output's bound is sum |coeff| * bound(input) >> 14 plus noise, mask and bypass bit; a coefficient
+ *             that would take it past min(2^30, int32 >> output_shift in force) is written as absent.  Output shifts
+ *             are drawn up to what the bound of their channel leaves.
+ * `wide` draws every field from its whole range with both ends favoured (rnd_rail). */
+static int64_t max64(int64_t a, int64_t b) { return a > b ? a : b; }
+static int64_t min64(int64_t a, int64_t b) { return a < b ? a : b; }
+
+/* largest |residual| of reference src/mlp.c:1152-1176, 1230-1236, plus mask()'s 2^q */
+static int64_t res_bound(unsigned cb, unsigned lsbs, unsigned q, int off)
+{
+    const unsigned lb = lsbs - q;
+    const int64_t a = off < 0 ? -(int64_t)off : off;
+    /* code book values 0..17 around 7, sign term at most 2^(lb+1): within 11 * 2^lb */
+    const int64_t m = cb ? (int64_t)11 << lb : (lb ? (int64_t)1 << (lb - 1) : 0);
+    return ((m + a) << q) + ((int64_t)1 << q);
+}
+
+static int64_t chan_v(const gen_t *g, const chan_t *ch) { return ch->rail_used ? 2 * g->vn : g->vn; }
+
+static int64_t chan_ff(const chan_t *ch, int64_t rb)
+{
+    return ch->iir.order ? ((ch->iir_sum * max64(ch->sbound, rb)) >> ch->iir_eref) + 1 : 0;
+}
+
+static int chan_fits(const gen_t *g, const chan_t *ch, int64_t rb)
+{
+    const int64_t v = chan_v(g, ch);
+    if (ch->rail)
+        return 4 * (chan_ff(ch, rb) + rb + 2) <= g->vn / 2;
+    return (ch->fir.order ? ((ch->fir_sum * v) >> ch->fir.shift) + 1 : 0) + chan_ff(ch, rb) + rb + 2 <= v;
+}
+
+static void ext_reset_matrices(const gen_t *g, ss_t *s)
+{
+    unsigned c;
+    for (c = 0; c < MAXCH; c++)
+        s->mat_bound[c] = 2 * g->vn;
+}
+
+/* shift, coeff_bits, coeff_shift, coefficients: reference src/mlp.c:1040-1055 (FIR), 1082-1097 (IIR);
+   coeff_bits 1..16 and coeff_bits + coeff_shift <= 16 are all the parser asks (src/mlp.c:1043-1047, 1085-1089) */
+static void put_coeffs(gen_t *g, bw_t *w, const int *coef, unsigned order, unsigned shift)
+{
+    unsigned cshift = 7, cbits, i;
+    int mx = 0, mn = 0;
+    for (i = 0; i < order; i++) {
+        unsigned tz = 0;
+        if (coef[i] == 0) continue;
+        while (tz < 7 && !((coef[i] >> tz) & 1)) tz++;
+        if (tz < cshift) cshift = tz;
+    }
+    if (g->wide)
+        cshift = (unsigned)rnd_rail(&g->rng, 0, (int)cshift);
+    for (i = 0; i < order; i++) {
+        const int v = coef[i] >> cshift; /* exact: low bits are zero */
+        if (v > mx) mx = v;
+        if (v < mn) mn = v;
+    }
+    cbits = bits_for_signed(mx, mn); /* -32768: coeff_bits + coeff_shift = 16 and the most negative code */
+    bw_put(w, 4, shift);
+    bw_put(w, 5, cbits);
+    bw_put(w, 3, cshift);
+    for (i = 0; i < order; i++)
+        bw_put_signed(w, cbits, coef[i] >> cshift);
+}
+
+/* FIR of the channel being built (`n`); `rb` its residual bound, `iir_kept`: the IIR in n stays in force.
+   wide: shift 0..15, the 4-bit field of reference src/mlp.c:1040 (no assertion on it) */
+static void put_fir_ext(gen_t *g, bw_t *w, chan_t *n, unsigned lim, int allow, unsigned fs, int64_t rb, int iir_kept)
+{
+    const unsigned order = allow ? rnd_below(&g->rng, lim + 1) : 0;
+    const int64_t v = chan_v(g, n);
+    int coef[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned shift, i;
+    int64_t sum = 0;
+    chan_t t;
+
+    bw_put(w, 4, order);
+    n->fir.order = order;
+    n->fir.shift = 0;
+    n->fir_sum = 0;
+    n->rail = 0;
+    if (!iir_kept)
+        n->iir.order = 0; /* (re-sent below: it does not count here) */
+    if (order == 0)
+        return;
+    t = *n;
+    t.rail = 1;
+    if (g->full && !n->rail_used && order >= 2 && (fs == 0 || fs == 15) && rb <= g->vn / 32 &&
+        chan_fits(g, &t, max64(rb, g->vn / 64)) && rnd_chance(&g->rng, 15)) {
+        shift = 15;
+        coef[0] = (rnd(&g->rng) & 1) ? 32767 : -32768;
+        coef[1] = -8192;
+        n->rail = n->rail_used = 1;
+        sum = 32768 + 8192;
+    } else {
+        const int64_t rbres = max64(rb, g->vn / 8);
+        int64_t room = v - 3 - rbres - chan_ff(n, rbres), budget;
+        shift = fs ? fs : (unsigned)(g->wide ? rnd_rail(&g->rng, 0, 15) : rnd_range(&g->rng, 8, 15));
+        if (room < 0) room = 0;
+        budget = min64(((int64_t)3 << shift) >> 2, (room << shift) / v);
+        for (i = 0; i < order; i++) {
+            int mag = (int)rnd_below(&g->rng, (uint32_t)(budget / 2 + 1));
+            if (mag > 32767) mag = 32767;
+            budget -= mag;
+            sum += mag;
+            coef[i] = (rnd(&g->rng) & 1) ? mag : -mag;
+        }
+    }
+    put_coeffs(g, w, coef, order, shift);
+    bw_put(w, 1, 0); /* must be 0, reference src/mlp.c:1056 */
+    n->fir.shift = shift;
+    n->fir_sum = sum;
+}
+
+/* IIR of the channel being built, after its FIR.  wide: order up to 8 - FIR order (src/mlp.c:1075-1077, 1260), shift and
+   coeff_shift as for the FIR (src/mlp.c:1082, 1086), state_bits 1..15 and state_shift 0..15 (src/mlp.c:1100-1105: 4-bit
+   fields, no assertion; state_bits 0 is read_signed(0), and v << state_shift has to stay an int) */
+static void put_iir_ext(gen_t *g, bw_t *w, chan_t *n, int64_t rb)
+{
+    const unsigned limit = 8 - n->fir.order;
+    unsigned order = 0, shift, eref, sbits, sshift, i;
+    int coef[8];
+    int64_t sb0, sres, room, budget, sum = 0;
+
+    if (limit)
+        order = g->wide ? (rnd_chance(&g->rng, 35) ? limit : rnd_below(&g->rng, limit + 1))
+                        : rnd_below(&g->rng, (limit > 4 ? 4 : limit) + 1);
+    bw_put(w, 4, order);
+    n->iir.order = order;
+    n->iir.shift = 0;
+    n->iir_sum = 0;
+    n->iir_eref = 0;
+    n->sbound = 0;
+    if (order == 0)
+        return;
+    /* the shift that applies is the FIR's while it has taps; both shifts > 0 must agree (src/mlp.c:1262-1269) */
+    shift = (unsigned)(g->wide ? rnd_rail(&g->rng, 0, 15) : rnd_range(&g->rng, 8, 15));
+    eref = shift;
+    if (n->fir.order && n->fir.shift)
+        shift = eref = n->fir.shift;
+    else if (n->fir.order)
+        eref = 0;
+    if (g->wide) {
+        sbits = (unsigned)rnd_rail(&g->rng, 1, 15);
+        sshift = (unsigned)rnd_rail(&g->rng, 0, 31 - sbits > 15 ? 15 : 31 - sbits);
+    } else {
+        sbits = (unsigned)rnd_range(&g->rng, 2, 12);
+        sshift = rnd_below(&g->rng, 5);
+    }
+    sb0 = ((int64_t)1 << (sbits - 1)) << sshift;
+    if (n->rail) {
+        const int64_t rbres = max64(rb, g->vn / 64);
+        room = g->vn / 8 - 3 - rbres;
+        sres = max64(sb0, rbres);
+    } else {
+        const int64_t v = chan_v(g, n), rbres = max64(rb, g->vn / 8);
+        room = v - 3 - rbres - (n->fir.order ? ((n->fir_sum * v) >> n->fir.shift) + 1 : 0);
+        sres = max64(sb0, rbres);
+    }
+    if (room < 0) room = 0;
+    budget = min64((int64_t)1 << eref, (room << eref) / sres);
+    for (i = 0; i < order; i++) {
+        int mag = (int)rnd_below(&g->rng, (uint32_t)(budget / 2 + 1));
+        if (mag > 32767) mag = 32767;
+        coef[i] = (rnd(&g->rng) & 1) ? mag : -mag;
+        if (g->full && i == 0 && budget >= 32768 && rnd_chance(&g->rng, 30)) {
+            coef[i] = (rnd(&g->rng) & 1) ? 32767 : -32768;
+            mag = 32768;
+        }
+        budget -= mag;
+        sum += mag;
+    }
+    put_coeffs(g, w, coef, order, shift);
+    bw_put(w, 1, 1); /* state present */
+    bw_put(w, 4, sbits);
+    bw_put(w, 4, sshift);
+    for (i = 0; i < order; i++)
+        bw_put_signed(w, sbits, rnd_range(&g->rng, -(1 << (sbits - 1)), (1 << (sbits - 1)) - 1));
+    n->iir.shift = shift;
+    n->iir_eref = eref;
+    n->iir_sum = sum;
+    n->sbound = sb0;
+}
+
+/* one channel's parameters, reference src/mlp.c:940-990 */
+static void put_channel_ext(gen_t *g, bw_t *w, ss_t *s, unsigned c, int restart)
+{
+    const unsigned f = g->f;
+    chan_t *ch = &s->ch[c];
+    const unsigned q = s->qss[c];
+    const int filters_ok = !g->leadin;
+    int send = rnd_chance(&g->rng, (restart || (f & MLP_SF_DISC)) ? 85 : 60);
+    int sf, si, so, off;
+    unsigned cb, lsbs;
+    int64_t rb;
+    chan_t n = *ch;
+
+    if (restart) {
+        memset(&n, 0, sizeof(n));
+        n.lsbs = 24;
+        n.rail_used = ch->rail_used;
+    }
+    if (!send && (n.lsbs < q || !chan_fits(g, &n, res_bound(n.codebook, n.lsbs, q, n.huff_off))))
+        send = 1;
+    bw_put(w, 1, (uint32_t)send);
+    if (!send) {
+        n.sbound = max64(n.sbound, res_bound(n.codebook, n.lsbs, q, n.huff_off));
+        *ch = n;
+        return;
+    }
+    sf = s->flags[3] && rnd_chance(&g->rng, restart ? 60 : ((f & MLP_SF_DISC) ? 80 : 50));
+    si = s->flags[2] && (f & MLP_SF_IIR) && filters_ok && rnd_chance(&g->rng, 40);
+    so = s->flags[1] && (f & MLP_SF_HUFFOFF) && rnd_chance(&g->rng, 50);
+
+    /* what the channel codes is decided first, against the taps that stay; the taps that are sent get what is left */
+    if (sf) {
+        n.fir.order = 0;
+        n.rail = 0;
+    }
+    if (si)
+        n.iir.order = 0;
+    off = n.huff_off;
+    if (so) {
+        /* huffman_offset: read_signed(15), src/mlp.c:967 */
+        const int64_t amax = ((g->vn / 64) >> q) - 2;
+        const int hi = (int)min64(amax, g->wide ? 16383 : 300);
+        off = g->wide ? rnd_rail(&g->rng, amax >= 16384 ? -16384 : -hi, hi) : rnd_range(&g->rng, -hi, hi);
+    }
+    if (g->leadin) {
+        cb = 0;
+        lsbs = 24;
+    } else if (g->full && rnd_chance(&g->rng, 30)) {
+        cb = 0;
+        lsbs = (unsigned)rnd_range(&g->rng, 20, 24);
+    } else {
+        cb = rnd_below(&g->rng, 4);
+        if (cb)
+            lsbs = q + (g->full ? (unsigned)rnd_rail(&g->rng, 0, 24 - (int)q) : rnd_below(&g->rng, 12));
+        else
+            lsbs = q + (unsigned)rnd_range(&g->rng, 0, 20);
+    }
+    if (lsbs > 24) lsbs = 24;
+    if (lsbs < q) lsbs = q;
+    while (!chan_fits(g, &n, rb = res_bound(cb, lsbs, q, off))) {
+        if (lsbs > q) {
+            lsbs--;
+        } else if (cb) {
+            cb = 0;
+        } else {
+            g->fail = 1;
+            break;
+        }
+    }
+    if (s->flags[3]) {
+        bw_put(w, 1, (uint32_t)sf);
+        if (sf) {
+            const int kept = !si && n.iir.order;
+            put_fir_ext(g, w, &n, kept ? 8 - n.iir.order : 8, filters_ok, (kept && n.iir.shift) ? n.iir.shift : 0,
+                        rb, kept);
+        }
+    }
+    if (s->flags[2]) {
+        bw_put(w, 1, (uint32_t)si);
+        if (si)
+            put_iir_ext(g, w, &n, rb);
+    }
+    if (s->flags[1]) {
+        bw_put(w, 1, (uint32_t)so);
+        if (so)
+            bw_put_signed(w, 15, off);
+    }
+    bw_put(w, 2, cb);
+    bw_put(w, 5, lsbs);
+    n.huff_off = off;
+    n.codebook = cb;
+    n.lsbs = lsbs;
+    if (!chan_fits(g, &n, rb))
+        g->fail = 1;
+    n.sbound = max64(n.sbound, rb);
+    *ch = n;
+}
+
+/* matrices, reference src/mlp.c:1003-1023.  wide: fractional_bits 0..14, all the parser admits (src/mlp.c:1012-1014) */
+static void put_matrices_ext(gen_t *g, bw_t *w, ss_t *s, unsigned maxlen)
+{
+    const unsigned f = g->f;
+    const unsigned ncoef = s->max_matrix_ch + 3;
+    const int64_t namp = (int64_t)128 << s->noise_shift;
+    unsigned m, c;
+    unsigned len = rnd_below(&g->rng, MAXMAT + 1);
+    if (len > maxlen)
+        len = maxlen;
+    s->matrix_len = len;
+    bw_put(w, 4, len);
+    ext_reset_matrices(g, s);
+    for (m = 0; m < len; m++) {
+        const unsigned out_ch = rnd_below(&g->rng, s->max_matrix_ch + 1);
+        unsigned frac = (unsigned)(g->wide ? rnd_rail(&g->rng, 0, 14) : rnd_range(&g->rng, 6, 14));
+        const unsigned bypass = rnd(&g->rng) & 1;
+        /* a coefficient on a rail: frac = 14 and the code -2^15 (or 2^15 - 1) */
+        const unsigned rail_c = (g->full && rnd_chance(&g->rng, 25)) ? rnd_below(&g->rng, s->max_matrix_ch + 1) : ncoef;
+        int64_t limit = min64((int64_t)1 << 30, (((int64_t)1 << 31) - 1) >> s->oshift[out_ch]) - 40000;
+        int64_t acc = 0;
+        if (rail_c < ncoef)
+            frac = 14;
+        bw_put(w, 4, out_ch);
+        bw_put(w, 4, frac);
+        bw_put(w, 1, bypass);
+        s->bypass[m] = bypass;
+        for (c = 0; c < ncoef; c++) {
+            const int64_t inb = c <= s->max_matrix_ch ? s->mat_bound[c] : namp;
+            int q14, present, v, lim = (1 << (frac + 1)) - 1;
+            int64_t cost;
+            if (c == out_ch) {
+                q14 = 16384 - (int)rnd_below(&g->rng, 4096);
+                present = 1;
+            } else if (c <= s->max_matrix_ch) {
+                const int mag = 1000 + (int)rnd_below(&g->rng, 1501);
+                q14 = (rnd(&g->rng) & 1) ? mag : -mag;
+                present = rnd_chance(&g->rng, 70);
+            } else {
+                q14 = (f & MLP_SF_NOISE) ? rnd_range(&g->rng, -600, 600) : 5;
+                present = rnd_chance(&g->rng, 60);
+            }
+            if (c == rail_c) {
+                q14 = (rnd(&g->rng) & 1) ? 32767 : -32768;
+                present = 1;
+            }
+            v = q14 >> (14 - frac);
+            if (v > lim) v = lim;
+            if (v < -lim - 1) v = -lim - 1;
+            cost = (int64_t)(v < 0 ? -v : v) * ((int64_t)1 << (14 - frac)) * inb;
+            if (present && ((acc + cost) >> 14) > limit)
+                present = 0;
+            bw_put(w, 1, (uint32_t)present);
+            if (present) {
+                acc += cost;
+                bw_put_signed(w, frac + 2, v);
+            }
+        }
+        /* floor of the shift, mask() with quant_step_size <= 15, the bypassed LSB (src/mlp.c:1349-1355) */
+        s->mat_bound[out_ch] = max64(2 * g->vn, (acc >> 14) + 2 + 32768 + 1);
+    }
+}
+
 /* ---- decoding parameters: reference src/mlp.c:866-990.
  * `restart`  : header_present
  * `first`    : first block of the frame (matrix-class changes are always legal there)
@@ -396,9 +788,10 @@ static void put_decoding_params(gen_t *g, bw_t *w, ss_t *s, int restart, int fir
                                 int recipe2, unsigned want_block_size)
 {
     const mlp_synth_cfg *cfg = g->cfg;
-    const unsigned f = cfg->profile ? cfg->features : 0;
+    const unsigned f = g->f;
     const int fuzz = cfg->profile != 0;
     const int matrix_ok = first || (f & MLP_SF_MIDMATRIX);
+    const int ext = g->full || g->wide;
     unsigned c;
 
     /* flags */
@@ -455,21 +848,41 @@ static void put_decoding_params(gen_t *g, bw_t *w, ss_t *s, int restart, int fir
         if (restart && (f & MLP_SF_MATRIXRAND) && rnd_chance(&g->rng, 15))
             send = 0;
         bw_put(w, 1, (uint32_t)send);
-        if (send)
+        if (send && ext)
+            put_matrices_ext(g, w, s, first ? MAXMAT : s->matrix_len);
+        else if (send)
             put_matrices(g, w, s, first ? MAXMAT : s->matrix_len);
         else if (restart)
             s->matrix_len = 0;
     } else if (restart) {
         s->matrix_len = 0;
     }
+    if (ext && s->matrix_len == 0)
+        ext_reset_matrices(g, s);
 
     /* output shifts (4s each, channels 0..max_matrix) */
     if (s->flags[5]) {
         int send = (f & MLP_SF_OUTSHIFT) && matrix_ok && (restart || ((f & MLP_SF_PARAMBLOCKS) && rnd_chance(&g->rng, 25)));
         bw_put(w, 1, (uint32_t)send);
-        if (send)
+        if (send && ext) {
+            /* output_shift: read_signed(4), reference src/mlp.c:922; 0..7 are the values that shift left (src/mlp.c:522) */
+            for (c = 0; c <= s->max_matrix_ch; c++) {
+                int mx = 0;
+                while (mx < 7 && (s->mat_bound[c] << (mx + 1)) < ((int64_t)1 << 31))
+                    mx++;
+                s->oshift[c] = (unsigned)(g->wide ? rnd_rail(&g->rng, 0, mx) : (int)rnd_below(&g->rng, (mx > 2 ? 2 : mx) + 1));
+                bw_put_signed(w, 4, (int)s->oshift[c]);
+            }
+        } else if (send) {
             for (c = 0; c <= s->max_matrix_ch; c++)
                 bw_put_signed(w, 4, (int)rnd_below(&g->rng, 3));
+        } else if (restart) {
+            for (c = 0; c < MAXCH; c++)
+                s->oshift[c] = 0;
+        }
+    } else if (restart) {
+        for (c = 0; c < MAXCH; c++)
+            s->oshift[c] = 0;
     }
 
     /* quant step sizes (4u each, channels 0..max_channel -- sic) */
@@ -478,7 +891,18 @@ static void put_decoding_params(gen_t *g, bw_t *w, ss_t *s, int restart, int fir
         bw_put(w, 1, (uint32_t)send);
         if (send) {
             for (c = 0; c <= s->max_ch; c++) {
-                unsigned q = rnd_below(&g->rng, 4);
+                unsigned q;
+                if (ext) {
+                    /* quant_step_size: read(4), reference src/mlp.c:932.  Kept so small that the channel's offset,
+                       shifted by it, and mask()'s 2^q stay a small part of vn (see "extended modes") */
+                    const int o = (c >= s->min_ch && !restart) ? s->ch[c].huff_off : 0;
+                    int mx = 0;
+                    while (mx < 15 && (((int64_t)(o < 0 ? -o : o) + 2) << (mx + 1)) <= g->vn / 64)
+                        mx++;
+                    q = (unsigned)(g->wide ? rnd_rail(&g->rng, 0, mx) : (int)rnd_below(&g->rng, (mx > 3 ? 3 : mx) + 1));
+                } else {
+                    q = rnd_below(&g->rng, 4);
+                }
                 s->qss[c] = q;
                 bw_put(w, 4, q);
             }
@@ -496,6 +920,10 @@ static void put_decoding_params(gen_t *g, bw_t *w, ss_t *s, int restart, int fir
         chan_t *ch = &s->ch[c];
         int filters_ok = !g->leadin;
         int send;
+        if (ext) {
+            put_channel_ext(g, w, s, c, restart);
+            continue;
+        }
         if (restart)
             send = fuzz ? rnd_chance(&g->rng, 85) : 0;
         else if (recipe2)
@@ -635,7 +1063,11 @@ static void put_rows(gen_t *g, bw_t *w, const ss_t *s, unsigned rows)
                 /* raw: residual = LSB - 2^(lsb_bits-1) (+offset), keep it within
                    +-2^15 for wide fields (BASELINE.md recipe), full range otherwise */
                 uint32_t l;
-                if (lsb_bits > 17) {
+                if (g->full) {
+                    /* the whole width of the field, its two ends now and then */
+                    const uint32_t r = rnd(&g->rng), msk = (1u << lsb_bits) - 1u;
+                    l = (r & 31) == 0 ? 0 : (r & 31) == 1 ? msk : (rnd(&g->rng) & msk);
+                } else if (lsb_bits > 17) {
                     int v = (int)(rnd(&g->rng) & 0xFFFF) - 32768;
                     l = (uint32_t)((1 << (lsb_bits - 1)) + v);
                 } else {
@@ -684,7 +1116,7 @@ static size_t build_substream(gen_t *g, ss_t *s, unsigned au, int restart_au, in
                               uint8_t *buf, size_t cap)
 {
     const mlp_synth_cfg *cfg = g->cfg;
-    const unsigned f = cfg->profile ? cfg->features : 0;
+    const unsigned f = g->f;
     const int fuzz = cfg->profile != 0;
     const int chained = (f & MLP_SF_CHAINED) && au != 0;
     bw_t w;
@@ -734,7 +1166,7 @@ static size_t build_substream(gen_t *g, ss_t *s, unsigned au, int restart_au, in
         bw_put(&w, 32, 0xD234D234u);
     }
     bw_align(&w, 16);
-    if (w.overflow)
+    if (w.overflow || g->fail)
         return 0;
     nbytes = w.bits >> 3;
     if (check) {
@@ -797,13 +1229,31 @@ size_t mlp_synth_stream(const mlp_synth_cfg *cfg, uint64_t seed, uint8_t *out, s
     size_t pos = 0;
     uint64_t frames = 0;
     uint8_t *ssbuf[2];
-    const unsigned f = cfg->profile ? cfg->features : 0;
+    unsigned f = cfg->profile ? cfg->features : 0;
     const unsigned S = cfg->n_substreams == 2 ? 2 : 1;
 
     pthread_once(&crc_once, crc_init);
     memset(&g, 0, sizeof(g));
     g.cfg = cfg;
     g.rng.x = (uint32_t)(seed * 2654435761u) ^ (uint32_t)(seed >> 32) ^ 0x9E3779B9u;
+    if (f & MLP_SF_WIDEPARAMS)
+        f |= MLP_SF_QSS | MLP_SF_OUTSHIFT | MLP_SF_HUFFOFF | MLP_SF_NOISE;
+    if (f & (MLP_SF_FULLSCALE | MLP_SF_WIDEPARAMS))
+        f |= MLP_SF_FIRRAND | MLP_SF_IIR | MLP_SF_MATRIXRAND | MLP_SF_MIXBOOKS;
+    g.f = f;
+    g.full = (f & MLP_SF_FULLSCALE) != 0;
+    g.wide = (f & MLP_SF_WIDEPARAMS) != 0;
+    if (g.full || g.wide) {
+        /* full scale needs 2^27: a 24-bit residual (2^23) through taps of gain 8 and an IIR, within 2^24 * 8 */
+        unsigned bits = 27;
+        if (!g.full)
+            bits = (unsigned)rnd_range(&g.rng, 17, 27);
+        else if (g.wide && rnd_chance(&g.rng, 35))
+            bits = (unsigned)rnd_range(&g.rng, 20, 27);
+        g.vn = (int64_t)1 << bits;
+        ext_reset_matrices(&g, &g.ss[0]);
+        ext_reset_matrices(&g, &g.ss[1]);
+    }
     g.nch = mlp_synth_channels(cfg->assignment);
     g.rows_per_au = mlp_synth_rows_per_au(cfg->rate_code);
     if (g.nch == 0 || cfg->restart_interval == 0)

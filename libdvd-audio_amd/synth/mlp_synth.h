@@ -44,6 +44,18 @@ extern "C" {
                                          sent and most of those re-send their FIR taps; fixed block positions       */
 #define MLP_SF_SYNCONLY    (1u << 20) /* a major sync in front of some access units that carry NO restart header:
                                          the reference re-reads the sync's parameters and decodes on (src/mlp.c:449-460) */
+#define MLP_SF_FULLSCALE   (1u << 21) /* signal at the scale the format allows: raw residuals (the 24-bit lead-in among
+                                         them) use the whole width of their field, whole blocks of 20..24 raw LSBs run
+                                         through active taps, huffman_lsbs up to 24 with a code book, and now and then
+                                         a FIR / IIR / matrix coefficient sits on a rail (+32767, -32768).  Implies
+                                         FIRRAND | IIR | MATRIXRAND | MIXBOOKS                                        */
+#define MLP_SF_WIDEPARAMS  (1u << 22) /* every parameter field over the whole range the reference's parser reads
+                                         without asserting (mlp_synth.c cites the lines): output_shift 0..7,
+                                         quant_step_size 0..15, huffman_offset -16384..16383, filter shift 0..15,
+                                         coeff_shift 0..7, IIR order up to 8, IIR state bits 1..15, noise_shift 0..15,
+                                         matrix fractional bits 0..14.  Implies FULLSCALE's set | QSS | OUTSHIFT |
+                                         HUFFOFF | NOISE.  Both bits keep the stream inside SURVEY.md A.4 by carrying a
+                                         bound on the signal (see "extended modes" in mlp_synth.c), never by trial     */
 
 typedef struct mlp_synth_cfg {
     uint32_t profile;          /* 0 = BASELINE.md recipe, 1 = fuzz (uses .features) */

@@ -203,7 +203,15 @@ struct mlp_oracle {
     vec_t out[MAX_CHANNELS];   /* the caller's "samples" */
     int32_t *residual;         /* scratch, block_size entries */
     size_t residual_cap;
+    mlp_oracle_stats *stats;   /* optional (mlp_oracle_decode_stats) */
 };
+
+static inline void peak(uint64_t *p, int64_t v)
+{
+    const uint64_t a = v < 0 ? (uint64_t)0 - (uint64_t)v : (uint64_t)v;
+    if (a > *p)
+        *p = a;
+}
 
 static int vec_push_n(vec_t *v, const int32_t *src, size_t n)
 {
@@ -233,7 +241,7 @@ static inline int32_t mask_q(int32_t x, unsigned q)
 /* ------------------------------------------------------- parameter parsing */
 
 /* mlp.c:809-854 */
-static int parse_restart_header(bits_t *b, substream_t *s)
+static int parse_restart_header(bits_t *b, substream_t *s, mlp_oracle_stats *st)
 {
     unsigned sync, noise_type, c;
     sync = rd(b, 13);
@@ -252,6 +260,8 @@ static int parse_restart_header(bits_t *b, substream_t *s)
         return 0;
     if (s->max_ch < s->min_ch || s->max_matrix_ch < s->max_ch)
         return 0;
+    if (st)
+        st->noise_shift[s->noise_shift]++;
     for (c = 0; c <= s->max_matrix_ch; c++)
         if (rd(b, 6) > s->max_matrix_ch) /* channel_assignment: validated only */
             return 0;
@@ -260,7 +270,7 @@ static int parse_restart_header(bits_t *b, substream_t *s)
 }
 
 /* mlp.c:995-1027 */
-static int parse_matrices(bits_t *b, substream_t *s, unsigned *envelope)
+static int parse_matrices(bits_t *b, substream_t *s, unsigned *envelope, mlp_oracle_stats *st)
 {
     unsigned m, c;
     s->matrix_len = rd(b, 4);
@@ -279,10 +289,16 @@ static int parse_matrices(bits_t *b, substream_t *s, unsigned *envelope)
         if ((frac = rd(b, 4)) > 14)
             return 0;
         mp->lsb_bypass = rd(b, 1);
+        if (st)
+            st->matrix_frac[frac]++;
         for (c = 0; c < s->max_matrix_ch + 3; c++) {
             int v = 0;
             if (rd(b, 1))
                 v = (int)((uint32_t)rd_signed(b, frac + 2) << (14 - frac));
+            if (st && v == -32768)
+                st->matrix_min_rail++;
+            if (st && v == 32767)
+                st->matrix_max_rail++;
             if (c < MAX_CHANNELS + 2)
                 mp->coeff[c] = v;
             else
@@ -293,11 +309,13 @@ static int parse_matrices(bits_t *b, substream_t *s, unsigned *envelope)
 }
 
 /* mlp.c:1029-1069 (FIR) and 1071-1120 (IIR) */
-static int parse_filter(bits_t *b, filter_t *f, int is_iir, unsigned *envelope)
+static int parse_filter(bits_t *b, filter_t *f, int is_iir, unsigned *envelope, mlp_oracle_stats *st)
 {
     unsigned order = rd(b, 4), i;
     if (order > 8)
         return 0;
+    if (st)
+        (is_iir ? st->iir_order : st->fir_order)[order]++;
     if (order == 0) {
         f->shift = 0;
         f->order = 0;
@@ -314,8 +332,17 @@ static int parse_filter(bits_t *b, filter_t *f, int is_iir, unsigned *envelope)
         if (coeff_bits + coeff_shift > 16)
             return 0;
         f->order = order;
-        for (i = 0; i < order; i++)
+        for (i = 0; i < order; i++) {
             f->coeff[i] = (int)((uint32_t)rd_signed(b, coeff_bits) << coeff_shift);
+            if (st && f->coeff[i] == -32768)
+                (*(is_iir ? &st->iir_min_rail : &st->fir_min_rail))++;
+            if (st && f->coeff[i] == 32767)
+                (*(is_iir ? &st->iir_max_rail : &st->fir_max_rail))++;
+        }
+        if (st) {
+            (is_iir ? st->iir_shift : st->fir_shift)[f->shift]++;
+            (is_iir ? st->iir_coeff_shift : st->fir_coeff_shift)[coeff_shift]++;
+        }
     }
     if (!is_iir) {
         if (rd(b, 1))
@@ -329,6 +356,12 @@ static int parse_filter(bits_t *b, filter_t *f, int is_iir, unsigned *envelope)
         unsigned state_bits = rd(b, 4), state_shift = rd(b, 4);
         if (state_bits == 0)
             *envelope = 1; /* read_signed(0) */
+        if (st) {
+            st->state_bits[state_bits]++;
+            st->state_shift[state_shift]++;
+            if (state_bits && state_bits - 1 + state_shift > st->state_top_bit_max)
+                st->state_top_bit_max = state_bits - 1 + state_shift;
+        }
         for (i = 0; i < order; i++)
             f->state[i] = (int)((uint32_t)rd_signed(b, state_bits) << state_shift);
         f->have = order;
@@ -337,7 +370,7 @@ static int parse_filter(bits_t *b, filter_t *f, int is_iir, unsigned *envelope)
 }
 
 /* mlp.c:856-993 */
-static int parse_decoding_params(bits_t *b, substream_t *s, int header, unsigned *envelope)
+static int parse_decoding_params(bits_t *b, substream_t *s, int header, unsigned *envelope, mlp_oracle_stats *st)
 {
     unsigned c;
 
@@ -362,7 +395,7 @@ static int parse_decoding_params(bits_t *b, substream_t *s, int header, unsigned
     }
 
     if (s->flags[6] && rd(b, 1)) {
-        if (!parse_matrices(b, s, envelope))
+        if (!parse_matrices(b, s, envelope, st))
             return 0;
     } else if (header) {
         s->matrix_len = 0;
@@ -375,6 +408,8 @@ static int parse_decoding_params(bits_t *b, substream_t *s, int header, unsigned
                 s->output_shift[c] = (unsigned)v;
             if (v < 0)
                 *envelope = 1; /* becomes a huge unsigned shift there */
+            else if (st)
+                st->output_shift[v]++;
         }
     } else if (header) {
         for (c = 0; c < MAX_CHANNELS; c++)
@@ -384,6 +419,8 @@ static int parse_decoding_params(bits_t *b, substream_t *s, int header, unsigned
     if (s->flags[4] && rd(b, 1)) {
         for (c = 0; c <= s->max_ch; c++) {
             unsigned v = rd(b, 4);
+            if (st)
+                st->qss[v]++;
             if (c < MAX_CHANNELS)
                 s->qss[c] = v;
         }
@@ -401,23 +438,27 @@ static int parse_decoding_params(bits_t *b, substream_t *s, int header, unsigned
         cp = &s->ch[c];
         if (rd(b, 1)) {
             if (s->flags[3] && rd(b, 1)) {
-                if (!parse_filter(b, &cp->fir, 0, envelope))
+                if (!parse_filter(b, &cp->fir, 0, envelope, st))
                     return 0;
             } else if (header) {
                 cp->fir.shift = 0;
                 cp->fir.order = 0;
             }
             if (s->flags[2] && rd(b, 1)) {
-                if (!parse_filter(b, &cp->iir, 1, envelope))
+                if (!parse_filter(b, &cp->iir, 1, envelope, st))
                     return 0;
             } else if (header) {
                 cp->iir.shift = 0;
                 cp->iir.order = 0;
                 cp->iir.have = 0;
             }
-            if (s->flags[1] && rd(b, 1))
+            if (s->flags[1] && rd(b, 1)) {
                 cp->huffman_offset = rd_signed(b, 15);
-            else if (header)
+                if (st && cp->huffman_offset < st->offset_min)
+                    st->offset_min = cp->huffman_offset;
+                if (st && cp->huffman_offset > st->offset_max)
+                    st->offset_max = cp->huffman_offset;
+            } else if (header)
                 cp->huffman_offset = 0;
             cp->codebook = rd(b, 2);
             {
@@ -427,6 +468,8 @@ static int parse_decoding_params(bits_t *b, substream_t *s, int header, unsigned
                 if (lsbs > 24)
                     return 0;
                 cp->huffman_lsbs = lsbs;
+                if (st && cp->codebook)
+                    st->lsbs_with_book[lsbs]++;
             }
         } else if (header) {
             cp->fir.shift = 0;
@@ -463,6 +506,12 @@ static int filter_channel(mlp_oracle *d, const int32_t *res, unsigned n, filter_
     /* the reference indexes state[len - 1 - j] with no bounds check */
     if (fir->order > fir->have || iir->order > iir->have)
         d->status |= MLP_ORA_ERR_ENVELOPE;
+    if (d->stats && fir->order + iir->order) {
+        if (fir->order + iir->order == 8)
+            d->stats->split8[fir->order]++;
+        if (shift + q > d->stats->shift_plus_qss_max)
+            d->stats->shift_plus_qss_max = shift + q;
+    }
 
     for (i = 0; i < n; i++) {
         int64_t sum = 0;
@@ -473,6 +522,17 @@ static int filter_channel(mlp_oracle *d, const int32_t *res, unsigned n, filter_
             sum += (int64_t)iir->coeff[j] * (int64_t)iir->state[j];
         ssum = (int32_t)(sum >> shift);
         value = mask_q((int32_t)((uint32_t)ssum + (uint32_t)res[i]), q);
+        if (d->stats) {
+            mlp_oracle_stats *st = d->stats;
+            const int64_t wide = (sum >> shift) + (int64_t)res[i];
+            peak(&st->peak_filter_acc, sum);
+            peak(&st->peak_sum, wide);
+            peak(&st->peak_sum, (wide & -((int64_t)1 << q)) - (sum >> shift));
+            if (wide < st->value_min)
+                st->value_min = wide;
+            if (wide > st->value_max)
+                st->value_max = wide;
+        }
         dst[i] = value;
         memmove(fir->state + 1, fir->state, (HIST - 1) * sizeof(int));
         fir->state[0] = value;
@@ -496,11 +556,11 @@ static unsigned decode_block(mlp_oracle *d, substream_t *s, bits_t *b)
 
     if (rd(b, 1)) {
         int restart = (int)rd(b, 1);
-        if (restart && !parse_restart_header(b, s)) {
+        if (restart && !parse_restart_header(b, s, d->stats)) {
             d->status |= MLP_ORA_ERR_RESTART;
             return 0;
         }
-        if (!parse_decoding_params(b, s, restart, &envelope)) {
+        if (!parse_decoding_params(b, s, restart, &envelope, d->stats)) {
             d->status |= envelope ? MLP_ORA_ERR_ENVELOPE : MLP_ORA_ERR_PARAMS;
             return 0;
         }
@@ -663,6 +723,11 @@ static void rematrix(mlp_oracle *d, substream_t *s)
                     sum += (int64_t)d->frame[c].v[i] * (int64_t)mp->coeff[c];
             sum += (int64_t)n0[i] * (int64_t)mp->coeff[s->max_matrix_ch + 1];
             sum += (int64_t)n1[i] * (int64_t)mp->coeff[s->max_matrix_ch + 2];
+            if (d->stats) {
+                peak(&d->stats->peak_matrix_acc, sum);
+                peak(&d->stats->peak_output, ((sum >> 14) & -((int64_t)1 << s->qss[mp->out_channel])) +
+                                                 (i < mp->bypassed_len ? mp->bypassed[i] : 0));
+            }
             if (i < d->frame[mp->out_channel].len)
                 d->frame[mp->out_channel].v[i] =
                     (int32_t)((uint32_t)mask_q((int32_t)(sum >> 14), s->qss[mp->out_channel]) +
@@ -814,6 +879,11 @@ static unsigned decode_frame(mlp_oracle *d, const uint8_t *p, size_t len)
     rematrix(d, last);
     for (c = 0; c <= last->max_matrix_ch && c < MAX_CHANNELS; c++) {
         const unsigned sh = last->output_shift[c];
+        if (d->stats) {
+            size_t i;
+            for (i = 0; i < d->frame[c].len; i++)
+                peak(&d->stats->peak_output, (int64_t)d->frame[c].v[i] * ((int64_t)1 << (sh & 31)));
+        }
         if (sh) {
             size_t i;
             for (i = 0; i < d->frame[c].len; i++)
@@ -920,12 +990,19 @@ size_t mlp_oracle_queued_bytes(const mlp_oracle *d) { return d->qlen - d->qpos; 
 long mlp_oracle_decode(const uint8_t *data, size_t len, size_t chunk, unsigned nch, int32_t *out,
                        size_t cap, unsigned *status)
 {
+    return mlp_oracle_decode_stats(data, len, chunk, nch, out, cap, status, NULL);
+}
+
+long mlp_oracle_decode_stats(const uint8_t *data, size_t len, size_t chunk, unsigned nch, int32_t *out,
+                             size_t cap, unsigned *status, mlp_oracle_stats *stats)
+{
     mlp_oracle *d = mlp_oracle_open(nch);
     size_t off = 0;
     long total = 0;
     unsigned c;
     if (!d)
         return -1;
+    d->stats = stats;
     if (chunk == 0)
         chunk = len ? len : 1;
     while (off < len) {

@@ -56,6 +56,33 @@ long mlp_oracle_decode(const uint8_t *data, size_t len, size_t chunk,
                        unsigned nch, int32_t *out, size_t cap,
                        unsigned *status);
 
+/* Optional statistics of a decode, for the tests that ask how far into the arithmetic a stream reaches and which
+ * parameter values it carries.  The four peaks are taken in 64 bits before anything is narrowed to int32, so a value
+ * of 2^31 or more in peak_sum / peak_output means the stream left the envelope although the decode
+ * went through.  The decode itself is the same with or without statistics. */
+typedef struct mlp_oracle_stats {
+    uint64_t peak_filter_acc;   /* |sum of FIR and IIR products|, mlp.c:1285-1291                              */
+    uint64_t peak_matrix_acc;   /* |sum of matrix products|, mlp.c:1342-1348                                   */
+    uint64_t peak_sum;          /* |(acc >> shift) + residual| and |value - (acc >> shift)|, mlp.c:1293-1299   */
+    uint64_t peak_output;       /* |matrix result| and |value * 2^output_shift|, mlp.c:1349-1355, 522 / 592    */
+    int64_t value_min, value_max; /* extremes of (acc >> shift) + residual                                     */
+    /* how often a parameter value was read (filters: those with taps) */
+    uint32_t output_shift[8], qss[16], noise_shift[16], matrix_frac[15];
+    uint32_t fir_shift[16], iir_shift[16], fir_coeff_shift[8], iir_coeff_shift[8];
+    uint32_t fir_order[9], iir_order[9], state_bits[16], state_shift[16];
+    uint32_t split8[9];         /* blocks filtered with FIR order k and IIR order 8 - k                         */
+    uint32_t fir_min_rail, fir_max_rail, iir_min_rail, iir_max_rail, matrix_min_rail, matrix_max_rail;
+    uint32_t lsbs_with_book[25];
+    int32_t offset_min, offset_max;
+    uint32_t state_top_bit_max; /* largest state_bits - 1 + state_shift                                         */
+    uint32_t shift_plus_qss_max; /* largest filter shift + quant_step_size of a block filtered with taps       */
+} mlp_oracle_stats;
+
+/* mlp_oracle_decode that also adds the decode's statistics to *stats (may be NULL; the caller zeroes it) */
+long mlp_oracle_decode_stats(const uint8_t *data, size_t len, size_t chunk,
+                             unsigned nch, int32_t *out, size_t cap,
+                             unsigned *status, mlp_oracle_stats *stats);
+
 /* test hooks (bit-reader contract, tables) */
 int mlp_oracle_test_read(const uint8_t *data, size_t len, const int *widths, int n, long *out);
 int mlp_oracle_test_crc8(unsigned i);

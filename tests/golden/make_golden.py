@@ -50,6 +50,12 @@ FIXTURES = [
     # parameters are compared and the decode goes on with the state it has; decode_block src/mlp.c:748-753)
     ("sync_only_6ch", 12, 1, 1, 32, 1, SF["SYNCONLY"] | SF["FIRRAND"] | SF["PARAMBLOCKS"] | SF["IIR"], 27, 8),
     ("sync_only_chained_2ss", 12, 1, 2, 32, 1, SF["SYNCONLY"] | SF["CHAINED"] | SF["FIRRAND"] | SF["MIXBOOKS"], 28, 5),
+    # the generator's extended modes (tests/test_fullscale_model.py): signal at full 24-bit scale through large taps,
+    # coefficients on the rails; every parameter field over the range the reference's parser reads
+    ("fullscale_6ch", 12, 1, 1, 12, 1, SF["FULLSCALE"], 31, 4),
+    ("wideparams_6ch", 12, 1, 1, 12, 1, SF["WIDEPARAMS"], 32, 4),
+    ("fullscale_wideparams_2ss", 12, 1, 2, 12, 1, SF["FULLSCALE"] | SF["WIDEPARAMS"], 33, 3),
+    ("fullscale_wideparams_chained_disc", 12, 1, 1, 12, 1, SF["FULLSCALE"] | SF["WIDEPARAMS"] | SF["CHAINED"] | SF["DISC"], 34, 4),
 ]
 
 

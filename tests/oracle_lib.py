@@ -29,6 +29,27 @@ def build_oracle():
     return ORACLE_SO
 
 
+class Stats(ctypes.Structure):
+    """mlp_oracle_stats (oracle/mlp_oracle.h): peaks taken in 64 bits before any narrowing, and how often each
+    parameter value was read"""
+    _fields_ = [("peak_filter_acc", ctypes.c_uint64), ("peak_matrix_acc", ctypes.c_uint64),
+                ("peak_sum", ctypes.c_uint64), ("peak_output", ctypes.c_uint64),
+                ("value_min", ctypes.c_int64), ("value_max", ctypes.c_int64),
+                ("output_shift", ctypes.c_uint32 * 8), ("qss", ctypes.c_uint32 * 16),
+                ("noise_shift", ctypes.c_uint32 * 16), ("matrix_frac", ctypes.c_uint32 * 15),
+                ("fir_shift", ctypes.c_uint32 * 16), ("iir_shift", ctypes.c_uint32 * 16),
+                ("fir_coeff_shift", ctypes.c_uint32 * 8), ("iir_coeff_shift", ctypes.c_uint32 * 8),
+                ("fir_order", ctypes.c_uint32 * 9), ("iir_order", ctypes.c_uint32 * 9),
+                ("state_bits", ctypes.c_uint32 * 16), ("state_shift", ctypes.c_uint32 * 16),
+                ("split8", ctypes.c_uint32 * 9),
+                ("fir_min_rail", ctypes.c_uint32), ("fir_max_rail", ctypes.c_uint32),
+                ("iir_min_rail", ctypes.c_uint32), ("iir_max_rail", ctypes.c_uint32),
+                ("matrix_min_rail", ctypes.c_uint32), ("matrix_max_rail", ctypes.c_uint32),
+                ("lsbs_with_book", ctypes.c_uint32 * 25),
+                ("offset_min", ctypes.c_int32), ("offset_max", ctypes.c_int32),
+                ("state_top_bit_max", ctypes.c_uint32), ("shift_plus_qss_max", ctypes.c_uint32)]
+
+
 class Oracle:
     def __init__(self):
         self.lib = ctypes.CDLL(build_oracle())
@@ -36,6 +57,10 @@ class Oracle:
         self.lib.mlp_oracle_decode.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
                                                ctypes.c_uint, ctypes.c_void_p, ctypes.c_size_t,
                                                ctypes.POINTER(ctypes.c_uint)]
+        self.lib.mlp_oracle_decode_stats.restype = ctypes.c_long
+        self.lib.mlp_oracle_decode_stats.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
+                                                     ctypes.c_uint, ctypes.c_void_p, ctypes.c_size_t,
+                                                     ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(Stats)]
 
     def decode(self, data, nch, max_frames, chunk=0):
         """-> (pcm int32 [nch, frames], frames, status)"""
@@ -48,6 +73,20 @@ class Oracle:
         if r < 0:
             raise RuntimeError("oracle output capacity too small")
         return out[:, :r].copy(), int(r), int(st.value)
+
+    def decode_stats(self, data, nch, max_frames, chunk=0, stats=None):
+        """decode() that also adds the decode's statistics to `stats` (a fresh Stats when None)
+        -> (pcm, frames, status, stats)"""
+        data = np.ascontiguousarray(data, np.uint8)
+        cap = int(max_frames) + 16
+        out = np.zeros((nch, cap), np.int32)
+        st = ctypes.c_uint()
+        stats = Stats() if stats is None else stats
+        r = self.lib.mlp_oracle_decode_stats(data.ctypes.data, len(data), chunk, nch, out.ctypes.data, cap,
+                                             ctypes.byref(st), ctypes.byref(stats))
+        if r < 0:
+            raise RuntimeError("oracle output capacity too small")
+        return out[:, :r].copy(), int(r), int(st.value), stats
 
     def wav_pack(self, planar, bits):
         """planar int32 [channels, frames] -> the WAV payload bytes dvda2wav writes (oracle/pcm_oracle.c)"""
