@@ -969,7 +969,12 @@ __global__ __launch_bounds__(COOP_THREADS) void k_coop(DecodeArgs a)
                     if (rd.pos > ss_end_bit)
                         err = ST_EOF;
                 }
-                if (!err && !(status & ST_CHAINED)) {
+                if (RESUME && err && (chk >> 2) == f) {
+                    // the reference verifies a substream before it decodes it (src/mlp.c:675-706): whatever the blocks of
+                    // a unit that fails its check tripped over -- an invalid code, a parameter out of range --, the fault
+                    // the caller of decode_packet is told is the check's, as the oracle's for the same bytes
+                    err = (chk & 1u) ? ST_PARITY : ST_CRC;
+                } else if (!err && !(status & ST_CHAINED)) {
                     if (frame_rows != rpa)
                         err = ST_TIMING;            // the sequential pass decodes such a stream in order
                     else if ((chk >> 2) == f)

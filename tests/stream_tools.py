@@ -19,6 +19,39 @@ def is_major_sync(stream, pos):
             (int(stream[pos + 20]) >> 4) in (1, 2))
 
 
+def padded_unit(b, which, new_size):
+    """stream `b` with access unit `which` grown to `new_size` bytes by zero bytes behind its last substream (the
+    reference ignores what follows the last substream of a frame, src/mlp.c:463-468: the size field says where the
+    next frame starts)"""
+    pos = 0
+    for _ in range(which):
+        pos += 2 * (((int(b[pos]) & 0x0F) << 8) | int(b[pos + 1]))
+    size = 2 * (((int(b[pos]) & 0x0F) << 8) | int(b[pos + 1]))
+    assert new_size % 2 == 0 and size < new_size <= 8190
+    out = np.concatenate([b[:pos + size], np.zeros(new_size - size, np.uint8), b[pos + size:]])
+    w = new_size // 2
+    out[pos] = (int(b[pos]) & 0xF0) | (w >> 8)
+    out[pos + 1] = w & 0xFF
+    return out
+
+
+def major_syncs(stream):
+    """byte offset of every major-sync access unit"""
+    return [p for p in frame_offsets(stream) if is_major_sync(stream, p)]
+
+
+def splice(a, b, sync_index):
+    """the access units of `a` in front of its `sync_index`-th major sync (0 = the stream's first), then `b` from its
+    `sync_index`-th major sync on"""
+    return np.concatenate([a[:major_syncs(a)[sync_index]], b[major_syncs(b)[sync_index]:]])
+
+
+def cuts_at_units(stream):
+    """where every complete access unit ends: fed as packets [0, c0), [c0, c1), ... each call holds one unit (the last
+    one also what follows the last complete unit)"""
+    return frame_offsets(stream)[1:] + [len(stream)]
+
+
 def change_sync_params(stream, which, g1_bps=None, assignment=None):
     """Returns a copy of `stream` whose `which`-th major syncs (indices into the list of major-sync access
     units, 0 = the stream's first) announce other stream parameters: group-1 bits-per-sample code and / or

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from tests import test_gpu_parity as T
+from tests.stream_tools import padded_unit
 
 pytestmark = pytest.mark.gpu
 
@@ -127,22 +128,6 @@ def test_the_library_picks_it_for_small_batches_and_not_for_large_ones(pkg, orac
     for i in range(0, 4200, 97):
         want, r, st = oracle.decode(streams[i], 2, int(frames[i]))
         assert st == 0 and infos[i].status == 0 and np.array_equal(pcm[i], want)
-
-
-def padded_unit(b, which, new_size):
-    """stream `b` with access unit `which` grown to `new_size` bytes by zero bytes behind its last substream (the
-    reference ignores what follows the last substream of a frame, src/mlp.c:463-468: the size field says where the
-    next frame starts)"""
-    pos = 0
-    for _ in range(which):
-        pos += 2 * (((int(b[pos]) & 0x0F) << 8) | int(b[pos + 1]))
-    size = 2 * (((int(b[pos]) & 0x0F) << 8) | int(b[pos + 1]))
-    assert new_size % 2 == 0 and size < new_size <= 8190
-    out = np.concatenate([b[:pos + size], np.zeros(new_size - size, np.uint8), b[pos + size:]])
-    w = new_size // 2
-    out[pos] = (int(b[pos]) & 0xF0) | (w >> 8)
-    out[pos + 1] = w & 0xFF
-    return out
 
 
 @pytest.mark.parametrize("S", [1, 2])
