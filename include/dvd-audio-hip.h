@@ -99,6 +99,17 @@ DVDA_Track_Reader *dvda_hip_open_track_reader_on(const DVDA_Track *track, int de
 void dvda_hip_set_presentation(int presentation);
 /* dvda_hip_open_track_reader_on with the presentation named too; the thread's defaults stay as they are */
 DVDA_Track_Reader *dvda_hip_open_track_reader_with(const DVDA_Track *track, int device, int wav_output, int presentation);
+/* on != 0: track readers opened afterwards (per calling thread, read when the reader is opened, like
+ * dvda_hip_set_wav_output) digest every piece of the track where it lies on the device, before any copy to the host:
+ * zlib's CRC-32 of the WAV data chunk dvda2wav writes for the track (the contract is in dvda_mlp_hip.h,
+ * dvda_pcm_hip_crc32).  Whole-track and windowed readers, MLP and raw-PCM tracks, int32 and WAV-payload output, the
+ * presentation.  Off (default): a reader launches and allocates exactly as without this call. */
+void dvda_hip_set_digest(int on);
+/* The track's digest and its payload bytes.  1: final for the track -- from open on for a whole-track reader, once the
+ * track has been read to its end for a windowed one (which joins its windows' digests as they are handed out: until
+ * then 0, with the digest of what has been handed out so far).  -1: the digest is not on, the reader failed, or the
+ * track's bit depth is neither 16 nor 24. */
+int dvda_hip_reader_crc32(const DVDA_Track_Reader *reader, unsigned *crc, unsigned long long *bytes);
 /* != 0: the reader holds the WAV payload only (opened with wav_output): dvda_read() on it returns 0 frames -- NOT
  * because the track is empty; take the payload with dvda_hip_reader_wav_payload() */
 int dvda_hip_reader_wav_only(const DVDA_Track_Reader *reader);

@@ -443,6 +443,59 @@ int dvda_mlp_hip_demux_sectors(const uint8_t *d_sectors, uint32_t n_sectors, uin
 int dvda_mlp_hip_pack_wav(const int32_t *d_pcm, uint64_t stride, unsigned channels, uint64_t frames,
                           unsigned bits_per_sample, uint8_t *d_out, void *stream);
 
+/* ------------------------------------------------------------------ digest of the decoded PCM
+ * A CRC-32 per stream, computed on the device from whichever layout the decode wrote, so that a caller who only
+ * verifies -- an archive against stored checksums, two rips of one disc, new kernels against recorded results --
+ * copies 4 bytes per stream to the host and not the payload (csrc/pcm_digest.h).
+ *
+ * The contract.  For one stream of `frames` PCM frames with `channels` channels at `bits` = 16 or 24, the payload is
+ * the byte string dvda2wav writes as the WAV data chunk: frames ascending, the channels of a frame in RIFF-WAVE order,
+ * every value v as bits / 8 little-endian bytes of (v & (2^(bits-1) - 1)) | (v < 0 ? 2^(bits-1) : 0) -- write_signed,
+ * exactly what dvda_mlp_hip_pack_wav and DVDA_PCM_WAV24 / WAV16 produce.  The digest is zlib's crc32 of that string:
+ * reflected polynomial 0xEDB88320, 0xFFFFFFFF as initial value and as final XOR; an empty payload gives 0.  It is the
+ * same number whichever of the four DVDA_PCM_* layouts the samples sit in.
+ *
+ * The kernels cut a payload into tiles of DVDA_CRC_TILE_BYTES, aligned to the payload's END (the first tile of a stream
+ * is the ragged one), and one workgroup joins a stream's tiles DVDA_CRC_JOIN_TILES per turn of its loop. */
+#define DVDA_CRC_TILE_BYTES  16384u
+#define DVDA_CRC_JOIN_TILES  256u
+
+/* where a stream lies in d_pcm: as d_out_off[i] / d_out_stride[i] of dvda_mlp_hip_decode say it, with the PCM frames
+ * and channels it holds.  channels outside 1..8 or frames above 2^40: an empty stream. */
+typedef struct dvda_pcm_crc_desc {
+    uint64_t off;         /* int32 units from d_pcm (WAV layouts: the payload starts at byte 4 * off)   */
+    uint64_t stride;      /* capacity in PCM frames (planar: distance between the channels' planes)    */
+    uint64_t frames;      /* PCM frames the digest covers; values behind them are not read              */
+    uint32_t channels;
+    uint32_t reserved;
+} dvda_pcm_crc_desc;
+
+/* The tier-free form: d_crc[i], d_nbytes[i] = digest and payload bytes of stream d_desc[i] (device arrays, n entries),
+ * from d_pcm in `layout` (DVDA_PCM_*).  Enqueued on `stream`: no host wait, no allocation.  max_total_bytes: a bound the
+ * host knows on the sum of the streams' payload bytes -- the launch and d_work are sized by it; a stream whose tiles
+ * fall outside it is reported as (0, 0), never read out of bounds.  d_work: dvda_pcm_hip_crc32_workspace_words(n,
+ * max_total_bytes) uint32 words, which need not be cleared between calls.  In the WAV layouts a stream's last, partly
+ * filled dword is read whole, and no word behind it.  The arguments are judged first, on any machine -- DVDA_HIP_EINVAL:
+ * bits other than 16 / 24, a WAV layout of the other depth, a null pointer, work_words too small; DVDA_HIP_ECAPACITY:
+ * 2^31 tiles or more -- then the device: DVDA_HIP_ENODEV without one (asked of the runtime once per process). */
+size_t dvda_pcm_hip_crc32_workspace_words(uint32_t n, uint64_t max_total_bytes);
+int dvda_pcm_hip_crc32(const int32_t *d_pcm, uint32_t layout, unsigned bits, const dvda_pcm_crc_desc *d_desc, uint32_t n,
+                       uint64_t max_total_bytes, uint32_t *d_crc, uint64_t *d_nbytes, uint32_t *d_work,
+                       size_t work_words, void *stream);
+
+/* The convenience call behind dvda_mlp_hip_decode (blocks): host_crc[i], host_nbytes[i] for the first n streams of the
+ * last decode, d_pcm / d_out_off / d_out_stride as that decode got them, in the context's layout.  Frames and channels
+ * are what dvda_mlp_hip_stream_info reports, so conceal mode's composed stream and the presentation's k channels count
+ * as they are; a stream that carries DVDA_ST_OVERFLOW gives (0, 0) -- its region does not hold it -- and every other
+ * stream digests the pcm_frames it reports.  The workspace belongs to the context and only grows. */
+int dvda_mlp_hip_pcm_crc32(dvda_mlp_hip_ctx *ctx, const int32_t *d_pcm, const uint64_t *d_out_off,
+                           const uint64_t *d_out_stride, unsigned bits, uint32_t *host_crc, uint64_t *host_nbytes,
+                           uint32_t n, void *stream);
+
+/* crc(A || B) from crc(A), crc(B) and B's length: how a caller joins pieces -- windows of a track, parts of a title
+ * decoded in several batches.  Host arithmetic; needs no device. */
+uint32_t dvda_pcm_hip_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+
 /* ------------------------------------------------------------------ tier B */
 /* The mlp.h mirror: same three calls, same meaning as reference src/mlp.h:29-42 /
  * src/mlp.c:265-354, with the reference's containers replaced by plain memory:

@@ -51,6 +51,9 @@ void dvda_hip_set_wav_output(int on) { g_wav_output = on != 0; }
 /* 1: MLP track readers opened afterwards decode the presentation substream 0 carries (DVDA_PRESENT_SUBSTREAM0) */
 static _Thread_local int g_present = 0;
 void dvda_hip_set_presentation(int presentation) { g_present = presentation == 1; }
+/* 1: readers opened afterwards digest every piece of PCM where it lies on the device (dvda_hip_reader_crc32) */
+static _Thread_local int g_digest = 0;
+void dvda_hip_set_digest(int on) { g_digest = on != 0; }
 
 /* the channel assignment a reader answers with: under the presentation a two-substream stream has k channels in the
  * identity assignment of k (MLP channel c = RIFF channel c, src/mlp.c:416-438), whatever its major sync names */
@@ -116,6 +119,9 @@ struct DVDA_Track_Reader_s {
     uint8_t *d_wav;            /* MLP reader opened under dvda_hip_set_wav_output(1): the decode kernels wrote the WAV
                                   payload themselves (DVDA_PCM_WAV24 / WAV16); there is no int32 PCM for dvda_read() */
     uint64_t wav_bytes;
+    int dg_state;              /* digest (dvda_hip_set_digest): 0 off, 1 = dg_crc / dg_bytes are the track's, -1 none (bit depth) */
+    uint32_t dg_crc;
+    uint64_t dg_bytes;
 };
 
 /* ------------------------------------------------------------------ files */
@@ -547,6 +553,31 @@ static int64_t find_sync_dev(const uint8_t *d_bytes, uint64_t from, uint64_t siz
     return at;
 }
 
+/* The digest of one piece of PCM where it lies on the device (dvda_pcm_hip_crc32): `frames` frames of `ch` channels at
+ * `bits` in `layout` at d_pcm, capacity `stride` frames.  Blocks; what it allocates it frees.  1 = ok. */
+static int piece_digest(const int32_t *d_pcm, uint32_t layout, unsigned bits, uint64_t stride, uint64_t frames, unsigned ch,
+                        uint32_t *crc, uint64_t *nbytes)
+{
+    const uint64_t bound = frames * ch * (bits / 8);
+    const size_t words = dvda_pcm_hip_crc32_workspace_words(1, bound);
+    const dvda_pcm_crc_desc desc = {0, stride, frames, ch, 0};
+    uint8_t *d = NULL;
+    int ok = 0;
+    *crc = 0;
+    *nbytes = 0;
+    /* desc (32 bytes) | nbytes (8) | crc (4, padded to 8) | workspace */
+    if (!dev_alloc((void **)&d, 48 + words * sizeof(uint32_t)))
+        return 0;
+    if (hipMemcpy(d, &desc, sizeof(desc), hipMemcpyHostToDevice) == hipSuccess &&
+        dvda_pcm_hip_crc32(d_pcm, layout, bits, (const dvda_pcm_crc_desc *)d, 1, bound, (uint32_t *)(d + 40),
+                           (uint64_t *)(d + 32), (uint32_t *)(d + 48), words, NULL) == DVDA_HIP_OK &&
+        hipMemcpy(nbytes, d + 32, sizeof(*nbytes), hipMemcpyDeviceToHost) == hipSuccess &&
+        hipMemcpy(crc, d + 40, sizeof(*crc), hipMemcpyDeviceToHost) == hipSuccess)
+        ok = 1;
+    (void)hipFree(d);
+    return ok;
+}
+
 static void windows_free(struct mlp_windows *w);
 
 static void reader_free(DVDA_Track_Reader *r)
@@ -743,6 +774,18 @@ static DVDA_Track_Reader *open_mlp(struct aob_set *aobs, const DVDA_Track *k)
             r->d_pcm = d_pcm;          /* the host copy is made by the first dvda_read() */
         }
         d_pcm = NULL;
+        if (g_digest) {
+            /* before any copy to the host: the track as the decode left it on the device */
+            const unsigned dbits = bits_of(info.group0_bps);
+            r->dg_state = -1;
+            if (dbits == 16 || dbits == 24) {
+                if (!piece_digest(direct ? (const int32_t *)r->d_wav : r->d_pcm,
+                                  direct ? (dbits == 24 ? DVDA_PCM_WAV24 : DVDA_PCM_WAV16) : DVDA_PCM_INTERLEAVED, dbits,
+                                  stride, r->frames, r->channels, &r->dg_crc, &r->dg_bytes))
+                    goto fail;
+                r->dg_state = 1;
+            }
+        }
     }
     goto done;
 fail:
@@ -799,6 +842,8 @@ struct win_slot {
     size_t cap;
     uint64_t frames;
     uint64_t stride;            /* != 0: int32 PLANAR [channel][stride] (raw-PCM windows: the order the un-swizzle writes) */
+    uint32_t crc;               /* digest of the window's payload and its bytes (dvda_hip_set_digest) */
+    uint64_t crc_bytes;
 };
 
 struct mlp_windows {
@@ -810,6 +855,10 @@ struct mlp_windows {
     int wav_request, wav_decided;   /* the opener asked for the payload; decided (from the first window's major sync:
                                        only a 16- or 24-bit stream is decoded straight into it) */
     int present;                /* 1: every window decodes the presentation of substream 0 (dvda_hip_set_presentation) */
+    int digest;                 /* 1: every window is digested on the device before it is copied (dvda_hip_set_digest); -1: the
+                                   stream's bit depth has no digest */
+    uint32_t dg_crc;            /* the windows handed out so far, joined (under `mu`, win_release()) */
+    uint64_t dg_bytes;
     int started, finished, failed;
     /* a raw-PCM track read in windows (round 6): sectors decode independently of each other (src/pcm.c:149: whole chunks
        per packet), so a window is a run of sectors and nothing crosses a cut but the count of frames delivered so far */
@@ -1274,6 +1323,17 @@ static int win_produce(struct mlp_windows *w, struct win_slot *out)
                 return 0;
             w->have_fir = 1;
         }
+        /* ---- the window's digest, from the device */
+        out->crc = 0;
+        out->crc_bytes = 0;
+        if (w->digest) {
+            const unsigned dbits = bits_of(info.group0_bps);
+            if (dbits != 16 && dbits != 24)
+                w->digest = -1;
+            else if (!piece_digest(w->d_pcm, wbits == 24 ? DVDA_PCM_WAV24 : wbits == 16 ? DVDA_PCM_WAV16 : DVDA_PCM_INTERLEAVED,
+                                   dbits, stride, info.pcm_frames, info.channels, &out->crc, &out->crc_bytes))
+                return 0;
+        }
         /* ---- PCM (or payload) to the host buffer */
         const size_t bytes = (size_t)info.pcm_frames * info.channels * (wbits ? wbits / 8 : 4);
         if (bytes > out->cap) {
@@ -1371,6 +1431,11 @@ static int win_produce_pcm(struct mlp_windows *w, struct win_slot *out)
     w->started = 1;
     if (!final && (got < want || w->next >= w->aobs.total))
         final = 1;                               /* the files end inside the track */
+    out->crc = 0;
+    out->crc_bytes = 0;
+    if (deliver && w->digest &&
+        !piece_digest(w->d_pcm, DVDA_PCM_PLANAR, bits, stride, deliver, ch, &out->crc, &out->crc_bytes))
+        return 0;                                /* (the planes as the un-swizzle left them: before packing and copy) */
     if (deliver) {
         if (w->wav_bits) {
             const size_t bytes = (size_t)deliver * ch * (bits / 8);
@@ -1485,6 +1550,11 @@ static struct win_slot *win_current(struct mlp_windows *w)
 static void win_release(struct mlp_windows *w)
 {
     pthread_mutex_lock(&w->mu);
+    if (w->digest > 0) {
+        /* the window is handed out: its digest joins the track's */
+        w->dg_crc = dvda_pcm_hip_crc32_combine(w->dg_crc, w->slot[w->tail].crc, w->slot[w->tail].crc_bytes);
+        w->dg_bytes += w->slot[w->tail].crc_bytes;
+    }
     w->tail = (w->tail + 1) % WIN_SLOTS;
     w->count--;
     w->served_in_slot = 0;
@@ -1549,6 +1619,7 @@ static DVDA_Track_Reader *open_mlp_windowed(const DVDA_Track *k)
     w->wav_bits = 0;
     w->wav_request = g_wav_output ? 1 : 0;
     w->present = g_present;
+    w->digest = g_digest;
     {
         struct win_slot *out = &w->slot[0];
         for (;;) {
@@ -1670,6 +1741,11 @@ static DVDA_Track_Reader *open_pcm(struct aob_set *aobs, const DVDA_Track *k, co
         r->stride = stride;
         r->d_pcm = d_pcm;
         d_pcm = NULL;
+        if (g_digest) {
+            if (!piece_digest(r->d_pcm, DVDA_PCM_PLANAR, bits, stride, deliver, r->channels, &r->dg_crc, &r->dg_bytes))
+                goto fail;
+            r->dg_state = 1;
+        }
         break;
     }
     goto done;
@@ -1724,6 +1800,7 @@ static DVDA_Track_Reader *open_pcm_windowed(const DVDA_Track *k, const uint8_t *
     w->wav_request = g_wav_output ? 1 : 0;
     w->wav_bits = w->wav_request ? (int)bits : 0;
     w->wav_decided = 1;
+    w->digest = g_digest;
     {
         /* the buffers the thread's last windowed reader left serve this one too (same device) */
         struct win_cache *c = &t_win_cache;
@@ -1884,6 +1961,32 @@ int dvda_hip_reader_failed(const DVDA_Track_Reader *r)
         pthread_mutex_unlock(&r->win->mu);
     }
     return f;
+}
+int dvda_hip_reader_crc32(const DVDA_Track_Reader *r, unsigned *crc, unsigned long long *bytes)
+{
+    if (!r)
+        return -1;
+    if (!r->win) {
+        if (r->dg_state != 1)
+            return -1;
+        if (crc)
+            *crc = r->dg_crc;
+        if (bytes)
+            *bytes = r->dg_bytes;
+        return 1;
+    }
+    struct mlp_windows *w = r->win;
+    pthread_mutex_lock(&w->mu);
+    /* final: the producer is done and every window has been handed out */
+    const int rc = (w->digest <= 0 || w->failed) ? -1 : (w->finished && w->count == 0) ? 1 : 0;
+    if (rc >= 0) {
+        if (crc)
+            *crc = w->dg_crc;
+        if (bytes)
+            *bytes = w->dg_bytes;
+    }
+    pthread_mutex_unlock(&w->mu);
+    return rc;
 }
 int dvda_hip_reader_memory(const DVDA_Track_Reader *r, unsigned long long *host_peak, unsigned long long *device_peak)
 {

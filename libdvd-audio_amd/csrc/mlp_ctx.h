@@ -119,6 +119,11 @@ struct dvda_mlp_hip_ctx {
     DevBuf<uint32_t> d_brec;
     DevBuf<uint32_t> d_frec;
     uint32_t iir_lanes;
+    // dvda_mlp_hip_pcm_crc32 (pcm_digest_run.h): grown on first use
+    DevBuf<dvda_pcm_crc_desc> d_crc_desc;   // [streams]
+    DevBuf<uint32_t> d_crc_out;         // [streams]
+    DevBuf<uint64_t> d_crc_bytes;       // [streams]
+    DevBuf<uint32_t> d_crc_work;
     DecodeSettings set;
     // call state
     const uint8_t *d_bytes;

@@ -25,6 +25,7 @@ EXPORTS = [
     "dvda_hip_reader_wav_payload", "dvda_hip_open_track_reader_on", "dvda_hip_reader_wav_only",
     "dvda_hip_reader_wav_next", "dvda_hip_reader_windowed", "dvda_hip_reader_memory", "dvda_hip_reader_failed",
     "dvda_hip_release_cached_buffers", "dvda_hip_set_presentation", "dvda_hip_open_track_reader_with",
+    "dvda_hip_set_digest", "dvda_hip_reader_crc32",
 ]
 
 _lib = None
@@ -85,6 +86,10 @@ def lib():
         L.dvda_hip_reader_failed.argtypes = [vp]
         L.dvda_hip_reader_memory.restype = ctypes.c_int
         L.dvda_hip_reader_memory.argtypes = [vp, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]
+        L.dvda_hip_set_digest.restype = None
+        L.dvda_hip_set_digest.argtypes = [ctypes.c_int]
+        L.dvda_hip_reader_crc32.restype = ctypes.c_int
+        L.dvda_hip_reader_crc32.argtypes = [vp, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_ulonglong)]
         _lib = L
     return _lib
 
@@ -116,7 +121,7 @@ def layout(audio_ts, titleset=1):
 
 
 def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0, fused=False, pieces=False,
-               presentation=0):
+               presentation=0, digest=False):
     """Decodes one track on the GPU.  Returns a dict: codec ("PCM"/"MLP"), bits, rate, channels,
     mask, status, and pcm = int32 [frames, channels] (interleaved, RIFF-WAVE order) read with
     dvda_read() in `chunk`-frame calls -- or, with wav=True, payload = the WAV data bytes packed
@@ -126,7 +131,10 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
     (dvda_hip_reader_wav_next: a long track's windows).  A track read in windows (info["windowed"]) reports the peaks of
     what it held in info["host_peak"] / info["device_peak"]; info["frames"] is then the count at the END of the read.
     presentation=1: the 2-channel presentation of a two-substream MLP track (dvda_hip_open_track_reader_with: substream 0
-    alone; info["channels"] is then k and the frames have k channels)."""
+    alone; info["channels"] is then k and the frames have k channels).
+    digest=True: the reader digests the track on the device (dvda_hip_set_digest): info["crc32"] / info["crc32_bytes"] =
+    zlib's CRC-32 of the track's WAV payload and its size (None when the bit depth has no digest), and
+    info["crc32_states"] = what dvda_hip_reader_crc32 returned right after the open and at the end of the read."""
     L = lib()
     d = L.dvda_open(audio_ts.encode(), None)
     if not d:
@@ -136,7 +144,11 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
         ts = L.dvda_open_titleset(d, titleset)
         t = L.dvda_open_title(ts, title) if ts else None
         k = L.dvda_open_track(t, track) if t else None
-        r = L.dvda_hip_open_track_reader_with(k, device, 1 if (fused and wav) else 0, presentation) if k else None
+        L.dvda_hip_set_digest(1 if digest else 0)
+        try:
+            r = L.dvda_hip_open_track_reader_with(k, device, 1 if (fused and wav) else 0, presentation) if k else None
+        finally:
+            L.dvda_hip_set_digest(0)            # (read when the reader is opened: nothing is left behind)
         if not r:
             raise RuntimeError("track %d/%d/%d cannot be opened for reading" % (titleset, title, track))
         ch = L.dvda_channel_count(r)
@@ -145,6 +157,8 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
                 "status": L.dvda_hip_reader_status(r), "frames": int(L.dvda_hip_reader_total_frames(r)),
                 "wav_only": bool(L.dvda_hip_reader_wav_only(r))}
         info["windowed"] = bool(L.dvda_hip_reader_windowed(r))
+        crc, nbytes = ctypes.c_uint(), ctypes.c_ulonglong()
+        first_state = L.dvda_hip_reader_crc32(r, ctypes.byref(crc), ctypes.byref(nbytes)) if digest else None
         if wav and pieces:
             got, sizes = [], []
             while True:
@@ -174,6 +188,11 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
             L.dvda_hip_reader_memory(r, ctypes.byref(hp), ctypes.byref(dp))
             info.update(host_peak=int(hp.value), device_peak=int(dp.value), frames=int(L.dvda_hip_reader_total_frames(r)),
                         failed=bool(L.dvda_hip_reader_failed(r)), status=L.dvda_hip_reader_status(r))
+        if digest:
+            state = L.dvda_hip_reader_crc32(r, ctypes.byref(crc), ctypes.byref(nbytes))
+            info["crc32_states"] = (first_state, state)
+            info["crc32"] = int(crc.value) if state == 1 else None
+            info["crc32_bytes"] = int(nbytes.value) if state == 1 else None
         return info
     finally:
         if r:

@@ -66,7 +66,18 @@ EXPORTS = ("dvda_mlp_hip_create", "dvda_mlp_hip_destroy", "dvda_mlp_hip_index", 
            "dvda_mlp_hip_shard", "dvda_mlp_hip_create_multi", "dvda_mlp_hip_destroy_multi",
            "dvda_mlp_hip_multi_devices", "dvda_mlp_hip_decode_multi", "dvda_mlp_hip_multi_device_time",
            "dvda_mlp_hip_set_conceal", "dvda_mlp_hip_conceal_spans",
-           "dvda_mlp_hip_set_presentation", "dvda_mlp_hip_present_time")
+           "dvda_mlp_hip_set_presentation", "dvda_mlp_hip_present_time",
+           "dvda_pcm_hip_crc32", "dvda_pcm_hip_crc32_workspace_words", "dvda_mlp_hip_pcm_crc32",
+           "dvda_pcm_hip_crc32_combine")
+
+CRC_TILE_BYTES = 16384      # DVDA_CRC_TILE_BYTES: the digest's tiles, aligned to the end of a stream's payload
+CRC_JOIN_TILES = 256        # DVDA_CRC_JOIN_TILES: tiles a join workgroup folds per turn of its loop
+
+
+class CrcDesc(ctypes.Structure):
+    """dvda_pcm_crc_desc of include/dvda_mlp_hip.h"""
+    _fields_ = [("off", ctypes.c_uint64), ("stride", ctypes.c_uint64), ("frames", ctypes.c_uint64),
+                ("channels", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 ST_CONCEALED = 1 << 30          # DVDA_ST_CONCEALED: conceal mode, the stream was damaged (not in ST_BENIGN)
 CONCEAL_LEADING, CONCEAL_TRAILING, CONCEAL_ROUNDS = 1, 2, 4     # DVDA_CONCEAL_* span flags
@@ -148,6 +159,12 @@ def lib():
         L.dvda_mlp_hip_set_initial_fir.argtypes = [vp, vp]
         L.dvda_mlp_hip_segment_fir.argtypes = [vp, u32, vp, vp]
         L.dvda_mlp_hip_conceal_spans.argtypes = [vp, u32, ctypes.POINTER(ConcealSpan), u32, ctypes.POINTER(u32), vp]
+        L.dvda_pcm_hip_crc32_workspace_words.restype = ctypes.c_size_t
+        L.dvda_pcm_hip_crc32_workspace_words.argtypes = [u32, u64]
+        L.dvda_pcm_hip_crc32.argtypes = [vp, u32, ctypes.c_uint, vp, u32, u64, vp, vp, vp, ctypes.c_size_t, vp]
+        L.dvda_mlp_hip_pcm_crc32.argtypes = [vp, vp, vp, vp, ctypes.c_uint, vp, vp, u32, vp]
+        L.dvda_pcm_hip_crc32_combine.restype = u32
+        L.dvda_pcm_hip_crc32_combine.argtypes = [u32, u32, u64]
         _lib = L
     return _lib
 
@@ -239,6 +256,16 @@ class Context:
         _check(lib().dvda_mlp_hip_segment_fir(self._h, segment, fir.ctypes.data, stream), "segment_fir")
         return fir
 
+    def pcm_crc32(self, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, bits, n=None, stream=0):
+        """dvda_mlp_hip_pcm_crc32: zlib CRC-32 of every stream's WAV payload at `bits`, computed on the device from the
+        PCM the last decode wrote -> list of (crc, payload bytes); blocks"""
+        n = self.n_streams if n is None else n
+        crc = np.zeros(n, np.uint32)
+        nbytes = np.zeros(n, np.uint64)
+        _check(lib().dvda_mlp_hip_pcm_crc32(self._h, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, bits, crc.ctypes.data,
+                                            nbytes.ctypes.data, n, stream), "dvda_mlp_hip_pcm_crc32")
+        return [(int(c), int(b)) for c, b in zip(crc, nbytes)]
+
     def decode_time(self):
         """mean device ms of a whole decode call (all passes); call before kernel_time(), which resets the ring"""
         ms = ctypes.c_double()
@@ -251,6 +278,55 @@ class Context:
         n = ctypes.c_uint32()
         _check(lib().dvda_mlp_hip_kernel_time(self._h, ctypes.byref(ms), ctypes.byref(n)), "kernel_time")
         return float(ms.value), int(n.value)
+
+
+def crc32_combine(crc_a, crc_b, len_b):
+    """dvda_pcm_hip_crc32_combine: crc(A || B) from crc(A), crc(B) and len(B); host arithmetic, needs no GPU"""
+    return int(lib().dvda_pcm_hip_crc32_combine(crc_a, crc_b, len_b))
+
+
+def pcm_crc32(d_pcm, layout, bits, desc, max_total_bytes=None, work=None):
+    """dvda_pcm_hip_crc32 over torch tensors: d_pcm an int32 tensor on the device holding the streams in `layout`,
+    desc a list of (off, stride, frames, channels) as dvda_pcm_crc_desc states them.  -> (crc, nbytes): device tensors
+    (int32 bit patterns of the CRCs, int64 byte counts).  Only the kernels are asynchronous, on torch's current stream:
+    this helper builds the descriptors on the host and copies them to the device (the host waits for that copy), and
+    allocates them, the two results and -- when none is passed -- the workspace; a caller that must not wait or
+    allocate keeps those on the device and calls dvda_pcm_hip_crc32 itself (tools/digest_bench.py).
+    max_total_bytes: bound on the sum of the payload bytes (default: computed from desc); work: an int32 workspace
+    tensor of at least pcm_crc32_workspace_words() elements (default: allocated here)."""
+    import torch
+    if not torch.cuda.is_available():
+        raise HipError("no GPU visible to torch: the PCM digest is HIP-only")
+    dev = d_pcm.device
+    n = len(desc)
+    rec = np.zeros(max(n, 1), np.dtype([("off", "<u8"), ("stride", "<u8"), ("frames", "<u8"), ("channels", "<u4"),
+                                         ("reserved", "<u4")]))
+    for i, (off, stride, frames, channels) in enumerate(desc):
+        rec[i] = (off, stride, frames, channels, 0)
+    if max_total_bytes is None:
+        max_total_bytes = int(sum(int(f) * int(c) * (bits // 8) for _, _, f, c in desc))
+    words = int(lib().dvda_pcm_hip_crc32_workspace_words(n, max_total_bytes))
+    if work is None:
+        work = torch.empty(words, dtype=torch.int32, device=dev)
+    d_desc = torch.from_numpy(rec.view(np.uint8).reshape(-1)).to(dev)
+    d_crc = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    d_nbytes = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    _check(lib().dvda_pcm_hip_crc32(d_pcm.data_ptr(), layout, bits, d_desc.data_ptr(), n, max_total_bytes,
+                                    d_crc.data_ptr(), d_nbytes.data_ptr(), work.data_ptr(), work.numel(), st),
+           "dvda_pcm_hip_crc32")
+    return d_crc[:n], d_nbytes[:n]
+
+
+def pcm_crc32_workspace_words(n, max_total_bytes):
+    return int(lib().dvda_pcm_hip_crc32_workspace_words(n, max_total_bytes))
+
+
+def crc_list(d_crc, d_nbytes):
+    """pcm_crc32's tensors -> list of (crc, nbytes) on the host (waits)"""
+    c = d_crc.cpu().numpy().view(np.uint32)
+    b = d_nbytes.cpu().numpy()
+    return [(int(x), int(y)) for x, y in zip(c, b)]
 
 
 ROWS_PER_AU = {0: 40, 8: 40, 1: 80, 9: 80, 2: 160, 10: 160}
@@ -270,7 +346,7 @@ def pack_streams(streams):
 
 
 def decode_streams(streams, device=0, max_segments=None, lanes_per_segment=0, layout=PCM_PLANAR, ctx=None,
-                   presentation=PRESENT_FULL):
+                   presentation=PRESENT_FULL, crc32=False, crc_bits=24):
     """Decodes a list of complete MLP byte streams on the GPU.
 
     Returns (pcm, infos): pcm[i] is an int32 array [channels, pcm_frames] in RIFF-WAVE
@@ -283,6 +359,8 @@ def decode_streams(streams, device=0, max_segments=None, lanes_per_segment=0, la
     and layout settings are set to this call's.
     presentation=PRESENT_SUBSTREAM0: two-substream streams come out as the k-channel presentation of substream 0
     (pcm[i] is [k, pcm_frames], infos[i].channels == k); one-substream streams as always.
+    crc32=True: -> (pcm, infos, digests), digests[i] = (zlib CRC-32 of stream i's WAV payload at crc_bits, its bytes),
+    computed on the device from the PCM where the decode wrote it (Context.pcm_crc32).
     """
     import torch
     if not torch.cuda.is_available():
@@ -348,6 +426,8 @@ def decode_streams(streams, device=0, max_segments=None, lanes_per_segment=0, la
             ctx.index(d_bytes.data_ptr(), total, d_off.data_ptr(), d_len.data_ptr(), len(streams), st)
             ctx.decode(d_pcm.data_ptr(), d_out_off.data_ptr(), d_stride.data_ptr(), st)
             infos = ctx.stream_info(stream=st)
+        digests = ctx.pcm_crc32(d_pcm.data_ptr(), d_out_off.data_ptr(), d_stride.data_ptr(), crc_bits, stream=st) \
+            if crc32 else None
         host = d_pcm.cpu().numpy()
         pcm = []
         for i, inf in enumerate(infos):
@@ -359,20 +439,23 @@ def decode_streams(streams, device=0, max_segments=None, lanes_per_segment=0, la
             else:
                 a = host[out_off[i]:out_off[i] + r * c].reshape(c, r)
             pcm.append(np.ascontiguousarray(a[:, :int(inf.pcm_frames)]))
-        return pcm, list(infos)
+        return (pcm, list(infos), digests) if crc32 else (pcm, list(infos))
     finally:
         if own:
             ctx.close()
 
 
-def decode_streams_concealed(streams, device=0, max_segments=None, lanes_per_segment=0, layout=PCM_PLANAR, init_fir=None):
+def decode_streams_concealed(streams, device=0, max_segments=None, lanes_per_segment=0, layout=PCM_PLANAR, init_fir=None,
+                             crc32=False, crc_bits=24):
     """decode_streams in conceal mode (dvda_mlp_hip_set_conceal): a damaged stream comes out as kept PCM ++ silence ++
     PCM of a fresh decoder ++ ... instead of a non-benign status (include/dvda_mlp_hip.h states the rule).
 
     -> (pcm, infos, spans).  pcm[i] as decode_streams gives it (int32 [channels, pcm_frames]) for PCM_PLANAR /
     PCM_INTERLEAVED, the payload bytes (uint8) for PCM_WAV24 / PCM_WAV16; spans[i] = list of
     (first_frame, frames, byte_off, byte_end, cause, flags), empty for a stream without damage.
-    init_fir: optional int32 [n_streams, 2, 48], the FIR history the streams start with (dvda_mlp_hip_set_initial_fir)."""
+    init_fir: optional int32 [n_streams, 2, 48], the FIR history the streams start with (dvda_mlp_hip_set_initial_fir).
+    crc32=True: -> (pcm, infos, spans, digests): (CRC-32, bytes) of every stream's WAV payload as it was handed out, at the
+    depth of the WAV layout or at crc_bits for the int32 layouts (Context.pcm_crc32)."""
     import torch
     if not torch.cuda.is_available():
         raise HipError("no GPU visible to torch: the MLP decode path is HIP-only")
@@ -420,6 +503,8 @@ def decode_streams_concealed(streams, device=0, max_segments=None, lanes_per_seg
             arr = (ConcealSpan * max(int(n.value), 1))()
             _check(lib().dvda_mlp_hip_conceal_spans(ctx._h, i, arr, int(n.value), ctypes.byref(n), st), "conceal_spans")
             spans.append([arr[k].as_tuple() for k in range(int(n.value))])
+        digests = ctx.pcm_crc32(d_pcm.data_ptr(), d_out_off.data_ptr(), d_stride.data_ptr(),
+                                {3: 24, 2: 16}.get(nb, crc_bits), stream=st) if crc32 else None
         host = d_pcm.cpu().numpy()
         pcm = []
         for i, inf in enumerate(infos):
@@ -432,7 +517,7 @@ def decode_streams_concealed(streams, device=0, max_segments=None, lanes_per_seg
                 pcm.append(np.ascontiguousarray(host[out_off[i]:out_off[i] + r * c].reshape(r, c).T[:, :f]))
             else:
                 pcm.append(np.ascontiguousarray(host[out_off[i]:out_off[i] + r * c].reshape(c, r)[:, :f]))
-        return pcm, list(infos), spans
+        return (pcm, list(infos), spans, digests) if crc32 else (pcm, list(infos), spans)
     finally:
         ctx.close()
 
@@ -484,10 +569,11 @@ def decode_streams_multi(streams, devices, layout=PCM_PLANAR, max_segments=None)
         lib().dvda_mlp_hip_destroy_multi(h)
 
 
-def decode_streams_wav(streams, bits, device=0, lanes_per_segment=0, presentation=PRESENT_FULL):
+def decode_streams_wav(streams, bits, device=0, lanes_per_segment=0, presentation=PRESENT_FULL, crc32=False):
     """Decodes complete MLP byte streams straight into the interleaved little-endian WAV payload dvda2wav
     writes (DVDA_PCM_WAV24 / DVDA_PCM_WAV16: the output stage fused into the decode kernels).
-    -> (list of uint8 arrays, infos)."""
+    -> (list of uint8 arrays, infos); crc32=True: -> (payloads, infos, digests), digests[i] = (CRC-32, bytes) of payload i
+    computed on the device (Context.pcm_crc32)."""
     import torch
     if not torch.cuda.is_available():
         raise HipError("no GPU visible to torch: the MLP decode path is HIP-only")
@@ -522,9 +608,11 @@ def decode_streams_wav(streams, bits, device=0, lanes_per_segment=0, presentatio
             if not any(inf.status & ST["OVERFLOW"] for inf in infos):
                 break
             rows = [max(r, int(inf.pcm_frames)) for r, inf in zip(rows, infos)]
+        digests = ctx.pcm_crc32(d_pcm.data_ptr(), d_out_off.data_ptr(), d_stride.data_ptr(), bits, stream=st) \
+            if crc32 else None
         host = d_pcm.cpu().numpy().view(np.uint8)
         out = [host[4 * o:4 * o + int(inf.pcm_frames) * int(inf.channels) * nb].copy() for o, inf in zip(out_off, infos)]
-        return out, list(infos)
+        return (out, list(infos), digests) if crc32 else (out, list(infos))
     finally:
         ctx.close()
 

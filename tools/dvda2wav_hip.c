@@ -56,7 +56,8 @@ static double now_s(void)
     return ts.tv_sec + ts.tv_nsec * 1e-9;
 }
 
-static int extract(DVDA_Title *title, unsigned track_num, const char *dir, int device, int fused_wav, int stereo)
+static int extract(DVDA_Title *title, unsigned track_num, const char *dir, int device, int fused_wav, int stereo,
+                   int crc, unsigned titleset_num)
 {
     const int timing = getenv("DVDA_TOOL_TIMING") != NULL;       /* diagnostic: where a track's wall-clock time goes */
     const double t_begin = now_s();
@@ -68,6 +69,8 @@ static int extract(DVDA_Title *title, unsigned track_num, const char *dir, int d
     }
     /* this tool only ever writes WAV files: MLP tracks are decoded straight into the payload */
     /* --stereo: a two-substream MLP track comes out as the 2-channel presentation its substream 0 carries */
+    /* --crc: the reader digests the track on the device, before the payload is copied (read when the reader is opened) */
+    dvda_hip_set_digest(crc);
     DVDA_Track_Reader *r = dvda_hip_open_track_reader_with(track, device, fused_wav, stereo);
     if (!r) {
         fprintf(stderr, "*** Error: unable to open track %u for reading\n", track_num);
@@ -77,8 +80,9 @@ static int extract(DVDA_Title *title, unsigned track_num, const char *dir, int d
     const double t_opened = now_s();
     char path[4096];
     const size_t n = strlen(dir);
-    snprintf(path, sizeof(path), "%s%strack-%2.2u-%2.2u.wav", dir, n && dir[n - 1] == '/' ? "" : "/",
-             dvda_title_number(title), dvda_track_number(track));
+    const unsigned title_number = dvda_title_number(title), track_number = dvda_track_number(track);
+    snprintf(path, sizeof(path), "%s%strack-%2.2u-%2.2u.wav", dir, n && dir[n - 1] == '/' ? "" : "/", title_number,
+             track_number);
     dvda_close_track(track);
     FILE *f = fopen(path, "wb");
     if (!f) {
@@ -119,6 +123,15 @@ static int extract(DVDA_Title *title, unsigned track_num, const char *dir, int d
     ok = fclose(f) == 0 && ok;
     /* (a window that could not be read or decoded ends the pieces early: that is a failed track, not a short one) */
     ok = ok && bytes == frames * channels * (bits / 8) && !dvda_hip_reader_failed(r);
+    if (ok && crc) {
+        /* final once the track has been read to its end: the CRC-32 of the data chunk just written */
+        unsigned v = 0;
+        unsigned long long vb = 0;
+        if (dvda_hip_reader_crc32(r, &v, &vb) == 1)
+            printf("CRC32 %u %u %u %08x %llu\n", titleset_num, title_number, track_number, v, vb);
+        else
+            printf("CRC32 %u %u %u none 0\n", titleset_num, title_number, track_number);
+    }
     if (ok)
         printf("* Wrote: \"%s\"\n", path);
     else
@@ -147,6 +160,8 @@ struct pool {
     const char *dir;
     int fused_wav;
     int stereo;                         /* --stereo: the 2-channel presentation of two-substream MLP tracks */
+    int crc;                            /* --crc: one CRC32 line per track */
+    unsigned titleset;
     int park;                           /* a worker that is through parks instead of ending (the fast way out) */
 };
 struct worker {
@@ -162,7 +177,8 @@ static void *work(void *arg)
         const unsigned i = atomic_fetch_add(&w->pool->next, 1);
         if (i >= w->pool->n_jobs)
             break;
-        if (!extract(w->pool->jobs[i].title, w->pool->jobs[i].track, w->pool->dir, w->device, w->pool->fused_wav, w->pool->stereo))
+        if (!extract(w->pool->jobs[i].title, w->pool->jobs[i].track, w->pool->dir, w->device, w->pool->fused_wav, w->pool->stereo,
+                     w->pool->crc, w->pool->titleset))
             atomic_fetch_add(&w->pool->failed, 1);
     }
     /* (what this thread's last windowed reader left for a next one would be freed when the thread ends -- 30 ms a worker.
@@ -188,6 +204,9 @@ static void usage(const char *prog)
            "  -d DIR, --dir=DIR         output directory (default: the working directory)\n"
            "  -2, --stereo              write the 2-channel presentation of multichannel MLP tracks (substream 0\n"
            "                            alone: the stereo mix a 2-channel player plays), not all channels\n"
+           "  -C, --crc                 print the CRC-32 (zlib) of every track's WAV data chunk, computed on the GPU, one\n"
+           "                            line per track on stdout: CRC32 <titleset> <title> <track> <crc, 8 hex digits>\n"
+           "                            <bytes> (\"none 0\" for a bit depth other than 16 / 24); -c is --cdrom\n"
            "  -g N, --gpu=N             HIP device (default 0)\n"
            "  -D LIST, --devices=LIST   comma-separated HIP devices: one worker thread per entry takes tracks in turn\n"
            "                            (default: up to four workers on the device of -g)\n"
@@ -201,14 +220,15 @@ int main(int argc, char *argv[])
                                        {"track", required_argument, 0, 't'},    {"dir", required_argument, 0, 'd'},
                                        {"gpu", required_argument, 0, 'g'},      {"help", no_argument, 0, 'h'},
                                        {"devices", required_argument, 0, 'D'},  {"stereo", no_argument, 0, '2'},
+                                       {"crc", no_argument, 0, 'C'},
                                        {0, 0, 0, 0}};
     const char *audio_ts = NULL, *dir = ".", *cdrom = NULL;
     unsigned titleset_num = 1, title_num = 0, track_num = 0;
-    int devices[64], n_devices = 0, one_device = 0, stereo = 0;
+    int devices[64], n_devices = 0, one_device = 0, stereo = 0, crc = 0;
     int c;
     if (getenv("DVDA_TOOL_TIMING"))
         fprintf(stderr, "timing: main at %.1f ms\n", now_s() * 1e3);
-    while ((c = getopt_long(argc, argv, "A:c:S:T:t:d:g:D:h2", longopts, NULL)) != -1) {
+    while ((c = getopt_long(argc, argv, "A:c:S:T:t:d:g:D:h2C", longopts, NULL)) != -1) {
         switch (c) {
         case 'A': audio_ts = optarg; break;
         case 'c': cdrom = optarg; break;
@@ -222,6 +242,7 @@ int main(int argc, char *argv[])
                 devices[n_devices++] = atoi(tok);
             break;
         case '2': stereo = 1; break;
+        case 'C': crc = 1; break;
         case 'h': usage(argv[0]); return 0;
         default: return 1;
         }
@@ -273,7 +294,7 @@ int main(int argc, char *argv[])
         for (unsigned i = 0; i < w; i++)
             devices[n_devices++] = one_device;
     }
-    struct pool pool = {jobs, n_jobs, 0, 0, 0, dir, fused_wav, stereo, getenv("DVDA_TOOL_FULL_TEARDOWN") == NULL};
+    struct pool pool = {jobs, n_jobs, 0, 0, 0, dir, fused_wav, stereo, crc, titleset_num, getenv("DVDA_TOOL_FULL_TEARDOWN") == NULL};
     struct worker workers[64];
     pthread_t th[64];
     int started[64];
