@@ -4,7 +4,7 @@ Only the hot path of tuffy/libdvd-audio lives here:
 
     csrc/      hand-written gfx950 HIP kernels + the C ABI of include/dvda_mlp_hip.h
     hipdec.py  ctypes binding of that C ABI (device memory via torch)
-    discdec.py ctypes binding of the disc-level API (include/dvd-audio-hip.h, csrc/dvda_disc.c)
+    discdec.py ctypes binding of the disc-level API (include/dvd-audio-hip.h, csrc/disc_ifo.c + csrc/disc_reader.c)
     synth/     synthetic MLP stream generator (tooling for tests and bench)
 
 The directory name carries a hyphen (it mirrors the reference's name); import it as

@@ -15,9 +15,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_SO = os.path.join(HERE, "libdvda_mlp_hip.so")
 SYNTH_SO = os.path.join(HERE, "synth", "libmlp_synth.so")
 DISC_SO = os.path.join(HERE, "libdvd_audio_hip.so")
-DISC_SRCS = [os.path.join(HERE, "csrc", "dvda_disc.c"),
-             os.path.join(os.path.dirname(HERE), "include", "dvd-audio-hip.h"),
-             os.path.join(os.path.dirname(HERE), "include", "dvda_mlp_hip.h")]
+# the disc tier: the IFO walk (host only), the track readers, what the two share; then the public headers
+DISC_C = [os.path.join(HERE, "csrc", f) for f in ("disc_ifo.c", "disc_reader.c")]
+DISC_HDR = os.path.join(os.path.dirname(HERE), "include", "dvd-audio-hip.h")
+DISC_SRCS = DISC_C + [os.path.join(HERE, "csrc", "disc_internal.h"), DISC_HDR,
+                      os.path.join(os.path.dirname(HERE), "include", "dvda_mlp_hip.h")]
 
 # [0] the HIP translation unit, [1] the streaming tier; behind them EVERY header under csrc/ (the staleness
 # test looks at all of them: an edit to any header mlp_hip.hip includes rebuilds the library)
@@ -84,7 +86,7 @@ def build_disc(force=False):
     if not force and not _stale(DISC_SO, DISC_SRCS + [HIP_SO]):
         return DISC_SO
     subprocess.run(["gcc", "-O2", "-fPIC", "-shared", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-                    "-o", DISC_SO, DISC_SRCS[0], "-L" + HERE, "-ldvda_mlp_hip", "-L/opt/rocm/lib", "-lamdhip64",
+                    "-o", DISC_SO] + DISC_C + ["-L" + HERE, "-ldvda_mlp_hip", "-L/opt/rocm/lib", "-lamdhip64",
                     "-lm", "-lpthread", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,/opt/rocm/lib"], check=True)
     return DISC_SO
 
@@ -95,7 +97,7 @@ TOOL_SRC = os.path.join(os.path.dirname(HERE), "tools", "dvda2wav_hip.c")
 
 def build_tool(force=False):
     """dvda2wav_hip: the command-line extractor on top of libdvd_audio_hip.so."""
-    if not force and not _stale(TOOL, [TOOL_SRC, DISC_SO, DISC_SRCS[1]]):
+    if not force and not _stale(TOOL, [TOOL_SRC, DISC_SO, DISC_HDR]):
         return TOOL
     os.makedirs(os.path.dirname(TOOL), exist_ok=True)
     subprocess.run(["gcc", "-O2", "-Wall", "-o", TOOL, TOOL_SRC, "-I" + os.path.join(os.path.dirname(HERE), "include"),

@@ -146,7 +146,7 @@ def test_mlp_tracks_decoded_straight_into_the_wav_payload(pkg, oracle):
 @pytest.mark.parametrize("kind", ["plain", "chained", "two_substreams", "syncs_without_restart"])
 def test_long_tracks_are_read_in_windows_of_bounded_memory(pkg, oracle, kind):
     """A track of more sectors than a window (DVDA_WINDOW_SECTORS) is read, demultiplexed and decoded window by window
-    (csrc/dvda_disc.c, "MLP track, in windows"; reference: src/dvd-audio.c:751-795 streams a track of any length): the
+    (csrc/disc_reader.c, "MLP track, in windows"; reference: src/dvd-audio.c:751-795 streams a track of any length): the
     windows are cut at major syncs, the bytes behind the cut and the FIR history at it (src/mlp.c:297-304: never cleared --
     the chained title needs it at every cut) are all that crosses a cut.  dvda_read() and the payload pieces give the
     oracle's PCM; what the reader holds does not grow with the track.  syncs_without_restart: most major syncs stand in
@@ -216,7 +216,7 @@ def test_long_tracks_are_read_in_windows_of_bounded_memory(pkg, oracle, kind):
 @pytest.mark.parametrize("bps_code,assignment", [(2, 12), (0, 1)])
 def test_long_raw_pcm_tracks_are_read_in_windows_of_bounded_memory(pkg, oracle, bps_code, assignment):
     """A raw-PCM track of more sectors than a window is read, un-swizzled and handed out window by window (round 6;
-    csrc/dvda_disc.c open_pcm_windowed; reference: src/dvd-audio.c:752-795, 1017-1083 streams a track packet by packet,
+    csrc/disc_reader.c open_pcm_windowed; reference: src/dvd-audio.c:752-795, 1017-1083 streams a track packet by packet,
     src/pcm.c:99-193): sectors decode independently, so nothing crosses a cut but the count of frames delivered.
     dvda_read() gives the samples that went in, the payload pieces their write_signed packing, the track after it
     starts where this one's PTS length is covered, and what the reader holds does not grow with the track."""

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""tools/fuzz_ifo.py -- CPU-only robustness run of the disc tier's IFO walk (csrc/dvda_disc.c) under
+"""tools/fuzz_ifo.py -- CPU-only robustness run of the disc tier's IFO walk (csrc/disc_ifo.c) under
 AddressSanitizer + UBSan: truncated, bit-flipped and padded AUDIO_TS.IFO / ATS_01_0.IFO files, every
 title / track that still opens is walked.  Build and run:
 
     gcc -O1 -g -fPIC -shared -fsanitize=address,undefined -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include \
-        -o /tmp/asan/libdvd_audio_hip.so libdvd-audio_amd/csrc/dvda_disc.c -Llibdvd-audio_amd \
+        -o /tmp/asan/libdvd_audio_hip.so libdvd-audio_amd/csrc/disc_ifo.c libdvd-audio_amd/csrc/disc_reader.c -Llibdvd-audio_amd \
         -ldvda_mlp_hip -L/opt/rocm/lib -lamdhip64 -lm -Wl,-rpath,$PWD/libdvd-audio_amd -Wl,-rpath,/opt/rocm/lib
     LD_PRELOAD=$(gcc -print-file-name=libasan.so):$(gcc -print-file-name=libubsan.so) \
         ASAN_OPTIONS=detect_leaks=0 python tools/fuzz_ifo.py
