@@ -187,17 +187,19 @@ class Context:
         self._h = ctypes.c_void_p()
         _check(lib().dvda_mlp_hip_create(ctypes.byref(self._h), device, max_streams, max_segments),
                "dvda_mlp_hip_create")
-        _check(lib().dvda_mlp_hip_set_lanes_per_segment(self._h, lanes_per_segment), "set_lanes")
-        _check(lib().dvda_mlp_hip_set_pcm_layout(self._h, layout), "set_pcm_layout")
+        self.set_lanes_per_segment(lanes_per_segment)
+        self.set_pcm_layout(layout)
         if CHAIN_FORM:
-            _check(lib().dvda_mlp_hip_set_chain_form(self._h, CHAIN_FORM), "set_chain_form")
+            self.set_chain_form(CHAIN_FORM)
         self.device = device
         self.n_streams = 0
+        self._batch = None
 
     def close(self):
         if self._h:
             lib().dvda_mlp_hip_destroy(self._h)
             self._h = ctypes.c_void_p()
+            self._batch = None
 
     def __del__(self):
         try:
@@ -205,10 +207,34 @@ class Context:
         except Exception:
             pass
 
+    def set_lanes_per_segment(self, lanes):
+        _check(lib().dvda_mlp_hip_set_lanes_per_segment(self._h, lanes), "set_lanes")
+
+    def set_pcm_layout(self, layout):
+        _check(lib().dvda_mlp_hip_set_pcm_layout(self._h, layout), "set_pcm_layout")
+
+    def set_chain_form(self, form):
+        _check(lib().dvda_mlp_hip_set_chain_form(self._h, form), "set_chain_form")
+
     def set_presentation(self, presentation):
         """dvda_mlp_hip_set_presentation: PRESENT_FULL (default) or PRESENT_SUBSTREAM0 -- two-substream streams decode
         to the k-channel presentation substream 0 carries; asks for a new index()"""
         _check(lib().dvda_mlp_hip_set_presentation(self._h, presentation), "dvda_mlp_hip_set_presentation")
+
+    def set_conceal(self, on):
+        _check(lib().dvda_mlp_hip_set_conceal(self._h, int(on)), "dvda_mlp_hip_set_conceal")
+
+    def set_initial_fir(self, d_fir_ptr):
+        """device pointer to int32 [n_streams][2][48], the FIR history the streams start with, or None: fresh decoders"""
+        _check(lib().dvda_mlp_hip_set_initial_fir(self._h, d_fir_ptr), "dvda_mlp_hip_set_initial_fir")
+
+    def conceal_spans(self, i, stream=0):
+        """spans of stream i from the last decode in conceal mode -> list of ConcealSpan.as_tuple()"""
+        n = ctypes.c_uint32()
+        _check(lib().dvda_mlp_hip_conceal_spans(self._h, i, None, 0, ctypes.byref(n), stream), "conceal_spans")
+        arr = (ConcealSpan * max(int(n.value), 1))()
+        _check(lib().dvda_mlp_hip_conceal_spans(self._h, i, arr, int(n.value), ctypes.byref(n), stream), "conceal_spans")
+        return [arr[k].as_tuple() for k in range(int(n.value))]
 
     def present_time(self):
         """-> (device ms of the strip kernels of the last index, source bytes, presentation bytes)"""
@@ -221,6 +247,12 @@ class Context:
         self.n_streams = n_streams
         _check(lib().dvda_mlp_hip_index(self._h, d_bytes_ptr, total_bytes, d_off_ptr, d_len_ptr,
                                         n_streams, stream), "dvda_mlp_hip_index")
+
+    def index_batch(self, batch, stream=0):
+        """index() of a Batch.  The library keeps the pointers, not the bytes, and the decode reads through them: the
+        context holds on to `batch` until the next index_batch() or close(), so it cannot be freed under a live index"""
+        self._batch = batch
+        self.index(batch.d_bytes.data_ptr(), batch.total, batch.d_off.data_ptr(), batch.d_len.data_ptr(), batch.n, stream)
 
     def decode(self, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, stream=0):
         _check(lib().dvda_mlp_hip_decode(self._h, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, stream),
@@ -345,6 +377,180 @@ def pack_streams(streams):
     return flat, np.asarray(offs, np.uint64), np.asarray(lens, np.uint64)
 
 
+def _cuda(device, what):
+    import torch
+    if not torch.cuda.is_available():
+        raise HipError("no GPU visible to torch: the %s path is HIP-only" % what)
+    return torch.device("cuda", device)
+
+
+class Batch:
+    """The input side of a decode on the device: the packed bytes (d_bytes, `total` of them in front of 64 spare ones)
+    and the n streams' ranges in them (d_off, d_len) -- what Context.index_batch reads.  The tensors must live as long
+    as an index of them is decoded: index_batch keeps the batch for that; a caller of the pointer-level index() keeps it."""
+
+    def __init__(self, streams=None, device=0, packed=None):
+        """packed: (flat, offs, lens) of bytes that are packed already (pack_streams, synth.batch), with any ranges in them"""
+        import torch
+        flat, offs, lens = pack_streams(streams) if packed is None else packed
+        self.dev = _cuda(device, "MLP decode")
+        self.d_bytes = torch.from_numpy(flat).to(self.dev)
+        self.total = int(len(flat) - 64)
+        self._ranges(offs, lens)
+
+    def _ranges(self, offs, lens):
+        import torch
+        self.d_off = torch.from_numpy(np.asarray(offs, np.int64)).to(self.dev)
+        self.d_len = torch.from_numpy(np.asarray(lens, np.int64)).to(self.dev)
+        self.n = len(self.d_off)
+
+    def with_ranges(self, offs, lens):
+        """the same bytes on the device under other ranges (the index checks ranges, it does not trust them)"""
+        import copy
+        other = copy.copy(self)
+        other._ranges(offs, lens)
+        return other
+
+    @property
+    def current_stream(self):
+        """torch's current stream on the batch's device (not a stream of the batch's own), as the C ABI takes it"""
+        import torch
+        return torch.cuda.current_stream(self.dev).cuda_stream
+
+
+def standard_rows(info):
+    """PCM frames a stream decodes to when every access unit has the standard length of its rate"""
+    return int(info.mlp_frames) * ROWS_PER_AU.get(int(info.group0_rate), 0)
+
+
+def grown_rows(rows, infos):
+    """the capacities a decode that reported DVDA_ST_OVERFLOW asks for: pcm_frames where that is more than the stream has"""
+    return [max(int(r), int(inf.pcm_frames)) for r, inf in zip(rows, infos)]
+
+
+def sample_bytes(layout):
+    return {PCM_WAV24: 3, PCM_WAV16: 2}.get(layout, 4)
+
+
+def region_words(rows, channels, layout):
+    """int32 words of one stream's output region: the values themselves, or the WAV payload rounded up to words plus
+    four, so that every stream starts dword-aligned with room for the kernels' whole-word stores"""
+    nb = sample_bytes(layout)
+    return rows * channels if nb == 4 else (rows * channels * nb + 3) // 4 + 4
+
+
+def region_layout(rows, channels, layout):
+    """-> (out_off[i] in int32 words, words of the buffer: at least 1) for regions laid end to end"""
+    out_off, pos = [], 0
+    for r, c in zip(rows, channels):
+        out_off.append(pos)
+        pos += region_words(r, c, layout)
+    return out_off, max(pos, 1)
+
+
+def cut_regions(host, out_off, rows, channels, frames, layout):
+    """a host copy of the PCM buffer (int32) -> per stream int32 [channels, min(frames, rows)] for PCM_PLANAR /
+    PCM_INTERLEAVED, the payload bytes (uint8) of that many frames for PCM_WAV24 / PCM_WAV16"""
+    nb = sample_bytes(layout)
+    pcm = []
+    for o, r, c, f in zip(out_off, rows, channels, frames):
+        f = min(int(f), r)
+        if nb != 4:
+            pcm.append(host.view(np.uint8)[4 * o:4 * o + f * c * nb].copy())
+        elif not r * c:
+            pcm.append(np.zeros((c, 0), np.int32))
+        elif layout == PCM_INTERLEAVED:
+            pcm.append(np.ascontiguousarray(host[o:o + r * c].reshape(r, c).T[:, :f]))
+        else:
+            pcm.append(np.ascontiguousarray(host[o:o + r * c].reshape(c, r)[:, :f]))
+    return pcm
+
+
+class PcmRegions:
+    """The output side of a decode on the device: d_pcm and, per stream, where its region starts (d_out_off, int32
+    words) and its capacity in PCM frames (d_stride = rows).  Regions lie end to end unless the caller places them
+    (out_off); the buffer ends `slack` words behind the last region and starts out filled with `fill` (None: as
+    allocated)."""
+
+    def __init__(self, rows, channels, layout=PCM_PLANAR, device=0, out_off=None, slack=0, fill=0):
+        import torch
+        self.dev = _cuda(device, "MLP decode")
+        self.rows, self.channels, self.layout = [int(r) for r in rows], [int(c) for c in channels], layout
+        self.out_off, words = region_layout(self.rows, self.channels, layout)
+        if out_off is not None:
+            self.out_off = [int(o) for o in out_off]
+            words = max([o + region_words(r, c, layout) for o, r, c in zip(self.out_off, self.rows, self.channels)] + [1])
+        if fill is None:
+            self.d_pcm = torch.empty(words + slack, dtype=torch.int32, device=self.dev)
+        else:
+            self.d_pcm = torch.full((words + slack,), fill, dtype=torch.int32, device=self.dev)
+        self.d_out_off = torch.tensor(self.out_off, dtype=torch.int64, device=self.dev)
+        self.d_stride = torch.tensor(self.rows, dtype=torch.int64, device=self.dev)
+
+    @classmethod
+    def for_infos(cls, infos, layout=PCM_PLANAR, device=0, **kw):
+        """regions of standard length for the streams of an index"""
+        return cls([standard_rows(inf) for inf in infos], [int(inf.channels) for inf in infos], layout, device, **kw)
+
+    def grown(self, infos):
+        """new regions with room for what the decode behind `infos` asked for (grown_rows)"""
+        return PcmRegions(grown_rows(self.rows, infos), self.channels, self.layout, self.dev.index)
+
+    @property
+    def ptrs(self):
+        """(d_pcm, d_out_off, d_out_stride) as Context.decode, decode_async and pcm_crc32 take them"""
+        return self.d_pcm.data_ptr(), self.d_out_off.data_ptr(), self.d_stride.data_ptr()
+
+    def to_host(self, infos):
+        """copies the buffer back (waits) and cuts it at the streams' pcm_frames (cut_regions)"""
+        return cut_regions(self.d_pcm.cpu().numpy(), self.out_off, self.rows, self.channels,
+                           [inf.pcm_frames for inf in infos], self.layout)
+
+
+def decode_batch(ctx, batch, layout, attempts=1, capacity="report", decode=Context.decode, crc_bits=None, stream=None):
+    """The decode sequence, once: index; regions of standard length in `layout` (what ctx is set to); up to `attempts`
+    rounds of decode, each after the first on regions grown to what DVDA_ST_OVERFLOW asked for and a new index; the
+    digest at crc_bits if given; the host copy.  -> (pcm as cut_regions gives it, infos, digests or None)
+    capacity: what more major syncs than the context holds (sync patterns in payload count too) lead to -- "report":
+    DVDA_ST_CAPACITY on the streams; "raise": HipError; a function: called with the count the index found, it returns
+    the larger context the sequence goes on with (the caller's to close).
+    decode: Context.decode or Context.decode_async.  stream: default torch's current one on the batch's device."""
+    st = batch.current_stream if stream is None else stream
+    ctx.index_batch(batch, st)
+    if capacity != "report":
+        try:
+            ctx.segment_count(st)
+        except HipError:
+            if capacity == "raise":
+                raise
+            found = ctypes.c_uint32()
+            lib().dvda_mlp_hip_segment_count(ctx._h, ctypes.byref(found), st)
+            ctx = capacity(int(found.value))
+            ctx.index_batch(batch, st)
+    infos = ctx.stream_info(stream=st)
+    regions = PcmRegions.for_infos(infos, layout, ctx.device)
+    for attempt in range(attempts):
+        if attempt:
+            regions = regions.grown(infos)
+            ctx.index_batch(batch, st)
+        decode(ctx, *regions.ptrs, st)
+        infos = ctx.stream_info(stream=st)
+        if not any(inf.status & ST["OVERFLOW"] for inf in infos):
+            break
+    digests = ctx.pcm_crc32(*regions.ptrs, crc_bits, stream=st) if crc_bits else None
+    return regions.to_host(infos), list(infos), digests
+
+
+def _context_for(ctx, batch, max_segments, lanes_per_segment, layout):
+    """-> (the caller's context set to this call's lanes and layout, or a context of the call's own; is it the call's own)"""
+    if ctx is None:
+        segments = max(64, batch.total // 64) if max_segments is None else max_segments
+        return Context(batch.dev.index, batch.n, segments, lanes_per_segment, layout), True
+    ctx.set_lanes_per_segment(lanes_per_segment)
+    ctx.set_pcm_layout(layout)
+    return ctx, False
+
+
 def decode_streams(streams, device=0, max_segments=None, lanes_per_segment=0, layout=PCM_PLANAR, ctx=None,
                    presentation=PRESENT_FULL, crc32=False, crc_bits=24):
     """Decodes a list of complete MLP byte streams on the GPU.
@@ -355,98 +561,38 @@ def decode_streams(streams, device=0, max_segments=None, lanes_per_segment=0, la
     library writes frame-major (the dvda_read order) and pcm[i] is that buffer viewed
     as [pcm_frames, channels] and transposed, so callers compare the same way.  Raises
     HipError if the HIP path is unavailable; never falls back to a CPU decoder.
-    `ctx`: a caller's Context to run on (it stays open and keeps its size: a batch it cannot hold raises); its lane
-    and layout settings are set to this call's.
+    `ctx`: a caller's Context to run on (it stays open and keeps its size: a batch it cannot hold raises); its lane,
+    layout and presentation settings are set to this call's.  A context of the call's own grows to the batch.
     presentation=PRESENT_SUBSTREAM0: two-substream streams come out as the k-channel presentation of substream 0
     (pcm[i] is [k, pcm_frames], infos[i].channels == k); one-substream streams as always.
     crc32=True: -> (pcm, infos, digests), digests[i] = (zlib CRC-32 of stream i's WAV payload at crc_bits, its bytes),
     computed on the device from the PCM where the decode wrote it (Context.pcm_crc32).
     """
-    import torch
-    if not torch.cuda.is_available():
-        raise HipError("no GPU visible to torch: the MLP decode path is HIP-only")
-    dev = torch.device("cuda", device)
-    flat, offs, lens = pack_streams(streams)
-    total = int(len(flat) - 64)
-    if max_segments is None:
-        max_segments = max(64, total // 64)
-    own = ctx is None
-    if own:
-        ctx = Context(device, len(streams), max_segments, lanes_per_segment, layout)
-    else:
-        _check(lib().dvda_mlp_hip_set_lanes_per_segment(ctx._h, lanes_per_segment), "set_lanes")
-        _check(lib().dvda_mlp_hip_set_pcm_layout(ctx._h, layout), "set_pcm_layout")
-    if presentation != PRESENT_FULL or not own:
-        ctx.set_presentation(presentation)
+    batch = Batch(streams, device)
+    ctx, own = _context_for(ctx, batch, max_segments, lanes_per_segment, layout)
+    made = [ctx]
+
+    def larger(found):
+        made[0].close()
+        made[0] = Context(device, batch.n, found + 64, lanes_per_segment, layout)
+        if presentation != PRESENT_FULL:
+            made[0].set_presentation(presentation)
+        return made[0]
+
     try:
-        d_bytes = torch.from_numpy(flat).to(dev)
-        d_off = torch.from_numpy(offs.astype(np.int64)).to(dev)
-        d_len = torch.from_numpy(lens.astype(np.int64)).to(dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        ctx.index(d_bytes.data_ptr(), total, d_off.data_ptr(), d_len.data_ptr(), len(streams), st)
-        try:
-            ctx.segment_count(st)
-        except HipError:
-            if not own:
-                raise
-            # more major syncs (sync patterns in payload count too) than the context holds: a larger one
-            v = ctypes.c_uint32()
-            lib().dvda_mlp_hip_segment_count(ctx._h, ctypes.byref(v), st)
-            ctx.close()
-            ctx = Context(device, len(streams), int(v.value) + 64, lanes_per_segment, layout)
-            if presentation != PRESENT_FULL:
-                ctx.set_presentation(presentation)
-            ctx.index(d_bytes.data_ptr(), total, d_off.data_ptr(), d_len.data_ptr(), len(streams), st)
-        infos = ctx.stream_info(stream=st)
-        rows, nch = [], []
-        for inf in infos:
-            r = int(inf.mlp_frames) * ROWS_PER_AU.get(int(inf.group0_rate), 0)
-            rows.append(r)
-            nch.append(int(inf.channels))
-        out_off, pos = [], 0
-        for r, c in zip(rows, nch):
-            out_off.append(pos)
-            pos += r * c
-        d_pcm = torch.zeros(max(pos, 1), dtype=torch.int32, device=dev)
-        d_out_off = torch.tensor(out_off, dtype=torch.int64, device=dev)
-        d_stride = torch.tensor(rows, dtype=torch.int64, device=dev)
-        ctx.decode(d_pcm.data_ptr(), d_out_off.data_ptr(), d_stride.data_ptr(), st)
-        infos = ctx.stream_info(stream=st)
-        if any(inf.status & ST["OVERFLOW"] for inf in infos):
-            # access units longer than the standard timing: the general pass reported the
-            # size it needs; allocate exactly that and decode again
-            rows = [max(r, int(inf.pcm_frames)) for r, inf in zip(rows, infos)]
-            out_off, pos = [], 0
-            for r, c in zip(rows, nch):
-                out_off.append(pos)
-                pos += r * c
-            d_pcm = torch.zeros(max(pos, 1), dtype=torch.int32, device=dev)
-            d_out_off = torch.tensor(out_off, dtype=torch.int64, device=dev)
-            d_stride = torch.tensor(rows, dtype=torch.int64, device=dev)
-            ctx.index(d_bytes.data_ptr(), total, d_off.data_ptr(), d_len.data_ptr(), len(streams), st)
-            ctx.decode(d_pcm.data_ptr(), d_out_off.data_ptr(), d_stride.data_ptr(), st)
-            infos = ctx.stream_info(stream=st)
-        digests = ctx.pcm_crc32(d_pcm.data_ptr(), d_out_off.data_ptr(), d_stride.data_ptr(), crc_bits, stream=st) \
-            if crc32 else None
-        host = d_pcm.cpu().numpy()
-        pcm = []
-        for i, inf in enumerate(infos):
-            r, c = rows[i], nch[i]
-            if not r * c:
-                a = np.zeros((c, 0), np.int32)
-            elif layout == PCM_INTERLEAVED:
-                a = host[out_off[i]:out_off[i] + r * c].reshape(r, c).T
-            else:
-                a = host[out_off[i]:out_off[i] + r * c].reshape(c, r)
-            pcm.append(np.ascontiguousarray(a[:, :int(inf.pcm_frames)]))
-        return (pcm, list(infos), digests) if crc32 else (pcm, list(infos))
+        if presentation != PRESENT_FULL or not own:
+            ctx.set_presentation(presentation)
+        # (int32 regions of r*c words, cut as [c, r], for any layout but PCM_INTERLEAVED)
+        pcm, infos, digests = decode_batch(ctx, batch, layout if layout == PCM_INTERLEAVED else PCM_PLANAR, attempts=2,
+                                           capacity=larger if own else "raise", crc_bits=crc_bits if crc32 else None)
+        return (pcm, infos, digests) if crc32 else (pcm, infos)
     finally:
         if own:
-            ctx.close()
+            made[0].close()
 
 
 def decode_streams_concealed(streams, device=0, max_segments=None, lanes_per_segment=0, layout=PCM_PLANAR, init_fir=None,
-                             crc32=False, crc_bits=24):
+                             crc32=False, crc_bits=24, ctx=None):
     """decode_streams in conceal mode (dvda_mlp_hip_set_conceal): a damaged stream comes out as kept PCM ++ silence ++
     PCM of a fresh decoder ++ ... instead of a non-benign status (include/dvda_mlp_hip.h states the rule).
 
@@ -455,71 +601,36 @@ def decode_streams_concealed(streams, device=0, max_segments=None, lanes_per_seg
     (first_frame, frames, byte_off, byte_end, cause, flags), empty for a stream without damage.
     init_fir: optional int32 [n_streams, 2, 48], the FIR history the streams start with (dvda_mlp_hip_set_initial_fir).
     crc32=True: -> (pcm, infos, spans, digests): (CRC-32, bytes) of every stream's WAV payload as it was handed out, at the
-    depth of the WAV layout or at crc_bits for the int32 layouts (Context.pcm_crc32)."""
+    depth of the WAV layout or at crc_bits for the int32 layouts (Context.pcm_crc32).
+    `ctx`: a caller's Context to run on: its lane and layout settings are set to this call's, its presentation to
+    PRESENT_FULL; conceal mode (and init_fir) are taken off it again when the call ends, however it ends.  It keeps its
+    size: a batch it cannot hold raises."""
     import torch
-    if not torch.cuda.is_available():
-        raise HipError("no GPU visible to torch: the MLP decode path is HIP-only")
-    dev = torch.device("cuda", device)
-    flat, offs, lens = pack_streams(streams)
-    total = int(len(flat) - 64)
-    if max_segments is None:
-        max_segments = max(64, total // 64)
-    nb = {PCM_WAV24: 3, PCM_WAV16: 2}.get(layout, 4)
-    ctx = Context(device, len(streams), max_segments, lanes_per_segment, layout)
+    batch = Batch(streams, device)
+    ctx, own = _context_for(ctx, batch, max_segments, lanes_per_segment, layout)
+    d_fir, done = None, False
     try:
-        _check(lib().dvda_mlp_hip_set_conceal(ctx._h, 1), "dvda_mlp_hip_set_conceal")
-        d_fir = None
+        if not own:
+            ctx.set_presentation(PRESENT_FULL)
+        ctx.set_conceal(True)           # (before the index)
         if init_fir is not None:
-            d_fir = torch.from_numpy(np.ascontiguousarray(init_fir, np.int32).reshape(len(streams), 2, 48)).to(dev)
-            _check(lib().dvda_mlp_hip_set_initial_fir(ctx._h, d_fir.data_ptr()), "dvda_mlp_hip_set_initial_fir")
-        d_bytes = torch.from_numpy(flat).to(dev)
-        d_off = torch.from_numpy(offs.astype(np.int64)).to(dev)
-        d_len = torch.from_numpy(lens.astype(np.int64)).to(dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        ctx.index(d_bytes.data_ptr(), total, d_off.data_ptr(), d_len.data_ptr(), len(streams), st)
-        infos = ctx.stream_info(stream=st)
-        rows = [int(inf.mlp_frames) * ROWS_PER_AU.get(int(inf.group0_rate), 0) for inf in infos]
-        nch = [int(inf.channels) for inf in infos]
-        for attempt in range(3):
-            out_off, pos = [], 0
-            for r, c in zip(rows, nch):
-                out_off.append(pos)
-                pos += r * c if nb == 4 else (r * c * nb + 3) // 4 + 4
-            d_pcm = torch.zeros(max(pos, 1), dtype=torch.int32, device=dev)
-            d_out_off = torch.tensor(out_off, dtype=torch.int64, device=dev)
-            d_stride = torch.tensor(rows, dtype=torch.int64, device=dev)
-            if attempt:
-                ctx.index(d_bytes.data_ptr(), total, d_off.data_ptr(), d_len.data_ptr(), len(streams), st)
-            ctx.decode(d_pcm.data_ptr(), d_out_off.data_ptr(), d_stride.data_ptr(), st)
-            infos = ctx.stream_info(stream=st)
-            if not any(inf.status & ST["OVERFLOW"] for inf in infos):
-                break
-            # silence and a fresh decoder's access units can need more than the index's count: the size needed
-            rows = [max(r, int(inf.pcm_frames)) for r, inf in zip(rows, infos)]
-        spans = []
-        for i in range(len(streams)):
-            n = ctypes.c_uint32()
-            _check(lib().dvda_mlp_hip_conceal_spans(ctx._h, i, None, 0, ctypes.byref(n), st), "conceal_spans")
-            arr = (ConcealSpan * max(int(n.value), 1))()
-            _check(lib().dvda_mlp_hip_conceal_spans(ctx._h, i, arr, int(n.value), ctypes.byref(n), st), "conceal_spans")
-            spans.append([arr[k].as_tuple() for k in range(int(n.value))])
-        digests = ctx.pcm_crc32(d_pcm.data_ptr(), d_out_off.data_ptr(), d_stride.data_ptr(),
-                                {3: 24, 2: 16}.get(nb, crc_bits), stream=st) if crc32 else None
-        host = d_pcm.cpu().numpy()
-        pcm = []
-        for i, inf in enumerate(infos):
-            r, c, f = rows[i], nch[i], min(int(inf.pcm_frames), rows[i])
-            if nb != 4:
-                pcm.append(host.view(np.uint8)[4 * out_off[i]:4 * out_off[i] + f * c * nb].copy())
-            elif not r * c:
-                pcm.append(np.zeros((c, 0), np.int32))
-            elif layout == PCM_INTERLEAVED:
-                pcm.append(np.ascontiguousarray(host[out_off[i]:out_off[i] + r * c].reshape(r, c).T[:, :f]))
-            else:
-                pcm.append(np.ascontiguousarray(host[out_off[i]:out_off[i] + r * c].reshape(c, r)[:, :f]))
-        return (pcm, list(infos), spans, digests) if crc32 else (pcm, list(infos), spans)
+            d_fir = torch.from_numpy(np.ascontiguousarray(init_fir, np.int32).reshape(batch.n, 2, 48)).to(batch.dev)
+            ctx.set_initial_fir(d_fir.data_ptr())
+        # silence and a fresh decoder's access units can need more than the index's count, and then once more
+        pcm, infos, digests = decode_batch(ctx, batch, layout, attempts=3, capacity="report" if own else "raise",
+                                           crc_bits={PCM_WAV24: 24, PCM_WAV16: 16}.get(layout, crc_bits) if crc32 else None)
+        spans = [ctx.conceal_spans(i, batch.current_stream) for i in range(batch.n)]
+        done = True
+        return (pcm, infos, spans, digests) if crc32 else (pcm, infos, spans)
     finally:
-        ctx.close()
+        if own:
+            ctx.close()
+        else:
+            rc = lib().dvda_mlp_hip_set_conceal(ctx._h, 0)
+            if d_fir is not None:
+                rc = rc or lib().dvda_mlp_hip_set_initial_fir(ctx._h, None)
+            if done:                    # (a call that failed reports its own error, not this one)
+                _check(rc, "leaving conceal mode")
 
 
 def shard_c(sizes, parts):
@@ -574,45 +685,15 @@ def decode_streams_wav(streams, bits, device=0, lanes_per_segment=0, presentatio
     writes (DVDA_PCM_WAV24 / DVDA_PCM_WAV16: the output stage fused into the decode kernels).
     -> (list of uint8 arrays, infos); crc32=True: -> (payloads, infos, digests), digests[i] = (CRC-32, bytes) of payload i
     computed on the device (Context.pcm_crc32)."""
-    import torch
-    if not torch.cuda.is_available():
-        raise HipError("no GPU visible to torch: the MLP decode path is HIP-only")
+    batch = Batch(streams, device)
     assert bits in (16, 24)
-    nb = bits // 8
-    dev = torch.device("cuda", device)
-    flat, offs, lens = pack_streams(streams)
-    total = int(len(flat) - 64)
-    ctx = Context(device, len(streams), max(64, total // 64), lanes_per_segment, PCM_WAV24 if bits == 24 else PCM_WAV16)
+    layout = PCM_WAV24 if bits == 24 else PCM_WAV16
+    ctx, _ = _context_for(None, batch, None, lanes_per_segment, layout)
     try:
         if presentation != PRESENT_FULL:
             ctx.set_presentation(presentation)
-        d_bytes = torch.from_numpy(flat).to(dev)
-        d_off = torch.from_numpy(offs.astype(np.int64)).to(dev)
-        d_len = torch.from_numpy(lens.astype(np.int64)).to(dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        ctx.index(d_bytes.data_ptr(), total, d_off.data_ptr(), d_len.data_ptr(), len(streams), st)
-        infos = ctx.stream_info(stream=st)
-        rows = [int(inf.mlp_frames) * ROWS_PER_AU.get(int(inf.group0_rate), 0) for inf in infos]
-        for attempt in range(2):
-            out_off, pos = [], 0
-            for r, inf in zip(rows, infos):
-                out_off.append(pos)
-                pos += (r * int(inf.channels) * nb + 3) // 4 + 4          # int32 units, dword-aligned starts
-            d_pcm = torch.zeros(max(pos, 1), dtype=torch.int32, device=dev)
-            d_out_off = torch.tensor(out_off, dtype=torch.int64, device=dev)
-            d_stride = torch.tensor(rows, dtype=torch.int64, device=dev)
-            if attempt:
-                ctx.index(d_bytes.data_ptr(), total, d_off.data_ptr(), d_len.data_ptr(), len(streams), st)
-            ctx.decode(d_pcm.data_ptr(), d_out_off.data_ptr(), d_stride.data_ptr(), st)
-            infos = ctx.stream_info(stream=st)
-            if not any(inf.status & ST["OVERFLOW"] for inf in infos):
-                break
-            rows = [max(r, int(inf.pcm_frames)) for r, inf in zip(rows, infos)]
-        digests = ctx.pcm_crc32(d_pcm.data_ptr(), d_out_off.data_ptr(), d_stride.data_ptr(), bits, stream=st) \
-            if crc32 else None
-        host = d_pcm.cpu().numpy().view(np.uint8)
-        out = [host[4 * o:4 * o + int(inf.pcm_frames) * int(inf.channels) * nb].copy() for o, inf in zip(out_off, infos)]
-        return (out, list(infos), digests) if crc32 else (out, list(infos))
+        out, infos, digests = decode_batch(ctx, batch, layout, attempts=2, crc_bits=bits if crc32 else None)
+        return (out, infos, digests) if crc32 else (out, infos)
     finally:
         ctx.close()
 

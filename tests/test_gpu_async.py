@@ -9,38 +9,15 @@ pytestmark = pytest.mark.gpu
 
 def _decode(pkg, streams, reserve, lanes=0, layout=None):
     """index + decode_async on a fresh context with `reserve` = (pcm_frames, segments, seq_streams) or None"""
-    import torch
     hip = pkg.hipdec
+    batch = hip.Batch(streams)
     layout = hip.PCM_PLANAR if layout is None else layout
-    dev = torch.device("cuda", 0)
-    flat, offs, lens = hip.pack_streams(streams)
-    total = int(len(flat) - 64)
-    ctx = hip.Context(0, len(streams), max(64, total // 64), lanes, layout)
+    ctx = hip.Context(0, batch.n, max(64, batch.total // 64), lanes, layout)
     try:
         if reserve is not None:
             ctx.reserve(*reserve)
-        d_bytes = torch.from_numpy(flat).to(dev)
-        d_off = torch.from_numpy(offs.astype(np.int64)).to(dev)
-        d_len = torch.from_numpy(lens.astype(np.int64)).to(dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        ctx.index(d_bytes.data_ptr(), total, d_off.data_ptr(), d_len.data_ptr(), len(streams), st)
-        infos = ctx.stream_info(stream=st)
-        rows = [int(i.mlp_frames) * hip.ROWS_PER_AU.get(int(i.group0_rate), 0) for i in infos]
-        nch = [int(i.channels) for i in infos]
-        out_off = np.concatenate([[0], np.cumsum([r * c for r, c in zip(rows, nch)])[:-1]]).astype(np.int64)
-        d_pcm = torch.zeros(max(int(sum(r * c for r, c in zip(rows, nch))), 1), dtype=torch.int32, device=dev)
-        d_out_off = torch.from_numpy(out_off).to(dev)
-        d_stride = torch.tensor(rows, dtype=torch.int64, device=dev)
-        ctx.decode_async(d_pcm.data_ptr(), d_out_off.data_ptr(), d_stride.data_ptr(), st)
-        infos = ctx.stream_info(stream=st)
-        host = d_pcm.cpu().numpy()
-        pcm = []
-        for i, inf in enumerate(infos):
-            r, c = rows[i], nch[i]
-            a = host[out_off[i]:out_off[i] + r * c]
-            a = a.reshape(r, c).T if layout == hip.PCM_INTERLEAVED else a.reshape(c, r)
-            pcm.append(np.ascontiguousarray(a[:, :int(inf.pcm_frames)]))
-        return pcm, list(infos)
+        pcm, infos, _ = hip.decode_batch(ctx, batch, layout, decode=hip.Context.decode_async)
+        return pcm, infos
     finally:
         ctx.close()
 

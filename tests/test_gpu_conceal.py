@@ -137,23 +137,16 @@ def test_batch_of_256_few_damaged(pkg, oracle):
 
 
 def test_decode_async_refused_in_conceal_mode(pkg):
-    import torch
     hd = pkg.hipdec
     b, _, _ = make_stream(pkg, 1, 0, n_aus=16)
-    flat, offs, lens = hd.pack_streams([b])
-    dev = torch.device("cuda", 0)
+    batch = hd.Batch([b])
+    st = batch.current_stream
     ctx = hd.Context(0, 1, 64)
     try:
-        assert hd.lib().dvda_mlp_hip_set_conceal(ctx._h, 1) == 0
-        d_bytes = torch.from_numpy(flat).to(dev)
-        d_off = torch.from_numpy(offs.astype(np.int64)).to(dev)
-        d_len = torch.from_numpy(lens.astype(np.int64)).to(dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        ctx.index(d_bytes.data_ptr(), len(flat) - 64, d_off.data_ptr(), d_len.data_ptr(), 1, st)
-        d_pcm = torch.zeros(6 * 16 * 80, dtype=torch.int32, device=dev)
-        d_oo = torch.zeros(1, dtype=torch.int64, device=dev)
-        d_os = torch.full((1,), 16 * 80, dtype=torch.int64, device=dev)
-        rc = hd.lib().dvda_mlp_hip_decode_async(ctx._h, d_pcm.data_ptr(), d_oo.data_ptr(), d_os.data_ptr(), st)
+        ctx.set_conceal(True)
+        ctx.index_batch(batch, st)
+        out = hd.PcmRegions([16 * 80], [6])
+        rc = hd.lib().dvda_mlp_hip_decode_async(ctx._h, *out.ptrs, st)      # (the raw return code is what is asserted)
         assert rc == -3                                 # DVDA_HIP_EINVAL
         n = ctypes.c_uint32(7)
         assert hd.lib().dvda_mlp_hip_conceal_spans(ctx._h, 0, None, 0, ctypes.byref(n), st) == 0 and n.value == 0
@@ -163,14 +156,10 @@ def test_decode_async_refused_in_conceal_mode(pkg):
 
 def _segment_fir(hd, b, segment):
     """FIR history [2][48] at the end of `segment` of stream b, from a decode of the whole stream"""
-    import torch
     ctx = hd.Context(0, 1, 1024)
     try:
         hd.decode_streams([b], ctx=ctx)
-        fir = np.zeros((2, 48), np.int32)
-        st = torch.cuda.current_stream(torch.device("cuda", 0)).cuda_stream
-        hd._check(hd.lib().dvda_mlp_hip_segment_fir(ctx._h, segment, fir.ctypes.data, st), "segment_fir")
-        return fir
+        return ctx.segment_fir(segment)
     finally:
         ctx.close()
 
@@ -205,35 +194,78 @@ def test_initial_fir_carried_into_the_kept_range(pkg, oracle, S):
 def test_second_decode_after_overflow_starts_from_the_index(pkg, oracle):
     # conceal mode reports a capacity that is too small (pcm_frames = what it needs); the same index decoded again --
     # conceal mode off -- reports what the plain decode reports, nothing of the concealed record
-    import torch
     hd = pkg.hipdec
     b, frames, rpa = make_stream(pkg, 1, 0)
     d = damaged_cases(b)["delete2048"]
     want, _ = cm.conceal(d, 6, rpa, oracle)
     _, plain = hd.decode_streams([d])
-    flat, offs, lens = hd.pack_streams([d])
-    dev = torch.device("cuda", 0)
-    st = torch.cuda.current_stream(dev).cuda_stream
+    batch = hd.Batch([d])
+    st = batch.current_stream
     ctx = hd.Context(0, 1, 1024)
     try:
-        d_bytes = torch.from_numpy(flat).to(dev)
-        d_off = torch.from_numpy(offs.astype(np.int64)).to(dev)
-        d_len = torch.from_numpy(lens.astype(np.int64)).to(dev)
-        ctx.index(d_bytes.data_ptr(), len(flat) - 64, d_off.data_ptr(), d_len.data_ptr(), 1, st)
-        cap = want.shape[1] - 1
-        d_pcm = torch.zeros(6 * cap, dtype=torch.int32, device=dev)
-        d_oo = torch.zeros(1, dtype=torch.int64, device=dev)
-        d_os = torch.full((1,), cap, dtype=torch.int64, device=dev)
-        hd._check(hd.lib().dvda_mlp_hip_set_conceal(ctx._h, 1), "set_conceal")
-        ctx.decode(d_pcm.data_ptr(), d_oo.data_ptr(), d_os.data_ptr(), st)
+        ctx.index_batch(batch, st)
+        out = hd.PcmRegions([want.shape[1] - 1], [6])
+        ctx.set_conceal(True)
+        ctx.decode(*out.ptrs, st)
         inf = ctx.stream_info(stream=st)[0]
         assert inf.status & hd.ST_CONCEALED and inf.status & hd.ST["OVERFLOW"]
         assert int(inf.pcm_frames) == want.shape[1]
-        hd._check(hd.lib().dvda_mlp_hip_set_conceal(ctx._h, 0), "set_conceal")
-        ctx.decode(d_pcm.data_ptr(), d_oo.data_ptr(), d_os.data_ptr(), st)
+        ctx.set_conceal(False)
+        ctx.decode(*out.ptrs, st)
         again = ctx.stream_info(stream=st)[0]
         ovf = hd.ST["OVERFLOW"]
         assert (again.status & ~ovf) == (plain[0].status & ~ovf) and not again.status & hd.ST_CONCEALED
         assert again.mlp_frames == plain[0].mlp_frames
+    finally:
+        ctx.close()
+
+
+def _three_streams(pkg):
+    """three 6-channel 96 kHz one-substream streams of 16 access units, one byte flipped in the middle of a unit of the second"""
+    streams = [make_stream(pkg, 1, 0, seed=40 + s, n_aus=16)[0] for s in range(3)]
+    offs = frame_offsets(streams[1])
+    streams[1] = streams[1].copy()
+    streams[1][offs[11] + (offs[12] - offs[11]) // 2] ^= 0x10
+    return streams
+
+
+def test_conceal_on_a_context_that_was_used_for_something_else(pkg, oracle):
+    """after a presentation decode on the same context: the result of a context of its own, and conceal mode off again"""
+    hd = pkg.hipdec
+    streams = _three_streams(pkg)
+    want_pcm, want_infos, want_spans = hd.decode_streams_concealed(streams)
+    ctx = hd.Context(0, 3, 64)
+    try:
+        hd.decode_streams(streams, ctx=ctx, presentation=hd.PRESENT_SUBSTREAM0)
+        pcm, infos, spans = hd.decode_streams_concealed(streams, ctx=ctx)
+        for got, want in zip(pcm, want_pcm):
+            assert got.shape == want.shape and np.array_equal(got, want)
+        assert [(int(i.pcm_frames), int(i.status)) for i in infos] == [(int(i.pcm_frames), int(i.status)) for i in want_infos]
+        assert spans == want_spans and spans[1] and not spans[0] and not spans[2]
+        assert infos[1].status & hd.ST_CONCEALED
+        plain, pinf = hd.decode_streams(streams, ctx=ctx)
+        assert pinf[1].status & ~(hd.ST_BENIGN | hd.ST_CONCEALED) and not pinf[1].status & hd.ST_CONCEALED, hex(pinf[1].status)
+        for k in (0, 2):
+            ref, r, st = oracle.decode(streams[k], 6, 16 * 80)
+            assert st == 0 and pinf[k].status & ~hd.ST_BENIGN == 0 and infos[k].status & ~hd.ST_BENIGN == 0
+            assert np.array_equal(plain[k], ref) and np.array_equal(pcm[k], ref)
+    finally:
+        ctx.close()
+
+
+def test_conceal_on_too_small_a_context_raises_and_leaves_conceal_off(pkg):
+    hd = pkg.hipdec
+    streams = _three_streams(pkg)
+    syncs = sum(1 for b in streams for o in frame_offsets(b) if is_major_sync(b, o))
+    ctx = hd.Context(0, 3, syncs - 2)               # holds the first two streams' major syncs, not the third's
+    try:
+        with pytest.raises(hd.HipError):
+            hd.decode_streams_concealed(streams, ctx=ctx)
+        # off again: the presentation, which a context in conceal mode refuses, can be chosen ...
+        ctx.set_presentation(hd.PRESENT_SUBSTREAM0)
+        ctx.set_presentation(hd.PRESENT_FULL)
+        # ... and the damaged stream alone, which the context holds, is reported and not concealed
+        _, infos = hd.decode_streams(streams[1:2], ctx=ctx)
+        assert infos[0].status & ~(hd.ST_BENIGN | hd.ST_CONCEALED) and not infos[0].status & hd.ST_CONCEALED, hex(infos[0].status)
     finally:
         ctx.close()

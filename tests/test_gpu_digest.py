@@ -218,31 +218,20 @@ def test_conceal_mode(pkg, oracle, layout, bits):
 
 def test_overflow_reports_nothing(pkg, oracle):
     """a stream given too small a capacity carries DVDA_ST_OVERFLOW: (0, 0); the stream beside it is digested"""
-    import torch
     hd = pkg.hipdec
     cases = [oracle_pcm(pkg, oracle, 0, seed) for seed in (0, 1)]
-    streams = [b for b, _ in cases]
-    dev = torch.device("cuda", 0)
-    flat, offs, lens = hd.pack_streams(streams)
-    total = int(len(flat) - 64)
-    ctx = hd.Context(0, len(streams), max(64, total // 64))
+    batch = hd.Batch([b for b, _ in cases])
+    st = batch.current_stream
+    ctx = hd.Context(0, batch.n, max(64, batch.total // 64))
     try:
-        d_bytes = torch.from_numpy(flat).to(dev)
-        d_off = torch.from_numpy(offs.astype(np.int64)).to(dev)
-        d_len = torch.from_numpy(lens.astype(np.int64)).to(dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        ctx.index(d_bytes.data_ptr(), total, d_off.data_ptr(), d_len.data_ptr(), len(streams), st)
-        infos = ctx.stream_info(stream=st)
-        rows = [int(i.mlp_frames) * hd.ROWS_PER_AU[int(i.group0_rate)] for i in infos]
+        ctx.index_batch(batch, st)
+        rows = [hd.standard_rows(i) for i in ctx.stream_info(stream=st)]
         rows[0] //= 2                                       # too small for stream 0
-        out_off = [0, rows[0] * 6]
-        d_pcm = torch.zeros(sum(r * 6 for r in rows) + 4, dtype=torch.int32, device=dev)
-        d_out_off = torch.tensor(out_off, dtype=torch.int64, device=dev)
-        d_stride = torch.tensor(rows, dtype=torch.int64, device=dev)
-        ctx.decode(d_pcm.data_ptr(), d_out_off.data_ptr(), d_stride.data_ptr(), st)
+        out = hd.PcmRegions(rows, [6, 6], slack=4)
+        ctx.decode(*out.ptrs, st)
         infos = ctx.stream_info(stream=st)
         assert infos[0].status & hd.ST["OVERFLOW"] and not infos[1].status & ~hd.ST_BENIGN
-        got = ctx.pcm_crc32(d_pcm.data_ptr(), d_out_off.data_ptr(), d_stride.data_ptr(), 24, stream=st)
+        got = ctx.pcm_crc32(*out.ptrs, 24, stream=st)
         payload = oracle.wav_pack(cases[1][1], 24)
         assert got == [(0, 0), (zlib.crc32(payload), len(payload))]
     finally:

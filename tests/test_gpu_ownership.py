@@ -10,8 +10,6 @@
 
 Every decode is held bit for bit against what the other GPU tests hold it against: the oracle, tests/conceal_model.py,
 tests/presentation_model.py."""
-import ctypes
-
 import numpy as np
 import pytest
 
@@ -50,58 +48,22 @@ def _check_presentation(hd, oracle, ctx, streams):
 
 
 def _check_concealed(hd, oracle, ctx, streams, cache):
-    """hipdec.decode_streams_concealed (planar), on the caller's context"""
-    import torch
-    dev = torch.device("cuda", ctx.device)
-    st = torch.cuda.current_stream(dev).cuda_stream
-    n = len(streams)
-    flat, offs, lens = hd.pack_streams(streams)
-    d_bytes = torch.from_numpy(flat).to(dev)
-    d_off = torch.from_numpy(offs.astype(np.int64)).to(dev)
-    d_len = torch.from_numpy(lens.astype(np.int64)).to(dev)
-    ctx.set_presentation(hd.PRESENT_FULL)
-    hd._check(hd.lib().dvda_mlp_hip_set_conceal(ctx._h, 1), "dvda_mlp_hip_set_conceal")
-    try:
-        ctx.index(d_bytes.data_ptr(), len(flat) - 64, d_off.data_ptr(), d_len.data_ptr(), n, st)
-        infos = ctx.stream_info(stream=st)
-        rows = [int(inf.mlp_frames) * hd.ROWS_PER_AU.get(int(inf.group0_rate), 0) for inf in infos]
-        nch = [int(inf.channels) for inf in infos]
-        for attempt in range(3):
-            out_off = np.concatenate([[0], np.cumsum([r * c for r, c in zip(rows, nch)])]).astype(np.int64)
-            d_pcm = torch.zeros(max(int(out_off[-1]), 1), dtype=torch.int32, device=dev)
-            d_out_off = torch.from_numpy(out_off[:-1].copy()).to(dev)
-            d_stride = torch.tensor(rows, dtype=torch.int64, device=dev)
-            if attempt:
-                ctx.index(d_bytes.data_ptr(), len(flat) - 64, d_off.data_ptr(), d_len.data_ptr(), n, st)
-            ctx.decode(d_pcm.data_ptr(), d_out_off.data_ptr(), d_stride.data_ptr(), st)
-            infos = ctx.stream_info(stream=st)
-            if not any(inf.status & hd.ST["OVERFLOW"] for inf in infos):
-                break
-            rows = [max(r, int(inf.pcm_frames)) for r, inf in zip(rows, infos)]     # (silence can need more than the index counted)
-        host = d_pcm.cpu().numpy()
-        damaged = 0
-        for i, (b, inf) in enumerate(zip(streams, infos)):
-            key = ("conceal", b.tobytes())
-            if key not in cache:
-                cache[key] = cm.conceal(b, 6, 80, oracle)
-            want, want_sp = cache[key]
-            got = host[out_off[i]:out_off[i] + rows[i] * nch[i]].reshape(nch[i], rows[i])[:, :int(inf.pcm_frames)]
-            cnt = ctypes.c_uint32()
-            hd._check(hd.lib().dvda_mlp_hip_conceal_spans(ctx._h, i, None, 0, ctypes.byref(cnt), st), "conceal_spans")
-            arr = (hd.ConcealSpan * max(int(cnt.value), 1))()
-            hd._check(hd.lib().dvda_mlp_hip_conceal_spans(ctx._h, i, arr, int(cnt.value), ctypes.byref(cnt), st), "conceal_spans")
-            sp = [arr[k].as_tuple() for k in range(int(cnt.value))]
-            assert int(inf.pcm_frames) == want.shape[1] and np.array_equal(got, want), \
-                "stream %d differs from the composed oracle expectation" % i
-            assert [s[:4] + (s[5] & 3,) for s in sp] == want_sp, i
-            if want_sp:
-                damaged += 1
-                assert inf.status & hd.ST_CONCEALED and not inf.status & ~(hd.ST_BENIGN | hd.ST_CONCEALED), hex(inf.status)
-            else:
-                assert inf.status & ~hd.ST_BENIGN == 0
-        return damaged
-    finally:
-        hd._check(hd.lib().dvda_mlp_hip_set_conceal(ctx._h, 0), "dvda_mlp_hip_set_conceal")
+    pcm, infos, spans = hd.decode_streams_concealed(streams, ctx=ctx)
+    damaged = 0
+    for i, (b, got, inf, sp) in enumerate(zip(streams, pcm, infos, spans)):
+        key = ("conceal", b.tobytes())
+        if key not in cache:
+            cache[key] = cm.conceal(b, 6, 80, oracle)
+        want, want_sp = cache[key]
+        assert int(inf.pcm_frames) == want.shape[1] and np.array_equal(got, want), \
+            "stream %d differs from the composed oracle expectation" % i
+        assert [s[:4] + (s[5] & 3,) for s in sp] == want_sp, i
+        if want_sp:
+            damaged += 1
+            assert inf.status & hd.ST_CONCEALED and not inf.status & ~(hd.ST_BENIGN | hd.ST_CONCEALED), hex(inf.status)
+        else:
+            assert inf.status & ~hd.ST_BENIGN == 0
+    return damaged
 
 
 def test_contexts_that_used_every_mode_leave_nothing_behind(pkg, oracle):

@@ -534,32 +534,26 @@ def test_device_code_book_decode_equals_the_tables_exhaustively(pkg, oracle):
 def test_output_buffer_not_16_byte_aligned(pkg, oracle, assignment, lanes, layout):
     """d_out_off / the buffer need not be 16-byte aligned: the kernels then leave the 16-byte stores
     for scalar ones (both PCM layouts; 6-, 2- and 5-channel flush paths)."""
-    import torch
     syn, hip = pkg.synth, pkg.hipdec
     lay = hip.PCM_INTERLEAVED if layout == "interleaved" else hip.PCM_PLANAR
-    dev = torch.device("cuda", 0)
     cfg = syn.make_cfg(assignment=assignment, rate_code=1, n_substreams=lanes if assignment != 12 or lanes == 2 else 1,
                        n_aus=24, profile=1, features=syn.SF_FAST, restart_interval=4)
     b, f = syn.stream(cfg, 4711)
     nch = syn.channels(assignment)
     want, r, st = oracle.decode(b, nch, f)
     assert st == 0
-    flat, offs, lens = hip.pack_streams([b])
-    d_bytes = torch.from_numpy(flat).to(dev)
-    d_off = torch.from_numpy(offs.astype(np.int64)).to(dev)
-    d_len = torch.from_numpy(lens.astype(np.int64)).to(dev)
+    batch = hip.Batch([b])
     for mis in (1, 2, 3):
         ctx = hip.Context(0, 1, 1024, 2 if cfg.n_substreams == 2 else lanes, lay)
         try:
-            ctx.index(d_bytes.data_ptr(), len(flat) - 64, d_off.data_ptr(), d_len.data_ptr(), 1, 0)
+            ctx.index_batch(batch)
             stride = f + 8
-            d_pcm = torch.full((stride * nch + 16,), 0x5A5A5A5A, dtype=torch.int32, device=dev)
-            d_oo = torch.tensor([mis], dtype=torch.int64, device=dev)
-            d_st = torch.tensor([stride], dtype=torch.int64, device=dev)
-            ctx.decode(d_pcm.data_ptr(), d_oo.data_ptr(), d_st.data_ptr(), 0)
+            out = hip.PcmRegions([stride], [nch], lay, out_off=[mis], slack=16 - mis, fill=0x5A5A5A5A)
+            assert out.d_pcm.numel() == stride * nch + 16
+            ctx.decode(*out.ptrs, 0)
             inf = ctx.stream_info()[0]
             assert inf.status & ~hip.ST_BENIGN == 0 and inf.pcm_frames == f
-            host = d_pcm.cpu().numpy()
+            host = out.d_pcm.cpu().numpy()
             body = host[mis:mis + stride * nch]
             got = body.reshape(stride, nch).T[:, :f] if lay == hip.PCM_INTERLEAVED else body.reshape(nch, stride)[:, :f]
             assert np.array_equal(got, want), "misalignment %d" % mis
@@ -608,21 +602,18 @@ def test_wave_flush_into_a_pcm_buffer_of_more_than_16_gb(pkg, oracle, monkeypatc
         b, f = syn.stream(cfg, 7000 + i)
         streams.append(b)
         frames.append(f)
-    flat, offs, lens = hip.pack_streams(streams)
-    d_bytes = torch.from_numpy(flat).to(dev)
-    d_off = torch.from_numpy(offs.astype(np.int64)).to(dev)
-    d_len = torch.from_numpy(lens.astype(np.int64)).to(dev)
+    batch = hip.Batch(streams)
     stride = max(frames)
     # titles 0..19 end just below element 2^32, titles 20..39 start just above it: both kinds of wave, and one that mixes them
     base = (1 << 32) - 20 * stride * 6
     out_off = np.array([base + i * stride * 6 + (64 if i >= 20 else 0) for i in range(n)], np.int64)
-    d_pcm = torch.empty(int(out_off[-1]) + stride * 6 + 64, dtype=torch.int32, device=dev)
+    out = hip.PcmRegions([stride] * n, [6] * n, hip.PCM_INTERLEAVED, out_off=out_off, slack=64, fill=None)
+    d_pcm = out.d_pcm
+    assert d_pcm.numel() == int(out_off[-1]) + stride * 6 + 64
     ctx = hip.Context(0, n, 4096, 1, hip.PCM_INTERLEAVED)
     try:
-        ctx.index(d_bytes.data_ptr(), len(flat) - 64, d_off.data_ptr(), d_len.data_ptr(), n, 0)
-        d_oo = torch.from_numpy(out_off).to(dev)
-        d_st = torch.full((n,), stride, dtype=torch.int64, device=dev)
-        ctx.decode(d_pcm.data_ptr(), d_oo.data_ptr(), d_st.data_ptr(), 0)
+        ctx.index_batch(batch)
+        ctx.decode(*out.ptrs, 0)
         infos = ctx.stream_info()
         for i in range(n):
             want, r, st = oracle.decode(streams[i], 6, frames[i])
@@ -631,7 +622,7 @@ def test_wave_flush_into_a_pcm_buffer_of_more_than_16_gb(pkg, oracle, monkeypatc
             assert np.array_equal(got, want), "title %d" % i
     finally:
         ctx.close()
-        del d_pcm
+        del d_pcm, out
         torch.cuda.empty_cache()
 
 
@@ -865,30 +856,22 @@ def test_two_wave_kernel_with_an_unaligned_output_offset_in_the_group(pkg, oracl
     values.  The two waves of the group used to choose different staging layouts (the idle twin of the
     single-substream segment never loaded the offset) and the two-substream title's channels came out transposed,
     status clean.  Found by tools/soak_reuse.py."""
-    import torch
     syn, hip = pkg.synth, pkg.hipdec
     c1 = syn.make_cfg(assignment=12, rate_code=0, n_substreams=1, n_aus=16, restart_interval=2)
     c2 = syn.make_cfg(assignment=12, rate_code=0, n_substreams=2, n_aus=24, restart_interval=1)
     (b1, f1), (b2, f2) = syn.stream(c1, 81), syn.stream(c2, 82)
     w1 = oracle.decode(b1, 6, f1)[0]
     w2 = oracle.decode(b2, 6, f2)[0]
-    flat, offs, lens = hip.pack_streams([b1, b1, b2])
-    dev = torch.device("cuda", 0)
-    d_bytes = torch.from_numpy(flat).to(dev)
-    d_off = torch.from_numpy(offs.astype(np.int64)).to(dev)
-    d_len = torch.from_numpy(lens.astype(np.int64)).to(dev)
-    out_off = np.array([0, f1 * 6 + 2, f1 * 12 + 8], np.int64)          # the second title starts 2 values off
-    stride = np.array([f1, f1, f2], np.int64)
-    pcm = torch.zeros(int(out_off[2] + f2 * 6 + 16), dtype=torch.int32, device=dev)
-    d_oo = torch.from_numpy(out_off).to(dev)
-    d_stride = torch.from_numpy(stride).to(dev)
+    batch = hip.Batch([b1, b1, b2])
+    out_off = [0, f1 * 6 + 2, f1 * 12 + 8]                              # the second title starts 2 values off
+    out = hip.PcmRegions([f1, f1, f2], [6, 6, 6], hip.PCM_INTERLEAVED, out_off=out_off, slack=16)
     for lanes in (2, 0):
         ctx = hip.Context(0, 3, 256, lanes_per_segment=lanes, layout=hip.PCM_INTERLEAVED)
-        ctx.index(d_bytes.data_ptr(), len(flat) - 64, d_off.data_ptr(), d_len.data_ptr(), 3, 0)
-        pcm.zero_()
-        ctx.decode(pcm.data_ptr(), d_oo.data_ptr(), d_stride.data_ptr(), 0)
+        ctx.index_batch(batch)
+        out.d_pcm.zero_()
+        ctx.decode(*out.ptrs, 0)
         infos = ctx.stream_info(3)
-        host = pcm.cpu().numpy()
+        host = out.d_pcm.cpu().numpy()
         ctx.close()
         for i, (want, f) in enumerate(((w1, f1), (w1, f1), (w2, f2))):
             assert infos[i].status & ~hip.ST_BENIGN == 0 and infos[i].pcm_frames == f
@@ -901,28 +884,22 @@ def test_stream_ranges_are_checked_not_trusted(pkg, oracle):
     twice, a list in descending order, a range that leaves the buffer, a misaligned start) used to send its
     walks anywhere -- a descending list ended in a GPU memory fault.  They are checked on the device: the
     offending streams are reported and not decoded, the others come out exact."""
-    import torch
     syn, hip = pkg.synth, pkg.hipdec
     cfg = syn.make_cfg(assignment=12, rate_code=1, n_aus=24)
     b, f = syn.stream(cfg, 5)
     want, r, st = oracle.decode(b, 6, f)
     flat, offs, lens = hip.pack_streams([b, b, b])
-    dev = torch.device("cuda", 0)
-    d_bytes = torch.from_numpy(flat).to(dev)
-    total = len(flat) - 64
+    packed = hip.Batch(packed=(flat, offs, lens))
     bad = hip.ST["IRREGULAR"]
 
     def run(o, l):
-        d_off = torch.from_numpy(np.asarray(o, np.int64)).to(dev)
-        d_len = torch.from_numpy(np.asarray(l, np.int64)).to(dev)
-        oo = torch.from_numpy(np.arange(3, dtype=np.int64) * f * 6).to(dev)
-        stride = torch.from_numpy(np.full(3, f, np.int64)).to(dev)
-        pcm = torch.zeros(3 * f * 6, dtype=torch.int32, device=dev)
+        out = hip.PcmRegions([f] * 3, [6] * 3)
         ctx = hip.Context(0, 3, 64)
-        ctx.index(d_bytes.data_ptr(), total, d_off.data_ptr(), d_len.data_ptr(), 3, 0)
-        ctx.decode(pcm.data_ptr(), oo.data_ptr(), stride.data_ptr(), 0)
+        batch = packed.with_ranges(o, l)
+        ctx.index_batch(batch)
+        ctx.decode(*out.ptrs, 0)
         infos = ctx.stream_info(3)
-        host = pcm.cpu().numpy().reshape(3, 6, f)
+        host = out.d_pcm.cpu().numpy().reshape(3, 6, f)
         ctx.close()
         return infos, host
 
@@ -952,19 +929,15 @@ def test_stream_ranges_are_checked_not_trusted(pkg, oracle):
     b2, f2 = syn.stream(cfg2, 6)
     want2, r2, st2 = oracle.decode(b2, 2, f2)
     flat2, offs2, lens2 = hip.pack_streams([b, b2, b2])
-    d_bytes2 = torch.from_numpy(flat2).to(dev)
-    d_off = torch.from_numpy(np.asarray([offs2[0], offs2[1], offs2[1]], np.int64)).to(dev)
-    d_len = torch.from_numpy(np.asarray(lens2, np.int64)).to(dev)
+    batch2 = hip.Batch(packed=(flat2, [offs2[0], offs2[1], offs2[1]], lens2))
     cap = max(f, f2)
-    oo = torch.from_numpy(np.arange(3, dtype=np.int64) * cap * 6).to(dev)
-    stride = torch.from_numpy(np.full(3, cap, np.int64)).to(dev)
-    pcm = torch.zeros(3 * cap * 6, dtype=torch.int32, device=dev)
+    out = hip.PcmRegions([cap] * 3, [6] * 3)
     ctx = hip.Context(0, 3, 64)
     for _ in range(2):                      # (twice on one context: the second index replays the first one's launches)
-        ctx.index(d_bytes2.data_ptr(), len(flat2) - 64, d_off.data_ptr(), d_len.data_ptr(), 3, 0)
-        ctx.decode(pcm.data_ptr(), oo.data_ptr(), stride.data_ptr(), 0)
+        ctx.index_batch(batch2)
+        ctx.decode(*out.ptrs, 0)
         infos = ctx.stream_info(3)
-        host = pcm.cpu().numpy()
+        host = out.d_pcm.cpu().numpy()
         assert infos[0].status == 0 and infos[0].pcm_frames == f
         assert np.array_equal(host[:cap * 6].reshape(6, cap)[:, :f], want)
         assert infos[1].status == 0 and infos[1].pcm_frames == f2
@@ -979,7 +952,6 @@ def test_decoding_one_index_more_than_once(pkg, oracle):
     counts, which segments the chain passes took) must not be taken by the second for its own findings: the
     overflow would stick, and the chain passes -- started from a count of NEWLY flagged segments -- would not run,
     leaving chained titles undecoded under a clean status."""
-    import torch
     syn, hip = pkg.synth, pkg.hipdec
     SF = syn.SF
     cfgs = [syn.make_cfg(assignment=12, rate_code=1, n_aus=24),
@@ -995,29 +967,19 @@ def test_decoding_one_index_more_than_once(pkg, oracle):
     nch = [syn.channels(c.assignment) for c in cfgs]
     want = [oracle.decode(b, n, f + 64) for (b, f), n in zip(made, nch)]
     assert all(st == 0 for _, _, st in want)
-    flat, offs, lens = hip.pack_streams(streams)
-    dev = torch.device("cuda", 0)
-    d_bytes = torch.from_numpy(flat).to(dev)
-    d_off = torch.from_numpy(offs.astype(np.int64)).to(dev)
-    d_len = torch.from_numpy(lens.astype(np.int64)).to(dev)
+    batch = hip.Batch(streams)
     n = len(streams)
     ctx = hip.Context(0, n, 256)
     try:
-        ctx.index(d_bytes.data_ptr(), len(flat) - 64, d_off.data_ptr(), d_len.data_ptr(), n, 0)
+        ctx.index_batch(batch)
         rows = [r for _, r, _ in want]
 
         def run(cap):
-            oo, pos = [], 0
-            for c, k in zip(cap, nch):
-                oo.append(pos)
-                pos += c * k
-            d_oo = torch.tensor(oo, dtype=torch.int64, device=dev)
-            d_st = torch.tensor(cap, dtype=torch.int64, device=dev)
-            pcm = torch.full((max(pos, 1),), 0x5A5A5A5A, dtype=torch.int32, device=dev)
-            ctx.decode(pcm.data_ptr(), d_oo.data_ptr(), d_st.data_ptr(), 0)
+            out = hip.PcmRegions(cap, nch, fill=0x5A5A5A5A)
+            ctx.decode(*out.ptrs, 0)
             infos = ctx.stream_info(n)
-            host = pcm.cpu().numpy()
-            return [host[o:o + c * k].reshape(k, c) for o, c, k in zip(oo, cap, nch)], infos
+            host = out.d_pcm.cpu().numpy()
+            return [host[o:o + c * k].reshape(k, c) for o, c, k in zip(out.out_off, cap, nch)], infos
 
         # first with half the room: every title overflows, says how much it needs
         got, infos = run([r // 2 for r in rows])
@@ -1034,18 +996,13 @@ def test_decoding_one_index_more_than_once(pkg, oracle):
 
 def test_too_small_a_context_is_reported_not_truncated(pkg, oracle):
     """more major syncs than max_segments used to come back as short PCM with status 0."""
-    import torch
     syn, hip = pkg.synth, pkg.hipdec
     cfg = syn.make_cfg(assignment=12, rate_code=1, n_aus=64, restart_interval=2)       # 32 segments per title
     streams = [syn.stream(cfg, 8800 + i)[0] for i in range(3)]
-    flat, offs, lens = hip.pack_streams(streams)
-    dev = torch.device("cuda", 0)
-    d_bytes = torch.from_numpy(flat).to(dev)
-    d_off = torch.from_numpy(offs.astype(np.int64)).to(dev)
-    d_len = torch.from_numpy(lens.astype(np.int64)).to(dev)
+    batch = hip.Batch(streams)
     ctx = hip.Context(0, 3, 40)                     # holds the first title and a quarter of the second
     try:
-        ctx.index(d_bytes.data_ptr(), len(flat) - 64, d_off.data_ptr(), d_len.data_ptr(), 3, 0)
+        ctx.index_batch(batch)
         with pytest.raises(hip.HipError):
             ctx.segment_count()
         infos = ctx.stream_info()

@@ -71,37 +71,19 @@ def _manual(pkg, streams, presentation=1, use_async=False, reserve=None, init_fi
     """index + decode on a context of the test's own; after(ctx, stream) runs before the context closes"""
     import torch
     hd = pkg.hipdec
-    dev = torch.device("cuda", 0)
-    flat, offs, lens = hd.pack_streams(streams)
-    total = int(len(flat) - 64)
-    ctx = hd.Context(0, len(streams), max(64, total // 64), lanes)
+    batch = hd.Batch(streams)
+    ctx = hd.Context(0, batch.n, max(64, batch.total // 64), lanes)
     try:
         ctx.set_presentation(presentation)
         if reserve is not None:
             ctx.reserve(*reserve)
         d_fir = None
         if init_fir is not None:
-            d_fir = torch.from_numpy(np.ascontiguousarray(init_fir, np.int32).reshape(len(streams), 2, 48)).to(dev)
-            hd._check(hd.lib().dvda_mlp_hip_set_initial_fir(ctx._h, d_fir.data_ptr()), "set_initial_fir")
-        d_bytes = torch.from_numpy(flat).to(dev)
-        d_off = torch.from_numpy(offs.astype(np.int64)).to(dev)
-        d_len = torch.from_numpy(lens.astype(np.int64)).to(dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        ctx.index(d_bytes.data_ptr(), total, d_off.data_ptr(), d_len.data_ptr(), len(streams), st)
-        infos = ctx.stream_info(stream=st)
-        rows = [int(i.mlp_frames) * hd.ROWS_PER_AU.get(int(i.group0_rate), 0) for i in infos]
-        nch = [int(i.channels) for i in infos]
-        out_off = np.concatenate([[0], np.cumsum([r * c for r, c in zip(rows, nch)])[:-1]]).astype(np.int64)
-        d_pcm = torch.zeros(max(int(sum(r * c for r, c in zip(rows, nch))), 1), dtype=torch.int32, device=dev)
-        d_out_off = torch.from_numpy(out_off).to(dev)
-        d_stride = torch.tensor(rows, dtype=torch.int64, device=dev)
-        (ctx.decode_async if use_async else ctx.decode)(d_pcm.data_ptr(), d_out_off.data_ptr(), d_stride.data_ptr(), st)
-        infos = ctx.stream_info(stream=st)
-        host = d_pcm.cpu().numpy()
-        pcm = [np.ascontiguousarray(host[out_off[i]:out_off[i] + rows[i] * nch[i]].reshape(nch[i], rows[i])
-                                    [:, :int(inf.pcm_frames)]) for i, inf in enumerate(infos)]
-        extra = after(ctx, st) if after else None
-        return pcm, list(infos), extra
+            d_fir = torch.from_numpy(np.ascontiguousarray(init_fir, np.int32).reshape(batch.n, 2, 48)).to(batch.dev)
+            ctx.set_initial_fir(d_fir.data_ptr())
+        pcm, infos, _ = hd.decode_batch(ctx, batch, hd.PCM_PLANAR, decode=hd.Context.decode_async if use_async else hd.Context.decode)
+        extra = after(ctx, batch.current_stream) if after else None
+        return pcm, infos, extra
     finally:
         ctx.close()
 

@@ -69,7 +69,7 @@ def phase_titles(pkg, oracle):
     cfg = syn.make_cfg(assignment=12, rate_code=1, n_substreams=1, n_aus=16)
     titles = _titles(pkg, oracle, [(cfg, 52000 + i) for i in range(130)])
     _, offs, _ = hip.pack_streams([t[0] for t in titles])
-    phases = (offs.astype(np.int64) % 64) // 16
+    phases = (offs % 64 // 16).astype(np.int64)
     counts = np.bincount(phases, minlength=4)
     assert (offs % 16 == 0).all() and (counts >= 8).all(), counts.tolist()     # every phase, each many times
     return titles

@@ -37,29 +37,21 @@ def main():
         fo = frame_offsets(flat[o:o + int(sizes[i])])
         j = len(fo) // 2 + 3
         dmg[o + fo[j] + (fo[j + 1] - fo[j]) // 2] ^= 0x10
-    dev = torch.device("cuda", 0)
-    st = torch.cuda.current_stream(dev).cuda_stream
-    total = int(len(flat) - 64)
-    rows = frames.astype(np.int64)
-    cap = rows + 65536                                  # room for silence longer than what the bytes say
-    out_off = np.concatenate([[0], np.cumsum(cap * 6)[:-1]]).astype(np.int64)
-    d_pcm = torch.zeros(int((cap * 6).sum()), dtype=torch.int32, device=dev)
-    d_oo = torch.from_numpy(out_off).to(dev)
-    d_os = torch.from_numpy(cap).to(dev)
-    d_off = torch.from_numpy(offs.astype(np.int64)).to(dev)
-    d_len = torch.from_numpy(sizes.astype(np.int64)).to(dev)
+    # (room for silence longer than what the bytes say)
+    out = hd.PcmRegions([int(f) + 65536 for f in frames], [6] * n, hd.PCM_INTERLEAVED)
     segs = n * ((args.aus + 7) // 8) + 64
     res = {"streams": n, "aus": args.aus, "damaged_titles": len(hit), "unit": "ms per step (index + decode)"}
     for name, buf, conceal in (("off_clean", flat, 0), ("on_clean", flat, 1), ("on_damaged", dmg, 1), ("off_clean_2", flat, 0)):
         ctx = hd.Context(0, n, segs, 0, hd.PCM_INTERLEAVED)
-        hd._check(hd.lib().dvda_mlp_hip_set_conceal(ctx._h, conceal), "set_conceal")
-        d_bytes = torch.from_numpy(buf).to(dev)
+        ctx.set_conceal(conceal)
+        batch = hd.Batch(packed=(buf, offs, sizes))
+        st = batch.current_stream
         times = []
         for k in range(args.warmup + args.steps):
             torch.cuda.synchronize()
             t = time.perf_counter()
-            ctx.index(d_bytes.data_ptr(), total, d_off.data_ptr(), d_len.data_ptr(), n, st)
-            ctx.decode(d_pcm.data_ptr(), d_oo.data_ptr(), d_os.data_ptr(), st)
+            ctx.index_batch(batch, st)
+            ctx.decode(*out.ptrs, st)
             torch.cuda.synchronize()
             if k >= args.warmup:
                 times.append((time.perf_counter() - t) * 1e3)
@@ -69,7 +61,7 @@ def main():
         res[name] = {"median_ms": round(float(np.median(times)), 3), "min_ms": round(float(np.min(times)), 3),
                      "max_ms": round(float(np.max(times)), 3), "concealed": conc, "non_benign": bad}
         ctx.close()
-        del d_bytes
+        del batch
     print(json.dumps(res))
 
 

@@ -12,7 +12,6 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 os.environ["DVDA_MLP_HIP_LIB"] = os.path.join(ROOT, "libdvd-audio_amd", "exp_count.so")
-import torch  # noqa: E402
 import libdvd_audio_amd as pkg  # noqa: E402
 from tests import oracle_lib  # noqa: E402
 
@@ -24,28 +23,22 @@ syn, hip = pkg.synth, pkg.hipdec
 L = hip.lib()
 L.dvda_mlp_hip_debug_counters.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 tot = np.zeros(16, np.uint64)
-dev = torch.device("cuda", 0)
 
 
 def run(b, f, asg, lanes, misalign=0):
     nch = syn.channels(asg)
-    flat, offs, lens = hip.pack_streams([b])
     ctx = hip.Context(0, 1, 1024, lanes)
-    d_bytes = torch.from_numpy(flat).to(dev)
-    d_off = torch.from_numpy(offs.astype(np.int64)).to(dev)
-    d_len = torch.from_numpy(lens.astype(np.int64)).to(dev)
-    ctx.index(d_bytes.data_ptr(), len(flat) - 64, d_off.data_ptr(), d_len.data_ptr(), 1, 0)
+    batch = hip.Batch([b])
+    ctx.index_batch(batch)
     stride = f + 64 + misalign
-    d_pcm = torch.zeros(stride * nch + 8, dtype=torch.int32, device=dev)
-    d_oo = torch.tensor([misalign], dtype=torch.int64, device=dev)
-    d_st = torch.tensor([stride], dtype=torch.int64, device=dev)
-    ctx.decode(d_pcm.data_ptr(), d_oo.data_ptr(), d_st.data_ptr(), 0)
+    regions = hip.PcmRegions([stride], [nch], out_off=[misalign], slack=8)
+    ctx.decode(*regions.ptrs, 0)
     inf = ctx.stream_info()[0]
     out = (ctypes.c_ulonglong * 16)()
     L.dvda_mlp_hip_debug_counters(ctx._h, out)
     tot[:] += np.array(list(out), np.uint64)
     want, r, st = oracle.decode(b, nch, f)
-    got = d_pcm.cpu().numpy()[misalign:misalign + stride * nch].reshape(nch, stride)[:, :inf.pcm_frames]
+    got = regions.d_pcm.cpu().numpy()[misalign:misalign + stride * nch].reshape(nch, stride)[:, :inf.pcm_frames]
     ok = st == 0 and (inf.status & ~hip.ST_BENIGN) == 0 and got.shape == want.shape and np.array_equal(got, want)
     ctx.close()
     return ok

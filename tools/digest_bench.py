@@ -38,17 +38,11 @@ def main():
     cfg = syn.make_cfg(assignment=12, rate_code=1, n_substreams=1, n_aus=args.aus)
     flat, offs, sizes, frames = syn.batch(cfg, 1, args.streams)
     n, nb = args.streams, args.bits // 8
-    dev = torch.device("cuda", 0)
-    st = torch.cuda.current_stream(dev).cuda_stream
-    total = int(len(flat) - 64)
+    batch = hd.Batch(packed=(flat, offs, sizes))
+    dev, st = batch.dev, batch.current_stream
     rows = frames.astype(np.int64)
-    out_off = np.concatenate([[0], np.cumsum(rows * 6)[:-1]]).astype(np.int64)
-    d_pcm = torch.zeros(int((rows * 6).sum()), dtype=torch.int32, device=dev)
-    d_oo = torch.from_numpy(out_off).to(dev)
-    d_os = torch.from_numpy(rows).to(dev)
-    d_off = torch.from_numpy(offs.astype(np.int64)).to(dev)
-    d_len = torch.from_numpy(sizes.astype(np.int64)).to(dev)
-    d_bytes = torch.from_numpy(flat).to(dev)
+    out = hd.PcmRegions(rows, [6] * n, hd.PCM_INTERLEAVED)
+    d_pcm, out_off = out.d_pcm, out.out_off
     ctx = hd.Context(0, n, n * ((args.aus + 7) // 8) + 64, 0, hd.PCM_INTERLEAVED)
 
     rec = np.zeros(n, np.dtype([("off", "<u8"), ("stride", "<u8"), ("frames", "<u8"), ("channels", "<u4"), ("r", "<u4")]))
@@ -62,8 +56,8 @@ def main():
     h_copy = torch.empty(payload, dtype=torch.uint8).pin_memory()
 
     def decode():
-        ctx.index(d_bytes.data_ptr(), total, d_off.data_ptr(), d_len.data_ptr(), n, st)
-        ctx.decode(d_pcm.data_ptr(), d_oo.data_ptr(), d_os.data_ptr(), st)
+        ctx.index_batch(batch, st)
+        ctx.decode(*out.ptrs, st)
 
     def digest():
         hd._check(hd.lib().dvda_pcm_hip_crc32(d_pcm.data_ptr(), hd.PCM_INTERLEAVED, args.bits, d_desc.data_ptr(), n, payload,

@@ -32,20 +32,13 @@ def shapes(syn, aus):
 class Side:
     """one setting: its context, its PCM buffer"""
 
-    def __init__(self, hd, torch, dev, n, nseg, presentation, d_bytes, total, d_off, d_len, st):
-        self.hd, self.torch, self.st, self.n = hd, torch, st, n
-        self.args = (d_bytes.data_ptr(), total, d_off.data_ptr(), d_len.data_ptr(), n, st)
-        self.ctx = hd.Context(0, n, nseg, 0, hd.PCM_INTERLEAVED)
+    def __init__(self, hd, torch, nseg, presentation, batch, st):
+        self.hd, self.torch, self.st, self.batch = hd, torch, st, batch
+        self.ctx = hd.Context(0, batch.n, nseg, 0, hd.PCM_INTERLEAVED)
         self.ctx.set_presentation(presentation)
-        self.ctx.index(*self.args)
-        infos = self.ctx.stream_info(stream=st)
-        rows = np.array([int(i.mlp_frames) * hd.ROWS_PER_AU[int(i.group0_rate)] for i in infos], np.int64)
-        nch = np.array([int(i.channels) for i in infos], np.int64)
-        out_off = np.concatenate([[0], np.cumsum(rows * nch)[:-1]]).astype(np.int64)
-        self.d_pcm = torch.zeros(int((rows * nch).sum()) + 16, dtype=torch.int32, device=dev)
-        self.d_out_off = torch.from_numpy(out_off).to(dev)
-        self.d_stride = torch.from_numpy(rows).to(dev)
-        self.channels = int(nch[0])
+        self.ctx.index_batch(batch, st)
+        self.out = hd.PcmRegions.for_infos(self.ctx.stream_info(stream=st), hd.PCM_INTERLEAVED, slack=16)
+        self.channels = self.out.channels[0]
         self.step()
         infos = self.ctx.stream_info(stream=st)
         bad = [i for i, inf in enumerate(infos) if inf.status & ~hd.ST_BENIGN]
@@ -55,8 +48,8 @@ class Side:
         self.wall, self.steps, self.rounds = 0.0, 0, []
 
     def step(self):
-        self.ctx.index(*self.args)
-        self.ctx.decode(self.d_pcm.data_ptr(), self.d_out_off.data_ptr(), self.d_stride.data_ptr(), self.st)
+        self.ctx.index_batch(self.batch, self.st)
+        self.ctx.decode(*self.out.ptrs, self.st)
 
     def run(self, steps):
         self.torch.cuda.synchronize()
@@ -87,14 +80,11 @@ def main():
              % (a.streams, a.aus, a.rounds, a.steps, torch.cuda.get_device_name(0))]
     for name, cfg in shapes(syn, a.aus):
         flat, offs, sizes, frames = syn.batch(cfg, 1, a.streams)
-        total = int(len(flat) - 64)
-        d_bytes = torch.from_numpy(flat).to(dev)
-        d_off = torch.from_numpy(offs.astype(np.int64)).to(dev)
-        d_len = torch.from_numpy(sizes.astype(np.int64)).to(dev)
+        batch = hd.Batch(packed=(flat, offs, sizes))
+        total = batch.total
         nseg = a.streams * ((a.aus + cfg.restart_interval - 1) // cfg.restart_interval + 2) + 1024
-        sides = [("full", Side(hd, torch, dev, a.streams, nseg, hd.PRESENT_FULL, d_bytes, total, d_off, d_len, st)),
-                 ("presentation", Side(hd, torch, dev, a.streams, nseg, hd.PRESENT_SUBSTREAM0, d_bytes, total, d_off,
-                                       d_len, st))]
+        sides = [("full", Side(hd, torch, nseg, hd.PRESENT_FULL, batch, st)),
+                 ("presentation", Side(hd, torch, nseg, hd.PRESENT_SUBSTREAM0, batch, st))]
         for _, s in sides:
             s.run(3)                                # warm-up (the index's graph is captured on the third call)
             s.wall, s.steps, s.rounds = 0.0, 0, []
@@ -122,7 +112,7 @@ def main():
         lines.append("  presentation / full = %.3f" % (res["presentation"] / res["full"]))
         for _, s in sides:
             s.ctx.close()
-        del sides, d_bytes
+        del sides, batch
         torch.cuda.empty_cache()
     text = "\n".join(lines) + "\n"
     sys.stdout.write(text)

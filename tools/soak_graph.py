@@ -20,21 +20,16 @@ oracle = oracle_lib.Oracle()
 syn, hip = pkg.synth, pkg.hipdec
 rng = np.random.RandomState(seed0)
 SLOTS, SLOT = 16, 96 * 1024
-dev = torch.device("cuda", 0)
-tstream = torch.cuda.Stream(dev)
-st = tstream.cuda_stream
 total = SLOTS * SLOT
-d_bytes = torch.zeros(total + 64, dtype=torch.uint8, device=dev)
-d_off = torch.from_numpy(np.arange(SLOTS, dtype=np.int64) * SLOT).to(dev)
-d_len = torch.zeros(SLOTS, dtype=torch.int64, device=dev)
+host = np.zeros(total + 64, np.uint8)
+batch = hip.Batch(packed=(host, np.arange(SLOTS) * SLOT, np.zeros(SLOTS)))        # (bytes and lengths rewritten per call)
+tstream = torch.cuda.Stream(batch.dev)
+st = tstream.cuda_stream
 CAP = 16384                                     # PCM frames per slot
-d_pcm = torch.zeros(SLOTS * CAP * 6, dtype=torch.int32, device=dev)
-d_oo = torch.from_numpy(np.arange(SLOTS, dtype=np.int64) * CAP * 6).to(dev)
-d_stride = torch.from_numpy(np.full(SLOTS, CAP, np.int64)).to(dev)
+regions = hip.PcmRegions([CAP] * SLOTS, [6] * SLOTS)
 ctx = hip.Context(0, SLOTS, 1 << 14, layout=hip.PCM_PLANAR)
 two = [12, 1, 0x14, 6, 9, 3, 17, 20]
 bad = cases = 0
-host = np.zeros(total + 64, np.uint8)
 for it in range(n):
     host[:] = 0
     lens = np.zeros(SLOTS, np.int64)
@@ -63,13 +58,13 @@ for it in range(n):
         lens[j] = len(b)
         meta[j] = (b, asg, f)
     with torch.cuda.stream(tstream):
-        d_bytes.copy_(torch.from_numpy(host), non_blocking=False)
-        d_len.copy_(torch.from_numpy(lens), non_blocking=False)
+        batch.d_bytes.copy_(torch.from_numpy(host), non_blocking=False)
+        batch.d_len.copy_(torch.from_numpy(lens), non_blocking=False)
     tstream.synchronize()
-    ctx.index(d_bytes.data_ptr(), total, d_off.data_ptr(), d_len.data_ptr(), SLOTS, st)
-    ctx.decode(d_pcm.data_ptr(), d_oo.data_ptr(), d_stride.data_ptr(), st)
+    ctx.index_batch(batch, st)
+    ctx.decode(*regions.ptrs, st)
     infos = ctx.stream_info(SLOTS, stream=st)
-    out = d_pcm.cpu().numpy()
+    out = regions.d_pcm.cpu().numpy()
     for j in range(SLOTS):
         if meta[j] is None:
             if infos[j].pcm_frames != 0:

@@ -33,16 +33,12 @@ else:
     flat, offs, sizes, frames = syn.batch(cfg, 1, n)
     nchs = np.full(n, 6, np.int64)
     nseg = n * 64
-dev = torch.device("cuda", 0)
-d_bytes = torch.from_numpy(flat).to(dev)
-d_off = torch.from_numpy(offs.astype(np.int64)).to(dev); d_len = torch.from_numpy(sizes.astype(np.int64)).to(dev)
-out_off = np.zeros(n, np.int64); out_off[1:] = np.cumsum(frames[:-1].astype(np.int64) * nchs[:-1])
-d_oo = torch.from_numpy(out_off).to(dev); d_st = torch.from_numpy(frames.astype(np.int64)).to(dev)
-d_pcm = torch.empty(int((frames.astype(np.int64) * nchs).sum()), dtype=torch.int32, device=dev)
+batch = hip.Batch(packed=(flat, offs, sizes))
+out_regions = hip.PcmRegions(frames, nchs, fill=None)
 ctx = hip.Context(0, n, nseg, lanes_per_segment=0)
 for it in range(2):
-    ctx.index(d_bytes.data_ptr(), len(flat) - 64, d_off.data_ptr(), d_len.data_ptr(), n, 0)
-    ctx.decode(d_pcm.data_ptr(), d_oo.data_ptr(), d_st.data_ptr(), 0)
+    ctx.index_batch(batch)
+    ctx.decode(*out_regions.ptrs, 0)
     torch.cuda.synchronize()
     out = (ctypes.c_ulonglong * 16)()
     hip.lib().dvda_mlp_hip_debug_counters.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
