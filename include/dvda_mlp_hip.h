@@ -420,7 +420,11 @@ int dvda_mlp_hip_selftest_bits(int device, const uint8_t *host_bytes, uint32_t n
  * it holds, per sector, what the sector contributed and where it starts in the output:
  *   d_work[s]                 PCM frames (or MLP payload bytes, for the demux call) of sector s
  *   d_work[n_sectors + s]     their exclusive prefix sum; d_work[2 * n_sectors] = the total
- * (the disc tier reads the prefix to cut a track at a sector boundary). */
+ * (the disc tier reads the prefix to cut a track at a sector boundary).
+ * stride must hold every PCM frame the sectors can contain -- at most n_sectors * 2 * (2048 / chunk bytes): the kernel
+ * does not clamp, a sector's frames are written wherever the counts before it put them.  d_pcm may have any 4-byte
+ * alignment and stride any parity (8-byte stores where d_pcm is 8-byte aligned and stride even, 4-byte stores
+ * otherwise: the same planes); d_sectors must be 16-byte aligned.  Values behind a channel's frames are not written. */
 size_t dvda_pcm_hip_workspace_words(uint32_t n_sectors);
 int dvda_pcm_hip_decode_sectors(const uint8_t *d_sectors, uint32_t n_sectors, unsigned bits_per_sample,
                                 unsigned channels, int32_t *d_pcm, uint64_t stride, uint32_t *d_work,
@@ -432,14 +436,21 @@ int dvda_pcm_hip_result(const uint32_t *d_work, uint32_t n_sectors, uint64_t *pc
 /* MLP track demux: AOB sectors of an MLP track -> the contiguous MLP byte
  * stream (every 0xBD packet with codec 0xA1, audio header and pad_2 stripped, in order: what
  * reference src/dvd-audio.c:1151-1227 enqueues packet by packet).  d_work as for the PCM tier;
- * dvda_pcm_hip_result() then returns the byte count in *pcm_frames and the malformed sectors. */
+ * dvda_pcm_hip_result() then returns the byte count in *pcm_frames and the malformed sectors.
+ * d_mlp must be 4-byte aligned.  mlp_cap may be smaller than the payload and need not be a multiple of 4: no byte at
+ * or behind it is written, every byte below the last whole dword under it (offsets < (mlp_cap & ~3)) is, the 1-3 bytes
+ * between may be left untouched (a dword that straddles the cap is dropped whole), and the byte count reported is
+ * still the full one. */
 int dvda_mlp_hip_demux_sectors(const uint8_t *d_sectors, uint32_t n_sectors, uint8_t *d_mlp,
                                uint64_t mlp_cap, uint32_t *d_work, void *stream);
 
 /* Output stage: planar int32 PCM -> the interleaved little-endian WAV payload
  * dvda2wav writes: frame-major interleave of reference src/dvd-audio.c:781-792, each value as
  * write_signed(bits) (utils/dvda2wav.c:326-334, src/bitstream.c:2846-2857).  bits = 16 or 24;
- * d_out receives frames * channels * bits/8 bytes. */
+ * d_out receives frames * channels * bits/8 bytes and not one more.  d_pcm may have any 4-byte alignment, d_out any
+ * byte alignment, stride any value >= frames (only the first `frames` values of a plane are read): 16-byte aligned
+ * planes (d_pcm and stride * 4) with a 4-byte aligned d_out take the fast kernel for whole 1024-frame blocks, anything
+ * else the generic one -- the same bytes. */
 int dvda_mlp_hip_pack_wav(const int32_t *d_pcm, uint64_t stride, unsigned channels, uint64_t frames,
                           unsigned bits_per_sample, uint8_t *d_out, void *stream);
 
