@@ -1014,6 +1014,22 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
 #pragma unroll
         for (int j = 0; j < (MU ? 8 : 1); j++)
             mu[m][j] = 0;
+    // the fast pass places a matrix's result in the staging tile by one LDS store behind the row's channels (see the row
+    // tail) instead of selecting it into one of six registers.  What that needs of a matrix changes at block headers
+    // only and is kept ready from there: where the output channel's plane starts in the tile (in int32 elements, in the
+    // tile's layout of this wave), the output channel's quantisation mask, and -- matrix 1 reads matrix 0's result as its
+    // input channel -- matrix 1's coefficient for matrix 0's output channel, taken out of the coefficients (0 in its place)
+    // (the two-substream lane has no four registers for the first two -- it parks a second substream's state -- and keeps
+    //  the two offsets, 11 bits each, and the two quantisation step sizes, 4 bits each from bit 22, in ONE: a field
+    //  extraction each per PCM frame)
+    constexpr bool PLACE = !GENERAL && !PARSE;
+    constexpr bool MPK = DUO;
+    uint32_t moff[2] = {0, 0};
+    uint32_t mqm[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
+    uint32_t mpk = 0;
+    int32_t mk = 0;
+    auto m_off = [&](int m) -> uint32_t { return MPK ? (mpk >> (11 * m)) & 0x7FFu : moff[m]; };
+    auto m_qm = [&](int m) -> uint32_t { return MPK ? 0xFFFFFFFFu << ((mpk >> (22 + 4 * m)) & 0xFu) : mqm[m]; };
 #pragma unroll
     for (int k = 0; k < NS; k++) {
 #pragma unroll
@@ -1117,7 +1133,8 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
     };
 
     // ---- noise + rematrix + output shift of one PCM frame (src/mlp.c:1327-1355, 515-525);
-    //      ch[0..7] in MLP channel order, shifted in place
+    //      ch[0..7] in MLP channel order, shifted in place.  The sequential pass's, which reads ch[] back: the fast pass
+    //      places a matrix's result in the staging tile instead (the row's tail, PLACE)
     auto rematrix = [&](int32_t(&ch)[MAXCH], uint32_t bypass_bits) {
         const uint32_t shifted = (seed >> 7) & 0xFFFFu;
         const int32_t n0 = (int32_t)((uint32_t)(int32_t)(int8_t)(seed >> 15) << noise_shift);
@@ -1154,41 +1171,10 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                 ch[c] = keep;
             }
         };
-        // the same from coefficients held one per register
-        auto one_matrix_u = [&](const int32_t(&c8)[MU ? 8 : 1], uint32_t m, bool on) {
-            int64_t acc = (int64_t)n0 * (int64_t)c8[MU ? 6 : 0] + (int64_t)n1 * (int64_t)c8[MU ? 7 : 0];
-#pragma unroll
-            for (int c = 0; c < 6; c++)
-                acc += (int64_t)ch[c] * (int64_t)c8[MU ? c : 0];
-            const uint32_t oc = nib(outch_pack, m);
-            const int32_t nv = (int32_t)((uint32_t)mask_q((int32_t)(acc >> 14), nib(qss_A, oc)) +
-                                         ((bypass_bits >> m) & 1u));
-            uint32_t oce = on ? oc : 0xFFu;
-            asm volatile("" : "+v"(oce));
-            uint64_t hit[6];
-#pragma unroll
-            for (int c = 0; c < 6; c++) {
-                hit[c] = __builtin_amdgcn_ballot_w64((uint32_t)c == oce);
-                asm volatile("" : "+s"(hit[c]));
-            }
-#pragma unroll
-            for (int c = 0; c < 6; c++) {
-                int32_t keep = ch[c];
-                asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(keep) : "v"(nv), "s"(hit[c]));
-                ch[c] = keep;
-            }
-        };
-        if constexpr (MU) {
-            if (__any(matrix_len > 0))
-                one_matrix_u(mu[0], 0, matrix_len > 0);
-            if (__any(matrix_len > 1))
-                one_matrix_u(mu[1], 1, matrix_len > 1);
-        } else {
         if (__any(matrix_len > 0))
             one_matrix(mreg[0], mnoise[0], 0, matrix_len > 0);
         if (__any(matrix_len > 1))
             one_matrix(mreg[1], mnoise[1], 1, matrix_len > 1);
-        }
         if (GENERAL && __builtin_expect(__any(matrix_len > 2), 0)) {   // (fast pass: such a segment is ST_COLD)
             for (uint32_t m = 2; m < matrix_len; m++) {    // cold: matrices 2.. live in the workspace
                 DVDA_COV(9);
@@ -1235,6 +1221,24 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
             hdr_now = hdr_now && go;
         }
         gate_turn++;
+        // (MU) the parser works on the packed words, mreg[] / mnoise[], like every other instance.  A wave that parses
+        // packs its one-per-register coefficients into them in front of the phase and unpacks them behind it, every lane
+        // of it: a coefficient is an int16, so nothing is lost, and across the long parser five registers a matrix are
+        // alive and not eight.  (Parsed straight into mu[], the sixteen were alive across the phase beside everything
+        // the parser needs; the allocator parked matrix 1's in scratch, and their reload's wait -- a wait for every older
+        // memory operation, the chunk and the PCM stores among them -- landed in the row's multiply-adds.)
+        const bool hdr_wave = MU && __any(hdr_now);
+        if constexpr (MU) {
+            if (hdr_wave) {
+#pragma unroll
+                for (int m = 0; m < 2; m++) {
+#pragma unroll
+                    for (int j = 0; j < 3; j++)
+                        mreg[m][j] = ((uint32_t)mu[m][MU ? 2 * j : 0] & 0xFFFFu) | ((uint32_t)mu[m][MU ? 2 * j + 1 : 0] << 16);
+                    mnoise[m] = ((uint32_t)mu[m][MU ? 6 : 0] & 0xFFFFu) | ((uint32_t)mu[m][MU ? 7 : 0] << 16);
+                }
+            }
+        }
         if (__builtin_expect(hdr_now, 0)) {
 #if defined(DVDA_EXP_STAMP)
             hstamp_t = clock64();
@@ -1526,12 +1530,6 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                                                 for (int jj = 0; jj < 4; jj++)
                                                     if ((uint32_t)mm == m && (uint32_t)jj == (c >> 1) && mat_mine) {
                                                         mreg[mm][jj] = word;
-                                                        if constexpr (MU) {
-                                                            if (jj < 3) {                           // ([6], [7] are the noise's)
-                                                                mu[mm][MU ? 2 * jj : 0] = lo16(word);
-                                                                mu[mm][MU ? 2 * jj + 1 : 0] = hi16(word);
-                                                            }
-                                                        }
                                                     }
                                         }
                                     } else {
@@ -1543,13 +1541,22 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                                     mnoise[0] = noise;
                                 if (m == 1 && mat_mine)
                                     mnoise[1] = noise;
-                                if constexpr (MU) {
+                            }
+                            if constexpr (PLACE) {
+                                // ---- matrix 1 takes matrix 0's result apart from the channels: acc1 = sum ch[c] m1[c] with
+                                //      m1[oc0] = 0, + nv0 * mk -- the same int64 sum, term for term
+                                if (mat_mine) {
+                                    mk = 0;
+                                    if (matrix_len > 1) {
+                                        const uint32_t oc0 = outch_pack & 0xFu;          // <= max_matrix_channel < 6 (checked)
 #pragma unroll
-                                    for (int mm = 0; mm < 2; mm++)
-                                        if ((uint32_t)mm == m && mat_mine) {
-                                            mu[mm][MU ? 6 : 0] = lo16(noise);
-                                            mu[mm][MU ? 7 : 0] = hi16(noise);
-                                        }
+                                        for (int jj = 0; jj < 3; jj++)
+                                            if ((uint32_t)jj == (oc0 >> 1)) {
+                                                const uint32_t word = mreg[1][jj];
+                                                mk = (oc0 & 1u) ? hi16(word) : lo16(word);
+                                                mreg[1][jj] = word & ((oc0 & 1u) ? 0x0000FFFFu : 0xFFFF0000u);
+                                            }
+                                    }
                                 }
                             }
                         } else if (restart) {
@@ -1824,6 +1831,20 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                 if (mat_mine) {
                     qss_A = qss_pack;
                     mmc_A = max_mat_ch;
+                    if constexpr (PLACE) {
+                        mpk = 0;
+#pragma unroll
+                        for (int m = 0; m < 2; m++) {
+                            const uint32_t oc = nib(outch_pack, m);                 // <= 5 (checked)
+                            const uint32_t off = oc * ((ILV && ilv_direct) ? 64u : (uint32_t)(OUT_ROWS * 64));
+                            if constexpr (MPK) {
+                                mpk |= (off << (11 * m)) | (nib(qss_pack, oc) << (22 + 4 * m));
+                            } else {
+                                moff[m] = off;
+                                mqm[m] = 0xFFFFFFFFu << nib(qss_pack, oc);
+                            }
+                        }
+                    }
                 }
                 const uint32_t cold_ml = matrix_len;        // (this substream's own matrix count)
                 if (matrix_class_change)
@@ -1884,6 +1905,20 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                 }
             }
         }
+        if constexpr (MU) {
+            if (hdr_wave) {
+#pragma unroll
+                for (int m = 0; m < 2; m++) {
+#pragma unroll
+                    for (int j = 0; j < 3; j++) {
+                        mu[m][MU ? 2 * j : 0] = lo16(mreg[m][j]);
+                        mu[m][MU ? 2 * j + 1 : 0] = hi16(mreg[m][j]);
+                    }
+                    mu[m][MU ? 6 : 0] = lo16(mnoise[m]);
+                    mu[m][MU ? 7 : 0] = hi16(mnoise[m]);
+                }
+            }
+        }
         if (hdr_now) {
             DVDA_HSTAMP(4);
 #if defined(DVDA_EXP_STAMP)
@@ -1910,7 +1945,11 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                     // one granule at a time, ring after ring: four registers.  Everything a lane keeps is live here, and
                     // with both rings' granules in flight together (up to eight, 32 registers) the allocator parked them
                     // in scratch inside the row loop -- a store behind every load, a wait for each (tests/test_isa_budget.py)
+                    // (defined HERE, by no instruction, like p0..p3 below: a load under a lane mask leaves the other lanes'
+                    //  value as it was, so an undefined granule is a value carried round this loop and through the whole
+                    //  turn around it, and the allocator parks that in scratch too)
                     uint4 q[1];
+                    asm volatile("" : "=v"(q[0].x), "=v"(q[0].y), "=v"(q[0].z), "=v"(q[0].w));
                     const int32_t n0 = rx.template fill_issue<1>(q);
                     rx.template fill_commit<1>(q, n0);
                     const int32_t n1 = rd.template fill_issue<1>(q);
@@ -2165,6 +2204,9 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
             }
             DVDA_STAMP(2);
         };
+        // fast pass: no row is left before the segment's standard length or the output capacity is reached -- asked here, in
+        // front of the row, for the edge in the row's tail and for the flush behind it
+        const bool no_room = PLACE && room == 0;
         auto row_tail = [&](int32_t (&ch)[MAXCH]) {
             if (owner) {
                 if (GENERAL) {
@@ -2180,8 +2222,99 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                             fr[c] = ch[c];
                         fr[MAXCH] = (int32_t)bypass_bits;
                     }
+                } else if constexpr (PLACE) {
+                    // ---- fast pass: noise, the row's channels into the staging tile, then each matrix's result on top
+                    //      of its output channel's value there.  DS operations of a wave execute in order: the later
+                    //      store is what a flush reads, also where both matrices write one channel.  Nothing is selected
+                    //      lane by lane: the stores run under the lanes that have the matrix, the mask the wave's branch
+                    //      tests anyway.  (Rounds 1-6 put the result into ch[0..5] by six compares and six selects per
+                    //      matrix, all of the slow issue class: docs/history.md A.13)
+                    const uint32_t shifted = (seed >> 7) & 0xFFFFu;
+                    const int32_t n0 = (int32_t)((uint32_t)(int32_t)(int8_t)(seed >> 15) << noise_shift);
+                    const int32_t n1 = (int32_t)((uint32_t)(int32_t)(int8_t)shifted << noise_shift);
+                    seed = (seed << 16) ^ shifted ^ (shifted << 5);
+                    const uint32_t ph = rows_done & (OUT_ROWS - 1);
+                    // which lanes have the matrices: asked once, in front of everything that runs under a lane mask
+                    const bool on0 = matrix_len > 0, on1 = matrix_len > 1;
+                    const uint64_t any0 = __ballot(on0), any1 = __ballot(on1);
+                    // (the output channel is <= max_matrix_channel < 6, checked at the headers: inside the tile)
+                    // Output shifts are rare (all zero on most streams): one test of the wave's chooses between two
+                    // versions of what follows.  A matrix reads the channels unshifted, so with shifts the values are
+                    // shifted on their way into the tile, a matrix's result by its output channel's count.
+                    // (And a version for each layout of the tile, [frame][channel][lane] and [channel][frame][lane]:
+                    //  the compiler otherwise merges the two sets of stores into one with the offsets in registers,
+                    //  an address computation per channel)
+                    auto stage_row = [&](auto with_shifts, auto frame_major) {
+                        constexpr bool OSH = decltype(with_shifts)::value;
+                        constexpr bool FM = decltype(frame_major)::value;
+                        int32_t *const Tb = &s_out[wv][0][0][lane] + ph * (FM ? 6u * 64u : 64u);
+                        auto out_c = [&](int c) -> int32_t {
+                            if constexpr (OSH)
+                                return (uint32_t)c <= mmc_A ? (int32_t)((uint32_t)ch[c] << nib(oshift_pack, c)) : ch[c];
+                            else
+                                return ch[c];
+                        };
+                        auto out_m = [&](uint32_t m, int32_t nv) -> int32_t {
+                            if constexpr (OSH) {
+                                const uint32_t oc = nib(outch_pack, m);
+                                return oc <= mmc_A ? (int32_t)((uint32_t)nv << nib(oshift_pack, oc)) : nv;
+                            } else {
+                                return nv;
+                            }
+                        };
+                        auto mac = [&](int m) -> int64_t {
+                            int64_t acc;
+                            if constexpr (MU) {
+                                acc = (int64_t)n0 * (int64_t)mu[m][MU ? 6 : 0] + (int64_t)n1 * (int64_t)mu[m][MU ? 7 : 0];
+#pragma unroll
+                                for (int c = 0; c < 6; c++)
+                                    acc += (int64_t)ch[c] * (int64_t)mu[m][MU ? c : 0];
+                            } else {
+                                acc = (int64_t)n0 * (int64_t)lo16(mnoise[m]) + (int64_t)n1 * (int64_t)hi16(mnoise[m]);
+#pragma unroll
+                                for (int c = 0; c < 6; c++)
+                                    acc += (int64_t)ch[c] * (int64_t)((c & 1) ? hi16(mreg[m][c >> 1]) : lo16(mreg[m][c >> 1]));
+                            }
+                            return acc;
+                        };
+                        if constexpr (FM) {
+#pragma unroll
+                            for (int c = 0; c < 6; c++)
+                                Tb[c * 64] = out_c(c);
+                        } else {
+#pragma unroll
+                            for (int c = 0; c < TP; c++)
+                                Tb[c * (OUT_ROWS * 64)] = out_c(c);
+                        }
+                        if (any0) {
+                            const int32_t nv0 = (int32_t)(((uint32_t)(int32_t)(mac(0) >> 14) & m_qm(0)) + (bypass_bits & 1u));
+                            if (on0)
+                                Tb[m_off(0)] = out_m(0, nv0);
+                            if (any1) {
+                                // (matrix 0's result, unshifted, as its channel: mk)
+                                const int64_t acc = mac(1) + (int64_t)nv0 * (int64_t)mk;
+                                const int32_t nv1 = (int32_t)(((uint32_t)(int32_t)(acc >> 14) & m_qm(1)) + ((bypass_bits >> 1) & 1u));
+                                if (on1)
+                                    Tb[m_off(1)] = out_m(1, nv1);
+                            }
+                        }
+                    };
+                    const bool osh = __any(oshift_pack != 0);
+                    if (ILV && ilv_direct) {
+                        if constexpr (ILV) {
+                            if (__builtin_expect(osh, 0))
+                                stage_row(std::true_type{}, std::true_type{});
+                            else
+                                stage_row(std::false_type{}, std::true_type{});
+                        }
+                    } else {
+                        if (__builtin_expect(osh, 0))
+                            stage_row(std::true_type{}, std::false_type{});
+                        else
+                            stage_row(std::false_type{}, std::false_type{});
+                    }
                 } else {
-                    if constexpr (PARSE) {
+                    {                       // (chain parse pass)
                         // ---- the row's residuals in MLP channel order, its bypassed LSBs and the noise seed it
                         //      is rematrixed with (stepped once per PCM frame, src/mlp.c:1327-1334)
 #pragma unroll
@@ -2193,8 +2326,6 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                         pq_s[OUT_ROWS - 1] = (int32_t)((seed & 0x7FFFFFu) | (bypass_bits << 23));
                         const uint32_t shifted = (seed >> 7) & 0xFFFFu;
                         seed = (seed << 16) ^ shifted ^ (shifted << 5);
-                    } else {
-                        rematrix(ch, bypass_bits);
                     }
                     // ---- into the LDS staging tile [channel][frame][lane]; rows advance in lockstep so
                     //      the frame phase is the same in every lane
@@ -2231,20 +2362,46 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                     }
                 }
             }
-            row++;
-            rows_done++;
-            if (GENERAL) {
-                if (row > row_limit) {
-                    status |= ST_TIMING;
-                    active = false;
+            if constexpr (PLACE) {
+                // ---- the row's counters.  The output row is row0 + rows_done, the rows written are what `room` has lost
+                //      (both derived where they are needed: at a flush, at the edge, at the end), and the edge -- no room
+                //      left: one 32-bit test per row, the 64-bit ones only there -- is one branch of the wave's
+                if (__builtin_expect(__any(no_room), 0)) {
+                    if (no_room) {
+                        const uint64_t row_now = row0 + rows_done;
+                        // past the segment's standard length it is a timing matter (the general pass then places the
+                        // rows where they really go), not a capacity one
+                        if (owner && row_now >= out_stride && row_now < row_limit) {
+                            status |= ST_OVERFLOW;
+                            active = false;
+                        }
+                        if (row_now + 1u > row_limit) {
+                            status |= ST_TIMING;   // more PCM frames than the standard access-unit length
+                            active = false;
+                        }
+                    } else {
+                        room--;
+                    }
+                } else {
+                    room--;
                 }
-            } else if (__builtin_expect(room == 0, 0)) {
-                if (row > row_limit) {
-                    status |= ST_TIMING;   // more PCM frames than the standard access-unit length
-                    active = false;
-                }
+                rows_done++;
             } else {
-                room--;
+                row++;
+                rows_done++;
+                if (GENERAL) {
+                    if (row > row_limit) {
+                        status |= ST_TIMING;
+                        active = false;
+                    }
+                } else if (__builtin_expect(room == 0, 0)) {
+                    if (row > row_limit) {
+                        status |= ST_TIMING;   // more PCM frames than the standard access-unit length
+                        active = false;
+                    }
+                } else {
+                    room--;
+                }
             }
             frame_rows++;
             rows_left--;
@@ -2420,6 +2577,10 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                     ch[c] = c < NS ? val[c < NS ? c : 0] : 0;
             }
             row_tail(ch);
+            // ---- RIFF order (src/mlp.c:527-533): every OUT_ROWS-th frame each channel's staged frames leave as
+            //      16-byte stores that together cover whole 32-byte sectors -- behind the ring commit below
+            if constexpr (PLACE)
+                flush = owner && !no_room && (rows_done & (OUT_ROWS - 1)) == 0;
         }
         if constexpr (GENERAL) {
             // ---- the two substreams of an access unit must end it at the same PCM frame.  (The passes in front
@@ -2495,6 +2656,9 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
         //      lockstep: what lane packing makes of a batch) and the tile is in output order, lane l stores piece
         //      q mod 6 of lane q / 6's run, q = 64 i + l in the i-th of six instructions: an instruction covers ten
         //      or eleven runs whole.
+        // (fast pass: the first of the OUT_ROWS staged frames, worked out where a flush needs it -- the row before this
+        //  turn's increment less OUT_ROWS - 1 -- and not carried and selected through every row)
+        auto out_row = [&]() -> uint64_t { return PLACE ? row0 + rows_done - (uint64_t)OUT_ROWS : flush_row; };
         bool coop_out = false;
         if constexpr (ILV && !GENERAL && !PARSE) {
             if (!WAVO && ilv_direct && a.wav_bits == 0u && a.coop_min_seg && n_seg >= a.coop_min_seg)
@@ -2503,7 +2667,7 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
         if (coop_out) {
             // where the lane's own run starts, in int32 elements from a.pcm (one 32-bit word to hand round when the
             // whole wave's fit: a PCM buffer of less than 16 GB; wave-uniform fall-back to two words otherwise)
-            const uint64_t doff = out_base + flush_row * 6u;
+            const uint64_t doff = out_base + out_row() * 6u;
             const bool off32 = !__any((doff >> 32) != 0);
             const uint32_t d_lo = (uint32_t)doff, d_hi = (uint32_t)(doff >> 32);
             const int32_t *const T0 = &s_out[GENERAL ? 0 : wv][0][0][0];
@@ -2531,7 +2695,7 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
         if (!GENERAL && !PARSE && ILV && flush && !coop_out) {
             // ---- frame-major: the OUT_ROWS frames are OUT_ROWS * channels consecutive values
             const int32_t *Tl = &s_out[GENERAL ? 0 : wv][0][0][GENERAL ? 0 : lane];
-            int32_t *dst = a.pcm + out_base + flush_row * nch_out;
+            int32_t *dst = a.pcm + out_base + out_row() * nch_out;
             // (the one-lane int32 frame-major instance has handed the payload to its WAVO twin; every other instance
             //  -- two-substream lane, sequential -- still writes it itself)
             constexpr bool WAV_ELSEWHERE = !PAIRED && !WAVO && !DUO;
@@ -2540,7 +2704,7 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                 //      OUT_ROWS * channels consecutive samples = `channels` groups of four; a group packs into
                 //      three dwords (24-bit) or two (16-bit); the lane's run is 12 (8) * channels contiguous bytes
                 const uint32_t nb = a.wav_bits >> 3;
-                uint32_t *wd = reinterpret_cast<uint32_t *>(a.pcm + out_base) + (flush_row * nch_out * nb >> 2);
+                uint32_t *wd = reinterpret_cast<uint32_t *>(a.pcm + out_base) + (out_row() * nch_out * nb >> 2);
                 if (ilv_direct && a.wav_bits == 24u) {
                     // six channels in identity order, 24-bit: 24 samples front to back -> 18 dwords = 72 bytes
                     uint32_t d[18];
@@ -2669,7 +2833,7 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
             for (int c = 0; c < 6; c++) {
                 if ((uint32_t)c < nch_out) {
                     const uint32_t wc = nib(wavepk, c);
-                    int32_t *dst = a.pcm + out_base + (uint64_t)wc * out_stride + flush_row;
+                    int32_t *dst = a.pcm + out_base + (uint64_t)wc * out_stride + out_row();
                     int32_t o[OUT_ROWS];
 #pragma unroll
                     for (int i = 0; i < OUT_ROWS; i++)
@@ -2761,8 +2925,14 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
         }
     }
     if (segi < n_seg) {
-        if (!GENERAL && !PARSE && owner && sub < S && mine)
-            a.seg_rows[segi] = rows_written;
+        if (!GENERAL && !PARSE && owner && sub < S && mine) {
+            // every row written took one from `room`
+            uint32_t room0 = 0;
+            const uint64_t edge = out_stride < row_limit ? out_stride : row_limit;
+            if (edge > row0)
+                room0 = edge - row0 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)(edge - row0);
+            a.seg_rows[segi] = room0 - room;
+        }
     }
 }
 

@@ -22,7 +22,18 @@ Regions, by what a basic block of the loop contains (static counts, cold branche
     rematrix + staging   what is left behind the last slot (LDS writes of the staging tile among it)
     other          the rest: row bookkeeping, the header parser and every cold branch inside the loop
 
-tests/test_isa_budget.py imports this module and holds every build to what profiles/isa_mix_after.txt records."""
+One more region is printed by itself, for every instance that does not parse only: the ROW TAIL -- noise, rematrix,
+staging and the row's bookkeeping.  It is not a set of whole blocks but a path: the instructions a wave executes from
+behind the last slot's block to the hand-written wait for the chunk (the first s_waitcnt vmcnt(0) that waits for nothing
+else, in a block without multiply-adds: a wait the compiler places for a reloaded coefficient sits among them), every
+conditional branch falling through and every unconditional one taken, so cold branches are left out and the masked
+blocks the wave walks through are counted.  One kind of conditional branch is taken: a forward s_cbranch_execz that skips an inner
+loop.  A row has no loop of its own; what loops there is the end of a block or a synchronous ring top-up, laid out in
+line under a lane mask that is empty in all but one row of a block.  The regions above and their numbers are what they
+were.
+
+tests/test_isa_budget.py imports this module and holds every build to what profiles/isa_mix_after.txt records;
+tests/test_isa_row_tail.py holds the row tail to profiles/isa_mix_row_tail_{before,after}.txt."""
 import collections
 import os
 import re
@@ -237,6 +248,78 @@ def regions(loop_blocks):
     return out
 
 
+def row_tail_path(blocks, loop_blocks):
+    """-> [Block]: the fall-through path from behind the last slot to the hand-written wait, as (partial) blocks.
+
+    `blocks` is the whole kernel in layout order (an unconditional branch may lead to a block the compiler laid out
+    behind the loop's hot piece), `loop_blocks` the row loop.  Empty when the loop has no slots or no such wait."""
+    def is_slot(b):
+        ops = [_b(o) for o, _, _ in b.ins]
+        return "v_ffbh_u32" in ops and "v_lshlrev_b64" in ops
+    slots = [b.name for b in loop_blocks if is_slot(b)]
+    if not slots:
+        return []
+    order = {b.name: j for j, b in enumerate(blocks)}
+    head = loop_blocks[0].name
+    j, path, seen = order[slots[-1]] + 1, [], set()
+    while j < len(blocks) and blocks[j].name not in seen:
+        b = blocks[j]
+        seen.add(b.name)
+        part, nxt = [], j + 1
+        mads = any(_b(o) == "v_mad_i64_i32" for o, _, _ in b.ins)
+        for op, operands, in_asm in b.ins:
+            part.append((op, operands, in_asm))
+            if op == "s_waitcnt" and operands.strip() == "vmcnt(0)" and not mads:
+                path.append(Block(b.name, b.loop, part))
+                return path
+            if op == "s_branch":
+                nxt = order.get(operands.strip().lstrip(".L"), len(blocks))
+                break
+            if op in ("s_endpgm", "s_setpc_b64"):
+                nxt = len(blocks)
+                break
+            if op == "s_cbranch_execz":
+                t = order.get(operands.strip().lstrip(".L"), -1)
+                if t > j and any(x.loop not in (head, None) for x in blocks[j + 1:t]):
+                    nxt = t
+                    break
+        path.append(Block(b.name, b.loop, part))
+        j = nxt
+    return []
+
+
+def vmcnt_waits_beside_mads(loop_blocks):
+    """-> [(block name, operands)]: every s_waitcnt that waits for vector memory in a row-loop block that holds a
+    v_mad_i64_i32 -- the filter's and the rematrix's multiply-adds must not wait for the chunk or for the PCM stores"""
+    out = []
+    for b in loop_blocks:
+        if any(_b(o) == "v_mad_i64_i32" for o, _, _ in b.ins):
+            out += [(b.name, a) for o, a, _ in b.ins if o == "s_waitcnt" and "vmcnt" in a]
+    return out
+
+
+def sgpr_pair_selects(blocks_):
+    """-> [(block name, operands)]: v_cndmask_b32_e64 whose mask is an SGPR pair"""
+    return [(b.name, a) for b in blocks_ for o, a, _ in b.ins
+            if o == "v_cndmask_b32_e64" and re.search(r",\s*s\[\d+:\d+\]\s*$", a)]
+
+
+def analyse_row_tail(path, rates=None):
+    """-> {instance name: dict(mix of the row tail's path, + path=[Block], vmcnt_beside_mads, sgpr_selects)} for every
+    instance with a rematrix (the chain parse pass has none)"""
+    rates = rates or Rates()
+    res = collections.OrderedDict()
+    for name, info, blocks, parents in kernels(path):
+        head, lb = row_loop(blocks, parents)
+        if head is None or not any(_b(o) == "v_mad_i64_i32" for b in lb for o, _, _ in b.ins):
+            continue
+        tail = row_tail_path(blocks, lb)
+        m = mix(tail, rates)
+        m.update(path=tail, vmcnt_beside_mads=vmcnt_waits_beside_mads(lb), sgpr_selects=sgpr_pair_selects(tail))
+        res[name] = m
+    return res
+
+
 def mix(blocks_, rates):
     """-> dict(total, valu, fast, slow, unclassified, cycles, hist, scratch, lane_moves)"""
     h, cls, unc = collections.Counter(), collections.Counter(), set()
@@ -289,6 +372,22 @@ def report(path, out=sys.stdout):
                 w("   %s: %s\n" % (r, ", ".join("%s %d" % (o, n) for o, n in m["hist"].most_common())))
         w("   whole row loop, VALU: %s\n" % ", ".join("%s %d" % (o, n) for o, n in whole["hist"].most_common() if o.startswith("v_")))
         w("   unclassified: %s\n" % (", ".join(sorted(whole["unclassified_ops"])) or "none"))
+    w("\n== row tail: the path from behind the last slot to the hand-written wait for the chunk (cold branches left out)\n")
+    w("   %-52s %6s %6s %6s %6s %7s %10s %8s %8s\n" % ("instance", "instr", "VALU", "fast", "slow", "unclass", "w.cycles",
+                                                       "vmwaits", "selects"))
+    tails = analyse_row_tail(path, rates)
+    for name, m in tails.items():
+        if not m["path"]:
+            w("   %-52s (no such path: the sequential pass rematrixes at the end of an access unit)\n" % name)
+            continue
+        w("   %-52s %6d %6d %6d %6d %7d %10.0f %8d %8d\n" % (name, m["total"], m["valu"], m["fast"], m["slow"],
+                                                            m["unclassified"], m["cycles"], len(m["vmcnt_beside_mads"]),
+                                                            len(m["sgpr_selects"])))
+    w("   (vmwaits: s_waitcnt vmcnt in a row-loop block that holds v_mad_i64_i32; selects: v_cndmask_b32_e64 on an SGPR pair "
+      "in the path)\n")
+    if HEADLINE in tails:
+        w("   headline, VALU: %s\n" % ", ".join("%s %d" % (o, n) for o, n in tails[HEADLINE]["hist"].most_common()
+                                                 if o.startswith("v_")))
 
 
 def main():
