@@ -26,7 +26,10 @@
  *      dvda_hip_close_mlpdecoder keep the exact call shape and return-value
  *      meaning of reference src/mlp.h:29-42 with the reference's BitstreamReader
  *      and aa_int containers replaced by (pointer, length) pairs; INTEGRATION.md
- *      shows the 40-line src/mlp.c replacement that binds them.
+ *      shows the 40-line src/mlp.c replacement that binds them.  A host that
+ *      serves many streams at once opens a group of such decoders
+ *      (dvda_hip_open_mlpdecoder_group): one call feeds every member its
+ *      packet, and all of them are decoded by one launch pair.
  *
  * All functions return 0 on success or a negative DVDA_HIP_E* code; they never
  * fall back to a CPU implementation.
@@ -534,6 +537,37 @@ size_t dvda_hip_mlpdecoder_queued_bytes(const dvda_hip_mlpdecoder *decoder);
  * that path takes (an access unit of non-standard length, src/mlp.c:719-738, or one larger than 4 KB) and every call
  * decodes from the stream's last major sync on through the batch tier, as rounds 1-3 did for every stream. */
 int dvda_hip_mlpdecoder_path(const dvda_hip_mlpdecoder *decoder);
+
+/* A group of n such decoders for a host that serves many streams at once (a ripper that reads several tracks in
+ * parallel, a service with many listeners): the members share nothing -- each behaves, call for call, as if it had been
+ * fed its packets alone through dvda_hip_mlpdecoder_decode_packet (returns, PCM, status, path, queued bytes; a member
+ * never sees another's stream, state or failure) -- but one call on the group decodes every member's packet with ONE
+ * launch pair, a workgroup per member, where n lone decoders pay n launch pairs one after the other.  (A call in which a
+ * member brings more than 48 access units / 48 KB runs further launch pairs, "steps", again for all such members at
+ * once; members on path 1 decode through the batch tier, one after the other.)  A HIP runtime failure of a step sets
+ * DVDA_ST_DEVICE on every member that took part in it.
+ * A group lives on ONE device and is used by ONE thread at a time.  It holds 229 KB of pinned host memory per member
+ * from open to close (58.5 MB at DVDA_STREAM_GROUP_MAX). */
+typedef struct dvda_hip_mlpdecoder_group dvda_hip_mlpdecoder_group;
+#define DVDA_STREAM_GROUP_MAX 256u
+
+/* n decoders (1 .. DVDA_STREAM_GROUP_MAX) on one device; NULL without a HIP device or with n out of range */
+dvda_hip_mlpdecoder_group *dvda_hip_open_mlpdecoder_group(unsigned n, int device);
+void dvda_hip_close_mlpdecoder_group(dvda_hip_mlpdecoder_group *group);
+unsigned dvda_hip_mlpdecoder_group_size(const dvda_hip_mlpdecoder_group *group);
+/* One call of dvda_hip_mlpdecoder_decode_packet for every member at once: member i is fed data[i][0, len[i])
+ * (len[i] == 0 or data[i] == NULL: no packet for it this time).  frames[i] = what its own decode_packet would have
+ * returned, planar[i * 6 + c] / channels[i] as there; the pointers are valid until the next call on the group.
+ * frames, planar and channels may each be NULL.  Returns the sum of frames[]. */
+unsigned long long dvda_hip_mlpdecoder_group_decode_packets(dvda_hip_mlpdecoder_group *group, const uint8_t *const data[],
+                                                            const size_t len[], unsigned frames[],
+                                                            const int32_t *planar[], unsigned channels[]);
+/* member i's dvda_hip_mlpdecoder_status / _queued_bytes / _path (i >= n or group == NULL: all-ones / 0 / -1) */
+unsigned dvda_hip_mlpdecoder_group_status(const dvda_hip_mlpdecoder_group *group, unsigned i);
+size_t dvda_hip_mlpdecoder_group_queued_bytes(const dvda_hip_mlpdecoder_group *group, unsigned i);
+int dvda_hip_mlpdecoder_group_path(const dvda_hip_mlpdecoder_group *group, unsigned i);
+/* how many steps (launch pairs) the group has run so far: what a caller pays */
+unsigned long long dvda_hip_mlpdecoder_group_steps(const dvda_hip_mlpdecoder_group *group);
 
 #ifdef __cplusplus
 }

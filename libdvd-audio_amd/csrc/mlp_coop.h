@@ -162,8 +162,9 @@ struct CoopResult {
     int32_t fir[2][48];         // the FIR histories in front of that unit ([substream][slot * 8 + tap]: what
                                 // dvda_mlp_hip_segment_fir hands out for the segment before it)
 };
-constexpr uint32_t SEG_STREAMING = 1u << 28;    // SegRec.flags of the streaming tier's one segment: major syncs may sit
+constexpr uint32_t SEG_STREAMING = 1u << 28;    // SegRec.flags of a streaming-tier segment: major syncs may sit
                                                 // on any of its access units (k_au_check, k_coop<false, true>)
+constexpr uint32_t SEG_FRESH = 1u << 29;        // ... and: this member's decoder has no state yet (its first step)
 
 // PARSE = false: the fast pass for small batches (everything up to PCM).
 // PARSE = true : the chain passes' parse pass for small batches -- workgroup j takes deferred segment def_list[j] and
@@ -172,8 +173,11 @@ constexpr uint32_t SEG_STREAMING = 1u << 28;    // SegRec.flags of the streaming
 //   rematrix parameters its last block left; k_chain_filter / k_chain_rematrix take it from there.  (One lane of
 //   k_decode needs 1.6 ms for a segment of eight units whatever the batch holds: for ONE chained title that was
 //   half of the whole decode.)
-// RESUME (streaming tier): one workgroup, segment 0 of a hand-made index; the decoder state comes from and goes back
-//   to CoopState; a major sync may sit on any access unit; the first block may run FIR taps (the history is here).
+// RESUME (streaming tier): workgroup i takes segment i of a hand-made index of one-segment streams -- member i of a
+//   group of decoders that share nothing (mlp_stepper.h; a lone decoder is a group of one); the decoder state comes
+//   from and goes back to CoopState[2 i + substream], what the step did goes to CoopResult[i]; a member with nothing
+//   to decode in this step has nframes == 0 and its workgroup leaves before it touches either.  A major sync may sit
+//   on any access unit; the first block may run FIR taps (the history is here).
 template <bool PARSE, bool RESUME = false>
 __global__ __launch_bounds__(COOP_THREADS) void k_coop(DecodeArgs a)
 {
@@ -267,8 +271,8 @@ __global__ __launch_bounds__(COOP_THREADS) void k_coop(DecodeArgs a)
     for (uint32_t i = lane; i < (uint32_t)COOP_ROWS; i += 64u)
         s_byp[i] = 0;
     bool resumed = false;
-    CoopState *const cst = RESUME ? a.coop_state + sub : nullptr;
-    CoopResult *const cres = RESUME ? a.coop_result : nullptr;
+    CoopState *const cst = RESUME ? a.coop_state + gl : nullptr;
+    CoopResult *const cres = RESUME ? a.coop_result + segi : nullptr;
     if constexpr (RESUME) {
         // (the result record lives in mapped host memory: every word of it is written by ONE lane -- lane 0 of the last
         //  substream's wave -- with plain stores, in program order)
@@ -276,7 +280,7 @@ __global__ __launch_bounds__(COOP_THREADS) void k_coop(DecodeArgs a)
             cres->status = 0;
             cres->frames_out = cres->rows_written = cres->sync_seen = 0;
         }
-        resumed = !a.coop_fresh && rfl(cst->valid) != 0;
+        resumed = !(sr.flags & SEG_FRESH) && rfl(cst->valid) != 0;
         if (resumed) {
             flags = rfl(cst->sc[0]);
             block_size = rfl(cst->sc[1]);

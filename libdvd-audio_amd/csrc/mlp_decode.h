@@ -305,9 +305,12 @@ struct DecodeArgs {
     WsCaps caps;                   // what the workspaces hold (consulted by the range-checked build only, mlp_bounds.h)
     uint32_t coop;                 // who decodes the batch: 0 the device decides (coop_takes), 64 always the wave-cooperative
                                    // kernel (mlp_coop.h), anything else always the lane kernels
-    struct CoopState *coop_state;  // streaming tier (k_coop<false, true>): the decoder state between calls, [2 substreams]
-    struct CoopResult *coop_result;    // ... and what the call did
-    uint32_t coop_fresh;           // ... != 0: a decoder's first call (no state yet)
+    struct CoopState *coop_state;  // streaming tier (k_coop<false, true>): the decoder state between calls,
+                                   // [2 * segment + substream]
+    struct CoopResult *coop_result;    // ... and what the step did, per segment (a first step: SEG_FRESH, mlp_coop.h)
+    uint32_t coop_spare;           // (not read.  It keeps the argument block at the size it had when one flag told the
+                                   //  streaming tier's one workgroup "no state yet": eight bytes shorter, k_coop<false, false>
+                                   //  comes out of the compiler with two more VGPRs)
 };
 
 // Which batches the wave-cooperative kernel takes (measured, tools/coop_bench.py, MI355X): one wave scans an access

@@ -61,6 +61,9 @@ EXPORTS = ("dvda_mlp_hip_create", "dvda_mlp_hip_destroy", "dvda_mlp_hip_index", 
            "dvda_mlp_hip_segment_fir", "dvda_mlp_hip_set_initial_fir",
            "dvda_hip_open_mlpdecoder", "dvda_hip_close_mlpdecoder", "dvda_hip_mlpdecoder_decode_packet",
            "dvda_hip_mlpdecoder_status", "dvda_hip_mlpdecoder_queued_bytes", "dvda_hip_mlpdecoder_path",
+           "dvda_hip_open_mlpdecoder_group", "dvda_hip_close_mlpdecoder_group", "dvda_hip_mlpdecoder_group_size",
+           "dvda_hip_mlpdecoder_group_decode_packets", "dvda_hip_mlpdecoder_group_status",
+           "dvda_hip_mlpdecoder_group_queued_bytes", "dvda_hip_mlpdecoder_group_path", "dvda_hip_mlpdecoder_group_steps",
            "dvda_pcm_hip_workspace_words", "dvda_pcm_hip_decode_sectors", "dvda_pcm_hip_result",
            "dvda_mlp_hip_demux_sectors", "dvda_mlp_hip_pack_wav",
            "dvda_mlp_hip_shard", "dvda_mlp_hip_create_multi", "dvda_mlp_hip_destroy_multi",
@@ -136,6 +139,24 @@ def lib():
         L.dvda_hip_mlpdecoder_queued_bytes.restype = ctypes.c_size_t
         L.dvda_hip_mlpdecoder_queued_bytes.argtypes = [vp]
         L.dvda_hip_mlpdecoder_path.argtypes = [vp]
+        L.dvda_hip_open_mlpdecoder_group.restype = vp
+        L.dvda_hip_open_mlpdecoder_group.argtypes = [ctypes.c_uint, ctypes.c_int]
+        L.dvda_hip_close_mlpdecoder_group.argtypes = [vp]
+        L.dvda_hip_close_mlpdecoder_group.restype = None
+        L.dvda_hip_mlpdecoder_group_size.restype = ctypes.c_uint
+        L.dvda_hip_mlpdecoder_group_size.argtypes = [vp]
+        L.dvda_hip_mlpdecoder_group_decode_packets.restype = ctypes.c_ulonglong
+        L.dvda_hip_mlpdecoder_group_decode_packets.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t),
+                                                               ctypes.POINTER(ctypes.c_uint),
+                                                               ctypes.POINTER(ctypes.POINTER(ctypes.c_int32)),
+                                                               ctypes.POINTER(ctypes.c_uint)]
+        L.dvda_hip_mlpdecoder_group_status.restype = ctypes.c_uint
+        L.dvda_hip_mlpdecoder_group_status.argtypes = [vp, ctypes.c_uint]
+        L.dvda_hip_mlpdecoder_group_queued_bytes.restype = ctypes.c_size_t
+        L.dvda_hip_mlpdecoder_group_queued_bytes.argtypes = [vp, ctypes.c_uint]
+        L.dvda_hip_mlpdecoder_group_path.argtypes = [vp, ctypes.c_uint]
+        L.dvda_hip_mlpdecoder_group_steps.restype = ctypes.c_ulonglong
+        L.dvda_hip_mlpdecoder_group_steps.argtypes = [vp]
         L.dvda_pcm_hip_workspace_words.restype = ctypes.c_size_t
         L.dvda_pcm_hip_workspace_words.argtypes = [u32]
         L.dvda_pcm_hip_decode_sectors.argtypes = [vp, u32, ctypes.c_uint, ctypes.c_uint, vp, u64, vp, vp]
@@ -743,6 +764,82 @@ class MLPDecoder:
     def close(self):
         if self._h:
             lib().dvda_hip_close_mlpdecoder(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+STREAM_GROUP_MAX = 256      # DVDA_STREAM_GROUP_MAX
+
+
+class MLPDecoderGroup:
+    """n MLPDecoders for a host that serves many streams at once (dvda_hip_open_mlpdecoder_group): the members share
+    nothing and each behaves as a lone MLPDecoder fed the same packets, but one decode_packets() call decodes every
+    member's packet with one launch pair.  One device, one thread at a time."""
+
+    def __init__(self, n, device=0):
+        self._h = None
+        self.n = int(n)
+        if 0 <= self.n < 2 ** 32:
+            self._h = lib().dvda_hip_open_mlpdecoder_group(self.n, device)
+        if not self._h:
+            raise HipError("dvda_hip_open_mlpdecoder_group failed (no GPU / HIP error, or n outside 1..%d): "
+                           "there is no CPU fallback" % STREAM_GROUP_MAX)
+        self._data = (ctypes.c_void_p * self.n)()
+        self._len = (ctypes.c_size_t * self.n)()
+        self._frames = (ctypes.c_uint * self.n)()
+        self._planar = (ctypes.POINTER(ctypes.c_int32) * (6 * self.n))()
+        self._nch = (ctypes.c_uint * self.n)()
+
+    def decode_packets(self, pieces, samples):
+        """pieces: n byte arrays (None or empty: no packet for that member this time); samples: n lists of six channel
+        lists, appended to as MLPDecoder.decode_packet does -> the n returns"""
+        if len(pieces) != self.n or len(samples) != self.n:
+            raise ValueError("a group of %d takes %d pieces and %d sample lists" % (self.n, self.n, self.n))
+        keep = []
+        for i, data in enumerate(pieces):
+            if data is None:
+                buf = np.zeros(0, np.uint8)
+            elif isinstance(data, np.ndarray):
+                buf = np.ascontiguousarray(data, np.uint8)
+            else:
+                buf = np.ascontiguousarray(np.frombuffer(bytes(data), np.uint8))
+            keep.append(buf)
+            self._data[i] = buf.ctypes.data if len(buf) else None
+            self._len[i] = len(buf)
+        lib().dvda_hip_mlpdecoder_group_decode_packets(self._h, self._data, self._len, self._frames, self._planar,
+                                                       self._nch)
+        out = []
+        for i in range(self.n):
+            f = int(self._frames[i])
+            if f:
+                for c in range(self._nch[i]):
+                    samples[i][c].extend(np.ctypeslib.as_array(self._planar[6 * i + c], shape=(f,)).tolist())
+            out.append(f)
+        return out
+
+    def status(self, i):
+        return int(lib().dvda_hip_mlpdecoder_group_status(self._h, i))
+
+    def queued_bytes(self, i):
+        return int(lib().dvda_hip_mlpdecoder_group_queued_bytes(self._h, i))
+
+    def path(self, i):
+        """member i's MLPDecoder.path"""
+        return int(lib().dvda_hip_mlpdecoder_group_path(self._h, i))
+
+    @property
+    def steps(self):
+        """launch pairs the group has run so far (dvda_hip_mlpdecoder_group_steps)"""
+        return int(lib().dvda_hip_mlpdecoder_group_steps(self._h))
+
+    def close(self):
+        if self._h:
+            lib().dvda_hip_close_mlpdecoder_group(self._h)
             self._h = None
 
     def __del__(self):
