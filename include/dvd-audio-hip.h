@@ -110,6 +110,22 @@ void dvda_hip_set_digest(int on);
  * then 0, with the digest of what has been handed out so far).  -1: the digest is not on, the reader failed, or the
  * track's bit depth is neither 16 nor 24. */
 int dvda_hip_reader_crc32(const DVDA_Track_Reader *reader, unsigned *crc, unsigned long long *bytes);
+/* on != 0: track readers opened afterwards (per calling thread, read when the reader is opened, exactly like
+ * dvda_hip_set_digest) make the level report of every piece of int32 PCM where it lies on the device, before any copy
+ * to the host: per channel min, max, exact sum and the values outside the nominal range of the track's
+ * dvda_bits_per_sample, and the frames of digital silence at both ends (the contract is in dvda_mlp_hip.h,
+ * dvda_pcm_levels / dvda_pcm_hip_levels).  Every reader that holds int32 PCM: whole-track and windowed, MLP and raw PCM,
+ * the presentation.  A reader opened for the WAV payload only holds no int32 PCM and has no report (dvda2wav_hip's
+ * readers are such readers: the extractor is out of scope).  Off (default): a reader launches and allocates exactly
+ * as without this call. */
+struct dvda_pcm_levels;
+void dvda_hip_set_levels(int on);
+/* The track's report.  1: final for the track -- from open on for a whole-track reader, once the track has been read
+ * to its end for a windowed one (which joins its windows' reports as they are handed out, dvda_pcm_hip_levels_combine:
+ * until then 0, with the report of what has been handed out so far).  -1: the report is not on, the reader failed, it
+ * is a WAV-payload-only reader (dvda_hip_reader_wav_only), or the track's bit depth is none of 16 / 20 / 24.  `out` may
+ * be NULL. */
+int dvda_hip_reader_levels(const DVDA_Track_Reader *reader, struct dvda_pcm_levels *out);
 /* != 0: the reader holds the WAV payload only (opened with wav_output): dvda_read() on it returns 0 frames -- NOT
  * because the track is empty; take the payload with dvda_hip_reader_wav_payload() */
 int dvda_hip_reader_wav_only(const DVDA_Track_Reader *reader);

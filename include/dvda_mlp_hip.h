@@ -510,6 +510,66 @@ int dvda_mlp_hip_pcm_crc32(dvda_mlp_hip_ctx *ctx, const int32_t *d_pcm, const ui
  * decoded in several batches.  Host arithmetic; needs no device. */
 uint32_t dvda_pcm_hip_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
 
+/* ------------------------------------------------------------------ level report of the decoded PCM
+ * The digest's sibling: what a caller who verifies a rip asks of the PCM besides "is it the same" -- did the WAV payload
+ * wrap, what is the peak of each channel, how much digital silence opens and closes the stream -- answered on the
+ * device from the int32 PCM where the decode wrote it (csrc/pcm_levels.h).  The decode clamps
+ * nothing to the nominal bit depth; write_signed, dvda_mlp_hip_pack_wav, DVDA_PCM_WAV24 / WAV16 and the digest all take a
+ * value modulo 2^bits, so a value outside the nominal range -- a damaged or concealed track can produce one -- is written
+ * as a different sample: `over` counts those.
+ *
+ * The contract.  For one stream of `frames` PCM frames with `channels` channels at nominal depth `bits` = 16, 20 or 24,
+ * channels in RIFF-WAVE order as they lie in the buffer, every figure exact.  An all-zero stream has lead_silent ==
+ * trail_silent == frames; frames == 0 gives a zeroed struct; entries at index `channels` and above are 0.  The report is
+ * the same for DVDA_PCM_PLANAR and DVDA_PCM_INTERLEAVED.  The WAV layouts are DVDA_HIP_EINVAL: their values are already
+ * wrapped, the report would say nothing.
+ *
+ * The kernels cut a stream into tiles of DVDA_LVL_TILE_FRAMES frames, aligned to the stream's START (the last tile is
+ * the ragged one).
+ *
+ * Out of scope: dvda2wav_hip (its readers are WAV-payload readers), the streaming tier, dvda_mlp_hip_decode_multi, RMS /
+ * loudness (a sum of squares of unclamped int32 values does not fit 64 bits), reports from the WAV layouts. */
+#define DVDA_LVL_TILE_FRAMES 4096u
+
+typedef struct dvda_pcm_levels {
+    uint64_t frames;          /* PCM frames covered */
+    uint64_t lead_silent;     /* frames from the start in which every channel is 0 */
+    uint64_t trail_silent;    /* frames up to the end in which every channel is 0 */
+    int64_t  sum[8];          /* exact sum of the channel's values */
+    uint64_t over[8];         /* values outside [-2^(bits-1), 2^(bits-1) - 1] */
+    int32_t  min[8], max[8];  /* smallest / largest value of the channel */
+} dvda_pcm_levels;
+
+/* The tier-free form: d_levels[i] = the report of stream d_desc[i] (device arrays, n entries; the digest's descriptor,
+ * unchanged: off, stride, frames, channels -- channels outside 1..8 or frames above 2^40: an empty stream), from d_pcm in
+ * `layout` (DVDA_PCM_PLANAR or DVDA_PCM_INTERLEAVED).  Enqueued on `stream`: no host wait, no allocation.
+ * max_total_frames: a bound the host knows on the sum of the streams' frames -- the launch and d_work are sized by it; a
+ * stream whose tiles fall outside it is reported as zeros (frames == 0 too), never read out of bounds.  d_work:
+ * dvda_pcm_hip_levels_workspace_words(n, max_total_frames) uint32 words, which need not be cleared between calls; the
+ * report is the same from run to run whatever they held (no atomics).  d_pcm + off may have any 4-byte alignment and a
+ * planar stride any parity: 16-byte loads wherever memory allows them, the values at a run's ragged ends one by one;
+ * nothing outside a stream's `frames` is read.  The arguments are judged first, on any machine -- DVDA_HIP_EINVAL: bits
+ * other than 16 / 20 / 24, a WAV layout, a null pointer, work_words too small; DVDA_HIP_ECAPACITY: 2^31 tiles or more --
+ * then the device: DVDA_HIP_ENODEV without one (asked of the runtime once per process). */
+size_t dvda_pcm_hip_levels_workspace_words(uint32_t n, uint64_t max_total_frames);
+int dvda_pcm_hip_levels(const int32_t *d_pcm, uint32_t layout, unsigned bits, const dvda_pcm_crc_desc *d_desc, uint32_t n,
+                        uint64_t max_total_frames, dvda_pcm_levels *d_levels, uint32_t *d_work, size_t work_words,
+                        void *stream);
+
+/* The convenience call behind dvda_mlp_hip_decode (blocks): host_levels[i] for the first n streams of the last decode,
+ * d_pcm / d_out_off / d_out_stride as that decode got them, in the context's layout (DVDA_HIP_EINVAL when that is a WAV
+ * one).  Frames and channels are what dvda_mlp_hip_stream_info reports, so conceal mode's composed stream -- its gaps
+ * are exact zeros -- and the presentation's k channels count as they are; a stream that carries DVDA_ST_OVERFLOW gives
+ * zeros.  The workspace belongs to the context and only grows. */
+int dvda_mlp_hip_pcm_levels(dvda_mlp_hip_ctx *ctx, const int32_t *d_pcm, const uint64_t *d_out_off,
+                            const uint64_t *d_out_stride, unsigned bits, dvda_pcm_levels *host_levels, uint32_t n,
+                            void *stream);
+
+/* levels(A || B) from levels(A) and levels(B): how a caller joins pieces -- windows of a track, parts of a title.  Lead:
+ * a.lead_silent == a.frames ? a.frames + b.lead_silent : a.lead_silent; trail symmetric; an operand with frames == 0 is
+ * neutral (its zero min / max do not reach the result).  Either operand may be `out`.  Host arithmetic; needs no device. */
+void dvda_pcm_hip_levels_combine(const dvda_pcm_levels *a, const dvda_pcm_levels *b, dvda_pcm_levels *out);
+
 /* ------------------------------------------------------------------ tier B */
 /* The mlp.h mirror: same three calls, same meaning as reference src/mlp.h:29-42 /
  * src/mlp.c:265-354, with the reference's containers replaced by plain memory:

@@ -42,12 +42,14 @@ struct reader_opts {
     int wav_output;             /* 1: MLP readers decode straight into the WAV payload */
     int present;                /* 1: MLP readers decode the presentation substream 0 carries (DVDA_PRESENT_SUBSTREAM0) */
     int digest;                 /* 1: every piece of PCM is digested where it lies on the device (dvda_hip_reader_crc32) */
+    int levels;                 /* 1: ... and its level report is made there (dvda_hip_reader_levels) */
 };
 static _Thread_local struct reader_opts t_opts;
 void dvda_hip_set_device(int device) { t_opts.device = device; }
 void dvda_hip_set_wav_output(int on) { t_opts.wav_output = on != 0; }
 void dvda_hip_set_presentation(int presentation) { t_opts.present = presentation == 1; }
 void dvda_hip_set_digest(int on) { t_opts.digest = on != 0; }
+void dvda_hip_set_levels(int on) { t_opts.levels = on != 0; }
 
 struct track_windows;               /* a long track read window by window (below) */
 
@@ -68,6 +70,8 @@ struct DVDA_Track_Reader_s {
     int dg_state;              /* digest (dvda_hip_set_digest): 0 off, 1 = dg_crc / dg_bytes are the track's, -1 none (bit depth) */
     uint32_t dg_crc;
     uint64_t dg_bytes;
+    int lv_state;              /* level report (dvda_hip_set_levels): 0 off, 1 = lv is the track's, -1 none (no int32 PCM, bit depth) */
+    dvda_pcm_levels lv;
 };
 
 /* fills the reader's record from the index's stream record; 0 = a channel count the assignment does not have.  Under
@@ -231,6 +235,28 @@ static int piece_digest(const int32_t *d_pcm, uint32_t layout, unsigned bits, ui
                            (uint64_t *)(d + 32), (uint32_t *)(d + 48), words, NULL) == DVDA_HIP_OK &&
         hipMemcpy(nbytes, d + 32, sizeof(*nbytes), hipMemcpyDeviceToHost) == hipSuccess &&
         hipMemcpy(crc, d + 40, sizeof(*crc), hipMemcpyDeviceToHost) == hipSuccess)
+        ok = 1;
+    (void)hipFree(d);
+    return ok;
+}
+
+/* The level report of one piece of int32 PCM where it lies on the device (dvda_pcm_hip_levels), as piece_digest() takes
+ * it; layout DVDA_PCM_PLANAR or DVDA_PCM_INTERLEAVED, bits 16 / 20 / 24.  Blocks; what it allocates it frees.  1 = ok. */
+static int piece_levels(const int32_t *d_pcm, uint32_t layout, unsigned bits, uint64_t stride, uint64_t frames, unsigned ch,
+                        dvda_pcm_levels *out)
+{
+    const size_t words = dvda_pcm_hip_levels_workspace_words(1, frames);
+    const dvda_pcm_crc_desc desc = {0, stride, frames, ch, 0};
+    const size_t head = sizeof(desc) + sizeof(*out);        /* desc (32 bytes) | report (216) | workspace */
+    uint8_t *d = NULL;
+    int ok = 0;
+    memset(out, 0, sizeof(*out));
+    if (!dev_alloc((void **)&d, head + words * sizeof(uint32_t)))
+        return 0;
+    if (hipMemcpy(d, &desc, sizeof(desc), hipMemcpyHostToDevice) == hipSuccess &&
+        dvda_pcm_hip_levels(d_pcm, layout, bits, (const dvda_pcm_crc_desc *)d, 1, frames, (dvda_pcm_levels *)(d + sizeof(desc)),
+                            (uint32_t *)(d + head), words, NULL) == DVDA_HIP_OK &&
+        hipMemcpy(out, d + sizeof(desc), sizeof(*out), hipMemcpyDeviceToHost) == hipSuccess)
         ok = 1;
     (void)hipFree(d);
     return ok;
@@ -516,6 +542,18 @@ static int stream_digest(const struct track_bufs *b, const dvda_mlp_stream_info 
     return piece_digest(b->d_pcm, layout_of(wav_bits), bits, stride, info->pcm_frames, info->channels, crc, nbytes);
 }
 
+/* level report of what decode_stream() left in d_pcm, before any copy: 1 = made, -1 = there is none (the decode wrote the
+ * WAV payload: no int32 PCM; or a bit depth other than 16 / 20 / 24), 0 = failure */
+static int stream_levels(const struct track_bufs *b, const dvda_mlp_stream_info *info, int wav_bits, uint64_t stride,
+                         dvda_pcm_levels *out)
+{
+    const unsigned bits = bits_of(info->group0_bps);
+    memset(out, 0, sizeof(*out));
+    if (wav_bits || (bits != 16 && bits != 20 && bits != 24))
+        return -1;
+    return piece_levels(b->d_pcm, DVDA_PCM_INTERLEAVED, bits, stride, info->pcm_frames, info->channels, out);
+}
+
 /* How many of the `total` PCM frames of `got` sectors a raw-PCM track takes, `done` of its `want` frames delivered
  * before them: whole packets until the length is covered, the opening packet regardless (open_pcm_track_reader /
  * decode_pcm_audio, src/dvd-audio.c:958-1084).  *covered = the track ends inside these sectors. */
@@ -610,6 +648,12 @@ static DVDA_Track_Reader *open_mlp(struct aob_set *aobs, const DVDA_Track *k, co
             goto fail;
         r->dg_state = rc;
     }
+    if (o->levels) {
+        const int rc = stream_levels(&b, &info, wav_bits, stride, &r->lv);
+        if (!rc)
+            goto fail;
+        r->lv_state = rc;
+    }
     if (wav_bits) {
         r->d_wav = (uint8_t *)b.d_pcm;
         r->wav_bytes = r->frames * r->channels * ((unsigned)wav_bits / 8);
@@ -665,6 +709,7 @@ struct win_slot {
     uint64_t stride;            /* != 0: int32 PLANAR [channel][stride] (raw-PCM windows: the order the un-swizzle writes) */
     uint32_t crc;               /* digest of the window's payload and its bytes (dvda_hip_set_digest) */
     uint64_t crc_bytes;
+    dvda_pcm_levels lv;         /* level report of the window's int32 PCM (dvda_hip_set_levels) */
 };
 
 struct track_windows {
@@ -681,6 +726,9 @@ struct track_windows {
                                    stream's bit depth has no digest */
     uint32_t dg_crc;            /* the windows handed out so far, joined (under `mu`, win_release()) */
     uint64_t dg_bytes;
+    int levels;                 /* 1: every window's int32 PCM is reported on the device before it is copied
+                                   (dvda_hip_set_levels); -1: there is none (the windows hold the WAV payload, or the bit depth) */
+    dvda_pcm_levels lv;         /* the windows handed out so far, joined (under `mu`, win_release()) */
     int started, finished, failed;
     /* a raw-PCM track read in windows (round 6): sectors decode independently of each other (src/pcm.c:149: whole chunks
        per packet), so a window is a run of sectors and nothing crosses a cut but the count of frames delivered so far */
@@ -897,6 +945,7 @@ static int win_produce(struct track_windows *w, struct win_slot *out)
     uint64_t total = 0, begin = 0, end = 0, stride = 0;
     out->frames = 0;
     out->stride = 0;
+    memset(&out->lv, 0, sizeof(out->lv));
     /* ---- sectors -> device -> MLP bytes, and where this window's new bytes begin and end: the end-of-track rule on
        the window that holds the track's last sector, with its look-ahead */
     for (unsigned extra = 8;; extra *= 4) {
@@ -998,6 +1047,14 @@ static int win_produce(struct track_windows *w, struct win_slot *out)
         if (rc < 0)
             w->digest = -1;
     }
+    /* ---- ... and its level report */
+    if (w->levels > 0) {
+        const int rc = stream_levels(b, &info, w->wav_bits, stride, &out->lv);
+        if (!rc)
+            return 0;
+        if (rc < 0)
+            w->levels = -1;
+    }
     /* ---- PCM (or payload) to the host buffer */
     const size_t bytes = (size_t)info.pcm_frames * info.channels * (w->wav_bits ? (unsigned)w->wav_bits / 8 : 4);
     if (!slot_reserve(b, out, bytes) ||
@@ -1023,6 +1080,7 @@ static int win_produce_pcm(struct track_windows *w, struct win_slot *out)
     int final = 0;
     out->frames = 0;
     out->stride = 0;
+    memset(&out->lv, 0, sizeof(out->lv));
     if (w->next + want > w->aobs.total || w->next + want < w->next)
         want = w->next < w->aobs.total ? w->aobs.total - w->next : 0;
     if (!sectors_to_device(b, &w->aobs, w->next, want, bits, ch, NULL, &got, &total, &stride))
@@ -1041,6 +1099,10 @@ static int win_produce_pcm(struct track_windows *w, struct win_slot *out)
     if (deliver && w->digest &&
         !piece_digest(b->d_pcm, DVDA_PCM_PLANAR, bits, stride, deliver, ch, &out->crc, &out->crc_bytes))
         return 0;                                /* (the planes as the un-swizzle left them: before packing and copy) */
+    if (w->levels > 0 && w->wav_bits)
+        w->levels = -1;                          /* a WAV-payload reader */
+    if (deliver && w->levels > 0 && !piece_levels(b->d_pcm, DVDA_PCM_PLANAR, bits, stride, deliver, ch, &out->lv))
+        return 0;
     if (deliver && w->wav_bits) {
         const size_t bytes = (size_t)deliver * ch * (bits / 8);
         if (!bufs_dev_room(b, (void **)&b->d_stream, &b->cap_stream, bytes + 64) ||
@@ -1132,6 +1194,8 @@ static void win_release(struct track_windows *w)
         w->dg_crc = dvda_pcm_hip_crc32_combine(w->dg_crc, w->slot[w->tail].crc, w->slot[w->tail].crc_bytes);
         w->dg_bytes += w->slot[w->tail].crc_bytes;
     }
+    if (w->levels > 0)
+        dvda_pcm_hip_levels_combine(&w->lv, &w->slot[w->tail].lv, &w->lv);
     w->tail = (w->tail + 1) % WIN_SLOTS;
     w->count--;
     w->served_in_slot = 0;
@@ -1161,6 +1225,7 @@ static DVDA_Track_Reader *windows_new(const DVDA_Track *k, const struct reader_o
     w->produce = produce;
     w->opts = *o;
     w->digest = o->digest;
+    w->levels = o->levels;
     w->next = k->s.first;
     w->last = k->s.last >= k->s.first ? k->s.last : k->s.first;
     w->window = window_sectors();
@@ -1264,6 +1329,11 @@ static DVDA_Track_Reader *open_pcm(struct aob_set *aobs, const DVDA_Track *k, co
         if (!piece_digest(r->d_pcm, DVDA_PCM_PLANAR, bits, stride, deliver, r->channels, &r->dg_crc, &r->dg_bytes))
             goto fail;
         r->dg_state = 1;
+    }
+    if (o->levels) {
+        if (!piece_levels(r->d_pcm, DVDA_PCM_PLANAR, bits, stride, deliver, r->channels, &r->lv))
+            goto fail;
+        r->lv_state = 1;
     }
     goto done;
 fail:
@@ -1424,6 +1494,26 @@ int dvda_hip_reader_crc32(const DVDA_Track_Reader *r, unsigned *crc, unsigned lo
         if (bytes)
             *bytes = w->dg_bytes;
     }
+    pthread_mutex_unlock(&w->mu);
+    return rc;
+}
+int dvda_hip_reader_levels(const DVDA_Track_Reader *r, dvda_pcm_levels *out)
+{
+    if (!r)
+        return -1;
+    if (!r->win) {
+        if (r->lv_state != 1)
+            return -1;
+        if (out)
+            *out = r->lv;
+        return 1;
+    }
+    struct track_windows *w = r->win;
+    pthread_mutex_lock(&w->mu);
+    /* final: the producer is done and every window has been handed out */
+    const int rc = (w->levels <= 0 || w->failed) ? -1 : (w->finished && w->count == 0) ? 1 : 0;
+    if (rc >= 0 && out)
+        *out = w->lv;
     pthread_mutex_unlock(&w->mu);
     return rc;
 }

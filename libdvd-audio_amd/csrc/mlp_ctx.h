@@ -124,6 +124,10 @@ struct dvda_mlp_hip_ctx {
     DevBuf<uint32_t> d_crc_out;         // [streams]
     DevBuf<uint64_t> d_crc_bytes;       // [streams]
     DevBuf<uint32_t> d_crc_work;
+    // dvda_mlp_hip_pcm_levels (pcm_levels_run.h): grown on first use
+    DevBuf<dvda_pcm_crc_desc> d_lvl_desc;   // [streams]
+    DevBuf<dvda_pcm_levels> d_lvl_out;  // [streams]
+    DevBuf<uint32_t> d_lvl_work;
     DecodeSettings set;
     // call state
     const uint8_t *d_bytes;

@@ -25,7 +25,7 @@ EXPORTS = [
     "dvda_hip_reader_wav_payload", "dvda_hip_open_track_reader_on", "dvda_hip_reader_wav_only",
     "dvda_hip_reader_wav_next", "dvda_hip_reader_windowed", "dvda_hip_reader_memory", "dvda_hip_reader_failed",
     "dvda_hip_release_cached_buffers", "dvda_hip_set_presentation", "dvda_hip_open_track_reader_with",
-    "dvda_hip_set_digest", "dvda_hip_reader_crc32",
+    "dvda_hip_set_digest", "dvda_hip_reader_crc32", "dvda_hip_set_levels", "dvda_hip_reader_levels",
 ]
 
 _lib = None
@@ -90,6 +90,10 @@ def lib():
         L.dvda_hip_set_digest.argtypes = [ctypes.c_int]
         L.dvda_hip_reader_crc32.restype = ctypes.c_int
         L.dvda_hip_reader_crc32.argtypes = [vp, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_ulonglong)]
+        L.dvda_hip_set_levels.restype = None
+        L.dvda_hip_set_levels.argtypes = [ctypes.c_int]
+        L.dvda_hip_reader_levels.restype = ctypes.c_int
+        L.dvda_hip_reader_levels.argtypes = [vp, ctypes.POINTER(hipdec.Levels)]
         _lib = L
     return _lib
 
@@ -121,7 +125,7 @@ def layout(audio_ts, titleset=1):
 
 
 def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0, fused=False, pieces=False,
-               presentation=0, digest=False):
+               presentation=0, digest=False, levels=False):
     """Decodes one track on the GPU.  Returns a dict: codec ("PCM"/"MLP"), bits, rate, channels,
     mask, status, and pcm = int32 [frames, channels] (interleaved, RIFF-WAVE order) read with
     dvda_read() in `chunk`-frame calls -- or, with wav=True, payload = the WAV data bytes packed
@@ -134,7 +138,11 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
     alone; info["channels"] is then k and the frames have k channels).
     digest=True: the reader digests the track on the device (dvda_hip_set_digest): info["crc32"] / info["crc32_bytes"] =
     zlib's CRC-32 of the track's WAV payload and its size (None when the bit depth has no digest), and
-    info["crc32_states"] = what dvda_hip_reader_crc32 returned right after the open and at the end of the read."""
+    info["crc32_states"] = what dvda_hip_reader_crc32 returned right after the open and at the end of the read.
+    levels=True: the reader makes the level report of the track's int32 PCM on the device (dvda_hip_set_levels):
+    info["levels"] = the report as hipdec.Levels.as_dict() gives it (None when the reader has none: a WAV-payload-only
+    reader), and info["levels_states"] = what dvda_hip_reader_levels returned right after the open and at the end."""
+    from . import hipdec
     L = lib()
     d = L.dvda_open(audio_ts.encode(), None)
     if not d:
@@ -145,10 +153,12 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
         t = L.dvda_open_title(ts, title) if ts else None
         k = L.dvda_open_track(t, track) if t else None
         L.dvda_hip_set_digest(1 if digest else 0)
+        L.dvda_hip_set_levels(1 if levels else 0)
         try:
             r = L.dvda_hip_open_track_reader_with(k, device, 1 if (fused and wav) else 0, presentation) if k else None
         finally:
             L.dvda_hip_set_digest(0)            # (read when the reader is opened: nothing is left behind)
+            L.dvda_hip_set_levels(0)
         if not r:
             raise RuntimeError("track %d/%d/%d cannot be opened for reading" % (titleset, title, track))
         ch = L.dvda_channel_count(r)
@@ -159,6 +169,8 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
         info["windowed"] = bool(L.dvda_hip_reader_windowed(r))
         crc, nbytes = ctypes.c_uint(), ctypes.c_ulonglong()
         first_state = L.dvda_hip_reader_crc32(r, ctypes.byref(crc), ctypes.byref(nbytes)) if digest else None
+        report = hipdec.Levels()
+        first_levels = L.dvda_hip_reader_levels(r, ctypes.byref(report)) if levels else None
         if wav and pieces:
             got, sizes = [], []
             while True:
@@ -193,6 +205,10 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
             info["crc32_states"] = (first_state, state)
             info["crc32"] = int(crc.value) if state == 1 else None
             info["crc32_bytes"] = int(nbytes.value) if state == 1 else None
+        if levels:
+            state = L.dvda_hip_reader_levels(r, ctypes.byref(report))
+            info["levels_states"] = (first_levels, state)
+            info["levels"] = report.as_dict() if state == 1 else None
         return info
     finally:
         if r:

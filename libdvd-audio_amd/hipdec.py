@@ -71,7 +71,9 @@ EXPORTS = ("dvda_mlp_hip_create", "dvda_mlp_hip_destroy", "dvda_mlp_hip_index", 
            "dvda_mlp_hip_set_conceal", "dvda_mlp_hip_conceal_spans",
            "dvda_mlp_hip_set_presentation", "dvda_mlp_hip_present_time",
            "dvda_pcm_hip_crc32", "dvda_pcm_hip_crc32_workspace_words", "dvda_mlp_hip_pcm_crc32",
-           "dvda_pcm_hip_crc32_combine")
+           "dvda_pcm_hip_crc32_combine",
+           "dvda_pcm_hip_levels", "dvda_pcm_hip_levels_workspace_words", "dvda_mlp_hip_pcm_levels",
+           "dvda_pcm_hip_levels_combine")
 
 CRC_TILE_BYTES = 16384      # DVDA_CRC_TILE_BYTES: the digest's tiles, aligned to the end of a stream's payload
 CRC_JOIN_TILES = 256        # DVDA_CRC_JOIN_TILES: tiles a join workgroup folds per turn of its loop
@@ -81,6 +83,26 @@ class CrcDesc(ctypes.Structure):
     """dvda_pcm_crc_desc of include/dvda_mlp_hip.h"""
     _fields_ = [("off", ctypes.c_uint64), ("stride", ctypes.c_uint64), ("frames", ctypes.c_uint64),
                 ("channels", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+LVL_TILE_FRAMES = 4096      # DVDA_LVL_TILE_FRAMES: the level report's tiles, aligned to the start of a stream
+
+
+class Levels(ctypes.Structure):
+    """dvda_pcm_levels of include/dvda_mlp_hip.h"""
+    _fields_ = [("frames", ctypes.c_uint64), ("lead_silent", ctypes.c_uint64), ("trail_silent", ctypes.c_uint64),
+                ("sum", ctypes.c_int64 * 8), ("over", ctypes.c_uint64 * 8), ("min", ctypes.c_int32 * 8),
+                ("max", ctypes.c_int32 * 8)]
+
+    def as_dict(self):
+        return dict(frames=int(self.frames), lead_silent=int(self.lead_silent), trail_silent=int(self.trail_silent),
+                    sum=[int(v) for v in self.sum], over=[int(v) for v in self.over], min=[int(v) for v in self.min],
+                    max=[int(v) for v in self.max])
+
+    @classmethod
+    def from_dict(cls, d):
+        return cls(d["frames"], d["lead_silent"], d["trail_silent"], (ctypes.c_int64 * 8)(*d["sum"]),
+                   (ctypes.c_uint64 * 8)(*d["over"]), (ctypes.c_int32 * 8)(*d["min"]), (ctypes.c_int32 * 8)(*d["max"]))
+
 
 ST_CONCEALED = 1 << 30          # DVDA_ST_CONCEALED: conceal mode, the stream was damaged (not in ST_BENIGN)
 CONCEAL_LEADING, CONCEAL_TRAILING, CONCEAL_ROUNDS = 1, 2, 4     # DVDA_CONCEAL_* span flags
@@ -186,6 +208,12 @@ def lib():
         L.dvda_mlp_hip_pcm_crc32.argtypes = [vp, vp, vp, vp, ctypes.c_uint, vp, vp, u32, vp]
         L.dvda_pcm_hip_crc32_combine.restype = u32
         L.dvda_pcm_hip_crc32_combine.argtypes = [u32, u32, u64]
+        L.dvda_pcm_hip_levels_workspace_words.restype = ctypes.c_size_t
+        L.dvda_pcm_hip_levels_workspace_words.argtypes = [u32, u64]
+        L.dvda_pcm_hip_levels.argtypes = [vp, u32, ctypes.c_uint, vp, u32, u64, vp, vp, ctypes.c_size_t, vp]
+        L.dvda_mlp_hip_pcm_levels.argtypes = [vp, vp, vp, vp, ctypes.c_uint, ctypes.POINTER(Levels), u32, vp]
+        L.dvda_pcm_hip_levels_combine.restype = None
+        L.dvda_pcm_hip_levels_combine.argtypes = [ctypes.POINTER(Levels), ctypes.POINTER(Levels), ctypes.POINTER(Levels)]
         _lib = L
     return _lib
 
@@ -319,6 +347,16 @@ class Context:
                                             nbytes.ctypes.data, n, stream), "dvda_mlp_hip_pcm_crc32")
         return [(int(c), int(b)) for c, b in zip(crc, nbytes)]
 
+    def pcm_levels(self, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, bits, n=None, stream=0):
+        """dvda_mlp_hip_pcm_levels: the level report of every stream at nominal depth `bits` (16, 20 or 24), computed on
+        the device from the int32 PCM the last decode wrote -> list of Levels.as_dict(); blocks.  HipError (EINVAL) when
+        the context's layout is a WAV one."""
+        n = self.n_streams if n is None else n
+        arr = (Levels * max(n, 1))()
+        _check(lib().dvda_mlp_hip_pcm_levels(self._h, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, bits, arr, n, stream),
+               "dvda_mlp_hip_pcm_levels")
+        return [arr[i].as_dict() for i in range(n)]
+
     def decode_time(self):
         """mean device ms of a whole decode call (all passes); call before kernel_time(), which resets the ring"""
         ms = ctypes.c_double()
@@ -373,6 +411,55 @@ def pcm_crc32(d_pcm, layout, bits, desc, max_total_bytes=None, work=None):
 
 def pcm_crc32_workspace_words(n, max_total_bytes):
     return int(lib().dvda_pcm_hip_crc32_workspace_words(n, max_total_bytes))
+
+
+def levels_combine(a, b):
+    """dvda_pcm_hip_levels_combine: the report of A || B from the reports of A and B (dicts as Levels.as_dict() gives
+    them); host arithmetic, needs no GPU"""
+    out = Levels()
+    lib().dvda_pcm_hip_levels_combine(ctypes.byref(Levels.from_dict(a)), ctypes.byref(Levels.from_dict(b)),
+                                      ctypes.byref(out))
+    return out.as_dict()
+
+
+def pcm_levels(d_pcm, layout, bits, desc, max_total_frames=None, work=None):
+    """dvda_pcm_hip_levels over torch tensors: d_pcm an int32 tensor on the device holding the streams in `layout`
+    (PCM_PLANAR or PCM_INTERLEAVED), desc a list of (off, stride, frames, channels) as dvda_pcm_crc_desc states them.
+    -> a uint8 device tensor [n, sizeof(Levels)] (levels_list brings it to the host).  Only the kernels are
+    asynchronous, on torch's current stream: like pcm_crc32, this helper builds the descriptors on the host, copies them
+    to the device and allocates them, the result and -- when none is passed -- the workspace.
+    max_total_frames: bound on the sum of the frames (default: computed from desc); work: an int32 workspace tensor of at
+    least pcm_levels_workspace_words() elements (default: allocated here)."""
+    import torch
+    if not torch.cuda.is_available():
+        raise HipError("no GPU visible to torch: the level report is HIP-only")
+    dev = d_pcm.device
+    n = len(desc)
+    rec = np.zeros(max(n, 1), np.dtype([("off", "<u8"), ("stride", "<u8"), ("frames", "<u8"), ("channels", "<u4"),
+                                         ("reserved", "<u4")]))
+    for i, (off, stride, frames, channels) in enumerate(desc):
+        rec[i] = (off, stride, frames, channels, 0)
+    if max_total_frames is None:
+        max_total_frames = int(sum(int(f) for _, _, f, c in desc if 1 <= int(c) <= 8))
+    words = int(lib().dvda_pcm_hip_levels_workspace_words(n, max_total_frames))
+    if work is None:
+        work = torch.empty(words, dtype=torch.int32, device=dev)
+    d_desc = torch.from_numpy(rec.view(np.uint8).reshape(-1)).to(dev)
+    d_out = torch.zeros((max(n, 1), ctypes.sizeof(Levels)), dtype=torch.uint8, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    _check(lib().dvda_pcm_hip_levels(d_pcm.data_ptr(), layout, bits, d_desc.data_ptr(), n, max_total_frames,
+                                     d_out.data_ptr(), work.data_ptr(), work.numel(), st), "dvda_pcm_hip_levels")
+    return d_out[:n]
+
+
+def pcm_levels_workspace_words(n, max_total_frames):
+    return int(lib().dvda_pcm_hip_levels_workspace_words(n, max_total_frames))
+
+
+def levels_list(d_levels):
+    """pcm_levels' tensor -> list of Levels.as_dict() on the host (waits)"""
+    raw = np.ascontiguousarray(d_levels.cpu().numpy())
+    return [Levels.from_buffer_copy(raw[i].tobytes()).as_dict() for i in range(raw.shape[0])]
 
 
 def crc_list(d_crc, d_nbytes):
@@ -528,10 +615,13 @@ class PcmRegions:
                            [inf.pcm_frames for inf in infos], self.layout)
 
 
-def decode_batch(ctx, batch, layout, attempts=1, capacity="report", decode=Context.decode, crc_bits=None, stream=None):
+def decode_batch(ctx, batch, layout, attempts=1, capacity="report", decode=Context.decode, crc_bits=None, stream=None,
+                 levels=None):
     """The decode sequence, once: index; regions of standard length in `layout` (what ctx is set to); up to `attempts`
     rounds of decode, each after the first on regions grown to what DVDA_ST_OVERFLOW asked for and a new index; the
     digest at crc_bits if given; the host copy.  -> (pcm as cut_regions gives it, infos, digests or None)
+    levels: a bit depth -- the level report at that depth too (Context.pcm_levels), appended: -> (pcm, infos, digests or
+    None, reports)
     capacity: what more major syncs than the context holds (sync patterns in payload count too) lead to -- "report":
     DVDA_ST_CAPACITY on the streams; "raise": HipError; a function: called with the count the index found, it returns
     the larger context the sequence goes on with (the caller's to close).
@@ -559,6 +649,8 @@ def decode_batch(ctx, batch, layout, attempts=1, capacity="report", decode=Conte
         if not any(inf.status & ST["OVERFLOW"] for inf in infos):
             break
     digests = ctx.pcm_crc32(*regions.ptrs, crc_bits, stream=st) if crc_bits else None
+    if levels is not None:
+        return regions.to_host(infos), list(infos), digests, ctx.pcm_levels(*regions.ptrs, levels, stream=st)
     return regions.to_host(infos), list(infos), digests
 
 
@@ -573,7 +665,7 @@ def _context_for(ctx, batch, max_segments, lanes_per_segment, layout):
 
 
 def decode_streams(streams, device=0, max_segments=None, lanes_per_segment=0, layout=PCM_PLANAR, ctx=None,
-                   presentation=PRESENT_FULL, crc32=False, crc_bits=24):
+                   presentation=PRESENT_FULL, crc32=False, crc_bits=24, levels=None):
     """Decodes a list of complete MLP byte streams on the GPU.
 
     Returns (pcm, infos): pcm[i] is an int32 array [channels, pcm_frames] in RIFF-WAVE
@@ -588,6 +680,8 @@ def decode_streams(streams, device=0, max_segments=None, lanes_per_segment=0, la
     (pcm[i] is [k, pcm_frames], infos[i].channels == k); one-substream streams as always.
     crc32=True: -> (pcm, infos, digests), digests[i] = (zlib CRC-32 of stream i's WAV payload at crc_bits, its bytes),
     computed on the device from the PCM where the decode wrote it (Context.pcm_crc32).
+    levels=<bits> (16, 20 or 24): the level report of every stream at that nominal depth (Context.pcm_levels) is appended
+    to the result: -> (pcm, infos, reports) or (pcm, infos, digests, reports).  layout must be an int32 one.
     """
     batch = Batch(streams, device)
     ctx, own = _context_for(ctx, batch, max_segments, lanes_per_segment, layout)
@@ -604,16 +698,17 @@ def decode_streams(streams, device=0, max_segments=None, lanes_per_segment=0, la
         if presentation != PRESENT_FULL or not own:
             ctx.set_presentation(presentation)
         # (int32 regions of r*c words, cut as [c, r], for any layout but PCM_INTERLEAVED)
-        pcm, infos, digests = decode_batch(ctx, batch, layout if layout == PCM_INTERLEAVED else PCM_PLANAR, attempts=2,
-                                           capacity=larger if own else "raise", crc_bits=crc_bits if crc32 else None)
-        return (pcm, infos, digests) if crc32 else (pcm, infos)
+        res = decode_batch(ctx, batch, layout if layout == PCM_INTERLEAVED else PCM_PLANAR, attempts=2,
+                           capacity=larger if own else "raise", crc_bits=crc_bits if crc32 else None, levels=levels)
+        pcm, infos, digests = res[:3]
+        return ((pcm, infos, digests) if crc32 else (pcm, infos)) + tuple(res[3:])
     finally:
         if own:
             made[0].close()
 
 
 def decode_streams_concealed(streams, device=0, max_segments=None, lanes_per_segment=0, layout=PCM_PLANAR, init_fir=None,
-                             crc32=False, crc_bits=24, ctx=None):
+                             crc32=False, crc_bits=24, ctx=None, levels=None):
     """decode_streams in conceal mode (dvda_mlp_hip_set_conceal): a damaged stream comes out as kept PCM ++ silence ++
     PCM of a fresh decoder ++ ... instead of a non-benign status (include/dvda_mlp_hip.h states the rule).
 
@@ -623,6 +718,8 @@ def decode_streams_concealed(streams, device=0, max_segments=None, lanes_per_seg
     init_fir: optional int32 [n_streams, 2, 48], the FIR history the streams start with (dvda_mlp_hip_set_initial_fir).
     crc32=True: -> (pcm, infos, spans, digests): (CRC-32, bytes) of every stream's WAV payload as it was handed out, at the
     depth of the WAV layout or at crc_bits for the int32 layouts (Context.pcm_crc32).
+    levels=<bits>: the level report of every stream as it was handed out -- the concealed gaps are exact zeros -- is
+    appended to the result (Context.pcm_levels; HipError for a WAV layout).
     `ctx`: a caller's Context to run on: its lane and layout settings are set to this call's, its presentation to
     PRESENT_FULL; conceal mode (and init_fir) are taken off it again when the call ends, however it ends.  It keeps its
     size: a batch it cannot hold raises."""
@@ -638,11 +735,12 @@ def decode_streams_concealed(streams, device=0, max_segments=None, lanes_per_seg
             d_fir = torch.from_numpy(np.ascontiguousarray(init_fir, np.int32).reshape(batch.n, 2, 48)).to(batch.dev)
             ctx.set_initial_fir(d_fir.data_ptr())
         # silence and a fresh decoder's access units can need more than the index's count, and then once more
-        pcm, infos, digests = decode_batch(ctx, batch, layout, attempts=3, capacity="report" if own else "raise",
-                                           crc_bits={PCM_WAV24: 24, PCM_WAV16: 16}.get(layout, crc_bits) if crc32 else None)
+        res = decode_batch(ctx, batch, layout, attempts=3, capacity="report" if own else "raise",
+                           crc_bits={PCM_WAV24: 24, PCM_WAV16: 16}.get(layout, crc_bits) if crc32 else None, levels=levels)
+        pcm, infos, digests = res[:3]
         spans = [ctx.conceal_spans(i, batch.current_stream) for i in range(batch.n)]
         done = True
-        return (pcm, infos, spans, digests) if crc32 else (pcm, infos, spans)
+        return ((pcm, infos, spans, digests) if crc32 else (pcm, infos, spans)) + tuple(res[3:])
     finally:
         if own:
             ctx.close()
