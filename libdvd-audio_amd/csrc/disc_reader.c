@@ -24,6 +24,7 @@
 #include <hip/hip_runtime_api.h>
 #include <math.h>
 #include <pthread.h>
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
@@ -53,6 +54,16 @@ void dvda_hip_set_levels(int on) { t_opts.levels = on != 0; }
 
 struct track_windows;               /* a long track read window by window (below) */
 
+/* The reports of a piece of PCM or of a track: the digest (dvda_hip_set_digest) and the level report
+ * (dvda_hip_set_levels).  Per report a state -- 0 off, 1 wanted and, once a piece is through, made (a windowed track:
+ * joined over the windows handed out so far), -1 this reader has none -- and its values. */
+struct pcm_reports {
+    int dg, lv;
+    uint32_t crc;               /* zlib CRC-32 of the WAV payload and its bytes */
+    uint64_t bytes;
+    dvda_pcm_levels levels;
+};
+
 struct DVDA_Track_Reader_s {
     dvda_codec_t codec;
     struct track_windows *win;     /* != NULL: the track is decoded in windows of bounded size as it is read */
@@ -67,11 +78,7 @@ struct DVDA_Track_Reader_s {
     uint8_t *d_wav;            /* MLP reader opened for the payload: the decode kernels wrote the WAV payload
                                   themselves (DVDA_PCM_WAV24 / WAV16); there is no int32 PCM for dvda_read() */
     uint64_t wav_bytes;
-    int dg_state;              /* digest (dvda_hip_set_digest): 0 off, 1 = dg_crc / dg_bytes are the track's, -1 none (bit depth) */
-    uint32_t dg_crc;
-    uint64_t dg_bytes;
-    int lv_state;              /* level report (dvda_hip_set_levels): 0 off, 1 = lv is the track's, -1 none (no int32 PCM, bit depth) */
-    dvda_pcm_levels lv;
+    struct pcm_reports rep;    /* a whole-track reader: the track's */
 };
 
 /* fills the reader's record from the index's stream record; 0 = a channel count the assignment does not have.  Under
@@ -215,51 +222,70 @@ static int64_t find_sync_dev(const uint8_t *d_bytes, uint64_t from, uint64_t siz
     return at;
 }
 
-/* The digest of one piece of PCM where it lies on the device (dvda_pcm_hip_crc32): `frames` frames of `ch` channels at
- * `bits` in `layout` at d_pcm, capacity `stride` frames.  Blocks; what it allocates it frees.  1 = ok. */
-static int piece_digest(const int32_t *d_pcm, uint32_t layout, unsigned bits, uint64_t stride, uint64_t frames, unsigned ch,
-                        uint32_t *crc, uint64_t *nbytes)
+/* The reports a reader wants (`have`: states > 0) of one piece of PCM where it lies on the device, into `out` (which may
+ * be `have`): `frames` frames of `ch` channels at `bits` in `layout` at d_pcm, capacity `stride` frames.  Which of them
+ * this reader has is decided here and nowhere else: a digest at 16 and 24 bits, a level report at 16, 20 and 24 bits of
+ * int32 PCM -- a reader that hands out the WAV payload (wav_payload) has none.  One block on the device holds the
+ * descriptor, the results and the workspace, the larger one where both reports run: they run one behind the other.
+ * Blocks; what it allocates it frees; allocates and launches nothing when there is nothing to make.  1 = ok. */
+static int piece_reports(struct pcm_reports *have, struct pcm_reports *out, int wav_payload, const int32_t *d_pcm,
+                         uint32_t layout, unsigned bits, uint64_t stride, uint64_t frames, unsigned ch)
 {
-    const uint64_t bound = frames * ch * (bits / 8);
-    const size_t words = dvda_pcm_hip_crc32_workspace_words(1, bound);
+    struct {
+        uint64_t bytes;
+        uint32_t crc, pad;
+        dvda_pcm_levels levels;
+    } res;
     const dvda_pcm_crc_desc desc = {0, stride, frames, ch, 0};
+    const uint64_t payload = frames * ch * (bits / 8);
+    if (have->dg > 0 && bits != 16 && bits != 24)
+        have->dg = -1;
+    if (have->lv > 0 && (wav_payload || (bits != 16 && bits != 20 && bits != 24)))
+        have->lv = -1;
+    const int dg = have->dg > 0, lv = have->lv > 0;
+    const size_t w_dg = dg ? dvda_pcm_hip_crc32_workspace_words(1, payload) : 0;
+    const size_t w_lv = lv ? dvda_pcm_hip_levels_workspace_words(1, frames) : 0;
+    const size_t words = w_dg > w_lv ? w_dg : w_lv;
     uint8_t *d = NULL;
-    int ok = 0;
-    *crc = 0;
-    *nbytes = 0;
-    /* desc (32 bytes) | nbytes (8) | crc (4, padded to 8) | workspace */
-    if (!dev_alloc((void **)&d, 48 + words * sizeof(uint32_t)))
+    out->dg = have->dg;
+    out->lv = have->lv;
+    out->crc = 0;
+    out->bytes = 0;
+    memset(&out->levels, 0, sizeof(out->levels));
+    if (!frames || !words)
+        return 1;                                /* (the reports of no frames are zeros) */
+    if (!dev_alloc((void **)&d, sizeof(desc) + sizeof(res) + words * sizeof(uint32_t)))
         return 0;
-    if (hipMemcpy(d, &desc, sizeof(desc), hipMemcpyHostToDevice) == hipSuccess &&
-        dvda_pcm_hip_crc32(d_pcm, layout, bits, (const dvda_pcm_crc_desc *)d, 1, bound, (uint32_t *)(d + 40),
-                           (uint64_t *)(d + 32), (uint32_t *)(d + 48), words, NULL) == DVDA_HIP_OK &&
-        hipMemcpy(nbytes, d + 32, sizeof(*nbytes), hipMemcpyDeviceToHost) == hipSuccess &&
-        hipMemcpy(crc, d + 40, sizeof(*crc), hipMemcpyDeviceToHost) == hipSuccess)
-        ok = 1;
+    uint8_t *d_res = d + sizeof(desc);
+    uint32_t *d_work = (uint32_t *)(d_res + sizeof(res));
+    const int ok =
+        hipMemcpy(d, &desc, sizeof(desc), hipMemcpyHostToDevice) == hipSuccess &&
+        (!dg || dvda_pcm_hip_crc32(d_pcm, layout, bits, (const dvda_pcm_crc_desc *)d, 1, payload,
+                                   (uint32_t *)(d_res + offsetof(__typeof__(res), crc)), (uint64_t *)d_res, d_work, words,
+                                   NULL) == DVDA_HIP_OK) &&
+        (!lv || dvda_pcm_hip_levels(d_pcm, layout, bits, (const dvda_pcm_crc_desc *)d, 1, frames,
+                                    (dvda_pcm_levels *)(d_res + offsetof(__typeof__(res), levels)), d_work, words,
+                                    NULL) == DVDA_HIP_OK) &&
+        hipMemcpy(&res, d_res, sizeof(res), hipMemcpyDeviceToHost) == hipSuccess;
     (void)hipFree(d);
+    if (ok && dg) {
+        out->crc = res.crc;
+        out->bytes = res.bytes;
+    }
+    if (ok && lv)
+        out->levels = res.levels;
     return ok;
 }
 
-/* The level report of one piece of int32 PCM where it lies on the device (dvda_pcm_hip_levels), as piece_digest() takes
- * it; layout DVDA_PCM_PLANAR or DVDA_PCM_INTERLEAVED, bits 16 / 20 / 24.  Blocks; what it allocates it frees.  1 = ok. */
-static int piece_levels(const int32_t *d_pcm, uint32_t layout, unsigned bits, uint64_t stride, uint64_t frames, unsigned ch,
-                        dvda_pcm_levels *out)
+/* a piece is handed out: its reports join the track's */
+static void reports_join(struct pcm_reports *track, const struct pcm_reports *piece)
 {
-    const size_t words = dvda_pcm_hip_levels_workspace_words(1, frames);
-    const dvda_pcm_crc_desc desc = {0, stride, frames, ch, 0};
-    const size_t head = sizeof(desc) + sizeof(*out);        /* desc (32 bytes) | report (216) | workspace */
-    uint8_t *d = NULL;
-    int ok = 0;
-    memset(out, 0, sizeof(*out));
-    if (!dev_alloc((void **)&d, head + words * sizeof(uint32_t)))
-        return 0;
-    if (hipMemcpy(d, &desc, sizeof(desc), hipMemcpyHostToDevice) == hipSuccess &&
-        dvda_pcm_hip_levels(d_pcm, layout, bits, (const dvda_pcm_crc_desc *)d, 1, frames, (dvda_pcm_levels *)(d + sizeof(desc)),
-                            (uint32_t *)(d + head), words, NULL) == DVDA_HIP_OK &&
-        hipMemcpy(out, d + sizeof(desc), sizeof(*out), hipMemcpyDeviceToHost) == hipSuccess)
-        ok = 1;
-    (void)hipFree(d);
-    return ok;
+    if (track->dg > 0) {
+        track->crc = dvda_pcm_hip_crc32_combine(track->crc, piece->crc, piece->bytes);
+        track->bytes += piece->bytes;
+    }
+    if (track->lv > 0)
+        dvda_pcm_hip_levels_combine(&track->levels, &piece->levels, &track->levels);
 }
 
 /* ------------------------------------------------------------------ the buffer set
@@ -532,28 +558,6 @@ static int decode_stream(struct track_bufs *b, uint64_t len, const int32_t *fir,
     return 1;
 }
 
-/* digest of what decode_stream() left in d_pcm, before any copy: 1 = made, -1 = the bit depth has none, 0 = failure */
-static int stream_digest(const struct track_bufs *b, const dvda_mlp_stream_info *info, int wav_bits, uint64_t stride,
-                         uint32_t *crc, uint64_t *nbytes)
-{
-    const unsigned bits = bits_of(info->group0_bps);
-    if (bits != 16 && bits != 24)
-        return -1;
-    return piece_digest(b->d_pcm, layout_of(wav_bits), bits, stride, info->pcm_frames, info->channels, crc, nbytes);
-}
-
-/* level report of what decode_stream() left in d_pcm, before any copy: 1 = made, -1 = there is none (the decode wrote the
- * WAV payload: no int32 PCM; or a bit depth other than 16 / 20 / 24), 0 = failure */
-static int stream_levels(const struct track_bufs *b, const dvda_mlp_stream_info *info, int wav_bits, uint64_t stride,
-                         dvda_pcm_levels *out)
-{
-    const unsigned bits = bits_of(info->group0_bps);
-    memset(out, 0, sizeof(*out));
-    if (wav_bits || (bits != 16 && bits != 20 && bits != 24))
-        return -1;
-    return piece_levels(b->d_pcm, DVDA_PCM_INTERLEAVED, bits, stride, info->pcm_frames, info->channels, out);
-}
-
 /* How many of the `total` PCM frames of `got` sectors a raw-PCM track takes, `done` of its `want` frames delivered
  * before them: whole packets until the length is covered, the opening packet regardless (open_pcm_track_reader /
  * decode_pcm_audio, src/dvd-audio.c:958-1084).  *covered = the track ends inside these sectors. */
@@ -641,19 +645,12 @@ static DVDA_Track_Reader *open_mlp(struct aob_set *aobs, const DVDA_Track *k, co
     r->stride = stride;
     if (!mlp_info_to_reader(r, &info, o->present))
         goto fail;
-    if (o->digest) {
-        /* before any copy to the host: the track as the decode left it on the device */
-        const int rc = stream_digest(&b, &info, wav_bits, stride, &r->dg_crc, &r->dg_bytes);
-        if (!rc)
-            goto fail;
-        r->dg_state = rc;
-    }
-    if (o->levels) {
-        const int rc = stream_levels(&b, &info, wav_bits, stride, &r->lv);
-        if (!rc)
-            goto fail;
-        r->lv_state = rc;
-    }
+    /* before any copy to the host: the track as the decode left it on the device */
+    r->rep.dg = o->digest;
+    r->rep.lv = o->levels;
+    if (!piece_reports(&r->rep, &r->rep, wav_bits != 0, b.d_pcm, layout_of(wav_bits), bits_of(info.group0_bps), stride,
+                       info.pcm_frames, info.channels))
+        goto fail;
     if (wav_bits) {
         r->d_wav = (uint8_t *)b.d_pcm;
         r->wav_bytes = r->frames * r->channels * ((unsigned)wav_bits / 8);
@@ -707,9 +704,7 @@ struct win_slot {
     size_t cap;
     uint64_t frames;
     uint64_t stride;            /* != 0: int32 PLANAR [channel][stride] (raw-PCM windows: the order the un-swizzle writes) */
-    uint32_t crc;               /* digest of the window's payload and its bytes (dvda_hip_set_digest) */
-    uint64_t crc_bytes;
-    dvda_pcm_levels lv;         /* level report of the window's int32 PCM (dvda_hip_set_levels) */
+    struct pcm_reports rep;     /* of the window, made on the device before it was copied */
 };
 
 struct track_windows {
@@ -722,13 +717,9 @@ struct track_windows {
     int wav_bits;               /* != 0: the windows hold the payload (DVDA_PCM_WAV24 / WAV16); < 0 until the first
                                    window's major sync has decided it: only a 16- or 24-bit stream is decoded straight
                                    into it */
-    int digest;                 /* 1: every window is digested on the device before it is copied (dvda_hip_set_digest); -1: the
-                                   stream's bit depth has no digest */
-    uint32_t dg_crc;            /* the windows handed out so far, joined (under `mu`, win_release()) */
-    uint64_t dg_bytes;
-    int levels;                 /* 1: every window's int32 PCM is reported on the device before it is copied
-                                   (dvda_hip_set_levels); -1: there is none (the windows hold the WAV payload, or the bit depth) */
-    dvda_pcm_levels lv;         /* the windows handed out so far, joined (under `mu`, win_release()) */
+    struct pcm_reports rep;     /* states: what every window is asked on the device before it is copied (-1: decided by the
+                                   first window's piece_reports()); values: the windows handed out so far, joined (under
+                                   `mu`, win_release()) */
     int started, finished, failed;
     /* a raw-PCM track read in windows (round 6): sectors decode independently of each other (src/pcm.c:149: whole chunks
        per packet), so a window is a run of sectors and nothing crosses a cut but the count of frames delivered so far */
@@ -945,7 +936,7 @@ static int win_produce(struct track_windows *w, struct win_slot *out)
     uint64_t total = 0, begin = 0, end = 0, stride = 0;
     out->frames = 0;
     out->stride = 0;
-    memset(&out->lv, 0, sizeof(out->lv));
+    memset(&out->rep, 0, sizeof(out->rep));
     /* ---- sectors -> device -> MLP bytes, and where this window's new bytes begin and end: the end-of-track rule on
        the window that holds the track's last sector, with its look-ahead */
     for (unsigned extra = 8;; extra *= 4) {
@@ -1037,24 +1028,10 @@ static int win_produce(struct track_windows *w, struct win_slot *out)
             return 0;
         w->have_fir = 1;
     }
-    /* ---- the window's digest, from the device */
-    out->crc = 0;
-    out->crc_bytes = 0;
-    if (w->digest) {
-        const int rc = stream_digest(b, &info, w->wav_bits, stride, &out->crc, &out->crc_bytes);
-        if (!rc)
-            return 0;
-        if (rc < 0)
-            w->digest = -1;
-    }
-    /* ---- ... and its level report */
-    if (w->levels > 0) {
-        const int rc = stream_levels(b, &info, w->wav_bits, stride, &out->lv);
-        if (!rc)
-            return 0;
-        if (rc < 0)
-            w->levels = -1;
-    }
+    /* ---- the window's reports, from the device */
+    if (!piece_reports(&w->rep, &out->rep, w->wav_bits != 0, b->d_pcm, layout_of(w->wav_bits), bits_of(info.group0_bps),
+                       stride, info.pcm_frames, info.channels))
+        return 0;
     /* ---- PCM (or payload) to the host buffer */
     const size_t bytes = (size_t)info.pcm_frames * info.channels * (w->wav_bits ? (unsigned)w->wav_bits / 8 : 4);
     if (!slot_reserve(b, out, bytes) ||
@@ -1080,7 +1057,7 @@ static int win_produce_pcm(struct track_windows *w, struct win_slot *out)
     int final = 0;
     out->frames = 0;
     out->stride = 0;
-    memset(&out->lv, 0, sizeof(out->lv));
+    memset(&out->rep, 0, sizeof(out->rep));
     if (w->next + want > w->aobs.total || w->next + want < w->next)
         want = w->next < w->aobs.total ? w->aobs.total - w->next : 0;
     if (!sectors_to_device(b, &w->aobs, w->next, want, bits, ch, NULL, &got, &total, &stride))
@@ -1094,14 +1071,8 @@ static int win_produce_pcm(struct track_windows *w, struct win_slot *out)
     w->started = 1;
     if (!final && (got < want || w->next >= w->aobs.total))
         final = 1;                               /* the files end inside the track */
-    out->crc = 0;
-    out->crc_bytes = 0;
-    if (deliver && w->digest &&
-        !piece_digest(b->d_pcm, DVDA_PCM_PLANAR, bits, stride, deliver, ch, &out->crc, &out->crc_bytes))
-        return 0;                                /* (the planes as the un-swizzle left them: before packing and copy) */
-    if (w->levels > 0 && w->wav_bits)
-        w->levels = -1;                          /* a WAV-payload reader */
-    if (deliver && w->levels > 0 && !piece_levels(b->d_pcm, DVDA_PCM_PLANAR, bits, stride, deliver, ch, &out->lv))
+    /* (the planes as the un-swizzle left them: before packing and copy) */
+    if (!piece_reports(&w->rep, &out->rep, w->wav_bits != 0, b->d_pcm, DVDA_PCM_PLANAR, bits, stride, deliver, ch))
         return 0;
     if (deliver && w->wav_bits) {
         const size_t bytes = (size_t)deliver * ch * (bits / 8);
@@ -1189,13 +1160,7 @@ static struct win_slot *win_current(struct track_windows *w)
 static void win_release(struct track_windows *w)
 {
     pthread_mutex_lock(&w->mu);
-    if (w->digest > 0) {
-        /* the window is handed out: its digest joins the track's */
-        w->dg_crc = dvda_pcm_hip_crc32_combine(w->dg_crc, w->slot[w->tail].crc, w->slot[w->tail].crc_bytes);
-        w->dg_bytes += w->slot[w->tail].crc_bytes;
-    }
-    if (w->levels > 0)
-        dvda_pcm_hip_levels_combine(&w->lv, &w->slot[w->tail].lv, &w->lv);
+    reports_join(&w->rep, &w->slot[w->tail].rep);
     w->tail = (w->tail + 1) % WIN_SLOTS;
     w->count--;
     w->served_in_slot = 0;
@@ -1224,8 +1189,8 @@ static DVDA_Track_Reader *windows_new(const DVDA_Track *k, const struct reader_o
     r->interleaved = 1;
     w->produce = produce;
     w->opts = *o;
-    w->digest = o->digest;
-    w->levels = o->levels;
+    w->rep.dg = o->digest;
+    w->rep.lv = o->levels;
     w->next = k->s.first;
     w->last = k->s.last >= k->s.first ? k->s.last : k->s.first;
     w->window = window_sectors();
@@ -1325,16 +1290,10 @@ static DVDA_Track_Reader *open_pcm(struct aob_set *aobs, const DVDA_Track *k, co
     r->stride = stride;
     r->d_pcm = b.d_pcm;
     b.d_pcm = NULL;
-    if (o->digest) {
-        if (!piece_digest(r->d_pcm, DVDA_PCM_PLANAR, bits, stride, deliver, r->channels, &r->dg_crc, &r->dg_bytes))
-            goto fail;
-        r->dg_state = 1;
-    }
-    if (o->levels) {
-        if (!piece_levels(r->d_pcm, DVDA_PCM_PLANAR, bits, stride, deliver, r->channels, &r->lv))
-            goto fail;
-        r->lv_state = 1;
-    }
+    r->rep.dg = o->digest;
+    r->rep.lv = o->levels;
+    if (!piece_reports(&r->rep, &r->rep, 0, r->d_pcm, DVDA_PCM_PLANAR, bits, stride, deliver, r->channels))
+        goto fail;
     goto done;
 fail:
     reader_free(r);
@@ -1471,50 +1430,41 @@ int dvda_hip_reader_failed(const DVDA_Track_Reader *r)
     }
     return f;
 }
-int dvda_hip_reader_crc32(const DVDA_Track_Reader *r, unsigned *crc, unsigned long long *bytes)
+/* the reader's reports as they stand: 1 = the track's, 0 = of the windows handed out so far, -1 = a failed reader */
+static int reader_reports(const DVDA_Track_Reader *r, struct pcm_reports *out)
 {
-    if (!r)
-        return -1;
     if (!r->win) {
-        if (r->dg_state != 1)
-            return -1;
-        if (crc)
-            *crc = r->dg_crc;
-        if (bytes)
-            *bytes = r->dg_bytes;
+        *out = r->rep;
         return 1;
     }
     struct track_windows *w = r->win;
     pthread_mutex_lock(&w->mu);
+    *out = w->rep;
     /* final: the producer is done and every window has been handed out */
-    const int rc = (w->digest <= 0 || w->failed) ? -1 : (w->finished && w->count == 0) ? 1 : 0;
-    if (rc >= 0) {
-        if (crc)
-            *crc = w->dg_crc;
-        if (bytes)
-            *bytes = w->dg_bytes;
-    }
+    const int rc = w->failed ? -1 : (w->finished && w->count == 0) ? 1 : 0;
     pthread_mutex_unlock(&w->mu);
+    return rc;
+}
+int dvda_hip_reader_crc32(const DVDA_Track_Reader *r, unsigned *crc, unsigned long long *bytes)
+{
+    struct pcm_reports rep;
+    const int rc = r ? reader_reports(r, &rep) : -1;
+    if (rc < 0 || rep.dg <= 0)
+        return -1;
+    if (crc)
+        *crc = rep.crc;
+    if (bytes)
+        *bytes = rep.bytes;
     return rc;
 }
 int dvda_hip_reader_levels(const DVDA_Track_Reader *r, dvda_pcm_levels *out)
 {
-    if (!r)
+    struct pcm_reports rep;
+    const int rc = r ? reader_reports(r, &rep) : -1;
+    if (rc < 0 || rep.lv <= 0)
         return -1;
-    if (!r->win) {
-        if (r->lv_state != 1)
-            return -1;
-        if (out)
-            *out = r->lv;
-        return 1;
-    }
-    struct track_windows *w = r->win;
-    pthread_mutex_lock(&w->mu);
-    /* final: the producer is done and every window has been handed out */
-    const int rc = (w->levels <= 0 || w->failed) ? -1 : (w->finished && w->count == 0) ? 1 : 0;
-    if (rc >= 0 && out)
-        *out = w->lv;
-    pthread_mutex_unlock(&w->mu);
+    if (out)
+        *out = rep.levels;
     return rc;
 }
 int dvda_hip_reader_memory(const DVDA_Track_Reader *r, unsigned long long *host_peak, unsigned long long *device_peak)

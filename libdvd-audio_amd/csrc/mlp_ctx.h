@@ -119,15 +119,12 @@ struct dvda_mlp_hip_ctx {
     DevBuf<uint32_t> d_brec;
     DevBuf<uint32_t> d_frec;
     uint32_t iir_lanes;
-    // dvda_mlp_hip_pcm_crc32 (pcm_digest_run.h): grown on first use
-    DevBuf<dvda_pcm_crc_desc> d_crc_desc;   // [streams]
-    DevBuf<uint32_t> d_crc_out;         // [streams]
-    DevBuf<uint64_t> d_crc_bytes;       // [streams]
-    DevBuf<uint32_t> d_crc_work;
-    // dvda_mlp_hip_pcm_levels (pcm_levels_run.h): grown on first use
-    DevBuf<dvda_pcm_crc_desc> d_lvl_desc;   // [streams]
-    DevBuf<dvda_pcm_levels> d_lvl_out;  // [streams]
-    DevBuf<uint32_t> d_lvl_work;
+    // dvda_mlp_hip_pcm_crc32 / dvda_mlp_hip_pcm_levels (pcm_report_run.h): grown on first use, and the same three for
+    // both reports.  What one report left in them is the other's to overwrite: a report reads no word of the workspace
+    // or the result block that the same call has not stored (both tests named test_poisoned_workspace pin that).
+    DevBuf<dvda_pcm_crc_desc> d_rep_desc;   // [streams]
+    DevBuf<uint64_t> d_rep_out;         // the results, laid out by the report (CrcReport::in / LvlReport::in)
+    DevBuf<uint32_t> d_rep_work;
     DecodeSettings set;
     // call state
     const uint8_t *d_bytes;

@@ -15,7 +15,7 @@
 //
 // Host code beside the core, each in a header included here: hip_ws.h (owning buffers and handles), mlp_ctx.h (the
 // context), mlp_conceal_run.h, mlp_present_run.h (the two modes), mlp_stepper.h (streaming tier), mlp_tiers.h (raw PCM,
-// demux, WAV payload), pcm_digest_run.h (CRC-32 of the decoded PCM), pcm_levels_run.h (its level report).
+// demux, WAV payload), pcm_report_run.h (the reports of the decoded PCM: its CRC-32, its levels).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -45,8 +45,7 @@
 #include "mlp_present_run.h"
 #include "mlp_stepper.h"
 #include "mlp_tiers.h"
-#include "pcm_digest_run.h"
-#include "pcm_levels_run.h"
+#include "pcm_report_run.h"
 
 // range-checked build: violations counted by the kernels so far (0 in the shipped library, which does not check)
 extern "C" int dvda_mlp_hip_bounds_violations(unsigned long long *out4)

@@ -25,19 +25,21 @@
 #include <type_traits>
 
 #include "../../include/dvda_mlp_hip.h"
+#include "pcm_tiles.h"
 
 namespace crc {
+
+using pcmt::find_stream;
+using pcmt::THREADS;
+using pcmt::WAVES;
 
 constexpr uint32_t POLY = 0xEDB88320u;
 constexpr uint32_t ONE = 0x80000000u;       // x^0
 constexpr int K = 16;                       // dwords per lane and tile
-constexpr int WAVES = 4;
-constexpr int THREADS = WAVES * 64;
 constexpr uint32_t TILE = DVDA_CRC_TILE_BYTES;
 constexpr uint32_t JOIN = DVDA_CRC_JOIN_TILES;
 static_assert(TILE == (uint32_t)THREADS * K * 4 && TILE % 256 == 0, "a tile is K dwords per lane of one workgroup");
 static_assert(JOIN == (uint32_t)THREADS, "the join folds one tile per thread and turn");
-constexpr uint32_t MAX_CHANNELS = 8;        // a descriptor with more (or none) is an empty stream
 constexpr uint32_t TILE_BLOCKS = 4096;      // workgroups of k_crc_tiles at most: they stride over the tile list
 
 __host__ __device__ constexpr uint32_t mulx(uint32_t a) { return (a >> 1) ^ ((a & 1u) ? POLY : 0u); }
@@ -102,7 +104,7 @@ __device__ const Tables d_tab = make_tables();
 // payload bytes of a stream (0 for a descriptor outside what the kernels take)
 __host__ __device__ __forceinline__ uint64_t stream_bytes(const dvda_pcm_crc_desc &d, uint32_t nb)
 {
-    if (d.channels == 0 || d.channels > MAX_CHANNELS || d.frames > (1ull << 40))
+    if (PCMT_NOT_TAKEN(d))
         return 0;
     return d.frames * d.channels * nb;
 }
@@ -215,37 +217,6 @@ __host__ __device__ __forceinline__ uint32_t mul_x2048(const uint32_t *s_mul, ui
     return s_mul[v & 255u] ^ s_mul[256u + ((v >> 8) & 255u)] ^ s_mul[512u + ((v >> 16) & 255u)] ^ s_mul[768u + (v >> 24)];
 }
 
-// XOR over the workgroup; every thread calls it, thread 0 holds the result (s_red: WAVES words)
-__device__ __forceinline__ uint32_t block_xor(uint32_t v, uint32_t *s_red)
-{
-    for (int o = 32; o; o >>= 1)
-        v ^= __shfl_xor(v, o, 64);
-    __syncthreads();                    // (s_red of the turn before has been read)
-    if ((threadIdx.x & 63u) == 0)
-        s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint32_t r = 0;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < WAVES; w++)
-            r ^= s_red[w];
-    return r;
-}
-
-// the stream that holds tile `b` of the flat list: the last one whose base is at or before b (streams without tiles
-// share their base with the stream behind them and are passed over)
-__host__ __device__ __forceinline__ uint32_t find_stream(const uint32_t *__restrict__ base, uint32_t n, uint32_t b)
-{
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (base[mid] <= b)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
 // ---- step 3: the raw CRC of every tile.  The workgroups stride over the flat tile list (as many of it as the
 //      caller's bound holds: tile_val has max_tiles entries).
 template <int LAYOUT>
@@ -260,9 +231,7 @@ __global__ __launch_bounds__(THREADS) void k_crc_tiles(const int32_t *__restrict
         s_mul[i] = d_tab.mul[i];
     const uint32_t weight = d_tab.lane_w[threadIdx.x];
     __syncthreads();
-    uint32_t total = base[n];
-    if (total > max_tiles)
-        total = max_tiles;
+    const uint32_t total = pcmt::list_tiles(base, n, max_tiles);
     const uint32_t g0 = (threadIdx.x >> 6) * (64u * K) + (threadIdx.x & 63u);
     for (uint32_t b = blockIdx.x; b < total; b += gridDim.x) {
         const uint32_t s = find_stream(base, n, b);
@@ -280,7 +249,7 @@ __global__ __launch_bounds__(THREADS) void k_crc_tiles(const int32_t *__restrict
 #pragma unroll
         for (int i = 0; i < K; i++)
             acc = mul_x2048(s_mul, acc) ^ v[i];
-        const uint32_t r = block_xor(gfmul(acc, weight), s_red);
+        const uint32_t r = pcmt::block_fold(gfmul(acc, weight), s_red, pcmt::FoldXor());
         if (threadIdx.x == 0)
             tile_val[b] = r;
     }
@@ -309,7 +278,7 @@ __global__ __launch_bounds__(THREADS) void k_crc_join(const dvda_pcm_crc_desc *_
             acc = gfmul(acc, step) ^ tile_val[first + (n_t - 1 - (uint32_t)r)];
         acc = gfmul(acc, d_tab.join_w[threadIdx.x]);
     }
-    const uint32_t raw = block_xor(acc, s_red);
+    const uint32_t raw = pcmt::block_fold(acc, s_red, pcmt::FoldXor());
     if (threadIdx.x == 0) {
         crc_out[s] = bytes ? raw ^ gfmul(0xFFFFFFFFu, xpow(8ull * bytes)) ^ 0xFFFFFFFFu : 0u;
         nbytes_out[s] = bytes;

@@ -25,14 +25,15 @@
 #include <stdint.h>
 
 #include "../../include/dvda_mlp_hip.h"
-#include "pcm_digest.h"
+#include "pcm_tiles.h"
 
 namespace lvl {
 
+using pcmt::MAX_CHANNELS;
+using pcmt::THREADS;
+using pcmt::WAVES;
+
 constexpr uint32_t TILE = DVDA_LVL_TILE_FRAMES;
-constexpr int WAVES = 4;
-constexpr int THREADS = WAVES * 64;
-constexpr uint32_t MAX_CHANNELS = 8;        // a descriptor with more (or none) is an empty stream
 constexpr uint32_t TILE_BLOCKS = 2048;      // workgroups of k_lvl_tiles at most (8 per CU): they stride over the tile list
 constexpr uint32_t REC = 2 + 5 * MAX_CHANNELS;     // words of a tile's record
 constexpr uint32_t NONE = 0xFFFFFFFFu;      // "no non-zero value" as a first index
@@ -42,7 +43,7 @@ static_assert(TILE % 4 == 0 && TILE * MAX_CHANNELS < (1u << 17), "run indices an
 // PCM frames of a stream (0 for a descriptor outside what the kernels take)
 __host__ __device__ __forceinline__ uint64_t stream_frames(const dvda_pcm_crc_desc &d)
 {
-    if (d.channels == 0 || d.channels > MAX_CHANNELS || d.frames > (1ull << 40))
+    if (PCMT_NOT_TAKEN(d))
         return 0;
     return d.frames;
 }
@@ -167,11 +168,9 @@ __global__ __launch_bounds__(THREADS, PLANAR ? 7 : 8) void k_lvl_tiles(const int
     __shared__ uint32_t s_rec[WAVES][REC];
     const uint32_t half = 1u << (bits - 1);
     const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63u;
-    uint32_t total = base[n];
-    if (total > max_tiles)
-        total = max_tiles;
+    const uint32_t total = pcmt::list_tiles(base, n, max_tiles);
     for (uint32_t b = blockIdx.x; b < total; b += gridDim.x) {
-        const uint32_t s = crc::find_stream(base, n, b);
+        const uint32_t s = pcmt::find_stream(base, n, b);
         const dvda_pcm_crc_desc d = desc[s];
         const uint32_t ch = d.channels;
         const uint64_t f0 = (uint64_t)(b - base[s]) * TILE;         // (a stream that has tiles has frames and 1..8 channels)
@@ -270,38 +269,6 @@ __global__ __launch_bounds__(THREADS, PLANAR ? 7 : 8) void k_lvl_tiles(const int
     }
 }
 
-// over the workgroup; every thread calls them, thread 0 holds the result (s_red: WAVES words)
-__device__ __forceinline__ uint64_t block_min_u64(uint64_t v, uint64_t *s_red)
-{
-    for (int o = 32; o; o >>= 1) {
-        const uint64_t x = __shfl_xor((unsigned long long)v, o, 64);
-        v = x < v ? x : v;
-    }
-    __syncthreads();                    // (s_red of the turn before has been read)
-    if ((threadIdx.x & 63u) == 0)
-        s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 0; w < WAVES; w++)
-            v = s_red[w] < v ? s_red[w] : v;
-    return v;
-}
-
-__device__ __forceinline__ uint64_t block_sum_u64(uint64_t v, uint64_t *s_red)
-{
-    for (int o = 32; o; o >>= 1)
-        v += __shfl_xor((unsigned long long)v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63u) == 0)
-        s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint64_t r = 0;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < WAVES; w++)
-            r += s_red[w];
-    return r;
-}
-
 // ---- step 4: one workgroup per stream joins the stream's records.  A stream whose tiles do not all lie inside the
 //      caller's bound is reported as zeros.
 __global__ __launch_bounds__(THREADS) void k_lvl_join(const dvda_pcm_crc_desc *__restrict__ desc, uint32_t n,
@@ -328,8 +295,8 @@ __global__ __launch_bounds__(THREADS) void k_lvl_join(const dvda_pcm_crc_desc *_
         if (l && ~((uint64_t)i * TILE + l) < not_end)
             not_end = ~((uint64_t)i * TILE + l);
     }
-    lead = block_min_u64(lead, s_red);
-    not_end = block_min_u64(not_end, s_red);
+    lead = pcmt::block_fold(lead, s_red, pcmt::FoldMin());
+    not_end = pcmt::block_fold(not_end, s_red, pcmt::FoldMin());
     if (threadIdx.x == 0) {
         out[s].frames = frames;
         out[s].lead_silent = lead;
@@ -347,10 +314,10 @@ __global__ __launch_bounds__(THREADS) void k_lvl_join(const dvda_pcm_crc_desc *_
                 over += r[2];
                 sum += (uint64_t)r[3] | (uint64_t)r[4] << 32;
             }
-        mn = block_min_u64(mn, s_red);
-        not_mx = block_min_u64(not_mx, s_red);
-        over = block_sum_u64(over, s_red);
-        sum = block_sum_u64(sum, s_red);
+        mn = pcmt::block_fold(mn, s_red, pcmt::FoldMin());
+        not_mx = pcmt::block_fold(not_mx, s_red, pcmt::FoldMin());
+        over = pcmt::block_fold(over, s_red, pcmt::FoldSum());
+        sum = pcmt::block_fold(sum, s_red, pcmt::FoldSum());
         if (threadIdx.x == 0) {
             const bool live = c < ch;
             out[s].min[c] = live ? (int32_t)((uint32_t)mn ^ 0x80000000u) : 0;

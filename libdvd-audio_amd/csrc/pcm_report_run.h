@@ -1,0 +1,276 @@
+// pcm_report_run.h -- host side of the reports of decoded PCM, the digest (pcm_digest.h) and the level report
+// (pcm_levels.h): what a report is to the driver, the one driver of the flat tile list (pcm_tiles.h), the one call that
+// runs a report behind a decode on the context's own buffers, and the host arithmetic that joins two pieces' results.
+#pragma once
+#include <vector>
+
+#include "mlp_ctx.h"
+#include "pcm_digest.h"
+#include "pcm_levels.h"
+
+// ---- a report, as the driver sees it: the unit its tiles are cut in and the words a tile leaves in the workspace, the
+//      layouts and depths it takes, where its results go, and its three launches
+struct CrcReport {
+    static constexpr uint32_t TILE = crc::TILE, TILE_WORDS = 1, TILE_BLOCKS = crc::TILE_BLOCKS;    // unit: payload bytes
+    uint32_t *d_crc;
+    uint64_t *d_nbytes;
+
+    bool has_out() const { return d_crc && d_nbytes; }
+    static bool takes(uint32_t layout, unsigned bits)
+    {
+        return layout <= DVDA_PCM_WAV16 && (bits == 16 || bits == 24) && !(layout == DVDA_PCM_WAV24 && bits != 24) &&
+               !(layout == DVDA_PCM_WAV16 && bits != 16);
+    }
+    static uint64_t units(const dvda_pcm_crc_desc &d, unsigned bits) { return d.frames * d.channels * (bits / 8); }
+    // the results of n streams in one block of uint64 words: the byte counts, then the digests
+    static size_t out_words(uint32_t n) { return (size_t)n + ((size_t)n + 1) / 2; }
+    static CrcReport in(uint64_t *d_out, uint32_t n) { return CrcReport{(uint32_t *)(d_out + n), d_out}; }
+
+    void plan(hipStream_t st, const dvda_pcm_crc_desc *d_desc, uint32_t n, unsigned bits, uint32_t *cnt) const
+    {
+        hipLaunchKernelGGL(crc::k_crc_plan, dim3((n + 255) / 256), dim3(256), 0, st, d_desc, n, bits / 8, cnt);
+    }
+    void tiles(dim3 grid, dim3 block, hipStream_t st, const int32_t *d_pcm, uint32_t layout, const dvda_pcm_crc_desc *d_desc,
+               uint32_t n, unsigned bits, const uint32_t *base, uint32_t *tile_val, uint32_t max_tiles) const
+    {
+        const uint32_t nb = bits / 8;
+        if (layout == DVDA_PCM_PLANAR)
+            hipLaunchKernelGGL(crc::k_crc_tiles<crc::SRC_PLANAR>, grid, block, 0, st, d_pcm, d_desc, n, nb, base, tile_val,
+                               max_tiles);
+        else if (layout == DVDA_PCM_INTERLEAVED)
+            hipLaunchKernelGGL(crc::k_crc_tiles<crc::SRC_FRAME_MAJOR>, grid, block, 0, st, d_pcm, d_desc, n, nb, base,
+                               tile_val, max_tiles);
+        else
+            hipLaunchKernelGGL(crc::k_crc_tiles<crc::SRC_WAV>, grid, block, 0, st, d_pcm, d_desc, n, nb, base, tile_val,
+                               max_tiles);
+    }
+    void join(dim3 block, hipStream_t st, const dvda_pcm_crc_desc *d_desc, uint32_t n, unsigned bits, const uint32_t *base,
+              const uint32_t *tile_val, uint32_t max_tiles) const
+    {
+        hipLaunchKernelGGL(crc::k_crc_join, dim3(n), block, 0, st, d_desc, n, bits / 8, base, tile_val, max_tiles, d_crc,
+                           d_nbytes);
+    }
+};
+
+struct LvlReport {
+    static constexpr uint32_t TILE = lvl::TILE, TILE_WORDS = lvl::REC, TILE_BLOCKS = lvl::TILE_BLOCKS;     // unit: frames
+    dvda_pcm_levels *d_levels;
+
+    bool has_out() const { return d_levels != nullptr; }
+    static bool takes(uint32_t layout, unsigned bits)
+    {
+        return (bits == 16 || bits == 20 || bits == 24) && (layout == DVDA_PCM_PLANAR || layout == DVDA_PCM_INTERLEAVED);
+    }
+    static uint64_t units(const dvda_pcm_crc_desc &d, unsigned) { return d.frames; }
+    static size_t out_words(uint32_t n) { return (size_t)n * (sizeof(dvda_pcm_levels) / sizeof(uint64_t)); }
+    static LvlReport in(uint64_t *d_out, uint32_t) { return LvlReport{(dvda_pcm_levels *)d_out}; }
+
+    void plan(hipStream_t st, const dvda_pcm_crc_desc *d_desc, uint32_t n, unsigned, uint32_t *cnt) const
+    {
+        hipLaunchKernelGGL(lvl::k_lvl_plan, dim3((n + 255) / 256), dim3(256), 0, st, d_desc, n, cnt);
+    }
+    void tiles(dim3 grid, dim3 block, hipStream_t st, const int32_t *d_pcm, uint32_t layout, const dvda_pcm_crc_desc *d_desc,
+               uint32_t n, unsigned bits, const uint32_t *base, uint32_t *rec, uint32_t max_tiles) const
+    {
+        if (layout == DVDA_PCM_PLANAR)
+            hipLaunchKernelGGL(lvl::k_lvl_tiles<true>, grid, block, 0, st, d_pcm, d_desc, n, (uint32_t)bits, base, rec,
+                               max_tiles);
+        else
+            hipLaunchKernelGGL(lvl::k_lvl_tiles<false>, grid, block, 0, st, d_pcm, d_desc, n, (uint32_t)bits, base, rec,
+                               max_tiles);
+    }
+    void join(dim3 block, hipStream_t st, const dvda_pcm_crc_desc *d_desc, uint32_t n, unsigned, const uint32_t *base,
+              const uint32_t *rec, uint32_t max_tiles) const
+    {
+        hipLaunchKernelGGL(lvl::k_lvl_join, dim3(n), block, 0, st, d_desc, n, base, rec, max_tiles, d_levels);
+    }
+};
+static_assert(sizeof(dvda_pcm_levels) % sizeof(uint64_t) == 0, "reports lie in a block of uint64 words");
+
+// ---- the driver of the flat tile list
+// tiles the list can hold for n streams of max_total units in all: every stream has at most one ragged tile
+template <class R>
+static inline uint64_t report_max_tiles(uint32_t n, uint64_t max_total)
+{
+    return max_total / R::TILE + n;
+}
+
+// workspace (uint32 words): tiles per stream [n + 1] | their exclusive scan [n + 1] | block sums of the scan | what the
+// tiles leave
+template <class R>
+static inline size_t report_workspace_words(uint32_t n, uint64_t max_total)
+{
+    return 2 * ((size_t)n + 1) + ((size_t)n + 1023) / 1024 + 2 + (size_t)report_max_tiles<R>(n, max_total) * R::TILE_WORDS;
+}
+
+// (asked of the runtime once per process)
+static bool report_have_device()
+{
+    static const bool have = [] {
+        int ndev = 0;
+        return hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
+    }();
+    return have;
+}
+
+// plan -> scan -> tiles -> join, enqueued on `stream_`.  The arguments are judged first, on any machine, then the device.
+template <class R>
+static int report_run(const R &r, const int32_t *d_pcm, uint32_t layout, unsigned bits, const dvda_pcm_crc_desc *d_desc,
+                      uint32_t n, uint64_t max_total, uint32_t *d_work, size_t work_words, void *stream_)
+{
+    if (!d_pcm || !d_desc || !d_work || !r.has_out() || !R::takes(layout, bits))
+        return DVDA_HIP_EINVAL;
+    if (work_words < report_workspace_words<R>(n, max_total))
+        return DVDA_HIP_EINVAL;
+    const uint64_t max_tiles = report_max_tiles<R>(n, max_total);
+    if (max_tiles >> 31)
+        return DVDA_HIP_ECAPACITY;
+    if (!report_have_device())
+        return DVDA_HIP_ENODEV;
+    if (n == 0)
+        return DVDA_HIP_OK;
+    hipStream_t st = (hipStream_t)stream_;
+    uint32_t *cnt = d_work;
+    uint32_t *base = cnt + n + 1;
+    uint32_t *tmp = base + n + 1;
+    uint32_t *tile_out = tmp + (n + 1023) / 1024 + 2;
+    r.plan(st, d_desc, n, bits, cnt);
+    enqueue_exscan(st, cnt, base, tmp, n, nullptr, n);
+    const dim3 grid((unsigned)(max_tiles < R::TILE_BLOCKS ? max_tiles : R::TILE_BLOCKS)), block(pcmt::THREADS);
+    r.tiles(grid, block, st, d_pcm, layout, d_desc, n, bits, base, tile_out, (uint32_t)max_tiles);
+    r.join(block, st, d_desc, n, bits, base, tile_out, (uint32_t)max_tiles);
+    HIP_TRY(hipGetLastError());
+    return DVDA_HIP_OK;
+}
+
+// The report of the first n (clamped to the batch; 0: nothing to do) streams of the context's last decode, on the
+// context's buffers: the descriptors from what dvda_mlp_hip_stream_info says and the caller's d_out_off / d_out_stride,
+// copied up, then the report, enqueued on `stream_`.  *r: where the results lie on the device; the caller copies them
+// down and waits.  Blocks for the descriptors.
+template <class R>
+static int report_of_decode(dvda_mlp_hip_ctx *c, const int32_t *d_pcm, const uint64_t *d_out_off,
+                            const uint64_t *d_out_stride, unsigned bits, uint32_t *n_io, void *stream_, R *r)
+{
+    if (!c->indexed)
+        return DVDA_HIP_ESTATE;
+    if (*n_io > c->n_streams)
+        *n_io = c->n_streams;
+    const uint32_t n = *n_io;
+    if (n == 0)
+        return DVDA_HIP_OK;
+    // frames and channels as the caller is told them: conceal mode's composed record and the presentation included
+    std::vector<dvda_mlp_stream_info> infos(n);
+    int rc = dvda_mlp_hip_stream_info(c, infos.data(), n, stream_);
+    if (rc)
+        return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<uint64_t> off(n), stride(n);
+    HIP_TRY(hipMemcpy(off.data(), d_out_off, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(stride.data(), d_out_stride, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    std::vector<dvda_pcm_crc_desc> desc(n);
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        dvda_pcm_crc_desc &d = desc[i];
+        d.off = off[i];
+        d.stride = stride[i];
+        // (an overflowed stream's region does not hold the stream)
+        d.frames = (infos[i].status & DVDA_ST_OVERFLOW) ? 0 : infos[i].pcm_frames;
+        d.channels = infos[i].channels;
+        d.reserved = 0;
+        total += R::units(d, bits);
+    }
+    if ((rc = c->d_rep_desc.grow(n)) != 0 || (rc = c->d_rep_out.grow(R::out_words(n))) != 0 ||
+        (rc = c->d_rep_work.grow(report_workspace_words<R>(n, total))) != 0)
+        return rc;
+    HIP_TRY(hipMemcpy(c->d_rep_desc, desc.data(), (size_t)n * sizeof(dvda_pcm_crc_desc), hipMemcpyHostToDevice));
+    *r = R::in(c->d_rep_out, n);
+    return report_run(*r, d_pcm, c->set.pcm_layout, bits, c->d_rep_desc, n, total, c->d_rep_work,
+                      (size_t)c->d_rep_work.cap, stream_);
+}
+
+// ---- the digest
+extern "C" size_t dvda_pcm_hip_crc32_workspace_words(uint32_t n, uint64_t max_total_bytes)
+{
+    return report_workspace_words<CrcReport>(n, max_total_bytes);
+}
+
+extern "C" int dvda_pcm_hip_crc32(const int32_t *d_pcm, uint32_t layout, unsigned bits, const dvda_pcm_crc_desc *d_desc,
+                                  uint32_t n, uint64_t max_total_bytes, uint32_t *d_crc, uint64_t *d_nbytes,
+                                  uint32_t *d_work, size_t work_words, void *stream_)
+{
+    return report_run(CrcReport{d_crc, d_nbytes}, d_pcm, layout, bits, d_desc, n, max_total_bytes, d_work, work_words,
+                      stream_);
+}
+
+extern "C" int dvda_mlp_hip_pcm_crc32(dvda_mlp_hip_ctx *c, const int32_t *d_pcm, const uint64_t *d_out_off,
+                                      const uint64_t *d_out_stride, unsigned bits, uint32_t *host_crc,
+                                      uint64_t *host_nbytes, uint32_t n, void *stream_)
+{
+    if (!c || !d_pcm || !d_out_off || !d_out_stride || !host_crc || !host_nbytes)
+        return DVDA_HIP_EINVAL;
+    CrcReport r{};
+    const int rc = report_of_decode(c, d_pcm, d_out_off, d_out_stride, bits, &n, stream_, &r);
+    if (rc || n == 0)
+        return rc;
+    hipStream_t st = (hipStream_t)stream_;
+    HIP_TRY(hipMemcpyAsync(host_crc, r.d_crc, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(host_nbytes, r.d_nbytes, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DVDA_HIP_OK;
+}
+
+extern "C" uint32_t dvda_pcm_hip_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b)
+{
+    // x has order 2^32 - 1 in the field, and 8 * len_b must not wrap: reduce the exponent first
+    const uint64_t e = ((len_b % 0xFFFFFFFFull) * 8u) % 0xFFFFFFFFull;
+    return crc::gfmul(crc_a, crc::xpow(e)) ^ crc_b;
+}
+
+// ---- the level report
+extern "C" size_t dvda_pcm_hip_levels_workspace_words(uint32_t n, uint64_t max_total_frames)
+{
+    return report_workspace_words<LvlReport>(n, max_total_frames);
+}
+
+extern "C" int dvda_pcm_hip_levels(const int32_t *d_pcm, uint32_t layout, unsigned bits, const dvda_pcm_crc_desc *d_desc,
+                                   uint32_t n, uint64_t max_total_frames, dvda_pcm_levels *d_levels, uint32_t *d_work,
+                                   size_t work_words, void *stream_)
+{
+    return report_run(LvlReport{d_levels}, d_pcm, layout, bits, d_desc, n, max_total_frames, d_work, work_words, stream_);
+}
+
+extern "C" int dvda_mlp_hip_pcm_levels(dvda_mlp_hip_ctx *c, const int32_t *d_pcm, const uint64_t *d_out_off,
+                                       const uint64_t *d_out_stride, unsigned bits, dvda_pcm_levels *host_levels, uint32_t n,
+                                       void *stream_)
+{
+    if (!c || !d_pcm || !d_out_off || !d_out_stride || !host_levels || !LvlReport::takes(c->set.pcm_layout, bits))
+        return DVDA_HIP_EINVAL;
+    LvlReport r{};
+    const int rc = report_of_decode(c, d_pcm, d_out_off, d_out_stride, bits, &n, stream_, &r);
+    if (rc || n == 0)
+        return rc;
+    hipStream_t st = (hipStream_t)stream_;
+    HIP_TRY(hipMemcpyAsync(host_levels, r.d_levels, (size_t)n * sizeof(dvda_pcm_levels), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DVDA_HIP_OK;
+}
+
+extern "C" void dvda_pcm_hip_levels_combine(const dvda_pcm_levels *a_, const dvda_pcm_levels *b_, dvda_pcm_levels *out)
+{
+    const dvda_pcm_levels a = *a_, b = *b_;         // (either may be `out`)
+    if (a.frames == 0 || b.frames == 0) {           // neutral: its zero min / max must not reach the result
+        *out = a.frames ? a : b;
+        return;
+    }
+    dvda_pcm_levels r;
+    r.frames = a.frames + b.frames;
+    r.lead_silent = a.lead_silent == a.frames ? a.frames + b.lead_silent : a.lead_silent;
+    r.trail_silent = b.trail_silent == b.frames ? b.frames + a.trail_silent : b.trail_silent;
+    for (int c = 0; c < 8; c++) {
+        r.sum[c] = (int64_t)((uint64_t)a.sum[c] + (uint64_t)b.sum[c]);
+        r.over[c] = a.over[c] + b.over[c];
+        r.min[c] = a.min[c] < b.min[c] ? a.min[c] : b.min[c];
+        r.max[c] = a.max[c] > b.max[c] ? a.max[c] : b.max[c];
+    }
+    *out = r;
+}

@@ -376,6 +376,25 @@ def crc32_combine(crc_a, crc_b, len_b):
     return int(lib().dvda_pcm_hip_crc32_combine(crc_a, crc_b, len_b))
 
 
+def _report_args(d_pcm, desc, what, max_total, work, workspace_words):
+    """What pcm_crc32 and pcm_levels hand their C entry point besides the results: the dvda_pcm_crc_desc records of `desc`
+    on d_pcm's device (the host waits for that copy), the workspace (`work`, or one allocated here from
+    workspace_words(n, max_total)) and torch's current stream.  -> (torch, n, d_desc, work, stream)"""
+    import torch
+    if not torch.cuda.is_available():
+        raise HipError("no GPU visible to torch: %s is HIP-only" % what)
+    dev = d_pcm.device
+    n = len(desc)
+    rec = np.zeros(max(n, 1), np.dtype([("off", "<u8"), ("stride", "<u8"), ("frames", "<u8"), ("channels", "<u4"),
+                                         ("reserved", "<u4")]))
+    for i, (off, stride, frames, channels) in enumerate(desc):
+        rec[i] = (off, stride, frames, channels, 0)
+    if work is None:
+        work = torch.empty(int(workspace_words(n, max_total)), dtype=torch.int32, device=dev)
+    d_desc = torch.from_numpy(rec.view(np.uint8).reshape(-1)).to(dev)
+    return torch, n, d_desc, work, torch.cuda.current_stream(dev).cuda_stream
+
+
 def pcm_crc32(d_pcm, layout, bits, desc, max_total_bytes=None, work=None):
     """dvda_pcm_hip_crc32 over torch tensors: d_pcm an int32 tensor on the device holding the streams in `layout`,
     desc a list of (off, stride, frames, channels) as dvda_pcm_crc_desc states them.  -> (crc, nbytes): device tensors
@@ -385,24 +404,12 @@ def pcm_crc32(d_pcm, layout, bits, desc, max_total_bytes=None, work=None):
     allocate keeps those on the device and calls dvda_pcm_hip_crc32 itself (tools/digest_bench.py).
     max_total_bytes: bound on the sum of the payload bytes (default: computed from desc); work: an int32 workspace
     tensor of at least pcm_crc32_workspace_words() elements (default: allocated here)."""
-    import torch
-    if not torch.cuda.is_available():
-        raise HipError("no GPU visible to torch: the PCM digest is HIP-only")
-    dev = d_pcm.device
-    n = len(desc)
-    rec = np.zeros(max(n, 1), np.dtype([("off", "<u8"), ("stride", "<u8"), ("frames", "<u8"), ("channels", "<u4"),
-                                         ("reserved", "<u4")]))
-    for i, (off, stride, frames, channels) in enumerate(desc):
-        rec[i] = (off, stride, frames, channels, 0)
     if max_total_bytes is None:
         max_total_bytes = int(sum(int(f) * int(c) * (bits // 8) for _, _, f, c in desc))
-    words = int(lib().dvda_pcm_hip_crc32_workspace_words(n, max_total_bytes))
-    if work is None:
-        work = torch.empty(words, dtype=torch.int32, device=dev)
-    d_desc = torch.from_numpy(rec.view(np.uint8).reshape(-1)).to(dev)
-    d_crc = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
-    d_nbytes = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
+    torch, n, d_desc, work, st = _report_args(d_pcm, desc, "the PCM digest", max_total_bytes, work,
+                                              lib().dvda_pcm_hip_crc32_workspace_words)
+    d_crc = torch.zeros(max(n, 1), dtype=torch.int32, device=d_pcm.device)
+    d_nbytes = torch.zeros(max(n, 1), dtype=torch.int64, device=d_pcm.device)
     _check(lib().dvda_pcm_hip_crc32(d_pcm.data_ptr(), layout, bits, d_desc.data_ptr(), n, max_total_bytes,
                                     d_crc.data_ptr(), d_nbytes.data_ptr(), work.data_ptr(), work.numel(), st),
            "dvda_pcm_hip_crc32")
@@ -430,23 +437,11 @@ def pcm_levels(d_pcm, layout, bits, desc, max_total_frames=None, work=None):
     to the device and allocates them, the result and -- when none is passed -- the workspace.
     max_total_frames: bound on the sum of the frames (default: computed from desc); work: an int32 workspace tensor of at
     least pcm_levels_workspace_words() elements (default: allocated here)."""
-    import torch
-    if not torch.cuda.is_available():
-        raise HipError("no GPU visible to torch: the level report is HIP-only")
-    dev = d_pcm.device
-    n = len(desc)
-    rec = np.zeros(max(n, 1), np.dtype([("off", "<u8"), ("stride", "<u8"), ("frames", "<u8"), ("channels", "<u4"),
-                                         ("reserved", "<u4")]))
-    for i, (off, stride, frames, channels) in enumerate(desc):
-        rec[i] = (off, stride, frames, channels, 0)
     if max_total_frames is None:
         max_total_frames = int(sum(int(f) for _, _, f, c in desc if 1 <= int(c) <= 8))
-    words = int(lib().dvda_pcm_hip_levels_workspace_words(n, max_total_frames))
-    if work is None:
-        work = torch.empty(words, dtype=torch.int32, device=dev)
-    d_desc = torch.from_numpy(rec.view(np.uint8).reshape(-1)).to(dev)
-    d_out = torch.zeros((max(n, 1), ctypes.sizeof(Levels)), dtype=torch.uint8, device=dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
+    torch, n, d_desc, work, st = _report_args(d_pcm, desc, "the level report", max_total_frames, work,
+                                              lib().dvda_pcm_hip_levels_workspace_words)
+    d_out = torch.zeros((max(n, 1), ctypes.sizeof(Levels)), dtype=torch.uint8, device=d_pcm.device)
     _check(lib().dvda_pcm_hip_levels(d_pcm.data_ptr(), layout, bits, d_desc.data_ptr(), n, max_total_frames,
                                      d_out.data_ptr(), work.data_ptr(), work.numel(), st), "dvda_pcm_hip_levels")
     return d_out[:n]
