@@ -97,7 +97,8 @@ DVDA_Track_Reader *dvda_hip_open_track_reader_on(const DVDA_Track *track, int de
  * dvda_hip_reader_wav_next() deliver k-channel frames.  One-substream MLP tracks and raw-PCM tracks are read as always.
  * 0 (default): the full decode. */
 void dvda_hip_set_presentation(int presentation);
-/* dvda_hip_open_track_reader_on with the presentation named too; the thread's defaults stay as they are */
+/* dvda_hip_open_track_reader_on with the presentation named too; the thread's defaults stay as they are (conceal mode
+ * is the thread's, or DVDA_CONCEAL's while the thread has not chosen: dvda_hip_set_conceal below) */
 DVDA_Track_Reader *dvda_hip_open_track_reader_with(const DVDA_Track *track, int device, int wav_output, int presentation);
 /* on != 0: track readers opened afterwards (per calling thread, read when the reader is opened, like
  * dvda_hip_set_wav_output) digest every piece of the track where it lies on the device, before any copy to the host:
@@ -126,6 +127,40 @@ void dvda_hip_set_levels(int on);
  * is a WAV-payload-only reader (dvda_hip_reader_wav_only), or the track's bit depth is none of 16 / 20 / 24.  `out` may
  * be NULL. */
 int dvda_hip_reader_levels(const DVDA_Track_Reader *reader, struct dvda_pcm_levels *out);
+/* on != 0: MLP track readers opened afterwards (per calling thread, read when the reader is opened, like
+ * dvda_hip_set_wav_output) conceal a damaged track instead of refusing it: the track comes out as
+ *     kept PCM ++ silence ++ PCM of a fresh decoder from the next usable major sync ++ ...
+ * exactly as conceal mode of the batch tier composes the track's whole MLP stream (the rule is in dvda_mlp_hip.h,
+ * dvda_mlp_hip_set_conceal).  The stream is the bytes the demux yields for the track's sectors, from the first
+ * major-sync pattern to the end-of-track rule; a sector the demux refuses (zero-filled, a bad pack header) contributes
+ * no bytes, and the codec probe skips a malformed sector inside the track.  dvda_read(), both payload calls, the digest
+ * and the level report see the composed track -- the silence is exact zeros.  A clean track reads exactly as without the
+ * option.  While this call has not been made on the thread, DVDA_CONCEAL=1 in the environment turns the option on: a
+ * program written against the reference's header -- its dvda2wav, linked against this library -- extracts a damaged
+ * disc that way.
+ * A long track is read in windows of bounded memory as without the option: each window is concealed on its own and the
+ * reader stitches what lies between two windows (history, silence, spans), so the track comes out as it would from one
+ * batch.  One stated exception: a hole of 65 536 frames or more takes its 65 536-frame wrap count from the mean bytes per
+ * frame of the track so far, not of the whole stream.
+ * Scope: together with the 2-channel presentation (dvda_hip_set_presentation(1)) the batch tier
+ * refuses conceal mode, and an MLP track reader does not open.  Raw-PCM tracks are read as always: a lost sector still
+ * shortens them.  Off (default): a reader launches, allocates and fails exactly as without this call.
+ * Lost sectors and alignment: a sector carries 2 021 MLP bytes and access units start at even offsets of the stream, so an
+ * odd number of sectors lost in a row leaves every unit behind them at an odd offset, where the index does not look: the
+ * rest of the track is then one TRAILING span.  An even number (and any damage inside sectors) resumes at the next usable
+ * major sync. */
+struct dvda_mlp_conceal_span;
+void dvda_hip_set_conceal(int on);
+/* dvda_hip_open_track_reader_with with conceal mode named too: 1 on, 0 off, < 0 as the thread (or DVDA_CONCEAL) has it;
+ * the thread's defaults stay as they are */
+DVDA_Track_Reader *dvda_hip_open_track_reader_concealing(const DVDA_Track *track, int device, int wav_output, int presentation,
+                                                         int conceal);
+/* What was concealed of the track: up to cap spans (dvda_mlp_conceal_span of dvda_mlp_hip.h) into spans, *n = how many
+ * there are (none for a clean track); in track terms -- PCM frames of the track, byte offsets from the first byte of the
+ * track's stream.  1: final for the track (from open on for a whole-track reader), 0: not yet final (a windowed
+ * reader before its last window has been produced: the spans so far), -1: the reader was opened without conceal mode.  dvda_hip_reader_status() carries
+ * DVDA_ST_CONCEALED once a span exists.  spans may be NULL with cap 0 (the count call). */
+int dvda_hip_reader_concealed(const DVDA_Track_Reader *reader, struct dvda_mlp_conceal_span *spans, unsigned cap, unsigned *n);
 /* != 0: the reader holds the WAV payload only (opened with wav_output): dvda_read() on it returns 0 frames -- NOT
  * because the track is empty; take the payload with dvda_hip_reader_wav_payload() */
 int dvda_hip_reader_wav_only(const DVDA_Track_Reader *reader);

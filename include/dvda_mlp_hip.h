@@ -216,6 +216,24 @@ typedef struct dvda_mlp_conceal_span {
  * spans, *n = how many there are (0 for a clean stream). */
 int dvda_mlp_hip_conceal_spans(dvda_mlp_hip_ctx *ctx, uint32_t stream, dvda_mlp_conceal_span *spans, uint32_t cap,
                                uint32_t *n, void *stream_);
+/* The edges of `stream` after the last dvda_mlp_hip_decode in conceal mode: what a caller that feeds a long stream piece by
+ * piece needs to join two pieces (blocks on `stream_`).  Valid for clean streams too: kept_begin 0, kept_end =
+ * bytes_consumed, fir = that of the last live segment.  DVDA_HIP_ESTATE when the last decode was not in conceal mode.  A
+ * clean stream costs a few small copies and no launch; the history behind each range of a damaged stream was gathered in
+ * the round that decoded the range (csrc/mlp_conceal.h, k_conceal_edge_fir: one small launch, one copy of 96 words per
+ * range to the host and one more blocking wait per round -- for batches with damage only). */
+typedef struct dvda_mlp_conceal_edges {
+    uint64_t kept_begin, kept_end; /* offsets from the stream's first byte: the first kept unit, and behind the last kept unit
+                                      (kept_begin == kept_end: nothing kept) */
+    uint32_t t_first, t_end;       /* 16-bit input timing of the first kept unit; behind the last one (t_first of the last
+                                      range + its PCM frames, mod 65536) */
+    uint64_t kept_bytes, kept_frames; /* sums over the kept ranges (for the caller's running mean) */
+    uint32_t ends_kept;            /* 1: the last kept range runs to the stream's end (no TRAILING span) */
+    uint32_t reserved;
+    int32_t  fir[2 * 48];          /* FIR history behind the last kept unit, layout of dvda_mlp_hip_segment_fir (entries of
+                                      channel slots a substream does not have are undefined there and here) */
+} dvda_mlp_conceal_edges;
+int dvda_mlp_hip_conceal_edges(dvda_mlp_hip_ctx *ctx, uint32_t stream, dvda_mlp_conceal_edges *out, void *stream_);
 
 /* Presentation (default DVDA_PRESENT_FULL; with it every output, status bit, launch and allocation is as without this
  * call, also after DVDA_PRESENT_SUBSTREAM0 was set and taken back).

@@ -19,7 +19,9 @@
  * as one batch (open_mlp, open_pcm), a long track window by window (win_produce, win_produce_pcm) -- are sequences of
  * them and differ in who owns the buffers and how long.
  *
- * Streams the reference would abort on (assert) make dvda_open_track_reader return NULL here.
+ * Streams the reference would abort on (assert) make dvda_open_track_reader return NULL here -- unless the reader is
+ * opened in conceal mode (dvda_hip_set_conceal): the decode then composes kept PCM and silence (conceal mode of the batch
+ * tier), and the windowed reader stitches what lies between two windows (win_conceal_stitch).
  */
 #include <hip/hip_runtime_api.h>
 #include <math.h>
@@ -44,13 +46,33 @@ struct reader_opts {
     int present;                /* 1: MLP readers decode the presentation substream 0 carries (DVDA_PRESENT_SUBSTREAM0) */
     int digest;                 /* 1: every piece of PCM is digested where it lies on the device (dvda_hip_reader_crc32) */
     int levels;                 /* 1: ... and its level report is made there (dvda_hip_reader_levels) */
+    int conceal;                /* 1: a damaged MLP track is concealed, not refused (dvda_hip_set_conceal) */
 };
 static _Thread_local struct reader_opts t_opts;
+static _Thread_local int t_conceal_set;     /* dvda_hip_set_conceal() was called on this thread: DVDA_CONCEAL no longer counts */
 void dvda_hip_set_device(int device) { t_opts.device = device; }
 void dvda_hip_set_wav_output(int on) { t_opts.wav_output = on != 0; }
 void dvda_hip_set_presentation(int presentation) { t_opts.present = presentation == 1; }
 void dvda_hip_set_digest(int on) { t_opts.digest = on != 0; }
 void dvda_hip_set_levels(int on) { t_opts.levels = on != 0; }
+void dvda_hip_set_conceal(int on)
+{
+    t_opts.conceal = on != 0;
+    t_conceal_set = 1;
+}
+
+/* the calling thread's options as a reader opened now gets them: while the thread has not said what it wants of conceal
+ * mode, DVDA_CONCEAL=1 in the environment turns it on (a program written against the reference's header has no call
+ * for it) */
+static struct reader_opts opts_now(void)
+{
+    struct reader_opts o = t_opts;
+    if (!t_conceal_set) {
+        const char *e = getenv("DVDA_CONCEAL");
+        o.conceal = e && e[0] == '1' && e[1] == 0;
+    }
+    return o;
+}
 
 struct track_windows;               /* a long track read window by window (below) */
 
@@ -79,6 +101,9 @@ struct DVDA_Track_Reader_s {
                                   themselves (DVDA_PCM_WAV24 / WAV16); there is no int32 PCM for dvda_read() */
     uint64_t wav_bytes;
     struct pcm_reports rep;    /* a whole-track reader: the track's */
+    int conceal;               /* opened in conceal mode (dvda_hip_set_conceal) */
+    dvda_mlp_conceal_span *spans;      /* ... and what was concealed, in track terms (dvda_hip_reader_concealed) */
+    unsigned n_spans;
 };
 
 /* fills the reader's record from the index's stream record; 0 = a channel count the assignment does not have.  Under
@@ -487,7 +512,13 @@ static int index_stream(struct track_bufs *b, const struct reader_opts *o, uint6
                 return 0;
         }
         /* (a context kept from the thread's last reader may have served the other presentation) */
+        /* (... or conceal mode, which it does not share a context with: taken off first, put on last) */
+        if (!o->conceal && dvda_mlp_hip_set_conceal(b->ctx, 0) != DVDA_HIP_OK)
+            return 0;
         if (dvda_mlp_hip_set_presentation(b->ctx, o->present ? DVDA_PRESENT_SUBSTREAM0 : DVDA_PRESENT_FULL) != DVDA_HIP_OK)
+            return 0;
+        /* (conceal mode of the presentation: the batch tier has none and says DVDA_HIP_EINVAL -- the reader does not open) */
+        if (o->conceal && dvda_mlp_hip_set_conceal(b->ctx, 1) != DVDA_HIP_OK)
             return 0;
         if (dvda_mlp_hip_index(b->ctx, b->d_stream, padded, b->d_meta + 0, b->d_meta + 1, 1, NULL) != DVDA_HIP_OK)
             return 0;
@@ -583,6 +614,7 @@ static void reader_free(DVDA_Track_Reader *r)
     free(r->pcm);
     (void)hipFree(r->d_wav);
     free(r->wav);
+    free(r->spans);
     if (r->d_pcm)
         (void)hipFree(r->d_pcm);
     free(r);
@@ -634,11 +666,21 @@ static DVDA_Track_Reader *open_mlp(struct aob_set *aobs, const DVDA_Track *k, co
     if (!decode_stream(&b, len, NULL, &wav_bits, &info, &stride))
         goto out;
     t_line(&t_mark, "decode");
-    if (info.status & ~(uint32_t)DVDA_ST_BENIGN)
-        goto out;                            /* the reference assert()s on such a stream */
+    /* the reference assert()s on a damaged stream; conceal mode hands it out composed (DVDA_ST_CONCEALED) */
+    if (info.status & ~(uint32_t)(DVDA_ST_BENIGN | (o->conceal ? DVDA_ST_CONCEALED : 0u)))
+        goto out;
     r = calloc(1, sizeof(*r));
     if (!r)
         goto out;
+    if (info.status & DVDA_ST_CONCEALED) {
+        /* the stream is the track's: the batch tier's spans are in track terms as they are */
+        uint32_t n = 0;
+        if (dvda_mlp_hip_conceal_spans(b.ctx, 0, NULL, 0, &n, NULL) != DVDA_HIP_OK ||
+            (r->spans = malloc((n ? n : 1) * sizeof(*r->spans))) == NULL ||
+            dvda_mlp_hip_conceal_spans(b.ctx, 0, r->spans, n, &n, NULL) != DVDA_HIP_OK)
+            goto fail;
+        r->n_spans = n;
+    }
     r->codec = DVDA_MLP;
     r->status = info.status;
     r->frames = info.pcm_frames;
@@ -732,6 +774,27 @@ struct track_windows {
     int32_t fir[2 * 48];
     int have_fir;
     struct track_bufs b;        /* kept for the whole track, and in the thread's cache for the next one */
+    /* conceal mode (opts.conceal): every window is a conceal-mode stream of its own; what lies between two of them is
+       stitched here (win_conceal_stitch).  Private to the producing thread but for `spans`. */
+    struct {
+        int have_edge;          /* a window so far kept something: t_end is the input timing behind its last kept unit */
+        uint32_t t_end, cause;  /* ... and the causes of the damage since */
+        uint64_t B;             /* stream bytes since: the tail behind kept_end, windows that kept nothing, the bytes in
+                                   front of the next kept_begin */
+        uint64_t pend_off;      /* track offset where those bytes begin */
+        uint64_t kept_bytes, kept_frames;       /* over the track so far: the running mean of the gap rule */
+        uint64_t base;          /* track offset of d_stream[0] */
+        uint64_t frames;        /* PCM frames decided so far, silence included */
+        uint64_t sil_left;      /* frames of silence still to hand out in front of the held window */
+        int held, held_final;   /* b.d_pcm holds a decoded window that waits behind that silence */
+        dvda_mlp_stream_info held_info;
+        uint64_t held_stride;
+        int32_t *d_zero;        /* device: one silent window of bounded size */
+        dvda_mlp_conceal_span *p_spans;         /* spans made since the last win_commit() */
+        unsigned p_n, p_cap;
+    } cw;
+    dvda_mlp_conceal_span *spans;       /* published under `mu` (win_commit) */
+    unsigned n_spans, cap_spans;
     /* what the stream is (first window) */
     dvda_mlp_stream_info info;
     unsigned status;            /* (with frames_total and `finished`: published under `mu`, win_commit()) */
@@ -849,6 +912,9 @@ static void windows_free(struct track_windows *w)
     }
     free(w->whole);
     free(w->pack_tmp);
+    free(w->spans);
+    free(w->cw.p_spans);
+    (void)hipFree(w->cw.d_zero);
     aob_close_all(&w->aobs);
     pthread_mutex_destroy(&w->mu);
     pthread_cond_destroy(&w->cv);
@@ -925,6 +991,196 @@ static int win_last_cut(struct track_windows *w, uint32_t n_seg, uint64_t restar
     return 0;
 }
 
+/* ---- conceal mode across windows.  The rule is the batch tier's, stated for a track's whole stream (dvda_mlp_hip.h);
+ * a window [0, cut) is decoded as a conceal-mode stream of its own, and what the batch tier cannot see is stitched here:
+ * a window's TRAILING span, whole windows that kept nothing and the next window's LEADING span are ONE span, whose silence
+ * -- the input-timing gap between the kept units on both sides, wrapped by the running mean of bytes per frame -- goes
+ * out in front of the next kept window as silent windows of bounded size. */
+#define SILENT_WINDOW_FRAMES 8192u
+
+/* conceal_gap of csrc/mlp_conceal_run.h: g + 65536 w frames, w >= 0 bringing B bytes per frame closest to m (no mean: g) */
+static uint64_t gap_frames(uint64_t B, uint32_t g, double m)
+{
+    if (!(m > 0.0))
+        return g;
+    double w0 = floor(((double)B / m - (double)g) / 65536.0);
+    if (w0 < 0.0)
+        w0 = 0.0;
+    uint64_t best = 0;
+    double bd = 0.0;
+    for (int k = 0; k < 2; k++) {
+        const uint64_t G = (uint64_t)g + 65536ull * ((uint64_t)w0 + (uint64_t)k);
+        const double d = G ? fabs((double)B / (double)G - m) : INFINITY;
+        if (k == 0 || d < bd) {
+            best = G;
+            bd = d;
+        }
+    }
+    return best;
+}
+
+static int cw_span(struct track_windows *w, uint64_t first, uint64_t frames, uint64_t off, uint64_t end, uint32_t cause,
+                   uint32_t flags)
+{
+    if (w->cw.p_n == w->cw.p_cap) {
+        const unsigned cap = w->cw.p_cap ? 2 * w->cw.p_cap : 16;
+        dvda_mlp_conceal_span *g = realloc(w->cw.p_spans, cap * sizeof(*g));
+        if (!g)
+            return 0;
+        w->cw.p_spans = g;
+        w->cw.p_cap = cap;
+    }
+    const dvda_mlp_conceal_span s = {first, frames, off, end, cause ? cause : DVDA_ST_NO_SYNC, flags};
+    w->cw.p_spans[w->cw.p_n++] = s;
+    w->p_status |= DVDA_ST_CONCEALED;
+    return 1;
+}
+
+/* `bytes` of the stream in front of d_stream[0 + ...] hold nothing to keep: they join the pending span */
+static void cw_drop(struct track_windows *w, uint64_t bytes, uint32_t cause)
+{
+    w->cw.B += bytes;
+    w->cw.cause |= cause;
+    w->cw.base += bytes;
+}
+
+/* the track ends: what is pending is its TRAILING span (LEADING too when nothing was ever kept) */
+static int cw_finish(struct track_windows *w)
+{
+    if (w->cw.B == 0 && w->cw.have_edge)
+        return 1;
+    if (w->cw.base == 0)
+        return 1;                                /* (an empty track) */
+    return cw_span(w, w->cw.frames, 0, w->cw.pend_off, w->cw.base, w->cw.cause,
+                   DVDA_CONCEAL_TRAILING | (w->cw.have_edge ? 0u : DVDA_CONCEAL_LEADING));
+}
+
+/* The window [0, cut) has been decoded in conceal mode: its spans and edges -> the track's spans, the silence in front of
+ * it (*gap frames) and the history the next window starts with.  1 = ok. */
+static int win_conceal_stitch(struct track_windows *w, uint64_t cut, const dvda_mlp_stream_info *info, int final, uint64_t *gap)
+{
+    struct track_bufs *b = &w->b;
+    dvda_mlp_conceal_edges e;
+    dvda_mlp_conceal_span *sp = NULL;
+    uint32_t n = 0, lead = 0, trail = 0, all = 0;
+    int ok = 0;
+    *gap = 0;
+    if (dvda_mlp_hip_conceal_edges(b->ctx, 0, &e, NULL) != DVDA_HIP_OK ||
+        dvda_mlp_hip_conceal_spans(b->ctx, 0, NULL, 0, &n, NULL) != DVDA_HIP_OK ||
+        (sp = malloc((n ? n : 1) * sizeof(*sp))) == NULL ||
+        dvda_mlp_hip_conceal_spans(b->ctx, 0, sp, n, &n, NULL) != DVDA_HIP_OK)
+        goto out;
+    for (uint32_t i = 0; i < n; i++) {
+        all |= sp[i].cause;
+        if (sp[i].flags & DVDA_CONCEAL_LEADING)
+            lead |= sp[i].cause;
+        if (sp[i].flags & DVDA_CONCEAL_TRAILING)
+            trail |= sp[i].cause;
+    }
+    const int kept = e.kept_end > e.kept_begin;
+    if (!kept) {
+        cw_drop(w, cut, all);
+    } else {
+        w->cw.B += e.kept_begin;
+        w->cw.cause |= lead;
+        if (w->cw.have_edge && w->cw.B > 0) {
+            const uint64_t kb = w->cw.kept_bytes + e.kept_bytes, kf = w->cw.kept_frames + e.kept_frames;
+            *gap = gap_frames(w->cw.B, (e.t_first - w->cw.t_end) & 0xFFFFu, kb && kf ? (double)kb / (double)kf : 0.0);
+            if (!cw_span(w, w->cw.frames, *gap, w->cw.pend_off, w->cw.base + e.kept_begin, w->cw.cause, 0))
+                goto out;
+        } else if (!w->cw.have_edge && w->cw.base + e.kept_begin > 0) {
+            if (!cw_span(w, 0, 0, 0, w->cw.base + e.kept_begin, w->cw.cause, DVDA_CONCEAL_LEADING))
+                goto out;
+        }
+        for (uint32_t i = 0; i < n; i++)
+            if (!(sp[i].flags & (DVDA_CONCEAL_LEADING | DVDA_CONCEAL_TRAILING)) &&
+                !cw_span(w, w->cw.frames + *gap + sp[i].first_frame, sp[i].frames, w->cw.base + sp[i].byte_off,
+                         w->cw.base + sp[i].byte_end, sp[i].cause, sp[i].flags))
+                goto out;
+        w->cw.frames += *gap + info->pcm_frames;
+        w->cw.have_edge = 1;
+        w->cw.t_end = e.t_end;
+        w->cw.kept_bytes += e.kept_bytes;
+        w->cw.kept_frames += e.kept_frames;
+        w->cw.B = e.ends_kept ? 0 : cut - e.kept_end;
+        w->cw.cause = e.ends_kept ? 0 : trail;
+        w->cw.pend_off = w->cw.base + e.kept_end;
+        w->cw.base += cut;
+    }
+    /* the next window: the history behind a range that ends kept; behind damage a fresh decoder -- an explicit zero
+       history (with none at all a first segment that continues the history would be DVDA_ST_ENVELOPE) */
+    if (!final) {
+        if (kept && e.ends_kept)
+            memcpy(w->fir, e.fir, sizeof(w->fir));
+        else
+            memset(w->fir, 0, sizeof(w->fir));
+        w->have_fir = 1;
+    }
+    ok = 1;
+out:
+    free(sp);
+    return ok;
+}
+
+/* the decoded window in b->d_pcm -> its reports and the pinned slot */
+static int win_deliver(struct track_windows *w, struct win_slot *out, const dvda_mlp_stream_info *info, uint64_t stride)
+{
+    struct track_bufs *b = &w->b;
+    if (!piece_reports(&w->rep, &out->rep, w->wav_bits != 0, b->d_pcm, layout_of(w->wav_bits), bits_of(info->group0_bps),
+                       stride, info->pcm_frames, info->channels))
+        return 0;
+    const size_t bytes = (size_t)info->pcm_frames * info->channels * (w->wav_bits ? (unsigned)w->wav_bits / 8 : 4);
+    if (!slot_reserve(b, out, bytes) ||
+        (bytes && hipMemcpy(out->host, b->d_pcm, bytes, hipMemcpyDeviceToHost) != hipSuccess))
+        return 0;
+    out->frames = info->pcm_frames;
+    w->p_frames += info->pcm_frames;
+    win_dev_sample(w);
+    return 1;
+}
+
+/* one silent window of at most SILENT_WINDOW_FRAMES of the silence that is left: zeros on the device, reports and copy
+   as for any other window */
+static int win_silence(struct track_windows *w, struct win_slot *out)
+{
+    dvda_mlp_stream_info info = w->cw.held_info;
+    const uint64_t n = w->cw.sil_left < SILENT_WINDOW_FRAMES ? w->cw.sil_left : SILENT_WINDOW_FRAMES;
+    const size_t cap = (size_t)SILENT_WINDOW_FRAMES * info.channels * sizeof(int32_t) + 64;
+    if (!w->cw.d_zero && !dev_alloc((void **)&w->cw.d_zero, cap))
+        return 0;
+    if (hipMemsetAsync(w->cw.d_zero, 0, cap, NULL) != hipSuccess)
+        return 0;
+    info.pcm_frames = n;
+    int32_t *const keep = w->b.d_pcm;
+    w->b.d_pcm = w->cw.d_zero;                   /* (win_deliver reads the set's PCM buffer) */
+    const int ok = win_deliver(w, out, &info, SILENT_WINDOW_FRAMES);
+    w->b.d_pcm = keep;
+    w->cw.sil_left -= n;
+    return ok;
+}
+
+/* stream bytes [from, from + keep) of d_stream wait on the host for the next window (conceal mode sizes the buffer with
+   little to spare: what a reader holds under damage is measured against a clean track's) */
+static int win_carry(struct track_windows *w, uint64_t from, uint64_t keep)
+{
+    struct track_bufs *b = &w->b;
+    if (keep > b->carry_cap) {
+        free(b->carry);
+        b->host_now -= b->carry_cap;
+        b->carry_cap = keep + (w->opts.conceal ? 0 : keep / 2) + 4096;
+        b->carry = malloc(b->carry_cap);
+        if (!b->carry) {
+            b->carry_cap = 0;
+            return 0;
+        }
+        bufs_host_add(b, b->carry_cap);
+    }
+    if (keep && hipMemcpy(b->carry, b->d_stream + from, keep, hipMemcpyDeviceToHost) != hipSuccess)
+        return 0;
+    w->carry_len = keep;
+    return 1;
+}
+
 /* One window into `out`: 1 = out holds frames (possibly none), 0 = failure.  Leaves "this was the track's last window",
  * the window's status bits and its frame count in w->p_*: the caller publishes them (win_commit, under w->mu once a
  * consumer exists).  Runs in the opener's thread for the first window, in the producer thread afterwards. */
@@ -937,6 +1193,18 @@ static int win_produce(struct track_windows *w, struct win_slot *out)
     out->frames = 0;
     out->stride = 0;
     memset(&out->rep, 0, sizeof(out->rep));
+    const int conceal = w->opts.conceal;
+    w->p_final = 0;
+    /* ---- conceal mode: silence that is still owed, then the decoded window that waits behind it */
+    if (w->cw.sil_left)
+        return win_silence(w, out);
+    if (w->cw.held) {
+        w->cw.held = 0;
+        if (!win_deliver(w, out, &w->cw.held_info, w->cw.held_stride))
+            return 0;
+        w->p_final = w->cw.held_final;
+        return 1;
+    }
     /* ---- sectors -> device -> MLP bytes, and where this window's new bytes begin and end: the end-of-track rule on
        the window that holds the track's last sector, with its look-ahead */
     for (unsigned extra = 8;; extra *= 4) {
@@ -971,10 +1239,13 @@ static int win_produce(struct track_windows *w, struct win_slot *out)
     w->started = 1;
     if (len == 0) {
         w->p_final = final;
+        if (conceal && final && !cw_finish(w))
+            return 0;
         return final;                        /* an empty track does not open */
     }
     uint32_t n_seg = 0, cut_seg = 0;
     uint64_t cut = len;
+    int forced = 0;
     if (!index_stream(b, &w->opts, len, &n_seg))
         return 0;
     if (!final) {
@@ -984,29 +1255,35 @@ static int win_produce(struct track_windows *w, struct win_slot *out)
         if (!have_cut) {
             /* no segment starts inside this window: all of it waits for the next one */
             cut = 0;
+            /* conceal mode, bounded memory under damage: more than a window's payload waiting and still no cut --
+               [0, len) is decoded as it is; if it ends kept (one long clean segment) it waits as ever, else what is kept
+               goes out and the rest joins the pending span: nothing is carried.  (What waits is then never more than a
+               window's payload: what the reader holds stays within one window of a clean track's.) */
+            forced = conceal && len > (uint64_t)w->window * 2021u;
         }
-        /* what follows the cut is kept (host copy: the device buffers are the next window's) */
-        const uint64_t keep = len - cut;
-        if (keep > b->carry_cap) {
-            free(b->carry);
-            b->host_now -= b->carry_cap;
-            b->carry_cap = keep + keep / 2 + 4096;
-            b->carry = malloc(b->carry_cap);
-            if (!b->carry) {
-                b->carry_cap = 0;
-                return 0;
-            }
-            bufs_host_add(b, b->carry_cap);
-        }
-        if (keep && hipMemcpy(b->carry, b->d_stream + cut, keep, hipMemcpyDeviceToHost) != hipSuccess)
+        /* what follows the cut is kept (host copy: the device buffers are the next window's); a window that is decoded
+           whole keeps its bytes only if it turns out to end kept (below) */
+        if (forced)
+            w->carry_len = 0;
+        else if (!win_carry(w, cut, len - cut))
             return 0;
-        w->carry_len = keep;
-        if (cut == 0)
+        if (cut == 0 && !forced)
             return 1;                        /* nothing to decode yet (out->frames == 0) */
-        if (!index_stream(b, &w->opts, cut, &n_seg))     /* the index of what is decoded now: whole segments */
+        if (forced)
+            cut = len;                       /* (the index of [0, len) is the one just made) */
+        else if (!index_stream(b, &w->opts, cut, &n_seg))     /* the index of what is decoded now: whole segments */
             return 0;
     } else {
         w->carry_len = 0;
+    }
+    if (conceal && n_seg == 0 && (final || forced)) {
+        /* not one major sync in these bytes: nothing to decode, nothing to keep */
+        cw_drop(w, cut, DVDA_ST_NO_SYNC);
+        w->carry_len = 0;
+        memset(w->fir, 0, sizeof(w->fir));
+        w->have_fir = 1;
+        w->p_final = final;
+        return !final || cw_finish(w);
     }
     /* ---- decode [0, cut) from the history the window before left (the payload or int32 frames: the bit depth is in
        the index's stream record, known before anything is decoded) */
@@ -1014,10 +1291,37 @@ static int win_produce(struct track_windows *w, struct win_slot *out)
     if (!decode_stream(b, cut, w->have_fir ? w->fir : NULL, &w->wav_bits, &info, &stride))
         return 0;
     w->p_status |= info.status;
-    if (info.status & ~(uint32_t)DVDA_ST_BENIGN)
+    if (info.status & ~(uint32_t)(DVDA_ST_BENIGN | (conceal ? DVDA_ST_CONCEALED : 0u)))
         return 0;                            /* the reference assert()s on such a stream */
     if (!w->info.channels)
         w->info = info;
+    if (conceal) {
+        /* ---- the window's spans and edges join the track's; the history comes from the edges */
+        uint64_t gap = 0;
+        if (forced) {
+            dvda_mlp_conceal_edges e;
+            if (dvda_mlp_hip_conceal_edges(b->ctx, 0, &e, NULL) != DVDA_HIP_OK)
+                return 0;
+            if (e.ends_kept)
+                return win_carry(w, 0, len); /* a long clean segment: it waits for its end as ever */
+        }
+        if (!win_conceal_stitch(w, cut, &info, final, &gap))
+            return 0;
+        if (final && !cw_finish(w))
+            return 0;
+        if (gap) {
+            w->cw.sil_left = gap;
+            w->cw.held = 1;
+            w->cw.held_final = final;
+            w->cw.held_info = info;
+            w->cw.held_stride = stride;
+            return win_silence(w, out);
+        }
+        if (!win_deliver(w, out, &info, stride))
+            return 0;
+        w->p_final = final;
+        return 1;
+    }
     /* ---- the history at the cut, for the next window */
     if (!final) {
         uint32_t last_seg = 0;
@@ -1103,6 +1407,23 @@ static void win_commit(struct track_windows *w)
     w->status |= w->p_status;
     w->frames_total += w->p_frames;
     w->p_frames = 0;
+    if (w->cw.p_n) {
+        if (w->n_spans + w->cw.p_n > w->cap_spans) {
+            const unsigned cap = 2 * (w->n_spans + w->cw.p_n);
+            dvda_mlp_conceal_span *g = realloc(w->spans, cap * sizeof(*g));
+            if (g) {
+                w->spans = g;
+                w->cap_spans = cap;
+            } else {
+                w->failed = 1;
+            }
+        }
+        if (w->n_spans + w->cw.p_n <= w->cap_spans) {
+            memcpy(w->spans + w->n_spans, w->cw.p_spans, w->cw.p_n * sizeof(*w->spans));
+            w->n_spans += w->cw.p_n;
+        }
+        w->cw.p_n = 0;
+    }
     if (w->p_final)
         w->finished = 1;
 }
@@ -1355,6 +1676,8 @@ static DVDA_Track_Reader *open_reader(const DVDA_Track *k, const struct reader_o
         if (aob_read(&aobs, s, 1, sec) != 1)
             break;
         const int rc = first_audio_packet(sec, &codec, &pad2, &body, &body_len);
+        if (rc < 0 && o->conceal && s < k->s.last)
+            continue;                            /* conceal mode: a malformed sector inside the track is not the end of it */
         if (rc < 0)
             break;
         if (rc == 0)
@@ -1365,6 +1688,8 @@ static DVDA_Track_Reader *open_reader(const DVDA_Track *k, const struct reader_o
             r = windowed ? open_pcm_windowed(k, body, o) : open_pcm(&aobs, k, body, o);
         break;
     }
+    if (r)
+        r->conceal = o->conceal;                /* (a raw-PCM track has nothing to conceal: no spans) */
 out:
     aob_close_all(&aobs);
     return r;
@@ -1373,17 +1698,30 @@ out:
 /* the calling thread's options, as they are now */
 DVDA_Track_Reader *dvda_open_track_reader(const DVDA_Track *k)
 {
-    const struct reader_opts o = t_opts;
+    const struct reader_opts o = opts_now();
     return open_reader(k, &o);
 }
 
 /* the options of THIS reader: the calling thread's defaults stay as they are, whatever happens */
 DVDA_Track_Reader *dvda_hip_open_track_reader_with(const DVDA_Track *k, int device, int wav_output, int presentation)
 {
-    struct reader_opts o = t_opts;
+    struct reader_opts o = opts_now();
     o.device = device;
     o.wav_output = wav_output != 0;
     o.present = presentation == 1;
+    return open_reader(k, &o);
+}
+
+/* ... and conceal mode named too (< 0: as the thread, or the environment, has it) */
+DVDA_Track_Reader *dvda_hip_open_track_reader_concealing(const DVDA_Track *k, int device, int wav_output, int presentation,
+                                                         int conceal)
+{
+    struct reader_opts o = opts_now();
+    o.device = device;
+    o.wav_output = wav_output != 0;
+    o.present = presentation == 1;
+    if (conceal >= 0)
+        o.conceal = conceal != 0;
     return open_reader(k, &o);
 }
 
@@ -1466,6 +1804,30 @@ int dvda_hip_reader_levels(const DVDA_Track_Reader *r, dvda_pcm_levels *out)
     if (out)
         *out = rep.levels;
     return rc;
+}
+/* what was concealed of the track: 1 = final, 0 = not yet (a windowed reader that still produces), -1 = opened without
+ * conceal mode */
+int dvda_hip_reader_concealed(const DVDA_Track_Reader *r, struct dvda_mlp_conceal_span *spans, unsigned cap, unsigned *n)
+{
+    if (!r || !r->conceal)
+        return -1;
+    if (r->win) {
+        /* a windowed reader: the spans of the windows produced so far; final once the last one has been */
+        struct track_windows *w = r->win;
+        pthread_mutex_lock(&w->mu);
+        if (n)
+            *n = w->n_spans;
+        for (unsigned i = 0; spans && i < cap && i < w->n_spans; i++)
+            spans[i] = w->spans[i];
+        const int rc = w->failed ? -1 : w->finished ? 1 : 0;
+        pthread_mutex_unlock(&w->mu);
+        return rc;
+    }
+    if (n)
+        *n = r->n_spans;
+    for (unsigned i = 0; spans && i < cap && i < r->n_spans; i++)
+        spans[i] = r->spans[i];
+    return 1;
 }
 int dvda_hip_reader_memory(const DVDA_Track_Reader *r, unsigned long long *host_peak, unsigned long long *device_peak)
 {

@@ -302,6 +302,37 @@ struct ConcealSrc {
     const int32_t *p[8];
 };
 
+// FIR history behind the last access unit of every stream of a decoded index (dvda_mlp_hip_conceal_edges: the streams are
+// the kept ranges of a round): a workgroup per stream finds its last live segment and gathers that segment's column of
+// the decode's FIR workspace -- element e of lane l = segment * 2 + substream lives at fir[e * lanes + l] -- into
+// out[stream][substream][48], the layout of dvda_mlp_hip_segment_fir.  A stream without a live segment gets zeros.
+__global__ __launch_bounds__(128) void k_conceal_edge_fir(const SegRec *__restrict__ seg, const uint32_t *__restrict__ n_seg_ptr,
+                                                          uint32_t max_seg, const StreamRec *__restrict__ streams,
+                                                          uint32_t n_streams, const int32_t *__restrict__ fir, uint32_t lanes,
+                                                          int32_t *__restrict__ out)
+{
+    __shared__ uint32_t s_last;
+    const uint32_t q = blockIdx.x;
+    if (q >= n_streams)
+        return;
+    if (threadIdx.x == 0) {
+        uint32_t n_cand = *n_seg_ptr, last = 0xFFFFFFFFu;
+        if (n_cand > max_seg)
+            n_cand = max_seg;
+        for (uint32_t h = streams[q].first_seg; h < n_cand && seg[h].stream == q; h++)
+            if (!(seg[h].flags & SEG_DEAD))
+                last = h;
+        s_last = last;
+    }
+    __syncthreads();
+    const uint32_t t = threadIdx.x;
+    if (t >= 96)
+        return;
+    const uint64_t lane = (uint64_t)s_last * 2 + t / 48;
+    const bool have = fir != nullptr && s_last != 0xFFFFFFFFu && lane < lanes;
+    out[(size_t)q * 96 + t] = have ? fir[(size_t)(t % 48) * lanes + lane] : 0;
+}
+
 __global__ __launch_bounds__(256) void k_conceal_move(const ConcealOp *__restrict__ ops, uint32_t n_ops, uint32_t layout,
                                                       int32_t *__restrict__ pcm, ConcealSrc srcs)
 {

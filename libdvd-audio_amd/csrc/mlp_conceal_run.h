@@ -14,6 +14,58 @@ extern "C" int dvda_mlp_hip_set_conceal(dvda_mlp_hip_ctx *c, int on)
     c->cc.on = on != 0;
     c->cc.spans.clear();
     c->cc.info.clear();
+    c->cc.ran = false;
+    return DVDA_HIP_OK;
+}
+
+extern "C" int dvda_mlp_hip_conceal_edges(dvda_mlp_hip_ctx *c, uint32_t stream, dvda_mlp_conceal_edges *out, void *stream_)
+{
+    if (!c || !out)
+        return DVDA_HIP_EINVAL;
+    if (!c->indexed || !c->cc.ran)
+        return DVDA_HIP_ESTATE;
+    if (stream >= c->n_streams || stream >= c->cc.h_streams.size())
+        return DVDA_HIP_EINVAL;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream_));
+    if (stream < c->cc.edges.size() && c->cc.edges[stream].reserved) {
+        *out = c->cc.edges[stream];
+        out->reserved = 0;
+        return DVDA_HIP_OK;
+    }
+    // a clean stream: all of it is kept; the history is that of its last live segment (no launch: a few small copies)
+    const StreamRec &r = c->cc.h_streams[stream];
+    memset(out, 0, sizeof(*out));
+    out->kept_end = out->kept_bytes = r.consumed;
+    out->kept_frames = r.rows;
+    uint64_t soff = 0, slen = 0;
+    HIP_TRY(hipMemcpy(&soff, c->d_soff + stream, sizeof(soff), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&slen, c->d_slen + stream, sizeof(slen), hipMemcpyDeviceToHost));
+    out->ends_kept = 1;
+    if (r.first_seg == 0xFFFFFFFFu || r.consumed < 4 || r.consumed > slen)
+        return DVDA_HIP_OK;
+    uint8_t head[4];
+    HIP_TRY(hipMemcpy(head, c->d_bytes + soff, sizeof(head), hipMemcpyDeviceToHost));
+    out->t_first = ((uint32_t)head[2] << 8) | head[3];
+    out->t_end = (out->t_first + (uint32_t)r.rows) & 0xFFFFu;
+    uint32_t n_cand = 0;
+    HIP_TRY(hipMemcpy(&n_cand, c->d_n_cand, sizeof(n_cand), hipMemcpyDeviceToHost));
+    if (n_cand > c->max_segments)
+        n_cand = c->max_segments;
+    uint32_t last = 0xFFFFFFFFu;
+    if (r.first_seg < n_cand) {
+        uint32_t n = n_cand - r.first_seg;
+        if (n > r.n_seg)
+            n = r.n_seg;
+        std::vector<SegRec> segs(n);
+        if (n)
+            HIP_TRY(hipMemcpy(segs.data(), c->d_seg + r.first_seg, (size_t)n * sizeof(SegRec), hipMemcpyDeviceToHost));
+        for (uint32_t k = 0; k < n; k++)
+            if (segs[k].stream == stream && !(segs[k].flags & SEG_DEAD))
+                last = r.first_seg + k;
+    }
+    if (last != 0xFFFFFFFFu && dvda_mlp_hip_segment_fir(c, last, out->fir, stream_) != DVDA_HIP_OK)
+        return DVDA_HIP_ENODEV;
     return DVDA_HIP_OK;
 }
 
@@ -48,6 +100,7 @@ struct CcItem {                 // a kept byte range of a damaged stream
     uint64_t scr_off, cap;      // its PCM in the round's scratch (int32 units), capacity / channel stride there (frames)
     uint64_t frames, units;
     uint32_t status, stream;
+    uint32_t fir_slot;          // its FIR history behind its last unit: edge_firs[fir_slot] (decoded clean)
 };
 struct CcStream {
     uint32_t id;
@@ -87,15 +140,26 @@ static int conceal_run(dvda_mlp_hip_ctx *c, int32_t *d_pcm, const uint64_t *d_ou
     const uint32_t ns = c->n_streams;
     c->cc.spans.assign(ns, std::vector<dvda_mlp_conceal_span>());
     c->cc.info.assign(ns, ConcealInfo());
+    c->cc.edges.clear();
+    c->cc.ran = false;
     std::vector<StreamRec> h(ns);
     HIP_TRY(hipMemcpyAsync(h.data(), c->d_streams, (size_t)ns * sizeof(StreamRec), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    c->cc.h_streams = h;
+    c->cc.ran = true;
     std::vector<uint32_t> dam;
     for (uint32_t i = 0; i < ns; i++)
         if (h[i].status & CONCEAL_DAMAGE)
             dam.push_back(i);
     if (dam.empty())
         return DVDA_HIP_OK;
+    c->cc.ran = false;                          // (until the batch is composed: a failure below leaves no edges)
+    {
+        dvda_mlp_conceal_edges none;
+        memset(&none, 0, sizeof(none));
+        c->cc.edges.assign(ns, none);
+    }
+    std::vector<int32_t> edge_firs;             // [slot][2][48]: the history behind every range that decoded clean
     std::vector<uint64_t> soff(ns), slen(ns), oo(ns), os(ns);
     HIP_TRY(hipMemcpyAsync(soff.data(), c->d_soff, (size_t)ns * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(slen.data(), c->d_slen, (size_t)ns * 8, hipMemcpyDeviceToHost, st));
@@ -251,6 +315,16 @@ static int conceal_run(dvda_mlp_hip_ctx *c, int32_t *d_pcm, const uint64_t *d_ou
             if (!redo)
                 break;
         }
+        // the history behind every range of this round, while the child's index is this round's (it is indexed again in
+        // the next one): dvda_mlp_hip_conceal_edges hands out the last kept range's
+        if ((rc = c->cc.d_edge_fir.grow(96 * (uint64_t)np)) != 0)
+            return rc;
+        hipLaunchKernelGGL(k_conceal_edge_fir, dim3(np), dim3(128), 0, st, x->d_seg, x->d_n_cand, x->max_segments, x->d_streams,
+                           np, x->d_fir, x->iir_lanes, c->cc.d_edge_fir);
+        HIP_TRY(hipGetLastError());
+        std::vector<int32_t> round_firs(96 * (size_t)np);
+        HIP_TRY(hipMemcpyAsync(round_firs.data(), c->cc.d_edge_fir, round_firs.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
         const bool last = round + 1 == CONCEAL_ROUNDS;
         bool again = false;
         // (a range whose decode reports DVDA_ST_ENVELOPE is not trusted either: the caller's streams may carry it, a range
@@ -277,6 +351,9 @@ static int conceal_run(dvda_mlp_hip_ctx *c, int32_t *d_pcm, const uint64_t *d_ou
                     it.frames = r.rows;
                     it.units = r.frames;
                     it.status = r.status;
+                    it.fir_slot = (uint32_t)(edge_firs.size() / 96);
+                    edge_firs.insert(edge_firs.end(), round_firs.begin() + 96 * (size_t)it.piece,
+                                     round_firs.begin() + 96 * (size_t)it.piece + 96);
                     nv.push_back(it);
                 } else if (last) {
                     // still damaged after the last round: concealed whole
@@ -368,7 +445,21 @@ static int conceal_run(dvda_mlp_hip_ctx *c, int32_t *d_pcm, const uint64_t *d_ou
         c->cc.info[i].rows = pos;
         c->cc.info[i].frames = units;
         c->cc.spans[i].swap(sp);
+        dvda_mlp_conceal_edges &e = c->cc.edges[i];
+        e.reserved = 1;                         // (valid; handed out as 0)
+        e.kept_bytes = K;
+        e.kept_frames = F;
+        if (prev) {
+            const CcItem &first = cs.items.front();
+            e.kept_begin = first.a - soff[i];
+            e.kept_end = prev->b - soff[i];
+            e.t_first = first.t_first;
+            e.t_end = (uint32_t)(prev->t_first + prev->frames) & 0xFFFFu;
+            e.ends_kept = prev->b >= end;
+            memcpy(e.fir, edge_firs.data() + 96 * (size_t)prev->fir_slot, sizeof(e.fir));
+        }
     }
+    c->cc.ran = true;
     const uint32_t nm = (uint32_t)moves.size(), nf = (uint32_t)fills.size();
     if (nm + nf) {
         if ((rc = c->cc.d_ops.grow((uint64_t)nm + nf)) != 0)

@@ -39,6 +39,10 @@ struct ConcealState {
     DevBuf<int32_t> d_scr[CONCEAL_ROUNDS];  // per round: the ranges' PCM, each laid out as the stream it belongs to
     DevBuf<ConcealOp> d_ops;
     DevBuf<int32_t> d_fir;                  // zero FIR history of the ranges' fresh decoders [pieces][2][48]
+    DevBuf<int32_t> d_edge_fir;             // FIR history behind each range of a round [pieces][2][48] (k_conceal_edge_fir); only grows
+    bool ran = false;                       // the last decode call ran in conceal mode (dvda_mlp_hip_conceal_edges)
+    std::vector<StreamRec> h_streams;       // ... and the stream records it read
+    std::vector<dvda_mlp_conceal_edges> edges;              // per stream of the last decode: the damaged ones (valid: reserved = 1)
     std::vector<std::vector<dvda_mlp_conceal_span>> spans;  // per stream of the last decode
     std::vector<ConcealInfo> info;                           // per stream of the last decode: the concealed ones
 

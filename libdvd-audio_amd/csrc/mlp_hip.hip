@@ -859,6 +859,7 @@ extern "C" int dvda_mlp_hip_decode(dvda_mlp_hip_ctx *c, int32_t *d_pcm, const ui
     if (c) {
         c->cc.spans.clear();
         c->cc.info.clear();
+        c->cc.ran = false;
     }
     const int rc = decode_impl(c, d_pcm, d_out_off, d_out_stride, stream_, true);
     if (rc != DVDA_HIP_OK || !c->cc.on)

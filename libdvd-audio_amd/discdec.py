@@ -26,6 +26,7 @@ EXPORTS = [
     "dvda_hip_reader_wav_next", "dvda_hip_reader_windowed", "dvda_hip_reader_memory", "dvda_hip_reader_failed",
     "dvda_hip_release_cached_buffers", "dvda_hip_set_presentation", "dvda_hip_open_track_reader_with",
     "dvda_hip_set_digest", "dvda_hip_reader_crc32", "dvda_hip_set_levels", "dvda_hip_reader_levels",
+    "dvda_hip_set_conceal", "dvda_hip_reader_concealed", "dvda_hip_open_track_reader_concealing",
 ]
 
 _lib = None
@@ -94,6 +95,12 @@ def lib():
         L.dvda_hip_set_levels.argtypes = [ctypes.c_int]
         L.dvda_hip_reader_levels.restype = ctypes.c_int
         L.dvda_hip_reader_levels.argtypes = [vp, ctypes.POINTER(hipdec.Levels)]
+        L.dvda_hip_open_track_reader_concealing.restype = ctypes.c_void_p
+        L.dvda_hip_open_track_reader_concealing.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4
+        L.dvda_hip_set_conceal.restype = None
+        L.dvda_hip_set_conceal.argtypes = [ctypes.c_int]
+        L.dvda_hip_reader_concealed.restype = ctypes.c_int
+        L.dvda_hip_reader_concealed.argtypes = [vp, ctypes.POINTER(hipdec.ConcealSpan), u, ctypes.POINTER(u)]
         _lib = L
     return _lib
 
@@ -125,7 +132,7 @@ def layout(audio_ts, titleset=1):
 
 
 def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0, fused=False, pieces=False,
-               presentation=0, digest=False, levels=False):
+               presentation=0, digest=False, levels=False, conceal=None):
     """Decodes one track on the GPU.  Returns a dict: codec ("PCM"/"MLP"), bits, rate, channels,
     mask, status, and pcm = int32 [frames, channels] (interleaved, RIFF-WAVE order) read with
     dvda_read() in `chunk`-frame calls -- or, with wav=True, payload = the WAV data bytes packed
@@ -141,7 +148,13 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
     info["crc32_states"] = what dvda_hip_reader_crc32 returned right after the open and at the end of the read.
     levels=True: the reader makes the level report of the track's int32 PCM on the device (dvda_hip_set_levels):
     info["levels"] = the report as hipdec.Levels.as_dict() gives it (None when the reader has none: a WAV-payload-only
-    reader), and info["levels_states"] = what dvda_hip_reader_levels returned right after the open and at the end."""
+    reader), and info["levels_states"] = what dvda_hip_reader_levels returned right after the open and at the end.
+    conceal=True: a damaged MLP track is concealed, not refused (dvda_hip_set_conceal): info["concealed"] = the spans as
+    6-tuples (first_frame, frames, byte_off, byte_end, cause, flags) in track terms, and info["concealed_states"] = what
+    dvda_hip_reader_concealed returned right after the open and at the end.  conceal=False says "off" explicitly; None
+    (default): as the calling thread has it (dvda_hip_set_conceal), or DVDA_CONCEAL=1 in the environment while the thread
+    has made no such call.  The option is this reader's (dvda_hip_open_track_reader_concealing): the thread's setting is
+    not touched."""
     from . import hipdec
     L = lib()
     d = L.dvda_open(audio_ts.encode(), None)
@@ -155,7 +168,8 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
         L.dvda_hip_set_digest(1 if digest else 0)
         L.dvda_hip_set_levels(1 if levels else 0)
         try:
-            r = L.dvda_hip_open_track_reader_with(k, device, 1 if (fused and wav) else 0, presentation) if k else None
+            r = L.dvda_hip_open_track_reader_concealing(k, device, 1 if (fused and wav) else 0, presentation,
+                                                        -1 if conceal is None else int(bool(conceal))) if k else None
         finally:
             L.dvda_hip_set_digest(0)            # (read when the reader is opened: nothing is left behind)
             L.dvda_hip_set_levels(0)
@@ -171,6 +185,8 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
         first_state = L.dvda_hip_reader_crc32(r, ctypes.byref(crc), ctypes.byref(nbytes)) if digest else None
         report = hipdec.Levels()
         first_levels = L.dvda_hip_reader_levels(r, ctypes.byref(report)) if levels else None
+        n_spans = ctypes.c_uint()
+        first_spans = L.dvda_hip_reader_concealed(r, None, 0, ctypes.byref(n_spans)) if conceal else None
         if wav and pieces:
             got, sizes = [], []
             while True:
@@ -209,6 +225,13 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
             state = L.dvda_hip_reader_levels(r, ctypes.byref(report))
             info["levels_states"] = (first_levels, state)
             info["levels"] = report.as_dict() if state == 1 else None
+        if conceal:
+            state = L.dvda_hip_reader_concealed(r, None, 0, ctypes.byref(n_spans))
+            arr = (hipdec.ConcealSpan * max(int(n_spans.value), 1))()
+            if state >= 0:
+                state = L.dvda_hip_reader_concealed(r, arr, int(n_spans.value), ctypes.byref(n_spans))
+            info["concealed_states"] = (first_spans, state)
+            info["concealed"] = [arr[i].as_tuple() for i in range(int(n_spans.value))] if state >= 0 else None
         return info
     finally:
         if r:

@@ -68,7 +68,7 @@ EXPORTS = ("dvda_mlp_hip_create", "dvda_mlp_hip_destroy", "dvda_mlp_hip_index", 
            "dvda_mlp_hip_demux_sectors", "dvda_mlp_hip_pack_wav",
            "dvda_mlp_hip_shard", "dvda_mlp_hip_create_multi", "dvda_mlp_hip_destroy_multi",
            "dvda_mlp_hip_multi_devices", "dvda_mlp_hip_decode_multi", "dvda_mlp_hip_multi_device_time",
-           "dvda_mlp_hip_set_conceal", "dvda_mlp_hip_conceal_spans",
+           "dvda_mlp_hip_set_conceal", "dvda_mlp_hip_conceal_spans", "dvda_mlp_hip_conceal_edges",
            "dvda_mlp_hip_set_presentation", "dvda_mlp_hip_present_time",
            "dvda_pcm_hip_crc32", "dvda_pcm_hip_crc32_workspace_words", "dvda_mlp_hip_pcm_crc32",
            "dvda_pcm_hip_crc32_combine",
@@ -116,6 +116,19 @@ class ConcealSpan(ctypes.Structure):
     def as_tuple(self):
         return (int(self.first_frame), int(self.frames), int(self.byte_off), int(self.byte_end), int(self.cause),
                 int(self.flags))
+
+
+class ConcealEdges(ctypes.Structure):
+    """dvda_mlp_conceal_edges of include/dvda_mlp_hip.h"""
+    _fields_ = [("kept_begin", ctypes.c_uint64), ("kept_end", ctypes.c_uint64), ("t_first", ctypes.c_uint32),
+                ("t_end", ctypes.c_uint32), ("kept_bytes", ctypes.c_uint64), ("kept_frames", ctypes.c_uint64),
+                ("ends_kept", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("fir", ctypes.c_int32 * 96)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k in ("kept_begin", "kept_end", "t_first", "t_end", "kept_bytes", "kept_frames",
+                                                 "ends_kept")}
+        d["fir"] = np.array(self.fir, np.int32).reshape(2, 48)
+        return d
 
 
 def lib():
@@ -202,6 +215,7 @@ def lib():
         L.dvda_mlp_hip_set_initial_fir.argtypes = [vp, vp]
         L.dvda_mlp_hip_segment_fir.argtypes = [vp, u32, vp, vp]
         L.dvda_mlp_hip_conceal_spans.argtypes = [vp, u32, ctypes.POINTER(ConcealSpan), u32, ctypes.POINTER(u32), vp]
+        L.dvda_mlp_hip_conceal_edges.argtypes = [vp, u32, ctypes.POINTER(ConcealEdges), vp]
         L.dvda_pcm_hip_crc32_workspace_words.restype = ctypes.c_size_t
         L.dvda_pcm_hip_crc32_workspace_words.argtypes = [u32, u64]
         L.dvda_pcm_hip_crc32.argtypes = [vp, u32, ctypes.c_uint, vp, u32, u64, vp, vp, vp, ctypes.c_size_t, vp]
@@ -284,6 +298,13 @@ class Context:
         arr = (ConcealSpan * max(int(n.value), 1))()
         _check(lib().dvda_mlp_hip_conceal_spans(self._h, i, arr, int(n.value), ctypes.byref(n), stream), "conceal_spans")
         return [arr[k].as_tuple() for k in range(int(n.value))]
+
+    def conceal_edges(self, i, stream=0):
+        """edges of stream i after the last decode in conceal mode -> ConcealEdges.as_dict(); HipError (ESTATE) when the
+        last decode was not in conceal mode"""
+        e = ConcealEdges()
+        _check(lib().dvda_mlp_hip_conceal_edges(self._h, i, ctypes.byref(e), stream), "conceal_edges")
+        return e.as_dict()
 
     def present_time(self):
         """-> (device ms of the strip kernels of the last index, source bytes, presentation bytes)"""

@@ -42,6 +42,9 @@ def main():
     ap.add_argument("--chained", action="store_true",
                     help="tracks as an encoder writes them: no raw lead-in at the restart points, the FIR history runs "
                          "through each track (the chain passes decode them)")
+    ap.add_argument("--conceal", action="store_true",
+                    help="dvda2wav_hip --conceal: the disc is clean, so this times what the option costs a clean track (see "
+                         "--aus for tracks longer than a window)")
     a = ap.parse_args()
     syn, disc = pkg.synth, pkg.disc
     tool = pkg._build.build_tool()
@@ -68,7 +71,8 @@ def main():
             samples += f * 6
         ats = disc.write_disc_titles(tmp, [tracks])
         aob = os.path.getsize(os.path.join(ats, "ATS_01_1.AOB"))
-        res = {"tracks": a.tracks, "samples": samples, "aob_bytes": aob, "chained": bool(a.chained), "devices": a.devices or "0"}
+        res = {"tracks": a.tracks, "samples": samples, "aob_bytes": aob, "chained": bool(a.chained), "devices": a.devices or "0",
+               "conceal": bool(a.conceal)}
         env = dict(os.environ, LD_LIBRARY_PATH=os.path.join(ROOT, "libdvd-audio_amd") + ":/opt/rocm/lib:" +
                    os.environ.get("LD_LIBRARY_PATH", ""))
         outs = {}
@@ -79,7 +83,8 @@ def main():
             os.makedirs(out)
             for rep in range(2 if name == "gpu" else 1):          # second GPU run: page cache + driver warm
                 t0 = time.time()
-                cmd = [exe, "-A", ats, "-d", out] + (["--devices", a.devices] if a.devices and name == "gpu" else [])
+                cmd = [exe, "-A", ats, "-d", out] + (["--devices", a.devices] if a.devices and name == "gpu" else []) + \
+                    (["--conceal"] if a.conceal and name == "gpu" else [])
                 r = subprocess.run(cmd, capture_output=True, text=True, env=env)
                 dt = time.time() - t0
                 assert r.returncode == 0, r.stderr[-2000:]

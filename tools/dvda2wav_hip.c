@@ -20,6 +20,7 @@
 #include <unistd.h>
 
 #include "dvd-audio-hip.h"
+#include "dvda_mlp_hip.h"           /* struct dvda_mlp_conceal_span (--conceal) */
 
 static void put16(uint8_t *p, unsigned v) { p[0] = v & 0xFF; p[1] = (v >> 8) & 0xFF; }
 static void put32(uint8_t *p, unsigned v) { put16(p, v & 0xFFFF); put16(p + 2, v >> 16); }
@@ -57,7 +58,7 @@ static double now_s(void)
 }
 
 static int extract(DVDA_Title *title, unsigned track_num, const char *dir, int device, int fused_wav, int stereo,
-                   int crc, unsigned titleset_num)
+                   int crc, int conceal, unsigned titleset_num)
 {
     const int timing = getenv("DVDA_TOOL_TIMING") != NULL;       /* diagnostic: where a track's wall-clock time goes */
     const double t_begin = now_s();
@@ -71,6 +72,9 @@ static int extract(DVDA_Title *title, unsigned track_num, const char *dir, int d
     /* --stereo: a two-substream MLP track comes out as the 2-channel presentation its substream 0 carries */
     /* --crc: the reader digests the track on the device, before the payload is copied (read when the reader is opened) */
     dvda_hip_set_digest(crc);
+    /* --conceal: a damaged MLP track is written with silence where the damage is, not refused (an explicit choice either
+       way: the tool's option decides, not DVDA_CONCEAL in the environment) */
+    dvda_hip_set_conceal(conceal);
     DVDA_Track_Reader *r = dvda_hip_open_track_reader_with(track, device, fused_wav, stereo);
     if (!r) {
         fprintf(stderr, "*** Error: unable to open track %u for reading\n", track_num);
@@ -132,6 +136,19 @@ static int extract(DVDA_Title *title, unsigned track_num, const char *dir, int d
         else
             printf("CRC32 %u %u %u none 0\n", titleset_num, title_number, track_number);
     }
+    if (ok && conceal) {
+        /* what was concealed of the track just written: one line per span */
+        unsigned n_spans = 0;
+        if (dvda_hip_reader_concealed(r, NULL, 0, &n_spans) == 1 && n_spans) {
+            struct dvda_mlp_conceal_span *sp = malloc(n_spans * sizeof(*sp));
+            if (sp && dvda_hip_reader_concealed(r, sp, n_spans, &n_spans) == 1)
+                for (unsigned i = 0; i < n_spans; i++)
+                    printf("CONCEALED %u %u %u %llu %llu %llu %llu %x %u\n", titleset_num, title_number, track_number,
+                           (unsigned long long)sp[i].first_frame, (unsigned long long)sp[i].frames,
+                           (unsigned long long)sp[i].byte_off, (unsigned long long)sp[i].byte_end, sp[i].cause, sp[i].flags);
+            free(sp);
+        }
+    }
     if (ok)
         printf("* Wrote: \"%s\"\n", path);
     else
@@ -161,6 +178,7 @@ struct pool {
     int fused_wav;
     int stereo;                         /* --stereo: the 2-channel presentation of two-substream MLP tracks */
     int crc;                            /* --crc: one CRC32 line per track */
+    int conceal;                        /* --conceal: damaged MLP tracks are concealed; one CONCEALED line per span */
     unsigned titleset;
     int park;                           /* a worker that is through parks instead of ending (the fast way out) */
 };
@@ -178,7 +196,7 @@ static void *work(void *arg)
         if (i >= w->pool->n_jobs)
             break;
         if (!extract(w->pool->jobs[i].title, w->pool->jobs[i].track, w->pool->dir, w->device, w->pool->fused_wav, w->pool->stereo,
-                     w->pool->crc, w->pool->titleset))
+                     w->pool->crc, w->pool->conceal, w->pool->titleset))
             atomic_fetch_add(&w->pool->failed, 1);
     }
     /* (what this thread's last windowed reader left for a next one would be freed when the thread ends -- 30 ms a worker.
@@ -207,6 +225,9 @@ static void usage(const char *prog)
            "  -C, --crc                 print the CRC-32 (zlib) of every track's WAV data chunk, computed on the GPU, one\n"
            "                            line per track on stdout: CRC32 <titleset> <title> <track> <crc, 8 hex digits>\n"
            "                            <bytes> (\"none 0\" for a bit depth other than 16 / 24); -c is --cdrom\n"
+           "  -K, --conceal             write a damaged MLP track with silence in place of the damage instead of failing\n"
+           "                            on it; one line per concealed span on stdout: CONCEALED <titleset> <title> <track>\n"
+           "                            <first_frame> <frames> <byte_off> <byte_end> <cause, hex> <flags>\n"
            "  -g N, --gpu=N             HIP device (default 0)\n"
            "  -D LIST, --devices=LIST   comma-separated HIP devices: one worker thread per entry takes tracks in turn\n"
            "                            (default: up to four workers on the device of -g)\n"
@@ -220,15 +241,15 @@ int main(int argc, char *argv[])
                                        {"track", required_argument, 0, 't'},    {"dir", required_argument, 0, 'd'},
                                        {"gpu", required_argument, 0, 'g'},      {"help", no_argument, 0, 'h'},
                                        {"devices", required_argument, 0, 'D'},  {"stereo", no_argument, 0, '2'},
-                                       {"crc", no_argument, 0, 'C'},
+                                       {"crc", no_argument, 0, 'C'},            {"conceal", no_argument, 0, 'K'},
                                        {0, 0, 0, 0}};
     const char *audio_ts = NULL, *dir = ".", *cdrom = NULL;
     unsigned titleset_num = 1, title_num = 0, track_num = 0;
-    int devices[64], n_devices = 0, one_device = 0, stereo = 0, crc = 0;
+    int devices[64], n_devices = 0, one_device = 0, stereo = 0, crc = 0, conceal = 0;
     int c;
     if (getenv("DVDA_TOOL_TIMING"))
         fprintf(stderr, "timing: main at %.1f ms\n", now_s() * 1e3);
-    while ((c = getopt_long(argc, argv, "A:c:S:T:t:d:g:D:h2C", longopts, NULL)) != -1) {
+    while ((c = getopt_long(argc, argv, "A:c:S:T:t:d:g:D:h2CK", longopts, NULL)) != -1) {
         switch (c) {
         case 'A': audio_ts = optarg; break;
         case 'c': cdrom = optarg; break;
@@ -243,6 +264,7 @@ int main(int argc, char *argv[])
             break;
         case '2': stereo = 1; break;
         case 'C': crc = 1; break;
+        case 'K': conceal = 1; break;
         case 'h': usage(argv[0]); return 0;
         default: return 1;
         }
@@ -294,7 +316,7 @@ int main(int argc, char *argv[])
         for (unsigned i = 0; i < w; i++)
             devices[n_devices++] = one_device;
     }
-    struct pool pool = {jobs, n_jobs, 0, 0, 0, dir, fused_wav, stereo, crc, titleset_num, getenv("DVDA_TOOL_FULL_TEARDOWN") == NULL};
+    struct pool pool = {jobs, n_jobs, 0, 0, 0, dir, fused_wav, stereo, crc, conceal, titleset_num, getenv("DVDA_TOOL_FULL_TEARDOWN") == NULL};
     struct worker workers[64];
     pthread_t th[64];
     int started[64];
