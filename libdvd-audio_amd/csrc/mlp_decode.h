@@ -747,6 +747,11 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
     constexpr int TP = 6;                                         // staged planes: the channels (the chain parse pass keeps
                                                                   // a row's bypassed LSBs and noise seed in registers: with two
                                                                   // more planes its workgroup was 34 KB of LDS and only three fit a CU)
+    // dwords from one plane of the staging tile to the next.  The headline instance pads a plane by one: the six lanes
+    // that store one run together in the wave's cooperative flush read six planes of ONE column, 64 dwords apart on one
+    // bank, and 65 apart on six (docs/history.md A.14).  A lane's own column stays conflict-free either way.  The
+    // two-substream lane has no LDS to spare for it, the packed-WAV twin and the other passes never read across columns.
+    constexpr int PS = (ILV && !GENERAL && !PARSE && !DUO && !WAVO) ? 65 : 64;
     constexpr int RD = DUO ? DUO_RING : RING_DWORDS;            // dwords a ring holds
     // the one-substream lane instances (fast pass and chain parse pass) refill by granules, the whole wave in the
     // same row (WAVE_FILL below); the sequential pass keeps the 64-byte chunk a lane asks for by itself
@@ -754,7 +759,7 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
     constexpr int RG = DUO ? DUO_GRAN : WAVE_FILL ? 4 : CHUNK_DWORDS;   // dwords a fill brings
     using Reader = BitReaderT<RD, RG>;
     __shared__ uint32_t s_ring[WAVES][DUO ? 2 : 1][RD + 1][64];     // + the mirror of plane 0 (DUO: a ring per substream)
-    __shared__ int32_t s_out[GENERAL ? 1 : WAVES][TP][OUT_ROWS][GENERAL ? 1 : 64];   // PCM staging
+    __shared__ int32_t s_out[GENERAL ? 1 : WAVES][TP][OUT_ROWS][GENERAL ? 1 : PS];   // PCM staging
     // sequential pass: the two lanes of a segment exchange their channels here
     constexpr bool XCH = PAIRED;
     __shared__ int32_t s_xch[XCH ? WAVES : 1][MAXCH][XCH ? 64 : 1];
@@ -1839,7 +1844,7 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
 #pragma unroll
                         for (int m = 0; m < 2; m++) {
                             const uint32_t oc = nib(outch_pack, m);                 // <= 5 (checked)
-                            const uint32_t off = oc * ((ILV && ilv_direct) ? 64u : (uint32_t)(OUT_ROWS * 64));
+                            const uint32_t off = oc * ((ILV && ilv_direct) ? (uint32_t)PS : (uint32_t)(OUT_ROWS * PS));
                             if constexpr (MPK) {
                                 mpk |= (off << (11 * m)) | (nib(qss_pack, oc) << (22 + 4 * m));
                             } else {
@@ -2250,7 +2255,7 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                     auto stage_row = [&](auto with_shifts, auto frame_major) {
                         constexpr bool OSH = decltype(with_shifts)::value;
                         constexpr bool FM = decltype(frame_major)::value;
-                        int32_t *const Tb = &s_out[wv][0][0][lane] + ph * (FM ? 6u * 64u : 64u);
+                        int32_t *const Tb = &s_out[wv][0][0][lane] + ph * (FM ? 6u * (uint32_t)PS : (uint32_t)PS);
                         auto out_c = [&](int c) -> int32_t {
                             if constexpr (OSH)
                                 return (uint32_t)c <= mmc_A ? (int32_t)((uint32_t)ch[c] << nib(oshift_pack, c)) : ch[c];
@@ -2282,12 +2287,18 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                         };
                         if constexpr (FM) {
 #pragma unroll
-                            for (int c = 0; c < 6; c++)
-                                Tb[c * 64] = out_c(c);
+                            for (int c = 0; c < 6; c++) {
+                                // (padded planes: the last two are past the 255 dwords a two-address store reaches.
+                                //  Fenced off, they stay two one-address stores at constant offsets; merged, the pair
+                                //  costs the row a second base address, one VALU instruction more than it had)
+                                if (PS != 64 && c >= 4)
+                                    asm volatile("" ::: "memory");
+                                Tb[c * PS] = out_c(c);
+                            }
                         } else {
 #pragma unroll
                             for (int c = 0; c < TP; c++)
-                                Tb[c * (OUT_ROWS * 64)] = out_c(c);
+                                Tb[c * (OUT_ROWS * PS)] = out_c(c);
                         }
                         if (any0) {
                             const int32_t nv0 = (int32_t)(((uint32_t)(int32_t)(mac(0) >> 14) & m_qm(0)) + (bypass_bits & 1u));
@@ -2333,13 +2344,13 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                     // ---- into the LDS staging tile [channel][frame][lane]; rows advance in lockstep so
                     //      the frame phase is the same in every lane
                     const uint32_t ph = rows_done & (OUT_ROWS - 1);
-                    int32_t(*T)[OUT_ROWS][GENERAL ? 1 : 64] =
+                    int32_t(*T)[OUT_ROWS][GENERAL ? 1 : PS] =
                         s_out[GENERAL ? 0 : wv];
                     if (ILV && ilv_direct) {
-                        int32_t *Td = &T[0][0][GENERAL ? 0 : lane] + ph * (6 * 64);
+                        int32_t *Td = &T[0][0][GENERAL ? 0 : lane] + ph * (6 * PS);
 #pragma unroll
                         for (int c = 0; c < 6; c++)
-                            Td[c * 64] = ch[c];
+                            Td[c * PS] = ch[c];
                     } else {
 #pragma unroll
                         for (int c = 0; c < TP; c++)
@@ -2679,20 +2690,65 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
             // is the same in every one of them
             const uint32_t l6 = ((uint32_t)lane * 43691u) >> 18;             // lane / 6
             const uint32_t pc = (uint32_t)lane - l6 * 6u;
-            const int32_t *const Tl6 = T0 + pc * (4 * 64) + l6;             // (the tile in output order: value v of a run in plane v)
+            const int32_t *const Tl6 = T0 + pc * (4 * PS) + l6;             // (the tile in output order: value v of a run in plane v)
             const bool l60 = lane < 60;
+            if (__builtin_expect(off32, 1)) {
+                // ---- the usual case, in phases and not piece by piece: the seven permutes of the runs' offsets first,
+                //      then the tile reads of four pieces and their stores, then those of the last three.  A store is an
+                //      asm with a memory clobber, which no tile read crosses: taken piece by piece, every piece waited for
+                //      its permute and then for its reads, fourteen LDS round trips in a row with nothing issued between
+                //      them.  Here the reads of a group are in flight together and the stores wait for them by count.
+                //      (the last instruction is lanes 0 .. 23's, the runs of lanes 60 .. 63: where the wave's mask
+                //      narrows is the only branch left; docs/history.md A.14)
+                uint32_t bo[7];
+#pragma unroll
+                for (uint32_t it7 = 0; it7 < 7u; it7++)
+                    bo[it7] = (uint32_t)__shfl((int)d_lo, (int)(l6 + 10u * it7), 64);
+                int32_t *const ob = a.pcm + pc * 4u;
+                if (l60) {
+                    // (a piece's four values through an index of its own, hidden from the optimizer: with one base for all
+                    //  the reads of a group it pairs them by offset -- planes of two pieces in one ds_read2_b32 -- and
+                    //  then moves every value into its store's register quad, sixteen v_mov for four pieces)
+                    const uint32_t ti = pc * (4u * PS) + l6;
+                    auto piece = [&](uint32_t k, int32_t(&q)[4]) {
+                        uint32_t tk = ti;
+                        asm volatile("" : "+v"(tk));          // (volatile: or the seven become one again)
+#pragma unroll
+                        for (uint32_t j = 0; j < 4u; j++)
+                            q[j] = T0[tk + 10u * k + j * PS];
+                    };
+                    int32_t v[4][4];
+#pragma unroll
+                    for (uint32_t k = 0; k < 4u; k++)
+                        piece(k, v[k]);
+#pragma unroll
+                    for (uint32_t k = 0; k < 4u; k++)
+                        DVDA_STORE_V4_COOP(ob + bo[k], v[k][0], v[k][1], v[k][2], v[k][3]);
+                    const bool last = lane < 24;
+#pragma unroll
+                    for (uint32_t k = 0; k < 2u; k++)
+                        piece(4u + k, v[k]);
+                    if (last)
+                        piece(6u, v[2]);
+#pragma unroll
+                    for (uint32_t k = 0; k < 2u; k++)
+                        DVDA_STORE_V4_COOP(ob + bo[4u + k], v[k][0], v[k][1], v[k][2], v[k][3]);
+                    if (last)
+                        DVDA_STORE_V4_COOP(ob + bo[6], v[2][0], v[2][1], v[2][2], v[2][3]);
+                }
+            } else {
+            // ---- a PCM buffer of 16 GB and more: two words per run, piece by piece
 #pragma unroll
             for (uint32_t it7 = 0; it7 < 7u; it7++) {
                 const uint32_t o = l6 + 10u * it7;                           // whose run
                 const uint32_t b_lo = (uint32_t)__shfl((int)d_lo, (int)o, 64);
-                uint64_t eo = b_lo;
-                if (!off32)
-                    eo |= (uint64_t)(uint32_t)__shfl((int)d_hi, (int)o, 64) << 32;
+                const uint64_t eo = b_lo | (uint64_t)(uint32_t)__shfl((int)d_hi, (int)o, 64) << 32;
                 if (l60 && (it7 < 6u || o < 64u)) {
                     int32_t *const od = a.pcm + eo + pc * 4u;
                     const int32_t *const Tp = Tl6 + 10u * it7;
-                    DVDA_STORE_V4_COOP(od, Tp[0], Tp[64], Tp[128], Tp[192]);
+                    DVDA_STORE_V4_COOP(od, Tp[0], Tp[PS], Tp[2 * PS], Tp[3 * PS]);
                 }
+            }
             }
         }
         if (!GENERAL && !PARSE && ILV && flush && !coop_out) {
@@ -2713,7 +2769,7 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                     uint32_t d[18];
 #pragma unroll
                     for (int g = 0; g < 6; g++) {
-                        const int32_t o[4] = {Tl[(4 * g) * 64], Tl[(4 * g + 1) * 64], Tl[(4 * g + 2) * 64], Tl[(4 * g + 3) * 64]};
+                        const int32_t o[4] = {Tl[(4 * g) * PS], Tl[(4 * g + 1) * PS], Tl[(4 * g + 2) * PS], Tl[(4 * g + 3) * PS]};
                         uint32_t t[3];
                         wav_pack4(o, 24u, t);
                         d[3 * g] = t[0];
@@ -2730,7 +2786,7 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                         int32_t o[4];
 #pragma unroll
                         for (int j = 0; j < 4; j++) {
-                            o[j] = ilv_direct ? Tl[(4 * v + j) * 64] : Tl[(nib(wave_inv, fw) * OUT_ROWS + fi) * 64];
+                            o[j] = ilv_direct ? Tl[(4 * v + j) * PS] : Tl[(nib(wave_inv, fw) * OUT_ROWS + fi) * PS];
                             fw++;
                             if (fw == nch_out) {
                                 fw = 0;
@@ -2749,13 +2805,13 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                 // the tile already is in output order: 24 consecutive planes, two per LDS read
 #pragma unroll
                 for (int v = 0; v < (OUT_ROWS * 6) / 4; v++)
-                    DVDA_STORE_V4_AT(dst, 16 * v, Tl[(4 * v) * 64], Tl[(4 * v + 1) * 64], Tl[(4 * v + 2) * 64],
-                                     Tl[(4 * v + 3) * 64]);
+                    DVDA_STORE_V4_AT(dst, 16 * v, Tl[(4 * v) * PS], Tl[(4 * v + 1) * PS], Tl[(4 * v + 2) * PS],
+                                     Tl[(4 * v + 3) * PS]);
             } else if (__all(nch_out == 2u && vec_ok)) {
                 // 2 channels: the four frames are one 32-byte sector
-                const int32_t *c0 = Tl + nib(wave_inv, 0) * (OUT_ROWS * 64), *c1 = Tl + nib(wave_inv, 1) * (OUT_ROWS * 64);
-                DVDA_STORE_V4_AT(dst, 0, c0[0], c1[0], c0[64], c1[64]);
-                DVDA_STORE_V4_AT(dst, 16, c0[128], c1[128], c0[192], c1[192]);
+                const int32_t *c0 = Tl + nib(wave_inv, 0) * (OUT_ROWS * PS), *c1 = Tl + nib(wave_inv, 1) * (OUT_ROWS * PS);
+                DVDA_STORE_V4_AT(dst, 0, c0[0], c1[0], c0[PS], c1[PS]);
+                DVDA_STORE_V4_AT(dst, 16, c0[2 * PS], c1[2 * PS], c0[3 * PS], c1[3 * PS]);
             } else {
                 // any channel count, lanes of different formats, unaligned buffers
                 uint32_t fi = 0, fw = 0;
@@ -2764,7 +2820,7 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                         int32_t o[4];
 #pragma unroll
                         for (int j = 0; j < 4; j++) {
-                            o[j] = Tl[(nib(wave_inv, fw) * OUT_ROWS + fi) * 64];
+                            o[j] = Tl[(nib(wave_inv, fw) * OUT_ROWS + fi) * PS];
                             fw++;
                             if (fw == nch_out) {
                                 fw = 0;
@@ -2792,7 +2848,7 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
             // ---- chain parse pass: four PCM frames of all eight planes are ONE 128-byte line of the segment's
             //      workspace ([row / 4][plane][row % 4], res_index()): the lane writes it whole, the filter pass's
             //      lanes of a chain read it together, the rematrix pass reads it once
-            int32_t(*T)[OUT_ROWS][GENERAL ? 1 : 64] = s_out[GENERAL ? 0 : wv];
+            int32_t(*T)[OUT_ROWS][GENERAL ? 1 : PS] = s_out[GENERAL ? 0 : wv];
             int32_t *dst = a.res + out_base + (flush_row >> 2) * 32u;
             if (!DVDA_RANGE_OK(out_base + (flush_row >> 2) * 32u, 32, a.caps.res, BT_RES))
                 dst = a.res;
@@ -2822,16 +2878,16 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                     const uint32_t pc = q - o * 6u;
                     const uint32_t b_lo = (uint32_t)__shfl((int)d_lo, (int)o, 64), b_hi = (uint32_t)__shfl((int)d_hi, (int)o, 64);
                     int32_t *const od = reinterpret_cast<int32_t *>(((uint64_t)b_hi << 32) | b_lo) + pc * 4u;
-                    const int32_t *const Tp = T0 + pc * (OUT_ROWS * 64) + o;
+                    const int32_t *const Tp = T0 + pc * (OUT_ROWS * PS) + o;
                     // (the store may still be reading its data registers when the next instructions issue, and what follows
                     //  here is this loop's own arithmetic in whatever registers the compiler likes: two wait states, as the
                     //  compiler pads its own stores -- tools/hazard_check.py looks at every store placed as inline asm)
-                    DVDA_STORE_V4_PAD(od, Tp[0], Tp[64], Tp[128], Tp[192]);
+                    DVDA_STORE_V4_PAD(od, Tp[0], Tp[PS], Tp[2 * PS], Tp[3 * PS]);
                 }
             }
         }
         if (!GENERAL && !PARSE && !ILV && flush) {
-            int32_t(*T)[OUT_ROWS][GENERAL ? 1 : 64] = s_out[GENERAL ? 0 : wv];
+            int32_t(*T)[OUT_ROWS][GENERAL ? 1 : PS] = s_out[GENERAL ? 0 : wv];
 #pragma unroll
             for (int c = 0; c < 6; c++) {
                 if ((uint32_t)c < nch_out) {
