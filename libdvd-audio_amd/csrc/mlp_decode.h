@@ -336,6 +336,12 @@ __device__ __forceinline__ int32_t mask_q(int32_t x, uint32_t q)
 {
     return (int32_t)((uint32_t)x & (0xFFFFFFFFu << q));
 }
+// "any lane of the wave" from the lane mask itself.  The mask of a condition that is a compare is the compare's own
+// result; of any other condition -- an AND of two, a value merged from two branches -- the compiler builds it by a select
+// on the condition's SGPR pair and a compare of what that gives, two slow-class VALU instructions, through __any() /
+// __ballot() and through the builtin alike: a test of the row loop ANDs the masks of its compares (docs/history.md A.15).
+__device__ __forceinline__ uint64_t wave_mask(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+__device__ __forceinline__ bool wave_any(bool p) { return wave_mask(p) != 0ull; }
 __device__ __forceinline__ uint32_t nib(uint32_t pack, uint32_t i) { return (pack >> (4 * i)) & 0xFu; }
 __device__ __forceinline__ int32_t lo16(uint32_t v) { return (int32_t)(v << 16) >> 16; }
 __device__ __forceinline__ int32_t hi16(uint32_t v) { return (int32_t)v >> 16; }
@@ -389,6 +395,51 @@ __device__ __forceinline__ void ring_store4(uint32_t *dst, const uint4 &a, bool 
     dst[-2 * 64] = be32(a.z);
     dst[-3 * 64] = be32(a.w);
 }
+
+// The plane arithmetic of a whole refill turn (the wave's refill, WAVE_FILL): a turn starts at ring dword f, a multiple
+// of 4, and its granule g begins at dword f + 4 g.  With f8 = f << 8 worked out once per turn, ring_turn_off(f8, g) is
+// how many BYTES that dword's plane lies below plane RD -- ((f + 4 g) mod RD) planes of 256 bytes, the 32-dword wrap in
+// the mask -- so the granule's slot is plane RD's address less this, and the granule starts the ring (its first dword
+// goes to the mirror plane as well: `first_plane`) exactly when this is 0.  An add and an and per granule where
+// BitReaderT::slot() and the test of the dword index took an add, a shift, two ands and a subtract.
+template <int RD>
+__host__ __device__ constexpr uint32_t ring_turn_off(uint32_t f8, uint32_t g)
+{
+    return (f8 + g * 0x400u) & ((uint32_t)(RD - 1) << 8);
+}
+// a dword's slot as BitReaderT::slot() has it, in dwords from the lane's column in plane 0
+template <int RD>
+__host__ __device__ constexpr uint32_t ring_slot_index(uint32_t d)
+{
+    return (uint32_t)(RD - (d & (RD - 1))) << 6;
+}
+// checked where it is compiled: every turn start that is a multiple of 4 modulo RD, in the first ring-ful, across the
+// wrap of the 32-bit dword index (f8 has lost f's high bits by then) and in between, every granule a turn of fn = 0 .. 4
+// can take, against slot() and the first_plane rule of the code this replaces; and the turn's advance of fillpos keeps
+// the next turn's start a multiple of 4
+template <int RD>
+__host__ __device__ constexpr bool ring_turn_off_ok()
+{
+    const uint32_t bases[] = {0u, (uint32_t)RD, 0x00FFFFE0u, 0x7FFFFFE0u, 0xFFFFFFC0u, 0xFFFFFFE0u};
+    for (uint32_t b : bases)
+        for (uint32_t k = 0; k < (uint32_t)RD; k += 4u)
+            for (uint32_t fn = 0; fn <= 4u; fn++) {
+                const uint32_t f = b + k, f8 = f << 8;
+                for (uint32_t g = 0; g < fn; g++) {
+                    const uint32_t d = f + 4u * g, off = ring_turn_off<RD>(f8, g);
+                    if ((off & 0xFFu) != 0u || off > (uint32_t)(RD - 4) * 256u)
+                        return false;                               // a whole plane, the granule's four inside planes 1 .. RD
+                    if ((uint32_t)RD * 64u - (off >> 2) != ring_slot_index<RD>(d))
+                        return false;
+                    if ((off == 0u) != ((d & (uint32_t)(RD - 1)) == 0u))
+                        return false;
+                }
+                if (((f + 4u * fn) & 3u) != 0u)
+                    return false;
+            }
+    return true;
+}
+static_assert(ring_turn_off_ok<RING_DWORDS>(), "ring_turn_off disagrees with BitReaderT::slot() / first_plane");
 
 // ---------------------------------------------------------------- cold helpers
 // Synchronous fill of one 64-byte chunk into a lane's ring slots (used after
@@ -444,7 +495,7 @@ struct BitReaderT {
 
     __device__ __forceinline__ uint32_t *slot(uint32_t d) const
     {
-        return ring + ((RD - (d & (RD - 1))) << 6);
+        return ring + ring_slot_index<RD>(d);
     }
     // the stream's 64 bits from the dword of the next unread bit on (big-endian value order): dword d + 1 is one
     // plane below dword d (the mirror plane below dword 31's)
@@ -571,6 +622,12 @@ struct BitReaderT {
     __device__ __forceinline__ void seek_byte(uint64_t byte_pos)
     {
         const uint32_t t = (uint32_t)(byte_pos >> 2);
+        // (the wave's refill does not keep lo_valid in its turns, where nothing reads it: brought up to date here, its
+        //  one reader -- fillpos only grows, so the last fill's bound is the bound)
+        if constexpr (G == 4 && RD > 16) {
+            if (fillpos - lo_valid > (uint32_t)RD)
+                lo_valid = fillpos - RD;
+        }
         if (!((int32_t)(t - lo_valid) >= 0 && (int32_t)(fillpos - t) > 0)) {
             fillpos = t & ~(uint32_t)(G - 1);                   // outside the ring: restart it
             lo_valid = fillpos;
@@ -763,13 +820,18 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
     // sequential pass: the two lanes of a segment exchange their channels here
     constexpr bool XCH = PAIRED;
     __shared__ int32_t s_xch[XCH ? WAVES : 1][MAXCH][XCH ? 64 : 1];
-    __shared__ uint32_t s_nchained[WAVES];          // fast pass: lanes of the wave that stopped on ST_CHAINED
+    // fast pass: lanes of the wave that stopped on ST_CHAINED.  (Not the two-substream lane's: its workgroup has no LDS
+    //  to spare -- with these 8 bytes it stood at 31 240, over the 31 232 at which four workgroups are known to share a
+    //  CU, DESIGN 3.1 -- and counts them from the lanes' status words where the wave is together, `wave_chained` below)
+    __shared__ uint32_t s_nchained[WAVES];
     // per lane and slot, what only the header parser reads of a slot's parameters (cold_word(): filter orders and
     // shifts).  A lane reads and writes its own column only, at block headers: 1.5 KB that leave pk[] to the row loop
     __shared__ uint16_t s_cold[WAVES][NS][64];
 
-    if (threadIdx.x < WAVES)
-        s_nchained[threadIdx.x] = 0;
+    if constexpr (!DUO) {
+        if (threadIdx.x < WAVES)
+            s_nchained[threadIdx.x] = 0;
+    }
     __syncthreads();
 
     const int lane = threadIdx.x & 63;
@@ -1069,6 +1131,13 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
     uint32_t oshift_pack = 0, qss_pack = 0;
     uint32_t qss_A = 0, mmc_A = 0;    // quant step sizes / max_matrix_channel the rematrix works with
     uint32_t gate_turn = 0;               // loop turn for the header gate (wave-uniform)
+    uint32_t wave_chained = 0;            // two-substream lane: lanes of the wave that stopped on ST_CHAINED (wave-uniform)
+    auto n_chained = [&]() -> uint32_t {
+        if constexpr (DUO)
+            return wave_chained;
+        else
+            return __hip_atomic_load(&s_nchained[wv], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    };
     // A segment whose first block carries no restart header: a major sync does not oblige the substreams to restart -- the
     // reference compares the sync's parameters and decodes on with the state it has (src/mlp.c:449-460, 748-753).  A lane
     // that starts at such a segment has no parameters: the stream goes to the sequential pass, which reaches the segment
@@ -1222,11 +1291,20 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
         // the wave pays the parser that much less often.  (Not in the sequential pass, whose lane pairs end access
         // units together.)
         bool hdr_now = active && (rows_left == 0 || (DUO && P0.rows_left == 0));
-        if (HDR_GATE && __builtin_expect(__any(hdr_now), 0)) {
-            const uint64_t m_need = __ballot(hdr_now), m_act = __ballot(active);
+        // (the lanes that need it as the AND of two lane masks, each a compare's own result: the mask of a condition
+        //  that is itself an AND costs a select and a compare to build, wave_mask() above)
+        //  (the two-substream lane's condition is an OR besides: it keeps the ballot of the condition, the per-instance rule)
+        const uint64_t m_need = DUO ? __ballot(hdr_now) : wave_mask(active) & wave_mask(rows_left == 0);
+        if (HDR_GATE && __builtin_expect(m_need != 0ull, 0)) {
+            const uint64_t m_act = __ballot(active);
             const bool go = m_need == m_act || (uint32_t)__popcll(m_need) >= HDR_GATE_LANES ||
                             (gate_turn & (HDR_GATE_TURNS - 1u)) == 0u;
             hdr_now = hdr_now && go;
+            // (every lane of the wave is here, the stopped ones too: the ones that stopped on ST_CHAINED, counted once
+            //  each, for the header phase that follows -- a phase later than a counter in LDS hears of them, and the
+            //  check is a matter of time only)
+            if constexpr (DUO && !PARSE)
+                wave_chained = (uint32_t)__popcll(~m_act & wave_mask((status & (ST_CHAINED | ST_COLD)) == ST_CHAINED));
         }
         gate_turn++;
         // (MU) the parser works on the packed words, mreg[] / mnoise[], like every other instance.  A wave that parses
@@ -1235,6 +1313,8 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
         // alive and not eight.  (Parsed straight into mu[], the sixteen were alive across the phase beside everything
         // the parser needs; the allocator parked matrix 1's in scratch, and their reload's wait -- a wait for every older
         // memory operation, the chunk and the PCM stores among them -- landed in the row's multiply-adds.)
+        // (asked of the lanes again, select and compare: taken from m_need and the gate's verdict, scalar work only, the
+        //  compiler lays the header parser out inside the row loop's hot piece -- docs/history.md A.15)
         const bool hdr_wave = MU && __any(hdr_now);
         if constexpr (MU) {
             if (hdr_wave) {
@@ -1388,7 +1468,7 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
             DVDA_HSTAMP(0);
             if (!GENERAL && !PARSE && active && frames_done < 2 && (frames_done | blocks_in_frame) != 0 &&
                 (__hip_atomic_load(&a.yield_req[segi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ||
-                 __hip_atomic_load(&s_nchained[wv], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= YIELD_LONELY)) {
+                 n_chained() >= YIELD_LONELY)) {
                 // the next segment chains to this one: both go to the chain passes -- or nearly every other lane
                 // of the wave has gone there, and this one would hold the pass for a whole segment's time
                 status |= ST_YIELD;
@@ -1870,7 +1950,7 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                     active = false;
                 } else if (!GENERAL && !PARSE && (status & ST_CHAINED)) {
                     active = false;            // left to the chain passes (needs the previous history)
-                    if (!(DUO && probe))
+                    if constexpr (!DUO)
                         atomicAdd(&s_nchained[wv], 1u);
                     // ... which start one segment earlier if that segment's lane hears of it in time: it is
                     // decoding a whole segment on its own (one lane of many per title) only to hand over its
@@ -1886,7 +1966,7 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                     //  one after the other, this one last; were it otherwise, the check at the next block header
                     //  does the same a block later: it is a matter of time only)
                     if (!GENERAL && !PARSE && frames_done < 2 &&
-                        __hip_atomic_load(&s_nchained[wv], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= YIELD_LONELY) {
+                        n_chained() >= YIELD_LONELY) {
                         status |= ST_YIELD;
                         active = false;
                     }
@@ -2002,8 +2082,10 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
             if (pf)
                 p1 = rd.gsrc[rd.fill_src() >> 2];
         } else if constexpr (WAVE_FILL) {
-            if (__any(active && rd.ahead() <= FILL_TURN)) {
-                const int32_t r = (RD - rd.ahead()) >> 2;
+            // (the dwords ahead, in bits -- a multiple of 32: the test and the granules there is room for from one difference)
+            const int32_t ahead_bits = (int32_t)((rd.fillpos << 5) - (rd.pos & ~31u));
+            if (wave_any(active && ahead_bits <= FILL_TURN * 32)) {
+                const int32_t r = (RD * 32 - ahead_bits) >> 7;
                 fn = active ? (r < 4 ? r : 4) : 0;
                 // past the buffer's end the granules come from its last ones (the spare bytes), as many as are asked for
                 const uint32_t end = rd.max_chunk + (uint32_t)CHUNK_DWORDS;
@@ -2042,7 +2124,7 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
             // ---- bypassed LSBs + residuals for one PCM frame (src/mlp.c:1194-1238)
             // all of the row's bypassed LSBs (at most one per matrix) are cut from the window at once
             // and dealt to their matrices in stream order -- straight-line, no per-bit read
-            if (__any(bypass_mask != 0)) {
+            if (wave_any(bypass_mask != 0)) {
                 const uint32_t cnt = (uint32_t)__popc(bypass_mask);          // <= MAXMAT
                 const uint32_t field = rd.read_resident(cnt);
                 // matrices 0 and 1 (the ones every real stream uses) directly, the rest in a cold loop
@@ -2636,21 +2718,28 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
             }
         } else if constexpr (WAVE_FILL) {
             // behind a branch of the wave's: a row without a turn runs none of it
-            if (__any(fn > 0)) {
-                const uint32_t f = rd.fillpos;
+            if (wave_any(fn > 0)) {
+                // one shift of the turn's first dword; a granule's slot is plane RD less ring_turn_off() bytes, and it
+                // starts the ring -- its first dword to the mirror plane too -- where that is 0 (checked against slot()
+                // and the dword index's own test by ring_turn_off_ok)
+                const uint32_t f = rd.fillpos, f8 = f << 8;
+                char *const top = reinterpret_cast<char *>(rd.ring) + RD * 256;
+                auto put = [&](uint32_t g, const uint4 &p) {
+                    const uint32_t off = ring_turn_off<RD>(f8, g);
+                    ring_store4<RD>(reinterpret_cast<uint32_t *>(top - off), p, off == 0u);
+                };
                 if (fn > 0) {
-                    ring_store4<RD>(rd.slot(f), p0, (f & (RD - 1)) == 0);
+                    put(0u, p0);
                     if (fn > 1) {
-                        ring_store4<RD>(rd.slot(f + 4u), p1, ((f + 4u) & (RD - 1)) == 0);
+                        put(1u, p1);
                         if (fn > 2) {
-                            ring_store4<RD>(rd.slot(f + 8u), p2, ((f + 8u) & (RD - 1)) == 0);
+                            put(2u, p2);
                             if (fn > 3)
-                                ring_store4<RD>(rd.slot(f + 12u), p3, ((f + 12u) & (RD - 1)) == 0);
+                                put(3u, p3);
                         }
                     }
+                    // (lo_valid is not kept here: seek_byte, which alone reads it, brings it up to date)
                     rd.fillpos = f + 4u * (uint32_t)fn;
-                    if (rd.fillpos - rd.lo_valid > (uint32_t)RD)
-                        rd.lo_valid = rd.fillpos - RD;                  // the oldest granules were overwritten
                 }
             }
         } else {
@@ -2676,13 +2765,18 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
         bool coop_out = false;
         if constexpr (ILV && !GENERAL && !PARSE) {
             if (!WAVO && ilv_direct && a.wav_bits == 0u && a.coop_min_seg && n_seg >= a.coop_min_seg)
-                coop_out = __ballot(flush) == ~0ull;
+                coop_out = wave_mask(flush) == ~0ull;
         }
         if (coop_out) {
             // where the lane's own run starts, in int32 elements from a.pcm (one 32-bit word to hand round when the
             // whole wave's fit: a PCM buffer of less than 16 GB; wave-uniform fall-back to two words otherwise)
-            const uint64_t doff = out_base + out_row() * 6u;
-            const bool off32 = !__any((doff >> 32) != 0);
+            // (six times the row as four times and twice it, two shift-and-adds: left to the compiler the product is two
+            //  64-bit multiply-adds and three moves between their register pairs)
+            const uint64_t orow = out_row();
+            uint64_t orow2 = orow << 1;
+            asm("" : "+v"(orow2));
+            const uint64_t doff = out_base + (orow << 2) + orow2;
+            const bool off32 = !wave_any((doff >> 32) != 0);
             const uint32_t d_lo = (uint32_t)doff, d_hi = (uint32_t)(doff >> 32);
             const int32_t *const T0 = &s_out[GENERAL ? 0 : wv][0][0][0];
             // lane l stores piece l mod 6 of the run of lane 10 i + l / 6 in the i-th of seven instructions (lanes 60..63
@@ -2700,22 +2794,36 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                 //      them.  Here the reads of a group are in flight together and the stores wait for them by count.
                 //      (the last instruction is lanes 0 .. 23's, the runs of lanes 60 .. 63: where the wave's mask
                 //      narrows is the only branch left; docs/history.md A.14)
+                //      (fast pass, A.15: a permute's lane is the instruction's own byte offset, 40 it7, on ONE address
+                //      register, 4 (l / 6) -- __shfl() masks and shifts an index of its own for each of the seven; lanes
+                //      24 and up of the seventh name a lane past 63 and rest)
                 uint32_t bo[7];
+                const uint32_t l6x4 = l6 << 2;
 #pragma unroll
                 for (uint32_t it7 = 0; it7 < 7u; it7++)
-                    bo[it7] = (uint32_t)__shfl((int)d_lo, (int)(l6 + 10u * it7), 64);
-                int32_t *const ob = a.pcm + pc * 4u;
+                    bo[it7] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(l6x4 + 40u * it7), (int)d_lo);
+                // a store's address is the lane's piece of the buffer and four bytes times the run's offset: one 32 x 32 + 64
+                // multiply-add with the four in a scalar register the optimizer cannot see through -- as a shift it is a
+                // 64-bit shift-and-add on a register pair whose high half a move has to clear first, seven times
+                char *const ob = reinterpret_cast<char *>(a.pcm + pc * 4u);
+                uint32_t four = 4u;
+                asm("" : "+s"(four));
+                auto at = [&](uint32_t k) { return reinterpret_cast<int32_t *>(ob + (uint64_t)bo[k] * four); };
                 if (l60) {
                     // (a piece's four values through an index of its own, hidden from the optimizer: with one base for all
                     //  the reads of a group it pairs them by offset -- planes of two pieces in one ds_read2_b32 -- and
                     //  then moves every value into its store's register quad, sixteen v_mov for four pieces)
-                    const uint32_t ti = pc * (4u * PS) + l6;
+                    // (A.15: that index is the LDS address of the lane's first value itself, worked out once a flush and
+                    //  hidden again in place in front of every piece -- no instruction; an index copied and scaled for
+                    //  each piece was a move and a shift-and-add, seven times)
+                    typedef const int32_t __attribute__((address_space(3))) *lds_i32p;
+                    uint32_t ta = (uint32_t)(uintptr_t)(T0 + pc * (4u * PS) + l6);
                     auto piece = [&](uint32_t k, int32_t(&q)[4]) {
-                        uint32_t tk = ti;
-                        asm volatile("" : "+v"(tk));          // (volatile: or the seven become one again)
+                        asm volatile("" : "+v"(ta));          // (volatile: or the seven become one again)
+                        const lds_i32p Tk = (lds_i32p)ta;
 #pragma unroll
                         for (uint32_t j = 0; j < 4u; j++)
-                            q[j] = T0[tk + 10u * k + j * PS];
+                            q[j] = Tk[10u * k + j * PS];
                     };
                     int32_t v[4][4];
 #pragma unroll
@@ -2723,7 +2831,7 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                         piece(k, v[k]);
 #pragma unroll
                     for (uint32_t k = 0; k < 4u; k++)
-                        DVDA_STORE_V4_COOP(ob + bo[k], v[k][0], v[k][1], v[k][2], v[k][3]);
+                        DVDA_STORE_V4_COOP(at(k), v[k][0], v[k][1], v[k][2], v[k][3]);
                     const bool last = lane < 24;
 #pragma unroll
                     for (uint32_t k = 0; k < 2u; k++)
@@ -2732,9 +2840,9 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
                         piece(6u, v[2]);
 #pragma unroll
                     for (uint32_t k = 0; k < 2u; k++)
-                        DVDA_STORE_V4_COOP(ob + bo[4u + k], v[k][0], v[k][1], v[k][2], v[k][3]);
+                        DVDA_STORE_V4_COOP(at(4u + k), v[k][0], v[k][1], v[k][2], v[k][3]);
                     if (last)
-                        DVDA_STORE_V4_COOP(ob + bo[6], v[2][0], v[2][1], v[2][2], v[2][3]);
+                        DVDA_STORE_V4_COOP(at(6u), v[2][0], v[2][1], v[2][2], v[2][3]);
                 }
             } else {
             // ---- a PCM buffer of 16 GB and more: two words per run, piece by piece

@@ -32,6 +32,14 @@ loop.  A row has no loop of its own; what loops there is the end of a block or a
 line under a lane mask that is empty in all but one row of a block.  The regions above and their numbers are what they
 were.
 
+Behind the row tail come the REST of the loop -- the blocks "other" lumps together and the latch the compiler lays out
+in front of the header, by sub-region (rest_regions: loop control, row gate and block bookkeeping, refill test,
+bypassed LSBs, the commit's test and end, flush decision, flush offsets and addresses, the flush lane by lane, the
+row tail's own blocks, cold code) -- and the TURNS: the path of a lockstep wave through one turn of the loop for a
+plain row, a row that requests and commits a refill, and a row that flushes (turn_path, whose docstring has the
+rules by which the static walk decides a branch), each with the part of it that lies outside the slots, the slot
+masks and the row tail.  tests/test_isa_row_rest.py holds that part to profiles/isa_mix_row_rest_{before,after}.txt.
+
 tests/test_isa_budget.py imports this module and holds every build to what profiles/isa_mix_after.txt records;
 tests/test_isa_row_tail.py holds the row tail to profiles/isa_mix_row_tail_{before,after}.txt."""
 import collections
@@ -288,6 +296,270 @@ def row_tail_path(blocks, loop_blocks):
     return []
 
 
+TURNS = ("plain", "refill", "flush")
+REST_REGIONS = ("loop control", "row gate and block bookkeeping", "refill test", "bypassed LSBs", "commit test and end",
+                "flush decision", "flush offsets and addresses", "flush lane by lane", "row tail's blocks", "cold")
+
+
+def _has(b, pred):
+    return any(pred(_b(o), a) for o, a, _ in b.ins)
+
+
+def _is_slot(b):
+    return _has(b, lambda o, a: o == "v_ffbh_u32") and _has(b, lambda o, a: o == "v_lshlrev_b64")
+
+
+def _is_pack(b):
+    """a block that only packs or unpacks registers: the save and restore round cold code laid out elsewhere"""
+    ops = [_b(o) for o, _, _ in b.ins if o not in ("s_waitcnt", "s_nop")]
+    return len(ops) >= 8 and all(o in ("v_and_b32", "v_lshl_or_b32", "v_bfe_i32", "v_ashrrev_i32") for o in ops)
+
+
+def _is_store(o, a=""):
+    return o.startswith("global_store") or o.startswith("flat_store")
+
+
+def _is_load(o, a=""):
+    return o.startswith("global_load") or o.startswith("flat_load")
+
+
+def _wait_block(blocks, loop_blocks):
+    """-> name of the block with the hand-written wait for the chunk (the end of the row tail), or None"""
+    tail = row_tail_path(blocks, loop_blocks)
+    return tail[-1].name if tail else None
+
+
+def latch_blocks(blocks, loop_blocks):
+    """-> [Block]: what the compiler laid out in front of the row loop's header for the branch back (loop control)"""
+    order = {b.name: j for j, b in enumerate(blocks)}
+    head, out, j = loop_blocks[0].name, [], order[loop_blocks[0].name] - 1
+    while j > 0 and blocks[j].loop == head and len(blocks[j].ins) <= 6:
+        out.insert(0, blocks[j])
+        j -= 1
+    return out
+
+
+def rest_regions(blocks, loop_blocks):
+    """-> ordered {sub-region: [Block]}: the blocks regions() calls "other", and the latch in front of the header, by
+    where they lie in the loop's hot piece and by what they hold (static counts, as regions() gives them)."""
+    reg = regions(loop_blocks)
+    other = {b.name for b in reg.get("other", [])}
+    head = loop_blocks[0].name
+    idx = {b.name: j for j, b in enumerate(loop_blocks)}
+    slots = [j for j, b in enumerate(loop_blocks) if _is_slot(b)]
+    wait = _wait_block(blocks, loop_blocks)
+    wait_at = idx.get(wait, len(loop_blocks))
+    inner = [j for j, b in enumerate(loop_blocks) if b.loop != head and slots and j < slots[0]]
+    top_end = inner[-1] if inner else -1
+    gate_at = next((j for j in range(slots[0] - 1, -1, -1) if any(
+        o.startswith("s_cbranch") and a.strip().lstrip(".L") == wait for o, a, _ in loop_blocks[j].ins)), -1) if slots else -1
+    perm = [j for j, b in enumerate(loop_blocks) if _has(b, lambda o, a: o == "v_perm_b32") and j > wait_at]
+    stores = [j for j, b in enumerate(loop_blocks) if _has(b, _is_store) and j > wait_at]
+    coop = [j for j, b in enumerate(loop_blocks) if _has(b, lambda o, a: o == "ds_bpermute_b32") and j > wait_at]
+    coop_end = max([j for j in stores if coop and j < coop[0] + 8] or [-1])
+    out = collections.OrderedDict((r, []) for r in REST_REGIONS)
+    out["loop control"] += latch_blocks(blocks, loop_blocks)
+    for j, b in enumerate(loop_blocks):
+        if b.name not in other:
+            continue
+        if b.loop != head or _is_pack(b):
+            r = "cold"
+        elif slots and j < slots[0]:
+            if _has(b, lambda o, a: o == "v_bcnt_u32_b32"):
+                r = "bypassed LSBs"
+            elif top_end < j < gate_at:
+                r = "refill test"
+            else:
+                r = "row gate and block bookkeeping"
+        elif j < wait_at:
+            r = "row tail's blocks"
+        elif j == wait_at or (perm and j <= perm[-1] + 1):
+            r = "commit test and end"
+        elif _has(b, lambda o, a: o in ("ds_bpermute_b32", "v_mad_u64_u32")) and (not coop or j <= coop_end):
+            r = "flush offsets and addresses"
+        elif (coop and j <= coop_end + 2) or (not coop and stores and j <= stores[0]):
+            r = "flush decision"
+        else:
+            r = "flush lane by lane"
+        out[r].append(b)
+    return out
+
+
+def turn_path(blocks, loop_blocks, turn):
+    """-> [Block]: what a lockstep wave executes in one turn of the row loop, header to the branch back, as (partial)
+    blocks; `turn` is "plain" (no refill, no flush), "refill" (the wave requests and commits granules) or "flush".
+
+    A static walk, so every branch is decided by what lies on its two sides -- the blocks reachable from one side and
+    not from the other, inside the loop's hot piece:
+      * a side is left out when it leads out of the hot piece (cold code laid out behind it), into an inner loop (the
+        synchronous top-up), into a block that only packs registers (the save and restore round the header parser),
+        to the branch back before the row is decoded, to loads or the ring's byte swap in a turn that does not
+        refill, or to the flush (lane permutes, 64-bit multiplies, stores) in a turn that does not flush or has
+        flushed already;
+      * a branch on the execution mask otherwise goes where a mask with lanes in it goes (s_cbranch_execz falls
+        through, s_cbranch_execnz is taken): the wave walks its masked blocks;
+      * a scalar branch otherwise goes to the side nearer to what the turn is about -- the test that every lane
+        flushes (s_cmp_eq_u64 vcc, -1), the loads and swaps of a refill, the permutes and stores of a flush -- and
+        falls through when neither side is.
+    Between the first slot and the hand-written wait this is the row tail's rule (row_tail_path); report() checks
+    that the two agree.  SQ_INSTS_VALU per launch is the check on the whole walk (docs/history.md A.15)."""
+    if not loop_blocks:
+        return []
+    order = {b.name: j for j, b in enumerate(blocks)}
+    piece = {b.name for b in loop_blocks}
+    head = loop_blocks[0].name
+    h = order[head]
+    latch = {b.name for b in latch_blocks(blocks, loop_blocks)}
+    wait = _wait_block(blocks, loop_blocks)
+    state = dict(past_wait=False, stored=False, flushed=False)
+
+    def tgt(a):
+        return a.strip().lstrip(".L")
+
+    def edges(j, pos):
+        """-> successor block indices of blocks[j] from instruction `pos` on (None: out of the hot piece or back)"""
+        out = []
+        for o, a, _ in blocks[j].ins[pos:]:
+            if o == "s_branch" or o.startswith("s_cbranch"):
+                out.append(order[tgt(a)] if tgt(a) in piece else None)
+                if o == "s_branch":
+                    return out
+            if o in ("s_endpgm", "s_setpc_b64"):
+                return out
+        out.append(j + 1 if j + 1 < len(blocks) and blocks[j + 1].name in piece else None)
+        return out
+
+    def reach(starts):
+        seen, todo = set(), [s for s in starts if s is not None]
+        while todo:
+            j = todo.pop()
+            if j in seen or j == h:
+                continue
+            seen.add(j)
+            todo += [e for e in edges(j, 0) if e is not None]
+        return seen
+
+    def unwanted(b):
+        if b.loop != head or _is_pack(b):
+            return True
+        if turn != "refill" and (_has(b, _is_load) or _has(b, lambda o, a: o == "v_perm_b32")):
+            return True
+        if (turn != "flush" or state["flushed"]) and (_has(b, _is_store) or
+                                                       _has(b, lambda o, a: o in ("ds_bpermute_b32", "v_mad_u64_u32"))):
+            return True
+        return False
+
+    def wanted(b):
+        if _has(b, lambda o, a: o == "s_cmp_eq_u64" and a.replace(" ", "") == "vcc,-1"):
+            return True
+        if turn == "refill" and (_has(b, _is_load) or _has(b, lambda o, a: o == "v_perm_b32")):
+            return True
+        return turn == "flush" and not state["flushed"] and (
+            _has(b, _is_store) or _has(b, lambda o, a: o in ("ds_bpermute_b32", "v_mad_u64_u32")))
+
+    def side(starts, direct_out, other):
+        """-> (left out?, distance to what the turn is about) of the side that starts at block indices `starts`"""
+        if direct_out:
+            return True, None
+        mine = reach(starts) - other
+        if any(unwanted(blocks[j]) for j in mine):
+            return True, None
+        dist, front, seen = 0, [s for s in starts if s in mine], set()
+        while front:
+            if any(wanted(blocks[j]) for j in front):
+                return False, dist
+            seen |= set(front)
+            front = [e for j in front for e in edges(j, 0) if e in mine and e not in seen]
+            dist += 1
+        return False, None
+
+    path, j, seen = [], h, set()
+    while j is not None and j not in seen:
+        seen.add(j)
+        b = blocks[j]
+        if b.name == wait:
+            state["past_wait"] = True
+        part, nxt = [], (j + 1 if j + 1 < len(blocks) else None)
+        for pos, (op, operands, in_asm) in enumerate(b.ins):
+            part.append((op, operands, in_asm))
+            if _is_store(_b(op)):
+                state["stored"] = True
+            if op == "s_branch":
+                nxt = order.get(tgt(operands))
+                break
+            if op in ("s_endpgm", "s_setpc_b64"):
+                nxt = None
+                break
+            if not op.startswith("s_cbranch"):
+                continue
+            t = tgt(operands)
+            back = t in latch or t == head
+            t_out = t not in piece and not back
+            rest = edges(j, pos + 1)
+            if back:
+                # the branch back: taken once the row is decoded and nothing the turn is about lies just ahead
+                front, near = [e for e in rest if e is not None], False
+                for _ in range(8):
+                    near = near or any(wanted(blocks[e]) for e in front)
+                    front = [e for x in front for e in edges(x, 0) if e is not None]
+                take = state["past_wait"] and not near
+            elif t_out or rest == [None]:
+                take = not t_out                 # one side leaves the hot piece: the other one
+            else:
+                r_t = reach([order[t]])
+                r_f = reach(rest)
+                out_t, d_t = side([order[t]], False, r_f)
+                out_f, d_f = side(rest, False, r_t)
+                if out_t != out_f:
+                    take = out_f
+                elif "exec" in op:
+                    take = op.endswith("execnz")
+                elif (d_t is None) != (d_f is None):
+                    take = d_f is None
+                else:
+                    take = d_t is not None and d_t < d_f
+            if take:
+                nxt = order.get(t)
+                break
+        path.append(Block(b.name, b.loop, part))
+        if state["stored"] and all(o.startswith("s_") for o, _, _ in part):
+            state["flushed"] = True              # a block of scalar work only behind a store: the turn has flushed
+        if nxt is not None and blocks[nxt].name in latch:
+            while nxt < h:                     # the latch in front of the header closes the turn
+                path.append(blocks[nxt])
+                nxt += 1
+            break
+        j = nxt
+    return path
+
+
+def analyse_turns(path, rates=None):
+    """-> {instance: {turn: dict(whole=mix, slots=mix, tail=mix, rest=mix, blocks=[names], tail_agrees=bool)}}"""
+    rates = rates or Rates()
+    res = collections.OrderedDict()
+    for name, info, blocks, parents in kernels(path):
+        head, lb = row_loop(blocks, parents)
+        if head is None or not any(_b(o) == "v_mad_i64_i32" for b in lb for o, _, _ in b.ins):
+            continue
+        tail = row_tail_path(blocks, lb)
+        if not tail:
+            continue
+        reg = regions(lb)
+        slot_names = {b.name for r, bs in reg.items() if r.startswith("slot") for b in bs}
+        tail_names = {b.name for b in tail}
+        res[name] = collections.OrderedDict()
+        for turn in TURNS:
+            p = turn_path(blocks, lb, turn)
+            mine = [b for b in p if b.name in tail_names]
+            res[name][turn] = dict(
+                whole=mix(p, rates), slots=mix([b for b in p if b.name in slot_names], rates), tail=mix(mine, rates),
+                rest=mix([b for b in p if b.name not in slot_names and b.name not in tail_names], rates),
+                blocks=[b.name for b in p],
+                tail_agrees=[b.name for b in mine] == [b.name for b in tail] and
+                [len(b.ins) for b in mine[:-1]] == [len(b.ins) for b in tail[:-1]])
+    return res
+
+
 def vmcnt_waits_beside_mads(loop_blocks):
     """-> [(block name, operands)]: every s_waitcnt that waits for vector memory in a row-loop block that holds a
     v_mad_i64_i32 -- the filter's and the rematrix's multiply-adds must not wait for the chunk or for the PCM stores"""
@@ -388,6 +660,47 @@ def report(path, out=sys.stdout):
     if HEADLINE in tails:
         w("   headline, VALU: %s\n" % ", ".join("%s %d" % (o, n) for o, n in tails[HEADLINE]["hist"].most_common()
                                                  if o.startswith("v_")))
+    report_rest(path, rates, out)
+
+
+def report_rest(path, rates, out):
+    """the row loop outside the slots and the row tail: "other" by sub-region (static), and the three kinds of turn"""
+    w = out.write
+    turns = analyse_turns(path, rates)
+    w("\n== the rest of the row loop: \"other\" and the latch in front of the header, by sub-region (static counts)\n")
+    for name, info, blocks, parents in kernels(path):
+        head, lb = row_loop(blocks, parents)
+        if name not in turns or not all(t["tail_agrees"] for t in turns[name].values()):
+            continue
+        w("   %s\n" % name)
+        w("   %-34s %6s %6s %6s %6s %7s %10s\n" % ("sub-region", "instr", "VALU", "fast", "slow", "unclass", "w.cycles"))
+        for r, bs in rest_regions(blocks, lb).items():
+            m = mix(bs, rates)
+            w("   %-34s %6d %6d %6d %6d %7d %10.0f\n" % (r, m["total"], m["valu"], m["fast"], m["slow"], m["unclassified"],
+                                                        m["cycles"]))
+    w("\n== turns: what a lockstep wave executes from the loop's header to the branch back (cold branches left out), and the\n"
+      "   part of it outside the slots, the slot masks and the row tail (\"rest\")\n")
+    w("   %-52s %-7s %6s %6s | %6s %6s %6s %6s %7s %10s\n" % ("instance", "turn", "instr", "VALU", "rest", "VALU", "fast", "slow",
+                                                            "unclass", "w.cycles"))
+    for name, t in turns.items():
+        if not all(d["tail_agrees"] for d in t.values()):
+            w("   %-52s (no walk: the row tail is not met on the way -- two substreams a lane)\n" % name)
+            continue
+        for turn in TURNS:
+            d, r = t[turn]["whole"], t[turn]["rest"]
+            w("   %-52s %-7s %6d %6d | %6d %6d %6d %6d %7d %10.0f\n" % (name, turn, d["total"], d["valu"], r["total"], r["valu"],
+                                                                       r["fast"], r["slow"], r["unclassified"], r["cycles"]))
+        p, f, x = (t[k]["rest"] for k in TURNS)
+        for share, label in ((0.25, "1/4"), (0.2, "1/5")):
+            w("   %-52s per row, refill share %s, flush 1/4: rest VALU %.1f, w.cycles %.0f\n" % (
+                "", label, p["valu"] + share * (f["valu"] - p["valu"]) + 0.25 * (x["valu"] - p["valu"]),
+                p["cycles"] + share * (f["cycles"] - p["cycles"]) + 0.25 * (x["cycles"] - p["cycles"])))
+    if HEADLINE in turns:
+        for turn in TURNS:
+            d = turns[HEADLINE][turn]
+            w("   headline, %s turn walks: %s\n" % (turn, " ".join(d["blocks"])))
+            w("   headline, %s turn, rest VALU: %s\n" % (turn, ", ".join(
+                "%s %d" % (o, n) for o, n in d["rest"]["hist"].most_common() if o.startswith("v_"))))
 
 
 def main():
