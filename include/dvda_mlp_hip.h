@@ -588,6 +588,74 @@ int dvda_mlp_hip_pcm_levels(dvda_mlp_hip_ctx *ctx, const int32_t *d_pcm, const u
  * neutral (its zero min / max do not reach the result).  Either operand may be `out`.  Host arithmetic; needs no device. */
 void dvda_pcm_hip_levels_combine(const dvda_pcm_levels *a, const dvda_pcm_levels *b, dvda_pcm_levels *out);
 
+/* ------------------------------------------------------------------ compare of two PCM buffers
+ * The third report: when two digests disagree -- two rips of one disc, a concealed track against a good one, a variant
+ * build against its parent, the planar against the frame-major instance of a kernel -- where do the two differ, in which
+ * channels, and by how much; answered on the device from both int32 buffers where they lie (csrc/pcm_compare.h,
+ * DESIGN.md section 14), 160 bytes per stream pair instead of two payloads.  Exact and the same from run to run.
+ *
+ * The contract.  Two sides, A and B, each with its own buffer, its own layout (DVDA_PCM_PLANAR or DVDA_PCM_INTERLEAVED,
+ * chosen per side: all four combinations) and its own descriptor array (the digest's descriptor, unchanged).  Stream i
+ * of A is compared with stream i of B over the first `compared` = min(frames_a, frames_b) frames; frames at and behind
+ * `compared` on the longer side are not read, and nothing outside a stream's `frames` is read on either side.
+ *   bits == 0           the values are compared as the int32 they are; |a - b| is taken in 64 bits, so it is at most
+ *                       2^32 - 1 and fits max_abs
+ *   bits == 16, 20, 24  each value is first taken as it would be written: w(v) = (v & (2^(bits-1) - 1)) -
+ *                       (v < 0 ? 2^(bits-1) : 0), write_signed(bits) read back -- the digest's rule, not plain
+ *                       truncation; two values that give the same WAV sample are equal, |w(a) - w(b)| is the difference
+ *   any other bits      DVDA_HIP_EINVAL
+ * Entries at index `channels` and above are 0.  The result is the same for every combination of layouts, for any 4-byte
+ * alignment of either side's `off` independently of the other's, and for any parity of a planar stride.
+ *
+ * The kernels cut a pair into tiles of DVDA_CMP_TILE_FRAMES frames, aligned to the streams' START.
+ *
+ * Out of scope: the WAV layouts (DVDA_HIP_EINVAL on either side), the disc tier (its readers keep PCM on the host once
+ * they are open, and windowed readers' windows do not line up between two discs), the streaming tier and
+ * dvda_mlp_hip_decode_multi, a search for a lag between the sides (a caller shifts off / frames in a descriptor), a merge
+ * that fills one rip's concealed spans from another (this report is its first step). */
+#define DVDA_CMP_TILE_FRAMES 4096u
+#define DVDA_CMP_SHAPE 1u          /* flags: nothing was compared: the channel counts differ, or a descriptor
+                                      is one the reports do not take (channels outside 1..8, frames > 2^40) */
+typedef struct dvda_pcm_diff {
+    uint64_t frames_a, frames_b;   /* as the descriptors say (0 for a descriptor that is not taken) */
+    uint64_t compared;             /* min(frames_a, frames_b); 0 with DVDA_CMP_SHAPE */
+    uint64_t diff_frames;          /* frames f < compared in which at least one channel differs */
+    uint64_t first_diff;           /* the smallest such f; == compared when there is none */
+    uint64_t diff_end;             /* the largest such f, + 1; 0 when there is none */
+    uint64_t runs;                 /* maximal runs of consecutive differing frames */
+    uint64_t diff_values[8];       /* per channel (RIFF-WAVE order, as in the buffers): values that differ */
+    uint32_t max_abs[8];           /* per channel: the largest |a - b| */
+    uint32_t channels, flags;      /* the pair's channel count (0 with DVDA_CMP_SHAPE); DVDA_CMP_* */
+} dvda_pcm_diff;                   /* 160 bytes */
+
+/* The tier-free form: d_diff[i] = the comparison of stream d_desc_a[i] of d_a (in layout_a) with stream d_desc_b[i] of
+ * d_b (in layout_b); device arrays, n entries each.  Enqueued on `stream`: no host wait, no allocation.
+ * max_total_frames: a bound the host knows on the sum of `compared` over all pairs -- the launch and d_work are sized by
+ * it; a pair whose tiles fall outside it is reported as a zeroed struct, never read out of bounds.  d_work:
+ * dvda_pcm_hip_compare_workspace_words(n, max_total_frames) uint32 words, which need not be cleared between calls (no
+ * atomics: every word the join reads was stored by the same call).  The arguments are judged first, on any machine --
+ * DVDA_HIP_EINVAL: bits other than 0 / 16 / 20 / 24, a WAV layout on either side, a null pointer, work_words too small;
+ * DVDA_HIP_ECAPACITY: 2^31 tiles or more -- then the device: DVDA_HIP_ENODEV without one. */
+size_t dvda_pcm_hip_compare_workspace_words(uint32_t n, uint64_t max_total_frames);
+int dvda_pcm_hip_compare(const int32_t *d_a, uint32_t layout_a, const dvda_pcm_crc_desc *d_desc_a,
+                         const int32_t *d_b, uint32_t layout_b, const dvda_pcm_crc_desc *d_desc_b,
+                         uint32_t n, unsigned bits, uint64_t max_total_frames, dvda_pcm_diff *d_diff,
+                         uint32_t *d_work, size_t work_words, void *stream);
+/* behind dvda_mlp_hip_decode (blocks): side A = the first n streams of the context's last decode, frames and
+ * channels as dvda_mlp_hip_stream_info reports them (conceal mode's composed stream and the presentation count as
+ * they are; a stream with DVDA_ST_OVERFLOW is an empty side); side B = the caller's buffer, layout and DEVICE
+ * descriptor array.  DVDA_HIP_EINVAL on a context that writes a WAV layout. */
+int dvda_mlp_hip_pcm_compare(dvda_mlp_hip_ctx *ctx, const int32_t *d_pcm, const uint64_t *d_out_off,
+                             const uint64_t *d_out_stride, const int32_t *d_other, uint32_t other_layout,
+                             const dvda_pcm_crc_desc *d_other_desc, unsigned bits, dvda_pcm_diff *host_diff,
+                             uint32_t n, void *stream);
+/* diff(A1 || A2, B1 || B2) from the diffs of the two pieces; host arithmetic, no device; either operand may be out.
+ * An operand with frames_a == frames_b == 0 and no flag is neutral.  Otherwise DVDA_HIP_EINVAL, `out` left alone, when
+ * the first operand has frames_a != frames_b (the pieces would not line up), when the operands' channel counts differ,
+ * or when either carries DVDA_CMP_SHAPE.  Counts add, max_abs is the maximum, first_diff / diff_end move by a.compared,
+ * and a run that crosses the seam counts once. */
+int dvda_pcm_hip_diff_combine(const dvda_pcm_diff *a, const dvda_pcm_diff *b, dvda_pcm_diff *out);
+
 /* ------------------------------------------------------------------ tier B */
 /* The mlp.h mirror: same three calls, same meaning as reference src/mlp.h:29-42 /
  * src/mlp.c:265-354, with the reference's containers replaced by plain memory:

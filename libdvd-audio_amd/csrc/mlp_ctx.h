@@ -123,11 +123,12 @@ struct dvda_mlp_hip_ctx {
     DevBuf<uint32_t> d_brec;
     DevBuf<uint32_t> d_frec;
     uint32_t iir_lanes;
-    // dvda_mlp_hip_pcm_crc32 / dvda_mlp_hip_pcm_levels (pcm_report_run.h): grown on first use, and the same three for
-    // both reports.  What one report left in them is the other's to overwrite: a report reads no word of the workspace
-    // or the result block that the same call has not stored (both tests named test_poisoned_workspace pin that).
+    // dvda_mlp_hip_pcm_crc32 / dvda_mlp_hip_pcm_levels / dvda_mlp_hip_pcm_compare (pcm_report_run.h): grown on first use,
+    // and the same three for every report.  What one report left in them is the next one's to overwrite: a report reads
+    // no word of the workspace or the result block that the same call has not stored (the tests named
+    // test_poisoned_workspace and test_deterministic_on_a_poisoned_workspace pin that).
     DevBuf<dvda_pcm_crc_desc> d_rep_desc;   // [streams]
-    DevBuf<uint64_t> d_rep_out;         // the results, laid out by the report (CrcReport::in / LvlReport::in)
+    DevBuf<uint64_t> d_rep_out;         // the results, laid out by the report (CrcReport::in / LvlReport::in / CmpReport::in)
     DevBuf<uint32_t> d_rep_work;
     DecodeSettings set;
     // call state

@@ -15,7 +15,7 @@
 //
 // Host code beside the core, each in a header included here: hip_ws.h (owning buffers and handles), mlp_ctx.h (the
 // context), mlp_conceal_run.h, mlp_present_run.h (the two modes), mlp_stepper.h (streaming tier), mlp_tiers.h (raw PCM,
-// demux, WAV payload), pcm_report_run.h (the reports of the decoded PCM: its CRC-32, its levels).
+// demux, WAV payload), pcm_report_run.h (the reports of the decoded PCM: its CRC-32, its levels, its compare with another buffer).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -39,6 +39,7 @@
 #include "wav_pack.h"
 #include "pcm_digest.h"
 #include "pcm_levels.h"
+#include "pcm_compare.h"
 
 #include "mlp_ctx.h"
 #include "mlp_conceal_run.h"

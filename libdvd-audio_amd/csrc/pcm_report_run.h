@@ -1,10 +1,11 @@
-// pcm_report_run.h -- host side of the reports of decoded PCM, the digest (pcm_digest.h) and the level report
-// (pcm_levels.h): what a report is to the driver, the one driver of the flat tile list (pcm_tiles.h), the one call that
+// pcm_report_run.h -- host side of the reports of decoded PCM, the digest (pcm_digest.h), the level report
+// (pcm_levels.h) and the compare (pcm_compare.h): what a report is to the driver, the one driver of the flat tile list (pcm_tiles.h), the one call that
 // runs a report behind a decode on the context's own buffers, and the host arithmetic that joins two pieces' results.
 #pragma once
 #include <vector>
 
 #include "mlp_ctx.h"
+#include "pcm_compare.h"
 #include "pcm_digest.h"
 #include "pcm_levels.h"
 
@@ -86,6 +87,45 @@ struct LvlReport {
     }
 };
 static_assert(sizeof(dvda_pcm_levels) % sizeof(uint64_t) == 0, "reports lie in a block of uint64 words");
+
+// The compare: side A is what the driver calls the PCM; side B -- buffer, layout, descriptors -- travels here.
+struct CmpReport {
+    static constexpr uint32_t TILE = cmp::TILE, TILE_WORDS = cmp::REC, TILE_BLOCKS = cmp::TILE_BLOCKS;     // unit: frames
+    dvda_pcm_diff *d_diff;
+    const int32_t *d_b;
+    uint32_t layout_b;
+    const dvda_pcm_crc_desc *d_desc_b;
+
+    static bool int32_layout(uint32_t layout) { return layout == DVDA_PCM_PLANAR || layout == DVDA_PCM_INTERLEAVED; }
+    bool has_out() const { return d_diff && d_b && d_desc_b && int32_layout(layout_b); }
+    static bool takes(uint32_t layout, unsigned bits)
+    {
+        return (bits == 0 || bits == 16 || bits == 20 || bits == 24) && int32_layout(layout);
+    }
+    // (side A's frames: at least what the pair compares)
+    static uint64_t units(const dvda_pcm_crc_desc &d, unsigned) { return d.frames; }
+    static size_t out_words(uint32_t n) { return (size_t)n * (sizeof(dvda_pcm_diff) / sizeof(uint64_t)); }
+    CmpReport in(uint64_t *d_out, uint32_t) const { return CmpReport{(dvda_pcm_diff *)d_out, d_b, layout_b, d_desc_b}; }
+
+    void plan(hipStream_t st, const dvda_pcm_crc_desc *d_desc, uint32_t n, unsigned, uint32_t *cnt) const
+    {
+        hipLaunchKernelGGL(cmp::k_cmp_plan, dim3((n + 255) / 256), dim3(256), 0, st, d_desc, d_desc_b, n, cnt);
+    }
+    void tiles(dim3 grid, dim3 block, hipStream_t st, const int32_t *d_a, uint32_t layout, const dvda_pcm_crc_desc *d_desc,
+               uint32_t n, unsigned bits, const uint32_t *base, uint32_t *rec, uint32_t max_tiles) const
+    {
+        const bool pa = layout == DVDA_PCM_PLANAR, pb = layout_b == DVDA_PCM_PLANAR;
+        auto k = pa ? (pb ? cmp::k_cmp_tiles<true, true> : cmp::k_cmp_tiles<true, false>)
+                    : (pb ? cmp::k_cmp_tiles<false, true> : cmp::k_cmp_tiles<false, false>);
+        hipLaunchKernelGGL(k, grid, block, 0, st, d_a, d_desc, d_b, d_desc_b, n, (uint32_t)bits, base, rec, max_tiles);
+    }
+    void join(dim3 block, hipStream_t st, const dvda_pcm_crc_desc *d_desc, uint32_t n, unsigned, const uint32_t *base,
+              const uint32_t *rec, uint32_t max_tiles) const
+    {
+        hipLaunchKernelGGL(cmp::k_cmp_join, dim3(n), block, 0, st, d_desc, d_desc_b, n, base, rec, max_tiles, d_diff);
+    }
+};
+static_assert(sizeof(dvda_pcm_diff) == 160, "dvda_pcm_diff is 160 bytes");
 
 // ---- the driver of the flat tile list
 // tiles the list can hold for n streams of max_total units in all: every stream has at most one ragged tile
@@ -183,7 +223,7 @@ static int report_of_decode(dvda_mlp_hip_ctx *c, const int32_t *d_pcm, const uin
         (rc = c->d_rep_work.grow(report_workspace_words<R>(n, total))) != 0)
         return rc;
     HIP_TRY(hipMemcpy(c->d_rep_desc, desc.data(), (size_t)n * sizeof(dvda_pcm_crc_desc), hipMemcpyHostToDevice));
-    *r = R::in(c->d_rep_out, n);
+    *r = r->in(c->d_rep_out, n);            // (a report that carries more than its results keeps it)
     return report_run(*r, d_pcm, c->set.pcm_layout, bits, c->d_rep_desc, n, total, c->d_rep_work,
                       (size_t)c->d_rep_work.cap, stream_);
 }
@@ -273,4 +313,70 @@ extern "C" void dvda_pcm_hip_levels_combine(const dvda_pcm_levels *a_, const dvd
         r.max[c] = a.max[c] > b.max[c] ? a.max[c] : b.max[c];
     }
     *out = r;
+}
+
+// ---- the compare
+extern "C" size_t dvda_pcm_hip_compare_workspace_words(uint32_t n, uint64_t max_total_frames)
+{
+    return report_workspace_words<CmpReport>(n, max_total_frames);
+}
+
+extern "C" int dvda_pcm_hip_compare(const int32_t *d_a, uint32_t layout_a, const dvda_pcm_crc_desc *d_desc_a,
+                                    const int32_t *d_b, uint32_t layout_b, const dvda_pcm_crc_desc *d_desc_b, uint32_t n,
+                                    unsigned bits, uint64_t max_total_frames, dvda_pcm_diff *d_diff, uint32_t *d_work,
+                                    size_t work_words, void *stream_)
+{
+    return report_run(CmpReport{d_diff, d_b, layout_b, d_desc_b}, d_a, layout_a, bits, d_desc_a, n, max_total_frames, d_work,
+                      work_words, stream_);
+}
+
+extern "C" int dvda_mlp_hip_pcm_compare(dvda_mlp_hip_ctx *c, const int32_t *d_pcm, const uint64_t *d_out_off,
+                                        const uint64_t *d_out_stride, const int32_t *d_other, uint32_t other_layout,
+                                        const dvda_pcm_crc_desc *d_other_desc, unsigned bits, dvda_pcm_diff *host_diff,
+                                        uint32_t n, void *stream_)
+{
+    CmpReport r{nullptr, d_other, other_layout, d_other_desc};
+    if (!c || !d_pcm || !d_out_off || !d_out_stride || !host_diff || !d_other || !d_other_desc ||
+        !CmpReport::int32_layout(other_layout) || !CmpReport::takes(c->set.pcm_layout, bits))
+        return DVDA_HIP_EINVAL;
+    const int rc = report_of_decode(c, d_pcm, d_out_off, d_out_stride, bits, &n, stream_, &r);
+    if (rc || n == 0)
+        return rc;
+    hipStream_t st = (hipStream_t)stream_;
+    HIP_TRY(hipMemcpyAsync(host_diff, r.d_diff, (size_t)n * sizeof(dvda_pcm_diff), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DVDA_HIP_OK;
+}
+
+extern "C" int dvda_pcm_hip_diff_combine(const dvda_pcm_diff *a_, const dvda_pcm_diff *b_, dvda_pcm_diff *out)
+{
+    if (!a_ || !b_ || !out)
+        return DVDA_HIP_EINVAL;
+    const dvda_pcm_diff a = *a_, b = *b_;           // (either may be `out`)
+    if ((a.flags | b.flags) & DVDA_CMP_SHAPE)
+        return DVDA_HIP_EINVAL;
+    const bool a_none = !a.frames_a && !a.frames_b && !a.flags, b_none = !b.frames_a && !b.frames_b && !b.flags;
+    if (a_none || b_none) {                         // neutral: its channel count does not reach the result
+        *out = a_none ? b : a;
+        return DVDA_HIP_OK;
+    }
+    if (a.frames_a != a.frames_b || a.channels != b.channels)
+        return DVDA_HIP_EINVAL;
+    dvda_pcm_diff r;
+    r.frames_a = a.frames_a + b.frames_a;
+    r.frames_b = a.frames_b + b.frames_b;
+    r.compared = a.compared + b.compared;
+    r.diff_frames = a.diff_frames + b.diff_frames;
+    r.first_diff = a.first_diff < a.compared ? a.first_diff : a.compared + b.first_diff;
+    r.diff_end = b.diff_end ? a.compared + b.diff_end : a.diff_end;
+    const bool seam = a.diff_end == a.compared && a.compared && b.compared && b.first_diff == 0;
+    r.runs = a.runs + b.runs - (seam ? 1 : 0);
+    for (int c = 0; c < 8; c++) {
+        r.diff_values[c] = a.diff_values[c] + b.diff_values[c];
+        r.max_abs[c] = a.max_abs[c] > b.max_abs[c] ? a.max_abs[c] : b.max_abs[c];
+    }
+    r.channels = a.channels;
+    r.flags = a.flags | b.flags;
+    *out = r;
+    return DVDA_HIP_OK;
 }

@@ -73,7 +73,9 @@ EXPORTS = ("dvda_mlp_hip_create", "dvda_mlp_hip_destroy", "dvda_mlp_hip_index", 
            "dvda_pcm_hip_crc32", "dvda_pcm_hip_crc32_workspace_words", "dvda_mlp_hip_pcm_crc32",
            "dvda_pcm_hip_crc32_combine",
            "dvda_pcm_hip_levels", "dvda_pcm_hip_levels_workspace_words", "dvda_mlp_hip_pcm_levels",
-           "dvda_pcm_hip_levels_combine")
+           "dvda_pcm_hip_levels_combine",
+           "dvda_pcm_hip_compare", "dvda_pcm_hip_compare_workspace_words", "dvda_mlp_hip_pcm_compare",
+           "dvda_pcm_hip_diff_combine")
 
 CRC_TILE_BYTES = 16384      # DVDA_CRC_TILE_BYTES: the digest's tiles, aligned to the end of a stream's payload
 CRC_JOIN_TILES = 256        # DVDA_CRC_JOIN_TILES: tiles a join workgroup folds per turn of its loop
@@ -102,6 +104,31 @@ class Levels(ctypes.Structure):
     def from_dict(cls, d):
         return cls(d["frames"], d["lead_silent"], d["trail_silent"], (ctypes.c_int64 * 8)(*d["sum"]),
                    (ctypes.c_uint64 * 8)(*d["over"]), (ctypes.c_int32 * 8)(*d["min"]), (ctypes.c_int32 * 8)(*d["max"]))
+
+
+CMP_TILE_FRAMES = 4096      # DVDA_CMP_TILE_FRAMES: the compare's tiles, aligned to the start of a stream pair
+CMP_SHAPE = 1               # DVDA_CMP_SHAPE: nothing was compared, the two descriptors do not go together
+
+
+class Diff(ctypes.Structure):
+    """dvda_pcm_diff of include/dvda_mlp_hip.h"""
+    _fields_ = [("frames_a", ctypes.c_uint64), ("frames_b", ctypes.c_uint64), ("compared", ctypes.c_uint64),
+                ("diff_frames", ctypes.c_uint64), ("first_diff", ctypes.c_uint64), ("diff_end", ctypes.c_uint64),
+                ("runs", ctypes.c_uint64), ("diff_values", ctypes.c_uint64 * 8), ("max_abs", ctypes.c_uint32 * 8),
+                ("channels", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+    _SCALARS = ("frames_a", "frames_b", "compared", "diff_frames", "first_diff", "diff_end", "runs", "channels", "flags")
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k in self._SCALARS}
+        d.update(diff_values=[int(v) for v in self.diff_values], max_abs=[int(v) for v in self.max_abs])
+        return d
+
+    @classmethod
+    def from_dict(cls, d):
+        out = cls(diff_values=(ctypes.c_uint64 * 8)(*d["diff_values"]), max_abs=(ctypes.c_uint32 * 8)(*d["max_abs"]))
+        for k in cls._SCALARS:
+            setattr(out, k, d[k])
+        return out
 
 
 ST_CONCEALED = 1 << 30          # DVDA_ST_CONCEALED: conceal mode, the stream was damaged (not in ST_BENIGN)
@@ -228,6 +255,11 @@ def lib():
         L.dvda_mlp_hip_pcm_levels.argtypes = [vp, vp, vp, vp, ctypes.c_uint, ctypes.POINTER(Levels), u32, vp]
         L.dvda_pcm_hip_levels_combine.restype = None
         L.dvda_pcm_hip_levels_combine.argtypes = [ctypes.POINTER(Levels), ctypes.POINTER(Levels), ctypes.POINTER(Levels)]
+        L.dvda_pcm_hip_compare_workspace_words.restype = ctypes.c_size_t
+        L.dvda_pcm_hip_compare_workspace_words.argtypes = [u32, u64]
+        L.dvda_pcm_hip_compare.argtypes = [vp, u32, vp, vp, u32, vp, u32, ctypes.c_uint, u64, vp, vp, ctypes.c_size_t, vp]
+        L.dvda_mlp_hip_pcm_compare.argtypes = [vp, vp, vp, vp, vp, u32, vp, ctypes.c_uint, ctypes.POINTER(Diff), u32, vp]
+        L.dvda_pcm_hip_diff_combine.argtypes = [ctypes.POINTER(Diff), ctypes.POINTER(Diff), ctypes.POINTER(Diff)]
         _lib = L
     return _lib
 
@@ -378,6 +410,26 @@ class Context:
                "dvda_mlp_hip_pcm_levels")
         return [arr[i].as_dict() for i in range(n)]
 
+    def pcm_compare(self, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, d_other, other_layout, other_desc, bits=0, n=None,
+                    stream=None):
+        """dvda_mlp_hip_pcm_compare: the first n streams of the last decode (side A, where the decode wrote them) against
+        the streams of d_other, an int32 device tensor in other_layout with other_desc a list of (off, stride, frames,
+        channels) (side B) -> list of Diff.as_dict(); blocks.  bits: 0 -- the int32 values as they are -- or 16 / 20 / 24:
+        the values as they would be written.  stream: default torch's current one on this context's device.  HipError
+        (EINVAL) when the context's layout is a WAV one."""
+        import torch
+        n = self.n_streams if n is None else n
+        if len(other_desc) < n:
+            raise HipError("pcm_compare: %d descriptors for %d streams" % (len(other_desc), n))
+        if stream is None:
+            stream = torch.cuda.current_stream(d_other.device).cuda_stream
+        d_desc = torch.from_numpy(_desc_records(other_desc[:n]).view(np.uint8).reshape(-1)).to(d_other.device)
+        arr = (Diff * max(n, 1))()
+        _check(lib().dvda_mlp_hip_pcm_compare(self._h, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, d_other.data_ptr(),
+                                              other_layout, d_desc.data_ptr(), bits, arr, n, stream),
+               "dvda_mlp_hip_pcm_compare")
+        return [arr[i].as_dict() for i in range(n)]
+
     def decode_time(self):
         """mean device ms of a whole decode call (all passes); call before kernel_time(), which resets the ring"""
         ms = ctypes.c_double()
@@ -397,6 +449,15 @@ def crc32_combine(crc_a, crc_b, len_b):
     return int(lib().dvda_pcm_hip_crc32_combine(crc_a, crc_b, len_b))
 
 
+def _desc_records(desc):
+    """a list of (off, stride, frames, channels) -> the dvda_pcm_crc_desc records (one at least, so that it has an address)"""
+    rec = np.zeros(max(len(desc), 1), np.dtype([("off", "<u8"), ("stride", "<u8"), ("frames", "<u8"), ("channels", "<u4"),
+                                                 ("reserved", "<u4")]))
+    for i, (off, stride, frames, channels) in enumerate(desc):
+        rec[i] = (off, stride, frames, channels, 0)
+    return rec
+
+
 def _report_args(d_pcm, desc, what, max_total, work, workspace_words):
     """What pcm_crc32 and pcm_levels hand their C entry point besides the results: the dvda_pcm_crc_desc records of `desc`
     on d_pcm's device (the host waits for that copy), the workspace (`work`, or one allocated here from
@@ -406,10 +467,7 @@ def _report_args(d_pcm, desc, what, max_total, work, workspace_words):
         raise HipError("no GPU visible to torch: %s is HIP-only" % what)
     dev = d_pcm.device
     n = len(desc)
-    rec = np.zeros(max(n, 1), np.dtype([("off", "<u8"), ("stride", "<u8"), ("frames", "<u8"), ("channels", "<u4"),
-                                         ("reserved", "<u4")]))
-    for i, (off, stride, frames, channels) in enumerate(desc):
-        rec[i] = (off, stride, frames, channels, 0)
+    rec = _desc_records(desc)
     if work is None:
         work = torch.empty(int(workspace_words(n, max_total)), dtype=torch.int32, device=dev)
     d_desc = torch.from_numpy(rec.view(np.uint8).reshape(-1)).to(dev)
@@ -476,6 +534,54 @@ def levels_list(d_levels):
     """pcm_levels' tensor -> list of Levels.as_dict() on the host (waits)"""
     raw = np.ascontiguousarray(d_levels.cpu().numpy())
     return [Levels.from_buffer_copy(raw[i].tobytes()).as_dict() for i in range(raw.shape[0])]
+
+
+def _compared(da, db):
+    """frames a pair of (off, stride, frames, channels) compares, as the kernels judge the descriptors"""
+    ok = da[3] == db[3] and 1 <= int(da[3]) <= 8 and max(int(da[2]), int(db[2])) <= 1 << 40
+    return min(int(da[2]), int(db[2])) if ok else 0
+
+
+def pcm_compare(d_a, layout_a, desc_a, d_b, layout_b, desc_b, bits=0, max_total_frames=None, work=None):
+    """dvda_pcm_hip_compare over torch tensors: d_a / d_b int32 tensors on one device holding the streams of side A / B in
+    layout_a / layout_b (PCM_PLANAR or PCM_INTERLEAVED, chosen per side), desc_a / desc_b lists of (off, stride, frames,
+    channels) of the same length: stream i of A is compared with stream i of B.  bits: 0 -- the int32 values as they
+    are -- or 16 / 20 / 24: as they would be written.  -> a uint8 device tensor [n, sizeof(Diff)] (diff_list brings it to
+    the host).  Only the kernels are asynchronous, on torch's current stream: like pcm_levels, this helper builds the
+    descriptors on the host, copies them to the device and allocates them, the result and -- when none is passed -- the
+    workspace.  max_total_frames: bound on the sum of the frames compared (default: computed from both descriptor
+    lists); work: an int32 workspace tensor of at least pcm_compare_workspace_words() elements."""
+    if len(desc_a) != len(desc_b):
+        raise HipError("pcm_compare: %d descriptors against %d" % (len(desc_a), len(desc_b)))
+    if max_total_frames is None:
+        max_total_frames = int(sum(_compared(a, b) for a, b in zip(desc_a, desc_b)))
+    torch, n, d_desc_a, work, st = _report_args(d_a, desc_a, "the PCM compare", max_total_frames, work,
+                                                lib().dvda_pcm_hip_compare_workspace_words)
+    d_desc_b = torch.from_numpy(_desc_records(desc_b).view(np.uint8).reshape(-1)).to(d_a.device)
+    d_out = torch.zeros((max(n, 1), ctypes.sizeof(Diff)), dtype=torch.uint8, device=d_a.device)
+    _check(lib().dvda_pcm_hip_compare(d_a.data_ptr(), layout_a, d_desc_a.data_ptr(), d_b.data_ptr(), layout_b,
+                                      d_desc_b.data_ptr(), n, bits, max_total_frames, d_out.data_ptr(), work.data_ptr(),
+                                      work.numel(), st), "dvda_pcm_hip_compare")
+    return d_out[:n]
+
+
+def pcm_compare_workspace_words(n, max_total_frames):
+    return int(lib().dvda_pcm_hip_compare_workspace_words(n, max_total_frames))
+
+
+def diff_list(d_diff):
+    """pcm_compare's tensor -> list of Diff.as_dict() on the host (waits)"""
+    raw = np.ascontiguousarray(d_diff.cpu().numpy())
+    return [Diff.from_buffer_copy(raw[i].tobytes()).as_dict() for i in range(raw.shape[0])]
+
+
+def diff_combine(a, b):
+    """dvda_pcm_hip_diff_combine: the diff of A1 || A2 against B1 || B2 from the diffs of the two pieces (dicts as
+    Diff.as_dict() gives them); host arithmetic, needs no GPU.  HipError (EINVAL) when the pieces do not line up"""
+    out = Diff()
+    _check(lib().dvda_pcm_hip_diff_combine(ctypes.byref(Diff.from_dict(a)), ctypes.byref(Diff.from_dict(b)),
+                                           ctypes.byref(out)), "dvda_pcm_hip_diff_combine")
+    return out.as_dict()
 
 
 def crc_list(d_crc, d_nbytes):
@@ -632,7 +738,7 @@ class PcmRegions:
 
 
 def decode_batch(ctx, batch, layout, attempts=1, capacity="report", decode=Context.decode, crc_bits=None, stream=None,
-                 levels=None):
+                 levels=None, to_host=True):
     """The decode sequence, once: index; regions of standard length in `layout` (what ctx is set to); up to `attempts`
     rounds of decode, each after the first on regions grown to what DVDA_ST_OVERFLOW asked for and a new index; the
     digest at crc_bits if given; the host copy.  -> (pcm as cut_regions gives it, infos, digests or None)
@@ -641,7 +747,8 @@ def decode_batch(ctx, batch, layout, attempts=1, capacity="report", decode=Conte
     capacity: what more major syncs than the context holds (sync patterns in payload count too) lead to -- "report":
     DVDA_ST_CAPACITY on the streams; "raise": HipError; a function: called with the count the index found, it returns
     the larger context the sequence goes on with (the caller's to close).
-    decode: Context.decode or Context.decode_async.  stream: default torch's current one on the batch's device."""
+    decode: Context.decode or Context.decode_async.  stream: default torch's current one on the batch's device.
+    to_host=False: no host copy -- the first element is the PcmRegions the last round decoded into, on the device."""
     st = batch.current_stream if stream is None else stream
     ctx.index_batch(batch, st)
     if capacity != "report":
@@ -665,9 +772,10 @@ def decode_batch(ctx, batch, layout, attempts=1, capacity="report", decode=Conte
         if not any(inf.status & ST["OVERFLOW"] for inf in infos):
             break
     digests = ctx.pcm_crc32(*regions.ptrs, crc_bits, stream=st) if crc_bits else None
+    pcm = regions.to_host(infos) if to_host else regions
     if levels is not None:
-        return regions.to_host(infos), list(infos), digests, ctx.pcm_levels(*regions.ptrs, levels, stream=st)
-    return regions.to_host(infos), list(infos), digests
+        return pcm, list(infos), digests, ctx.pcm_levels(*regions.ptrs, levels, stream=st)
+    return pcm, list(infos), digests
 
 
 def _context_for(ctx, batch, max_segments, lanes_per_segment, layout):
@@ -766,6 +874,37 @@ def decode_streams_concealed(streams, device=0, max_segments=None, lanes_per_seg
                 rc = rc or lib().dvda_mlp_hip_set_initial_fir(ctx._h, None)
             if done:                    # (a call that failed reports its own error, not this one)
                 _check(rc, "leaving conceal mode")
+
+
+def compare_streams(streams_a, streams_b, device=0, layout_a=PCM_INTERLEAVED, layout_b=PCM_INTERLEAVED, bits=0,
+                    conceal=False):
+    """Two rips of the same titles: decodes both lists of complete MLP byte streams (the one decode sequence,
+    decode_batch, each batch on a context of its own, in layout_a / layout_b; conceal=True: both in conceal mode) and
+    compares stream i of A with stream i of B where the decodes wrote them (Context.pcm_compare) -- no PCM is copied to
+    the host.  -> (infos_a, infos_b, diffs), diffs[i] a Diff.as_dict().  bits as pcm_compare takes it.  A stream whose
+    region the decode could not fill (DVDA_ST_OVERFLOW after the sequence's attempts) is an empty side."""
+    if len(streams_a) != len(streams_b):
+        raise HipError("compare_streams: %d streams against %d" % (len(streams_a), len(streams_b)))
+    sides = []
+    try:
+        for streams, layout in ((streams_a, layout_a), (streams_b, layout_b)):
+            if layout not in (PCM_PLANAR, PCM_INTERLEAVED):
+                raise HipError("compare_streams: the compare takes the int32 layouts only (EINVAL)")
+            batch = Batch(streams, device)
+            ctx, _ = _context_for(None, batch, None, 0, layout)
+            sides.append((ctx, batch))
+            if conceal:
+                ctx.set_conceal(True)       # (before the index)
+            regions, infos, _ = decode_batch(ctx, batch, layout, attempts=3 if conceal else 2, to_host=False)
+            sides[-1] = (ctx, batch, regions, infos)
+        (ctx_a, batch_a, reg_a, infos_a), (_, _, reg_b, infos_b) = sides
+        desc_b = [(o, r, 0 if inf.status & ST["OVERFLOW"] else int(inf.pcm_frames), int(inf.channels))
+                  for o, r, inf in zip(reg_b.out_off, reg_b.rows, infos_b)]
+        diffs = ctx_a.pcm_compare(*reg_a.ptrs, reg_b.d_pcm, layout_b, desc_b, bits, stream=batch_a.current_stream)
+        return infos_a, infos_b, diffs
+    finally:
+        for side in sides:
+            side[0].close()
 
 
 def shard_c(sizes, parts):
