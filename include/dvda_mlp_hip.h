@@ -108,7 +108,9 @@ extern "C" {
 typedef struct dvda_mlp_hip_ctx dvda_mlp_hip_ctx;
 
 typedef struct dvda_mlp_stream_info {
-    uint64_t mlp_frames;      /* complete access units found                                  */
+    uint64_t mlp_frames;      /* complete access units that yield PCM: those of the live segments without
+                                 the units dropped for a major sync with other parameters
+                                 (DVDA_ST_SYNC_CHANGE); bytes_consumed covers the dropped ones too          */
     uint64_t pcm_frames;      /* PCM frames decoded per channel                               */
     uint64_t bytes_consumed;  /* bytes covered by complete access units                       */
     uint32_t status;          /* DVDA_ST_* bits                                               */
@@ -116,7 +118,10 @@ typedef struct dvda_mlp_stream_info {
     uint32_t substreams;      /* 1 or 2 (from the first major sync)                           */
     uint32_t assignment;      /* 5-bit channel assignment                                     */
     uint32_t group0_bps, group1_bps, group0_rate, group1_rate;  /* major sync codes          */
-    uint32_t segments;        /* restart-delimited segments (units of parallel decode)        */
+    uint32_t segments;        /* major-sync candidates the stream has in the segment list, from its first one
+                                 to the last in front of the next stream's: the restart-delimited segments
+                                 (units of parallel decode) AND the retired ones (DVDA_ST_FALSE_SYNC) among
+                                 them -- the length of the stream's run of segment indices                  */
     uint32_t reserved;
 } dvda_mlp_stream_info;
 
@@ -317,6 +322,12 @@ int dvda_mlp_hip_stream_info(dvda_mlp_hip_ctx *ctx, dvda_mlp_stream_info *infos,
 
 /* Number of segments found by the last index call (blocks on `stream`). */
 int dvda_mlp_hip_segment_count(dvda_mlp_hip_ctx *ctx, uint32_t *n_segments, void *stream);
+
+/* How the last dvda_mlp_hip_index call's launches went out (read-only, no device work): *state is 0 before the
+ * first index (or for one on the NULL stream before any other), 1 when the call's buffers, counts and stream were
+ * noted and its kernels launched directly, 2 when the launch sequence was captured or replayed as a hipGraph,
+ * -1 when the graph is switched off (DVDA_INDEX_GRAPH=0, or a capture / replay failed on this context). */
+int dvda_mlp_hip_index_graph_state(dvda_mlp_hip_ctx *ctx, int *state);
 
 /* Average duration in milliseconds of the fast-pass kernel launches recorded since
  * the last call (HIP events on the launch stream, a ring of the newest 256 decode calls made at

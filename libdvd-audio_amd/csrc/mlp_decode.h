@@ -3114,7 +3114,8 @@ __global__ __launch_bounds__(256) void k_finalize(const SegRec *__restrict__ seg
                                                   const uint32_t *__restrict__ seg_rows,
                                                   StreamRec *__restrict__ streams, uint32_t n_streams,
                                                   DecodeSummary *__restrict__ summary,
-                                                  uint32_t *__restrict__ seq_list, uint32_t collect, uint32_t last)
+                                                  uint32_t *__restrict__ seq_list, uint32_t collect, uint32_t last,
+                                                  const uint32_t *__restrict__ seg_check)
 {
     // FIN_GROUP lanes per stream share the walk over its segments (a title of the bench batch has 64: one lane per
     // stream walked them one dependent load after the other, 56 us for 4 096 streams)
@@ -3154,7 +3155,10 @@ __global__ __launch_bounds__(256) void k_finalize(const SegRec *__restrict__ seg
         for (uint32_t i = r.first_seg + j; i < r.first_seg + r.n_seg; i += FIN_GROUP) {
             const uint32_t ss = seg_status[i];
             rows += seg_rows[i];
-            st |= ss | (seg[i].flags & ~SEG_DEAD);      // (what the index found on the segment stays)
+            // (what the index found on the segment stays -- on a LIVE one: what a retired candidate's own walk ran
+            //  into, DVDA_ST_EOF on the zeros behind a sync pattern in padding, say, is nobody's finding, as in k_link)
+            const uint32_t sf = seg[i].flags;
+            st |= ss | ((sf & SEG_DEAD) ? 0u : sf);
             if ((ss & ST_DEFERRED) && !(ss & ST_GENERAL) && !(ss & ~ST_INFO)) {
                 waits = 1;
                 if (last)
@@ -3176,6 +3180,23 @@ __global__ __launch_bounds__(256) void k_finalize(const SegRec *__restrict__ seg
         rows = ((uint64_t)rhi << 32) | rlo;
         if (collect && waits)
             atomicAdd(&summary->waiting, 1u);
+        if ((st & 0x3FCu) != 0 && seg_check) {
+            // The reference verifies a substream BEFORE it decodes it (src/mlp.c:675-706), and goes on with the next
+            // access unit after a failure: whatever the blocks of a unit that fails its check tripped over first here
+            // -- a restart sync, an invalid code, substreams that disagree and a pass that decodes in order --, the
+            // stream has that unit, and the reference says parity / CRC-8 for it.  k_au_check's verdicts (first failing
+            // unit per live segment and substream) are added to a stream that carries a decode error; a clean one does
+            // not come here.  (As k_coop<.., RESUME> does for the streaming tier, unit by unit.)
+            for (uint32_t i = r.first_seg; i < r.first_seg + r.n_seg; i++) {
+                if (seg[i].flags & SEG_DEAD)
+                    continue;
+                for (uint32_t u = 0; u < 2u; u++) {
+                    const uint32_t v = seg_check[2 * (size_t)i + u];
+                    if (v != 0xFFFFFFFFu)
+                        st |= (v & 1u) ? ST_PARITY : ST_CRC;
+                }
+            }
+        }
         r.frames = seg_fbase[r.first_seg + r.n_seg] - seg_fbase[r.first_seg];
         r.rows = rows;
         r.status = st;

@@ -654,7 +654,8 @@ static void enqueue_finalize(dvda_mlp_hip_ctx *c, hipStream_t st, bool last)
 {
     const dim3 fgrid((unsigned)(((uint64_t)c->n_streams * FIN_GROUP + 255) / 256));
     hipLaunchKernelGGL(k_finalize, fgrid, dim3(256), 0, st, c->d_seg, c->d_seg_fbase, c->d_seg_status, c->d_seg_rows,
-                       c->d_streams, c->n_streams, c->d_summary, c->d_seq_list, last ? 0u : 1u, last ? 1u : 0u);
+                       c->d_streams, c->n_streams, c->d_summary, c->d_seq_list, last ? 0u : 1u, last ? 1u : 0u,
+                       c->d_seg_check);
 }
 
 // ---- fast pass: every segment, a lane (or a workgroup of the cooperative kernel) each
@@ -952,6 +953,15 @@ extern "C" int dvda_mlp_hip_segment_count(dvda_mlp_hip_ctx *c, uint32_t *n_segme
     //  come back with a larger context, as without the presentation; else the count is the inner context's)
     dvda_mlp_hip_ctx *x = pp_inner(c);
     return x ? dvda_mlp_hip_segment_count(x, n_segments, stream_) : DVDA_HIP_OK;
+}
+
+// how the last index call's launches went out (idx_graph_state, mlp_ctx.h): tests read it to know the replay ran
+extern "C" int dvda_mlp_hip_index_graph_state(dvda_mlp_hip_ctx *c, int *state)
+{
+    if (!c || !state)
+        return DVDA_HIP_EINVAL;
+    *state = c->idx_graph_state;
+    return DVDA_HIP_OK;
 }
 
 // mean device ms of the newest decode calls in the event ring, each from its first kernel to the event end_of(slot)

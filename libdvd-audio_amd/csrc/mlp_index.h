@@ -363,8 +363,9 @@ __device__ __forceinline__ void chase_one(uint32_t i, const uint8_t *__restrict_
     r.ndrop = 0;
     r.prev = 0xFFFFFFFFu;
     uint64_t p = off;
-    const bool outside = off >= s_end;          // bytes between two streams' ranges (or a stream of length 0: a
-                                                // range the index refused): nobody's candidate, nobody's finding
+    const bool outside = off >= s_end || off < s_begin;     // bytes between two streams' ranges (or a stream of length 0:
+                                                // a range the index refused), or in front of the first stream's, which
+                                                // find_stream looks up to stream 0: nobody's candidate, nobody's finding
     if (outside) {
         r.flags = SEG_DEAD;
         r.end = off;
@@ -416,7 +417,11 @@ __device__ __forceinline__ void chase_one(uint32_t i, const uint8_t *__restrict_
                 // times: the candidate there walks on its own and must not run to the stream's end)
                 if (((packed_sync_at(bytes, p) ^ r.sync) & SYNC_PARAMS) == 0 || (!own && r.ndrop >= MAX_DROP))
                     break;
-                r.ndrop++;
+                // (dropped only if it is complete: a stream cut inside such a unit, behind its major sync, does not
+                //  count it among nframes either -- the next turn stops there with DVDA_ST_TRUNCATED)
+                const uint32_t sz = 2u * ((((uint32_t)hdr & 0x0Fu) << 8) | (((uint32_t)hdr >> 8) & 0xFFu));
+                if (p + sz <= s_end)
+                    r.ndrop++;
             }
         }
         r.nframes = n;
@@ -481,6 +486,15 @@ __device__ __forceinline__ void mark_dead_one(uint32_t i, uint32_t n_cand, const
     // for nothing, and it is retired here when an earlier walk went through it
     const uint32_t want = streams[s].sync & SYNC_PARAMS;
     const bool foreign = (seg[i].sync & SYNC_PARAMS) != want;
+    if (foreign && seg[i].nframes == 0 && !(seg[i].flags & ((1u << 16) | SEG_DEAD))) {
+        // a major sync with other parameters whose own access unit does not fit into the stream: the stream was cut
+        // inside a unit the reference would have dropped.  No walk goes THROUGH it (the one that arrives stops with
+        // DVDA_ST_TRUNCATED, as at any cut unit), so nothing below retires it, and alive it would make the stream
+        // DVDA_ST_IRREGULAR in k_link -- for a tail the reference does not even read.
+        seg[i].flags |= SEG_DEAD;
+        seg_frames[i] = 0;
+        return;
+    }
     // does a chain land exactly here?
     // (the look-behind and the look-ahead are bounded in candidates of the stream's OWN parameters -- a run of foreign
     //  ones, which a walk goes through whole, is stepped over however long it is: round 5, more than MAX_DROP dropped

@@ -75,7 +75,7 @@ EXPORTS = ("dvda_mlp_hip_create", "dvda_mlp_hip_destroy", "dvda_mlp_hip_index", 
            "dvda_pcm_hip_levels", "dvda_pcm_hip_levels_workspace_words", "dvda_mlp_hip_pcm_levels",
            "dvda_pcm_hip_levels_combine",
            "dvda_pcm_hip_compare", "dvda_pcm_hip_compare_workspace_words", "dvda_mlp_hip_pcm_compare",
-           "dvda_pcm_hip_diff_combine")
+           "dvda_pcm_hip_diff_combine", "dvda_mlp_hip_index_graph_state")
 
 CRC_TILE_BYTES = 16384      # DVDA_CRC_TILE_BYTES: the digest's tiles, aligned to the end of a stream's payload
 CRC_JOIN_TILES = 256        # DVDA_CRC_JOIN_TILES: tiles a join workgroup folds per turn of its loop
@@ -182,6 +182,7 @@ def lib():
         L.dvda_mlp_hip_reserve.argtypes = [vp, u64, u32, u32]
         L.dvda_mlp_hip_stream_info.argtypes = [vp, ctypes.POINTER(StreamInfo), u32, vp]
         L.dvda_mlp_hip_segment_count.argtypes = [vp, ctypes.POINTER(u32), vp]
+        L.dvda_mlp_hip_index_graph_state.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
         L.dvda_mlp_hip_kernel_time.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(u32)]
         L.dvda_mlp_hip_decode_time.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(u32)]
         L.dvda_mlp_hip_set_lanes_per_segment.argtypes = [vp, u32]
@@ -377,6 +378,13 @@ class Context:
     def segment_count(self, stream=0):
         v = ctypes.c_uint32()
         _check(lib().dvda_mlp_hip_segment_count(self._h, ctypes.byref(v), stream), "segment_count")
+        return int(v.value)
+
+    def index_graph_state(self):
+        """dvda_mlp_hip_index_graph_state: 1 the last index was launched directly and its key noted, 2 it went out as a
+        hipGraph (captured or replayed), -1 the graph is off for this context, 0 nothing noted yet"""
+        v = ctypes.c_int()
+        _check(lib().dvda_mlp_hip_index_graph_state(self._h, ctypes.byref(v)), "index_graph_state")
         return int(v.value)
 
     def segment_info(self, segment, stream=0):

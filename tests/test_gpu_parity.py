@@ -335,29 +335,9 @@ def test_linearity_free_property_checksum_of_large_batch(pkg, oracle):
         assert np.array_equal(pcm1[i], pcm2[i]) and np.array_equal(pcm1[i], want)
 
 
-def _inject_false_sync(stream, frame_index):
-    """Grows one access unit by 64 ignored tail bytes that look exactly like a major-sync access
-    unit header (the reference ignores everything behind the last substream, src/mlp.c:470-610)."""
-    b = stream
-    pos = 0
-    for _ in range(frame_index):
-        pos += 2 * (((int(b[pos]) & 0xF) << 8) | int(b[pos + 1]))
-    size = 2 * (((int(b[pos]) & 0xF) << 8) | int(b[pos + 1]))
-    fake = np.zeros(64, np.uint8)
-    fake[0:2] = [0x00, 0x40]                      # size field: 0x40 words = 128 bytes
-    fake[4:8] = [0xF8, 0x72, 0x6F, 0xBB]
-    fake[8:10] = [0x22, 0x11]
-    fake[11] = 12
-    fake[20] = 0x10                               # substream count 1
-    new_size = size + 64
-    out = np.concatenate([b[:pos], b[pos:pos + size], fake, b[pos + size:]]).astype(np.uint8)
-    out[pos] = (out[pos] & 0xF0) | ((new_size // 2) >> 8)
-    out[pos + 1] = (new_size // 2) & 0xFF
-    return out
-
-
 @pytest.mark.parametrize("S", [1, 2])
 def test_false_sync_pattern_in_ignored_bytes_is_resolved(pkg, oracle, S):
+    from tests.index_model import inject_false_sync as _inject_false_sync   # (64 ignored tail bytes: a major-sync header)
     syn, hip = pkg.synth, pkg.hipdec
     cfg = syn.make_cfg(assignment=12, rate_code=1, n_substreams=S, n_aus=40)
     clean, frames = syn.stream(cfg, 1234)
@@ -933,7 +913,8 @@ def test_stream_ranges_are_checked_not_trusted(pkg, oracle):
     cap = max(f, f2)
     out = hip.PcmRegions([cap] * 3, [6] * 3)
     ctx = hip.Context(0, 3, 64)
-    for _ in range(2):                      # (twice on one context: the second index replays the first one's launches)
+    for _ in range(2):                      # (twice on one context, launched directly both times: the NULL stream is
+                                            #  never captured -- the replay as a graph is tests/test_gpu_index.py's)
         ctx.index_batch(batch2)
         ctx.decode(*out.ptrs, 0)
         infos = ctx.stream_info(3)
