@@ -127,6 +127,24 @@ void dvda_hip_set_levels(int on);
  * is a WAV-payload-only reader (dvda_hip_reader_wav_only), or the track's bit depth is none of 16 / 20 / 24.  `out` may
  * be NULL. */
 int dvda_hip_reader_levels(const DVDA_Track_Reader *reader, struct dvda_pcm_levels *out);
+/* block_frames != 0: track readers opened afterwards (per calling thread, read when the reader is opened, like
+ * dvda_hip_set_levels) make the energy report of every piece of int32 PCM where it lies on the device, before any copy
+ * to the host: per block of block_frames frames and channel the exact sum of squares and the largest |v| (the contract
+ * is in dvda_mlp_hip.h, dvda_pcm_energy_block / dvda_pcm_hip_energy).  The grid is the track's, anchored at track frame
+ * 0: a windowed reader gives every window the lead that is left of the block the track is in, and joins the windows'
+ * blocks as they are handed out (dvda_pcm_hip_energy_append); conceal mode's silent windows are pieces like any other.
+ * Every reader that holds int32 PCM: whole-track and windowed, MLP and raw PCM, the presentation.  A reader opened for
+ * the WAV payload only has no report, nor has one opened with a block_frames outside DVDA_NRG_MIN_BLOCK ..
+ * DVDA_NRG_MAX_BLOCK.  0 (default): off, a reader launches and allocates exactly as without this call. */
+struct dvda_pcm_energy_block;
+void dvda_hip_set_energy(unsigned block_frames);
+/* The track's blocks: up to `cap` of them into `blocks` (may be NULL), their count into *n (may be NULL).  1: final for
+ * the track; 0: the blocks of what has been handed out so far (a windowed reader; the last of them may still grow);
+ * -1: the report is not on, the reader failed, or it is a WAV-payload-only reader -- nothing is written.  The track's
+ * block array is the report itself (168 bytes per block, on the host): it is not part of the window-bounded host
+ * figure of dvda_hip_reader_memory. */
+int dvda_hip_reader_energy(const DVDA_Track_Reader *reader, struct dvda_pcm_energy_block *blocks, unsigned long long cap,
+                           unsigned long long *n);
 /* on != 0: MLP track readers opened afterwards (per calling thread, read when the reader is opened, like
  * dvda_hip_set_wav_output) conceal a damaged track instead of refusing it: the track comes out as
  *     kept PCM ++ silence ++ PCM of a fresh decoder from the next usable major sync ++ ...

@@ -556,8 +556,9 @@ uint32_t dvda_pcm_hip_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len
  * The kernels cut a stream into tiles of DVDA_LVL_TILE_FRAMES frames, aligned to the stream's START (the last tile is
  * the ragged one).
  *
- * Out of scope: dvda2wav_hip (its readers are WAV-payload readers), the streaming tier, dvda_mlp_hip_decode_multi, RMS /
- * loudness (a sum of squares of unclamped int32 values does not fit 64 bits), reports from the WAV layouts. */
+ * Out of scope: dvda2wav_hip (its readers are WAV-payload readers), the streaming tier, dvda_mlp_hip_decode_multi,
+ * reports from the WAV layouts.  RMS and peak over time are the energy report's (below: sums of squares as 128 bits);
+ * K-weighted loudness stays out there too. */
 #define DVDA_LVL_TILE_FRAMES 4096u
 
 typedef struct dvda_pcm_levels {
@@ -666,6 +667,81 @@ int dvda_mlp_hip_pcm_compare(dvda_mlp_hip_ctx *ctx, const int32_t *d_pcm, const 
  * or when either carries DVDA_CMP_SHAPE.  Counts add, max_abs is the maximum, first_diff / diff_end move by a.compared,
  * and a run that crosses the seam counts once. */
 int dvda_pcm_hip_diff_combine(const dvda_pcm_diff *a, const dvda_pcm_diff *b, dvda_pcm_diff *out);
+
+/* ------------------------------------------------------------------ energy report of the decoded PCM
+ * The fourth report: what a ripper or an archive computes from every sample over time -- the RMS level of a track, its
+ * crest factor, the block statistics a dynamic-range meter works from, the min / max envelope a GUI draws -- comes from
+ * two figures per block of frames and channel: the sum of v * v and the largest |v|.  They are computed on the device
+ * from the int32 PCM where the decode wrote it (csrc/pcm_energy.h), 168 bytes per block instead
+ * of the payload.  A square of an int32 is at most 2^62 and a stream has at most 2^40 frames, so a sum is below 2^102:
+ * two 64-bit words hold it exactly.  Integer arithmetic throughout: the same words in any order, from either layout,
+ * from run to run.
+ *
+ * The contract.  One stream of `frames` PCM frames with `channels` channels, int32 PCM in DVDA_PCM_PLANAR or
+ * DVDA_PCM_INTERLEAVED, channels as they lie in the buffer, values as they are: nothing is clamped, there is no `bits`.
+ * The block grid: a block length `block_frames` = B in DVDA_NRG_MIN_BLOCK .. DVDA_NRG_MAX_BLOCK (otherwise
+ * DVDA_HIP_EINVAL) and, per stream, the length `lead` in 1 .. B of the first block (a NULL array: B for every stream; a
+ * lead outside 1 .. B: the stream has no blocks).  Frame f lies in block 0 when f < lead, else in block
+ * 1 + (f - lead) / B; nblocks = 0 for no frames, else 1 + ceil(max(frames - lead, 0) / B).  `lead` is there so that a
+ * piece of a longer track -- a window -- can sit on the track's grid.  Entries at index `channels` and above are 0.  A
+ * descriptor the other reports do not take (channels outside 1..8, frames above 2^40) has no blocks.  The two int32
+ * layouts give the same report; the WAV layouts are DVDA_HIP_EINVAL, as for the level report.
+ *
+ * The kernels cut a block into pieces of at most DVDA_NRG_PIECE_FRAMES frames, one workgroup per piece.
+ *
+ * What a caller derives from these integers -- RMS in dBFS, crest factor, a DR figure, an overview -- is host
+ * arithmetic of the caller's.  Out of scope: K-weighted loudness (BS.1770: floating-point filtering, it cannot be
+ * exact), dvda2wav_hip, the streaming tier, dvda_mlp_hip_decode_multi, reports from the WAV layouts. */
+#define DVDA_NRG_MIN_BLOCK    64u
+#define DVDA_NRG_MAX_BLOCK    16777216u
+#define DVDA_NRG_PIECE_FRAMES 4096u
+
+typedef struct dvda_pcm_energy_block {   /* 168 bytes */
+    uint64_t sq_lo[8], sq_hi[8];  /* sum of v*v of the channel over the block = sq_hi * 2^64 + sq_lo, exact   */
+    uint32_t peak[8];             /* largest |v| of the channel in the block (2^31 for v = -2^31)             */
+    uint32_t frames;              /* frames the block holds: B, fewer in a first block (lead) and in the last */
+    uint32_t reserved;            /* 0 */
+} dvda_pcm_energy_block;
+
+/* The tier-free form.  Stream i (descriptor d_desc[i], first block d_lead[i] frames; device arrays, n entries) leaves
+ * its records in d_blocks[d_block_off[i] + j] for j < d_block_cap[i], and in d_nblocks[i] how many blocks it has: more
+ * than its cap means that only cap were written, and nothing was written behind them.  Enqueued on `stream`: no host
+ * wait, no allocation.  max_total_frames: a bound the host knows on the sum of the streams' frames -- the launch and
+ * d_work are sized by it (at most max_total_frames / DVDA_NRG_PIECE_FRAMES + max_total_frames / B + 2 n pieces); a
+ * stream whose pieces fall outside it reports 0 blocks and is never read out of bounds.  d_work:
+ * dvda_pcm_hip_energy_workspace_words(n, max_total_frames, block_frames) uint32 words (0 for a block_frames outside its
+ * range), which need not be cleared between calls; no atomics, the words are the same from run to run.  d_pcm + off may
+ * have any 4-byte alignment and a planar stride any parity; nothing outside a stream's `frames` is read.  The arguments
+ * are judged first, on any machine -- DVDA_HIP_EINVAL: block_frames outside its range, a WAV layout, a null pointer
+ * other than d_lead, work_words too small; DVDA_HIP_ECAPACITY: 2^31 pieces or more -- then the device: DVDA_HIP_ENODEV
+ * without one. */
+size_t dvda_pcm_hip_energy_workspace_words(uint32_t n, uint64_t max_total_frames, uint32_t block_frames);
+int dvda_pcm_hip_energy(const int32_t *d_pcm, uint32_t layout, const dvda_pcm_crc_desc *d_desc, uint32_t n,
+                        uint32_t block_frames, const uint32_t *d_lead /* or NULL */, uint64_t max_total_frames,
+                        dvda_pcm_energy_block *d_blocks, const uint64_t *d_block_off, const uint64_t *d_block_cap,
+                        uint64_t *d_nblocks, uint32_t *d_work, size_t work_words, void *stream);
+
+/* behind dvda_mlp_hip_decode (blocks): the blocks of the first n streams of the last decode, every stream's grid
+ * starting at its first frame (lead = B).  Frames and channels are what dvda_mlp_hip_stream_info reports: conceal
+ * mode's composed stream and the presentation's k channels count as they are; a stream that carries DVDA_ST_OVERFLOW
+ * has no blocks.  The streams lie back to back in host_blocks, stream i in [host_first[i], host_first[i + 1]).  When
+ * cap_blocks is too small: DVDA_HIP_ECAPACITY with host_first[n] = the count needed and nothing else written.
+ * DVDA_HIP_EINVAL on a context that writes a WAV layout.  The workspace belongs to the context and only grows. */
+int dvda_mlp_hip_pcm_energy(dvda_mlp_hip_ctx *ctx, const int32_t *d_pcm, const uint64_t *d_out_off,
+                            const uint64_t *d_out_stride, uint32_t block_frames, dvda_pcm_energy_block *host_blocks,
+                            uint64_t cap_blocks, uint64_t *host_first /* [n + 1] */, uint32_t n, void *stream);
+
+/* Host arithmetic; needs no device.
+ * append: joins a piece's blocks to a track's (*n_track blocks in track[0, cap), a grid that starts at the track's first
+ * frame).  When the track's last block is short (frames < B) the piece's first block is added into it -- 128-bit add
+ * with carry, the larger peak, frames added -- and a sum of frames above B is DVDA_HIP_EINVAL: the piece was not on the
+ * grid (so is a sum below B with more blocks behind it, and a short block inside the piece).  The rest of the piece is
+ * appended.  DVDA_HIP_ECAPACITY when cap does not hold the result.  On an error nothing
+ * is written.  `piece` must not overlap `track`.  The lead of the next piece is B - (frames so far mod B).
+ * total: folds n blocks into one record: sums added, the largest peak; its `frames` field saturates at 2^32 - 1. */
+int dvda_pcm_hip_energy_append(dvda_pcm_energy_block *track, uint64_t *n_track, uint64_t cap,
+                               const dvda_pcm_energy_block *piece, uint64_t n_piece, uint32_t block_frames);
+void dvda_pcm_hip_energy_total(const dvda_pcm_energy_block *blocks, uint64_t n, dvda_pcm_energy_block *out);
 
 /* ------------------------------------------------------------------ tier B */
 /* The mlp.h mirror: same three calls, same meaning as reference src/mlp.h:29-42 /

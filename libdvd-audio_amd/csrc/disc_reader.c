@@ -47,6 +47,7 @@ struct reader_opts {
     int digest;                 /* 1: every piece of PCM is digested where it lies on the device (dvda_hip_reader_crc32) */
     int levels;                 /* 1: ... and its level report is made there (dvda_hip_reader_levels) */
     int conceal;                /* 1: a damaged MLP track is concealed, not refused (dvda_hip_set_conceal) */
+    unsigned energy;            /* != 0: ... and its energy report on a grid of that many frames (dvda_hip_reader_energy) */
 };
 static _Thread_local struct reader_opts t_opts;
 static _Thread_local int t_conceal_set;     /* dvda_hip_set_conceal() was called on this thread: DVDA_CONCEAL no longer counts */
@@ -55,6 +56,7 @@ void dvda_hip_set_wav_output(int on) { t_opts.wav_output = on != 0; }
 void dvda_hip_set_presentation(int presentation) { t_opts.present = presentation == 1; }
 void dvda_hip_set_digest(int on) { t_opts.digest = on != 0; }
 void dvda_hip_set_levels(int on) { t_opts.levels = on != 0; }
+void dvda_hip_set_energy(unsigned block_frames) { t_opts.energy = block_frames; }
 void dvda_hip_set_conceal(int on)
 {
     t_opts.conceal = on != 0;
@@ -76,15 +78,26 @@ static struct reader_opts opts_now(void)
 
 struct track_windows;               /* a long track read window by window (below) */
 
-/* The reports of a piece of PCM or of a track: the digest (dvda_hip_set_digest) and the level report
- * (dvda_hip_set_levels).  Per report a state -- 0 off, 1 wanted and, once a piece is through, made (a windowed track:
- * joined over the windows handed out so far), -1 this reader has none -- and its values. */
+/* The reports of a piece of PCM or of a track: the digest (dvda_hip_set_digest), the level report
+ * (dvda_hip_set_levels) and the energy report (dvda_hip_set_energy).  Per report a state -- 0 off, 1 wanted and, once a
+ * piece is through, made (a windowed track: joined over the windows handed out so far), -1 this reader has none -- and
+ * its values.  The energy report's blocks are the record's own (rep_reset frees them): a piece's lie on the track's
+ * grid, which is anchored at track frame 0, and join the track's when the piece is handed out. */
 struct pcm_reports {
-    int dg, lv;
+    int dg, lv, ng;
     uint32_t crc;               /* zlib CRC-32 of the WAV payload and its bytes */
     uint64_t bytes;
     dvda_pcm_levels levels;
+    uint32_t ng_block;          /* the grid's block length */
+    dvda_pcm_energy_block *ng_blocks;
+    uint64_t ng_n, ng_cap;
 };
+
+static void rep_reset(struct pcm_reports *r)
+{
+    free(r->ng_blocks);
+    memset(r, 0, sizeof(*r));
+}
 
 struct DVDA_Track_Reader_s {
     dvda_codec_t codec;
@@ -250,11 +263,14 @@ static int64_t find_sync_dev(const uint8_t *d_bytes, uint64_t from, uint64_t siz
 /* The reports a reader wants (`have`: states > 0) of one piece of PCM where it lies on the device, into `out` (which may
  * be `have`): `frames` frames of `ch` channels at `bits` in `layout` at d_pcm, capacity `stride` frames.  Which of them
  * this reader has is decided here and nowhere else: a digest at 16 and 24 bits, a level report at 16, 20 and 24 bits of
- * int32 PCM -- a reader that hands out the WAV payload (wav_payload) has none.  One block on the device holds the
- * descriptor, the results and the workspace, the larger one where both reports run: they run one behind the other.
+ * int32 PCM, an energy report of int32 PCM at a block length the report takes -- a reader that hands out the WAV payload
+ * (wav_payload) has neither of the two.  `before`: the track's frames in front of the piece: the energy report's grid is
+ * the track's, so the piece's first block has what is left of the block the track is in.  One block on the device holds
+ * the descriptor, the results and the workspace, the largest one where several reports run: they run one behind the
+ * other; the energy report's lead, counts and blocks lie behind the workspace.
  * Blocks; what it allocates it frees; allocates and launches nothing when there is nothing to make.  1 = ok. */
 static int piece_reports(struct pcm_reports *have, struct pcm_reports *out, int wav_payload, const int32_t *d_pcm,
-                         uint32_t layout, unsigned bits, uint64_t stride, uint64_t frames, unsigned ch)
+                         uint32_t layout, unsigned bits, uint64_t stride, uint64_t frames, unsigned ch, uint64_t before)
 {
     struct {
         uint64_t bytes;
@@ -267,22 +283,45 @@ static int piece_reports(struct pcm_reports *have, struct pcm_reports *out, int 
         have->dg = -1;
     if (have->lv > 0 && (wav_payload || (bits != 16 && bits != 20 && bits != 24)))
         have->lv = -1;
-    const int dg = have->dg > 0, lv = have->lv > 0;
+    if (have->ng > 0 && (wav_payload || have->ng_block < DVDA_NRG_MIN_BLOCK || have->ng_block > DVDA_NRG_MAX_BLOCK))
+        have->ng = -1;
+    const int dg = have->dg > 0, lv = have->lv > 0, ng = have->ng > 0;
     const size_t w_dg = dg ? dvda_pcm_hip_crc32_workspace_words(1, payload) : 0;
     const size_t w_lv = lv ? dvda_pcm_hip_levels_workspace_words(1, frames) : 0;
-    const size_t words = w_dg > w_lv ? w_dg : w_lv;
+    const uint32_t nrg_b = have->ng_block;
+    const size_t w_ng = ng ? dvda_pcm_hip_energy_workspace_words(1, frames, nrg_b) : 0;
+    const size_t w_two = w_dg > w_lv ? w_dg : w_lv;
+    const size_t words = w_two > w_ng ? w_two : w_ng;
+    /* the energy report: { lead, -, off, cap, nblocks } and the piece's blocks */
+    const uint32_t lead = ng ? nrg_b - (uint32_t)(before % nrg_b) : 0;
+    const uint64_t ng_n = !ng || !frames ? 0 : 1 + ((frames > lead ? frames - lead : 0) + nrg_b - 1) / nrg_b;
+    const uint64_t ng_head[4] = {lead, 0, ng_n, 0};
+    const size_t ng_at = (sizeof(desc) + sizeof(res) + words * sizeof(uint32_t) + 7) & ~(size_t)7;
+    const size_t ng_bytes = ng ? sizeof(ng_head) + (size_t)ng_n * sizeof(dvda_pcm_energy_block) : 0;
+    dvda_pcm_energy_block *ng_blocks = NULL;
     uint8_t *d = NULL;
     out->dg = have->dg;
     out->lv = have->lv;
+    out->ng = have->ng;
+    out->ng_block = nrg_b;
     out->crc = 0;
     out->bytes = 0;
     memset(&out->levels, 0, sizeof(out->levels));
+    free(out->ng_blocks);
+    out->ng_blocks = NULL;
+    out->ng_n = out->ng_cap = 0;
     if (!frames || !words)
-        return 1;                                /* (the reports of no frames are zeros) */
-    if (!dev_alloc((void **)&d, sizeof(desc) + sizeof(res) + words * sizeof(uint32_t)))
+        return 1;                                /* (the reports of no frames are zeros, and no blocks) */
+    if (ng && (ng_blocks = malloc((size_t)ng_n * sizeof(*ng_blocks))) == NULL)
         return 0;
+    if (!dev_alloc((void **)&d, ng ? ng_at + ng_bytes : sizeof(desc) + sizeof(res) + words * sizeof(uint32_t))) {
+        free(ng_blocks);
+        return 0;
+    }
     uint8_t *d_res = d + sizeof(desc);
     uint32_t *d_work = (uint32_t *)(d_res + sizeof(res));
+    uint64_t *d_ng = (uint64_t *)(d + ng_at);    /* (only where the energy report runs) */
+    uint64_t ng_got = 0;
     const int ok =
         hipMemcpy(d, &desc, sizeof(desc), hipMemcpyHostToDevice) == hipSuccess &&
         (!dg || dvda_pcm_hip_crc32(d_pcm, layout, bits, (const dvda_pcm_crc_desc *)d, 1, payload,
@@ -291,8 +330,20 @@ static int piece_reports(struct pcm_reports *have, struct pcm_reports *out, int 
         (!lv || dvda_pcm_hip_levels(d_pcm, layout, bits, (const dvda_pcm_crc_desc *)d, 1, frames,
                                     (dvda_pcm_levels *)(d_res + offsetof(__typeof__(res), levels)), d_work, words,
                                     NULL) == DVDA_HIP_OK) &&
-        hipMemcpy(&res, d_res, sizeof(res), hipMemcpyDeviceToHost) == hipSuccess;
+        hipMemcpy(&res, d_res, sizeof(res), hipMemcpyDeviceToHost) == hipSuccess &&
+        (!ng || (hipMemcpy(d_ng, ng_head, sizeof(ng_head), hipMemcpyHostToDevice) == hipSuccess &&
+                 dvda_pcm_hip_energy(d_pcm, layout, (const dvda_pcm_crc_desc *)d, 1, nrg_b, (const uint32_t *)d_ng, frames,
+                                     (dvda_pcm_energy_block *)(d_ng + 4), d_ng + 1, d_ng + 2, d_ng + 3, d_work, words,
+                                     NULL) == DVDA_HIP_OK &&
+                 hipMemcpy(&ng_got, d_ng + 3, sizeof(ng_got), hipMemcpyDeviceToHost) == hipSuccess && ng_got == ng_n &&
+                 hipMemcpy(ng_blocks, d_ng + 4, (size_t)ng_n * sizeof(*ng_blocks), hipMemcpyDeviceToHost) == hipSuccess));
     (void)hipFree(d);
+    if (ok && ng) {
+        out->ng_blocks = ng_blocks;
+        out->ng_n = out->ng_cap = ng_n;
+    } else {
+        free(ng_blocks);
+    }
     if (ok && dg) {
         out->crc = res.crc;
         out->bytes = res.bytes;
@@ -311,6 +362,20 @@ static void reports_join(struct pcm_reports *track, const struct pcm_reports *pi
     }
     if (track->lv > 0)
         dvda_pcm_hip_levels_combine(&track->levels, &piece->levels, &track->levels);
+    if (track->ng > 0 && piece->ng_n) {
+        /* (a piece that cannot be joined leaves a reader without the report: -1, as for one that was never made) */
+        if (track->ng_n + piece->ng_n > track->ng_cap) {
+            const uint64_t cap = 2 * (track->ng_n + piece->ng_n);
+            dvda_pcm_energy_block *g = realloc(track->ng_blocks, (size_t)cap * sizeof(*g));
+            if (g) {
+                track->ng_blocks = g;
+                track->ng_cap = cap;
+            }
+        }
+        if (dvda_pcm_hip_energy_append(track->ng_blocks, &track->ng_n, track->ng_cap, piece->ng_blocks, piece->ng_n,
+                                       track->ng_block) != DVDA_HIP_OK)
+            track->ng = -1;
+    }
 }
 
 /* ------------------------------------------------------------------ the buffer set
@@ -615,6 +680,7 @@ static void reader_free(DVDA_Track_Reader *r)
     (void)hipFree(r->d_wav);
     free(r->wav);
     free(r->spans);
+    free(r->rep.ng_blocks);
     if (r->d_pcm)
         (void)hipFree(r->d_pcm);
     free(r);
@@ -690,8 +756,10 @@ static DVDA_Track_Reader *open_mlp(struct aob_set *aobs, const DVDA_Track *k, co
     /* before any copy to the host: the track as the decode left it on the device */
     r->rep.dg = o->digest;
     r->rep.lv = o->levels;
+    r->rep.ng = o->energy != 0;
+    r->rep.ng_block = o->energy;
     if (!piece_reports(&r->rep, &r->rep, wav_bits != 0, b.d_pcm, layout_of(wav_bits), bits_of(info.group0_bps), stride,
-                       info.pcm_frames, info.channels))
+                       info.pcm_frames, info.channels, 0))
         goto fail;
     if (wav_bits) {
         r->d_wav = (uint8_t *)b.d_pcm;
@@ -759,6 +827,7 @@ struct track_windows {
     int wav_bits;               /* != 0: the windows hold the payload (DVDA_PCM_WAV24 / WAV16); < 0 until the first
                                    window's major sync has decided it: only a 16- or 24-bit stream is decoded straight
                                    into it */
+    uint64_t rep_before;        /* the track's frames that went through piece_reports() so far (the producing thread's) */
     struct pcm_reports rep;     /* states: what every window is asked on the device before it is copied (-1: decided by the
                                    first window's piece_reports()); values: the windows handed out so far, joined (under
                                    `mu`, win_release()) */
@@ -909,7 +978,9 @@ static void windows_free(struct track_windows *w)
     for (int i = 0; i < WIN_SLOTS; i++) {
         c->slot[i] = w->slot[i];
         c->slot[i].frames = 0;
+        rep_reset(&c->slot[i].rep);
     }
+    free(w->rep.ng_blocks);
     free(w->whole);
     free(w->pack_tmp);
     free(w->spans);
@@ -1127,8 +1198,9 @@ static int win_deliver(struct track_windows *w, struct win_slot *out, const dvda
 {
     struct track_bufs *b = &w->b;
     if (!piece_reports(&w->rep, &out->rep, w->wav_bits != 0, b->d_pcm, layout_of(w->wav_bits), bits_of(info->group0_bps),
-                       stride, info->pcm_frames, info->channels))
+                       stride, info->pcm_frames, info->channels, w->rep_before))
         return 0;
+    w->rep_before += info->pcm_frames;
     const size_t bytes = (size_t)info->pcm_frames * info->channels * (w->wav_bits ? (unsigned)w->wav_bits / 8 : 4);
     if (!slot_reserve(b, out, bytes) ||
         (bytes && hipMemcpy(out->host, b->d_pcm, bytes, hipMemcpyDeviceToHost) != hipSuccess))
@@ -1192,7 +1264,7 @@ static int win_produce(struct track_windows *w, struct win_slot *out)
     uint64_t total = 0, begin = 0, end = 0, stride = 0;
     out->frames = 0;
     out->stride = 0;
-    memset(&out->rep, 0, sizeof(out->rep));
+    rep_reset(&out->rep);
     const int conceal = w->opts.conceal;
     w->p_final = 0;
     /* ---- conceal mode: silence that is still owed, then the decoded window that waits behind it */
@@ -1334,8 +1406,9 @@ static int win_produce(struct track_windows *w, struct win_slot *out)
     }
     /* ---- the window's reports, from the device */
     if (!piece_reports(&w->rep, &out->rep, w->wav_bits != 0, b->d_pcm, layout_of(w->wav_bits), bits_of(info.group0_bps),
-                       stride, info.pcm_frames, info.channels))
+                       stride, info.pcm_frames, info.channels, w->rep_before))
         return 0;
+    w->rep_before += info.pcm_frames;
     /* ---- PCM (or payload) to the host buffer */
     const size_t bytes = (size_t)info.pcm_frames * info.channels * (w->wav_bits ? (unsigned)w->wav_bits / 8 : 4);
     if (!slot_reserve(b, out, bytes) ||
@@ -1361,7 +1434,7 @@ static int win_produce_pcm(struct track_windows *w, struct win_slot *out)
     int final = 0;
     out->frames = 0;
     out->stride = 0;
-    memset(&out->rep, 0, sizeof(out->rep));
+    rep_reset(&out->rep);
     if (w->next + want > w->aobs.total || w->next + want < w->next)
         want = w->next < w->aobs.total ? w->aobs.total - w->next : 0;
     if (!sectors_to_device(b, &w->aobs, w->next, want, bits, ch, NULL, &got, &total, &stride))
@@ -1376,8 +1449,10 @@ static int win_produce_pcm(struct track_windows *w, struct win_slot *out)
     if (!final && (got < want || w->next >= w->aobs.total))
         final = 1;                               /* the files end inside the track */
     /* (the planes as the un-swizzle left them: before packing and copy) */
-    if (!piece_reports(&w->rep, &out->rep, w->wav_bits != 0, b->d_pcm, DVDA_PCM_PLANAR, bits, stride, deliver, ch))
+    if (!piece_reports(&w->rep, &out->rep, w->wav_bits != 0, b->d_pcm, DVDA_PCM_PLANAR, bits, stride, deliver, ch,
+                       w->rep_before))
         return 0;
+    w->rep_before += deliver;
     if (deliver && w->wav_bits) {
         const size_t bytes = (size_t)deliver * ch * (bits / 8);
         if (!bufs_dev_room(b, (void **)&b->d_stream, &b->cap_stream, bytes + 64) ||
@@ -1512,6 +1587,8 @@ static DVDA_Track_Reader *windows_new(const DVDA_Track *k, const struct reader_o
     w->opts = *o;
     w->rep.dg = o->digest;
     w->rep.lv = o->levels;
+    w->rep.ng = o->energy != 0;
+    w->rep.ng_block = o->energy;
     w->next = k->s.first;
     w->last = k->s.last >= k->s.first ? k->s.last : k->s.first;
     w->window = window_sectors();
@@ -1613,7 +1690,9 @@ static DVDA_Track_Reader *open_pcm(struct aob_set *aobs, const DVDA_Track *k, co
     b.d_pcm = NULL;
     r->rep.dg = o->digest;
     r->rep.lv = o->levels;
-    if (!piece_reports(&r->rep, &r->rep, 0, r->d_pcm, DVDA_PCM_PLANAR, bits, stride, deliver, r->channels))
+    r->rep.ng = o->energy != 0;
+    r->rep.ng_block = o->energy;
+    if (!piece_reports(&r->rep, &r->rep, 0, r->d_pcm, DVDA_PCM_PLANAR, bits, stride, deliver, r->channels, 0))
         goto fail;
     goto done;
 fail:
@@ -1803,6 +1882,31 @@ int dvda_hip_reader_levels(const DVDA_Track_Reader *r, dvda_pcm_levels *out)
         return -1;
     if (out)
         *out = rep.levels;
+    return rc;
+}
+int dvda_hip_reader_energy(const DVDA_Track_Reader *r, dvda_pcm_energy_block *blocks, unsigned long long cap,
+                           unsigned long long *n)
+{
+    if (!r)
+        return -1;
+    /* (the blocks are copied under the lock: a window handed out meanwhile moves the track's array) */
+    struct track_windows *w = r->win;
+    int rc = 1;
+    if (w)
+        pthread_mutex_lock(&w->mu);
+    const struct pcm_reports *rep = w ? &w->rep : &r->rep;
+    if (w)
+        rc = w->failed ? -1 : (w->finished && w->count == 0) ? 1 : 0;
+    if (rep->ng <= 0)
+        rc = -1;
+    if (rc >= 0) {
+        if (n)
+            *n = rep->ng_n;
+        for (uint64_t j = 0; blocks && j < cap && j < rep->ng_n; j++)
+            blocks[j] = rep->ng_blocks[j];
+    }
+    if (w)
+        pthread_mutex_unlock(&w->mu);
     return rc;
 }
 /* what was concealed of the track: 1 = final, 0 = not yet (a windowed reader that still produces), -1 = opened without

@@ -1,5 +1,5 @@
 // pcm_report_run.h -- host side of the reports of decoded PCM, the digest (pcm_digest.h), the level report
-// (pcm_levels.h) and the compare (pcm_compare.h): what a report is to the driver, the one driver of the flat tile list (pcm_tiles.h), the one call that
+// (pcm_levels.h), the compare (pcm_compare.h) and the energy report (pcm_energy.h): what a report is to the driver, the one driver of the flat tile list (pcm_tiles.h), the one call that
 // runs a report behind a decode on the context's own buffers, and the host arithmetic that joins two pieces' results.
 #pragma once
 #include <vector>
@@ -7,6 +7,7 @@
 #include "mlp_ctx.h"
 #include "pcm_compare.h"
 #include "pcm_digest.h"
+#include "pcm_energy.h"
 #include "pcm_levels.h"
 
 // ---- a report, as the driver sees it: the unit its tiles are cut in and the words a tile leaves in the workspace, the
@@ -127,6 +128,48 @@ struct CmpReport {
 };
 static_assert(sizeof(dvda_pcm_diff) == 160, "dvda_pcm_diff is 160 bytes");
 
+// The energy report: its unit is a piece of a block, so the grid -- B, the leads -- travels here with the four outputs,
+// and the bound on its list is its own.
+struct NrgReport {
+    static constexpr uint32_t TILE = nrg::PIECE, TILE_WORDS = nrg::REC, TILE_BLOCKS = nrg::TILE_BLOCKS;    // unit: frames
+    uint32_t block_frames;
+    const uint32_t *d_lead;
+    dvda_pcm_energy_block *d_blocks;
+    const uint64_t *d_block_off, *d_block_cap;
+    uint64_t *d_nblocks;
+
+    static bool block_ok(uint32_t b) { return b >= DVDA_NRG_MIN_BLOCK && b <= DVDA_NRG_MAX_BLOCK; }
+    bool has_out() const { return block_ok(block_frames) && d_blocks && d_block_off && d_block_cap && d_nblocks; }
+    static bool takes(uint32_t layout, unsigned) { return layout == DVDA_PCM_PLANAR || layout == DVDA_PCM_INTERLEAVED; }
+    // every block has at most one ragged piece, and a stream at most frames / B + 2 blocks
+    uint64_t max_tiles(uint32_t n, uint64_t max_total) const
+    {
+        return max_total / nrg::PIECE + max_total / block_frames + 2ull * n;
+    }
+
+    void plan(hipStream_t st, const dvda_pcm_crc_desc *d_desc, uint32_t n, unsigned, uint32_t *cnt) const
+    {
+        hipLaunchKernelGGL(nrg::k_nrg_plan, dim3((n + 255) / 256), dim3(256), 0, st, d_desc, n, block_frames, d_lead, cnt);
+    }
+    void tiles(dim3 grid, dim3 block, hipStream_t st, const int32_t *d_pcm, uint32_t layout, const dvda_pcm_crc_desc *d_desc,
+               uint32_t n, unsigned, const uint32_t *base, uint32_t *rec, uint32_t max_tiles) const
+    {
+        if (layout == DVDA_PCM_PLANAR)
+            hipLaunchKernelGGL(nrg::k_nrg_tiles<true>, grid, block, 0, st, d_pcm, d_desc, n, block_frames, d_lead, base, rec,
+                               max_tiles);
+        else
+            hipLaunchKernelGGL(nrg::k_nrg_tiles<false>, grid, block, 0, st, d_pcm, d_desc, n, block_frames, d_lead, base, rec,
+                               max_tiles);
+    }
+    void join(dim3 block, hipStream_t st, const dvda_pcm_crc_desc *d_desc, uint32_t n, unsigned, const uint32_t *base,
+              const uint32_t *rec, uint32_t max_tiles) const
+    {
+        hipLaunchKernelGGL(nrg::k_nrg_join, dim3(n), block, 0, st, d_desc, n, block_frames, d_lead, base, rec, max_tiles,
+                           d_blocks, d_block_off, d_block_cap, d_nblocks);
+    }
+};
+static_assert(sizeof(dvda_pcm_energy_block) == 168, "dvda_pcm_energy_block is 168 bytes");
+
 // ---- the driver of the flat tile list
 // tiles the list can hold for n streams of max_total units in all: every stream has at most one ragged tile
 template <class R>
@@ -141,6 +184,24 @@ template <class R>
 static inline size_t report_workspace_words(uint32_t n, uint64_t max_total)
 {
     return 2 * ((size_t)n + 1) + ((size_t)n + 1023) / 1024 + 2 + (size_t)report_max_tiles<R>(n, max_total) * R::TILE_WORDS;
+}
+
+// ... for a report `r` that may supply its own bound, max_tiles(n, max_total), from what it carries (the energy report's
+// pieces depend on its block length); a report without one has the bound above
+template <class R>
+static inline auto report_max_tiles(const R &r, uint32_t n, uint64_t max_total, int) -> decltype(r.max_tiles(n, max_total))
+{
+    return r.max_tiles(n, max_total);
+}
+template <class R>
+static inline uint64_t report_max_tiles(const R &, uint32_t n, uint64_t max_total, long)
+{
+    return report_max_tiles<R>(n, max_total);
+}
+template <class R>
+static inline size_t report_workspace_words(const R &r, uint32_t n, uint64_t max_total)
+{
+    return 2 * ((size_t)n + 1) + ((size_t)n + 1023) / 1024 + 2 + (size_t)report_max_tiles(r, n, max_total, 0) * R::TILE_WORDS;
 }
 
 // (asked of the runtime once per process)
@@ -160,9 +221,9 @@ static int report_run(const R &r, const int32_t *d_pcm, uint32_t layout, unsigne
 {
     if (!d_pcm || !d_desc || !d_work || !r.has_out() || !R::takes(layout, bits))
         return DVDA_HIP_EINVAL;
-    if (work_words < report_workspace_words<R>(n, max_total))
+    if (work_words < report_workspace_words(r, n, max_total))
         return DVDA_HIP_EINVAL;
-    const uint64_t max_tiles = report_max_tiles<R>(n, max_total);
+    const uint64_t max_tiles = report_max_tiles(r, n, max_total, 0);
     if (max_tiles >> 31)
         return DVDA_HIP_ECAPACITY;
     if (!report_have_device())
@@ -183,13 +244,11 @@ static int report_run(const R &r, const int32_t *d_pcm, uint32_t layout, unsigne
     return DVDA_HIP_OK;
 }
 
-// The report of the first n (clamped to the batch; 0: nothing to do) streams of the context's last decode, on the
-// context's buffers: the descriptors from what dvda_mlp_hip_stream_info says and the caller's d_out_off / d_out_stride,
-// copied up, then the report, enqueued on `stream_`.  *r: where the results lie on the device; the caller copies them
-// down and waits.  Blocks for the descriptors.
-template <class R>
-static int report_of_decode(dvda_mlp_hip_ctx *c, const int32_t *d_pcm, const uint64_t *d_out_off,
-                            const uint64_t *d_out_stride, unsigned bits, uint32_t *n_io, void *stream_, R *r)
+// The descriptors of the first n (clamped to the batch; 0: nothing to do) streams of the context's last decode, on the
+// host: frames and channels from what dvda_mlp_hip_stream_info says, off / stride from the caller's d_out_off /
+// d_out_stride, copied down.  Blocks.
+static int report_decode_descs(dvda_mlp_hip_ctx *c, const uint64_t *d_out_off, const uint64_t *d_out_stride, uint32_t *n_io,
+                               void *stream_, std::vector<dvda_pcm_crc_desc> *desc_)
 {
     if (!c->indexed)
         return DVDA_HIP_ESTATE;
@@ -207,8 +266,8 @@ static int report_of_decode(dvda_mlp_hip_ctx *c, const int32_t *d_pcm, const uin
     std::vector<uint64_t> off(n), stride(n);
     HIP_TRY(hipMemcpy(off.data(), d_out_off, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(stride.data(), d_out_stride, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    std::vector<dvda_pcm_crc_desc> desc(n);
-    uint64_t total = 0;
+    std::vector<dvda_pcm_crc_desc> &desc = *desc_;
+    desc.resize(n);
     for (uint32_t i = 0; i < n; i++) {
         dvda_pcm_crc_desc &d = desc[i];
         d.off = off[i];
@@ -217,8 +276,25 @@ static int report_of_decode(dvda_mlp_hip_ctx *c, const int32_t *d_pcm, const uin
         d.frames = (infos[i].status & DVDA_ST_OVERFLOW) ? 0 : infos[i].pcm_frames;
         d.channels = infos[i].channels;
         d.reserved = 0;
-        total += R::units(d, bits);
     }
+    return DVDA_HIP_OK;
+}
+
+// The report of the first n (clamped to the batch; 0: nothing to do) streams of the context's last decode, on the
+// context's buffers: the descriptors copied up, then the report, enqueued on `stream_`.  *r: where the results lie on
+// the device; the caller copies them down and waits.  Blocks for the descriptors.
+template <class R>
+static int report_of_decode(dvda_mlp_hip_ctx *c, const int32_t *d_pcm, const uint64_t *d_out_off,
+                            const uint64_t *d_out_stride, unsigned bits, uint32_t *n_io, void *stream_, R *r)
+{
+    std::vector<dvda_pcm_crc_desc> desc;
+    int rc = report_decode_descs(c, d_out_off, d_out_stride, n_io, stream_, &desc);
+    const uint32_t n = *n_io;
+    if (rc || n == 0)
+        return rc;
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; i++)
+        total += R::units(desc[i], bits);
     if ((rc = c->d_rep_desc.grow(n)) != 0 || (rc = c->d_rep_out.grow(R::out_words(n))) != 0 ||
         (rc = c->d_rep_work.grow(report_workspace_words<R>(n, total))) != 0)
         return rc;
@@ -379,4 +455,132 @@ extern "C" int dvda_pcm_hip_diff_combine(const dvda_pcm_diff *a_, const dvda_pcm
     r.flags = a.flags | b.flags;
     *out = r;
     return DVDA_HIP_OK;
+}
+
+// ---- the energy report
+extern "C" size_t dvda_pcm_hip_energy_workspace_words(uint32_t n, uint64_t max_total_frames, uint32_t block_frames)
+{
+    if (!NrgReport::block_ok(block_frames))
+        return 0;
+    return report_workspace_words(NrgReport{block_frames, nullptr, nullptr, nullptr, nullptr, nullptr}, n, max_total_frames);
+}
+
+extern "C" int dvda_pcm_hip_energy(const int32_t *d_pcm, uint32_t layout, const dvda_pcm_crc_desc *d_desc, uint32_t n,
+                                   uint32_t block_frames, const uint32_t *d_lead, uint64_t max_total_frames,
+                                   dvda_pcm_energy_block *d_blocks, const uint64_t *d_block_off, const uint64_t *d_block_cap,
+                                   uint64_t *d_nblocks, uint32_t *d_work, size_t work_words, void *stream_)
+{
+    return report_run(NrgReport{block_frames, d_lead, d_blocks, d_block_off, d_block_cap, d_nblocks}, d_pcm, layout, 0, d_desc,
+                      n, max_total_frames, d_work, work_words, stream_);
+}
+
+extern "C" int dvda_mlp_hip_pcm_energy(dvda_mlp_hip_ctx *c, const int32_t *d_pcm, const uint64_t *d_out_off,
+                                       const uint64_t *d_out_stride, uint32_t block_frames,
+                                       dvda_pcm_energy_block *host_blocks, uint64_t cap_blocks, uint64_t *host_first, uint32_t n,
+                                       void *stream_)
+{
+    if (!c || !d_pcm || !d_out_off || !d_out_stride || !host_first || (!host_blocks && cap_blocks) ||
+        !NrgReport::block_ok(block_frames) || !NrgReport::takes(c->set.pcm_layout, 0))
+        return DVDA_HIP_EINVAL;
+    std::vector<dvda_pcm_crc_desc> desc;
+    int rc = report_decode_descs(c, d_out_off, d_out_stride, &n, stream_, &desc);
+    if (rc)
+        return rc;
+    // the streams back to back: what each needs is known here (every grid starts at its stream's first frame)
+    std::vector<uint64_t> first((size_t)n + 1), arr(3 * (size_t)n);
+    uint64_t total = 0, blocks = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        first[i] = blocks;
+        blocks += nrg::grid_of(desc[i], block_frames, block_frames).blocks();
+        total += PCMT_NOT_TAKEN(desc[i]) ? 0 : desc[i].frames;
+    }
+    first[n] = blocks;
+    if (blocks > cap_blocks) {
+        host_first[n] = blocks;
+        return DVDA_HIP_ECAPACITY;
+    }
+    for (uint32_t i = 0; i <= n; i++)
+        host_first[i] = first[i];
+    if (n == 0 || blocks == 0)
+        return DVDA_HIP_OK;
+    // d_rep_out: the blocks (21 words each) | off [n] | cap [n] | nblocks [n]
+    constexpr size_t BW = sizeof(dvda_pcm_energy_block) / sizeof(uint64_t);
+    NrgReport r{block_frames, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if ((rc = c->d_rep_desc.grow(n)) != 0 || (rc = c->d_rep_out.grow(blocks * BW + 3 * (uint64_t)n)) != 0 ||
+        (rc = c->d_rep_work.grow(report_workspace_words(r, n, total))) != 0)
+        return rc;
+    for (uint32_t i = 0; i < n; i++) {
+        arr[i] = first[i];
+        arr[n + i] = first[i + 1] - first[i];
+        arr[2 * (size_t)n + i] = 0;
+    }
+    uint64_t *d_arr = c->d_rep_out + blocks * BW;
+    HIP_TRY(hipMemcpy(c->d_rep_desc, desc.data(), (size_t)n * sizeof(dvda_pcm_crc_desc), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_arr, arr.data(), arr.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    r.d_blocks = (dvda_pcm_energy_block *)(uint64_t *)c->d_rep_out;
+    r.d_block_off = d_arr;
+    r.d_block_cap = d_arr + n;
+    r.d_nblocks = d_arr + 2 * (size_t)n;
+    rc = report_run(r, d_pcm, c->set.pcm_layout, 0, c->d_rep_desc, n, total, c->d_rep_work, (size_t)c->d_rep_work.cap, stream_);
+    if (rc)
+        return rc;
+    hipStream_t st = (hipStream_t)stream_;
+    HIP_TRY(hipMemcpyAsync(host_blocks, r.d_blocks, (size_t)blocks * sizeof(dvda_pcm_energy_block), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DVDA_HIP_OK;
+}
+
+static inline void nrg_add(dvda_pcm_energy_block *t, const dvda_pcm_energy_block &p)
+{
+    for (int c = 0; c < 8; c++) {
+        t->sq_lo[c] += p.sq_lo[c];
+        t->sq_hi[c] += p.sq_hi[c] + (t->sq_lo[c] < p.sq_lo[c] ? 1u : 0u);
+        t->peak[c] = p.peak[c] > t->peak[c] ? p.peak[c] : t->peak[c];
+    }
+}
+
+extern "C" int dvda_pcm_hip_energy_append(dvda_pcm_energy_block *track, uint64_t *n_track, uint64_t cap,
+                                          const dvda_pcm_energy_block *piece, uint64_t n_piece, uint32_t block_frames)
+{
+    if (!n_track || (!track && cap) || (!piece && n_piece) || !NrgReport::block_ok(block_frames) || *n_track > cap)
+        return DVDA_HIP_EINVAL;
+    if (n_piece == 0)
+        return DVDA_HIP_OK;
+    const uint64_t have = *n_track;
+    const bool merge = have && track[have - 1].frames < block_frames;
+    // on the grid: the block the piece opens or completes has at most B frames, and exactly B when more blocks follow
+    // it; behind it only the piece's last block is short
+    const uint64_t head = (merge ? track[have - 1].frames : 0u) + (uint64_t)piece[0].frames;
+    if (head > block_frames || (n_piece > 1 && head != block_frames))
+        return DVDA_HIP_EINVAL;
+    for (uint64_t j = 1; j < n_piece; j++)
+        if (piece[j].frames > block_frames || (j + 1 < n_piece && piece[j].frames != block_frames))
+            return DVDA_HIP_EINVAL;
+    const uint64_t need = have + n_piece - (merge ? 1 : 0);
+    if (need > cap)
+        return DVDA_HIP_ECAPACITY;
+    uint64_t j = 0;
+    if (merge) {
+        nrg_add(&track[have - 1], piece[0]);
+        track[have - 1].frames += piece[0].frames;
+        j = 1;
+    }
+    for (uint64_t at = have; j < n_piece; j++, at++)
+        track[at] = piece[j];
+    *n_track = need;
+    return DVDA_HIP_OK;
+}
+
+extern "C" void dvda_pcm_hip_energy_total(const dvda_pcm_energy_block *blocks, uint64_t n, dvda_pcm_energy_block *out)
+{
+    dvda_pcm_energy_block r = {};
+    uint64_t frames = 0;
+    for (uint64_t j = 0; j < n; j++) {
+        nrg_add(&r, blocks[j]);
+        frames += blocks[j].frames;
+        if (frames > 0xFFFFFFFFull)
+            frames = 0xFFFFFFFFull;
+    }
+    r.frames = (uint32_t)frames;
+    *out = r;
 }

@@ -26,6 +26,7 @@ EXPORTS = [
     "dvda_hip_reader_wav_next", "dvda_hip_reader_windowed", "dvda_hip_reader_memory", "dvda_hip_reader_failed",
     "dvda_hip_release_cached_buffers", "dvda_hip_set_presentation", "dvda_hip_open_track_reader_with",
     "dvda_hip_set_digest", "dvda_hip_reader_crc32", "dvda_hip_set_levels", "dvda_hip_reader_levels",
+    "dvda_hip_set_energy", "dvda_hip_reader_energy",
     "dvda_hip_set_conceal", "dvda_hip_reader_concealed", "dvda_hip_open_track_reader_concealing",
 ]
 
@@ -95,6 +96,11 @@ def lib():
         L.dvda_hip_set_levels.argtypes = [ctypes.c_int]
         L.dvda_hip_reader_levels.restype = ctypes.c_int
         L.dvda_hip_reader_levels.argtypes = [vp, ctypes.POINTER(hipdec.Levels)]
+        L.dvda_hip_set_energy.restype = None
+        L.dvda_hip_set_energy.argtypes = [ctypes.c_uint]
+        L.dvda_hip_reader_energy.restype = ctypes.c_int
+        L.dvda_hip_reader_energy.argtypes = [vp, ctypes.POINTER(hipdec.EnergyBlock), ctypes.c_ulonglong,
+                                             ctypes.POINTER(ctypes.c_ulonglong)]
         L.dvda_hip_open_track_reader_concealing.restype = ctypes.c_void_p
         L.dvda_hip_open_track_reader_concealing.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4
         L.dvda_hip_set_conceal.restype = None
@@ -132,7 +138,7 @@ def layout(audio_ts, titleset=1):
 
 
 def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0, fused=False, pieces=False,
-               presentation=0, digest=False, levels=False, conceal=None):
+               presentation=0, digest=False, levels=False, conceal=None, energy=0):
     """Decodes one track on the GPU.  Returns a dict: codec ("PCM"/"MLP"), bits, rate, channels,
     mask, status, and pcm = int32 [frames, channels] (interleaved, RIFF-WAVE order) read with
     dvda_read() in `chunk`-frame calls -- or, with wav=True, payload = the WAV data bytes packed
@@ -149,6 +155,10 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
     levels=True: the reader makes the level report of the track's int32 PCM on the device (dvda_hip_set_levels):
     info["levels"] = the report as hipdec.Levels.as_dict() gives it (None when the reader has none: a WAV-payload-only
     reader), and info["levels_states"] = what dvda_hip_reader_levels returned right after the open and at the end.
+    energy=<block_frames>: the reader makes the energy report of the track's int32 PCM on the device, on a grid of that
+    block length anchored at the track's first frame (dvda_hip_set_energy): info["energy"] = the track's blocks as
+    hipdec.EnergyBlock.as_dict() gives them (None when the reader has none), and info["energy_states"] = what
+    dvda_hip_reader_energy returned right after the open and at the end, info["energy_counts"] the block counts then.
     conceal=True: a damaged MLP track is concealed, not refused (dvda_hip_set_conceal): info["concealed"] = the spans as
     6-tuples (first_frame, frames, byte_off, byte_end, cause, flags) in track terms, and info["concealed_states"] = what
     dvda_hip_reader_concealed returned right after the open and at the end.  conceal=False says "off" explicitly; None
@@ -167,12 +177,14 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
         k = L.dvda_open_track(t, track) if t else None
         L.dvda_hip_set_digest(1 if digest else 0)
         L.dvda_hip_set_levels(1 if levels else 0)
+        L.dvda_hip_set_energy(int(energy))
         try:
             r = L.dvda_hip_open_track_reader_concealing(k, device, 1 if (fused and wav) else 0, presentation,
                                                         -1 if conceal is None else int(bool(conceal))) if k else None
         finally:
             L.dvda_hip_set_digest(0)            # (read when the reader is opened: nothing is left behind)
             L.dvda_hip_set_levels(0)
+            L.dvda_hip_set_energy(0)
         if not r:
             raise RuntimeError("track %d/%d/%d cannot be opened for reading" % (titleset, title, track))
         ch = L.dvda_channel_count(r)
@@ -185,6 +197,9 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
         first_state = L.dvda_hip_reader_crc32(r, ctypes.byref(crc), ctypes.byref(nbytes)) if digest else None
         report = hipdec.Levels()
         first_levels = L.dvda_hip_reader_levels(r, ctypes.byref(report)) if levels else None
+        n_blocks = ctypes.c_ulonglong()
+        first_energy = L.dvda_hip_reader_energy(r, None, 0, ctypes.byref(n_blocks)) if energy else None
+        first_blocks = int(n_blocks.value)
         n_spans = ctypes.c_uint()
         first_spans = L.dvda_hip_reader_concealed(r, None, 0, ctypes.byref(n_spans)) if conceal else None
         if wav and pieces:
@@ -225,6 +240,15 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
             state = L.dvda_hip_reader_levels(r, ctypes.byref(report))
             info["levels_states"] = (first_levels, state)
             info["levels"] = report.as_dict() if state == 1 else None
+        if energy:
+            state = L.dvda_hip_reader_energy(r, None, 0, ctypes.byref(n_blocks))
+            info["energy_states"] = (first_energy, state)
+            info["energy_counts"] = (first_blocks, int(n_blocks.value))
+            info["energy"] = None
+            if state == 1:
+                arr = (hipdec.EnergyBlock * max(int(n_blocks.value), 1))()
+                L.dvda_hip_reader_energy(r, arr, n_blocks.value, ctypes.byref(n_blocks))
+                info["energy"] = [arr[j].as_dict() for j in range(int(n_blocks.value))]
         if conceal:
             state = L.dvda_hip_reader_concealed(r, None, 0, ctypes.byref(n_spans))
             arr = (hipdec.ConcealSpan * max(int(n_spans.value), 1))()

@@ -75,7 +75,9 @@ EXPORTS = ("dvda_mlp_hip_create", "dvda_mlp_hip_destroy", "dvda_mlp_hip_index", 
            "dvda_pcm_hip_levels", "dvda_pcm_hip_levels_workspace_words", "dvda_mlp_hip_pcm_levels",
            "dvda_pcm_hip_levels_combine",
            "dvda_pcm_hip_compare", "dvda_pcm_hip_compare_workspace_words", "dvda_mlp_hip_pcm_compare",
-           "dvda_pcm_hip_diff_combine", "dvda_mlp_hip_index_graph_state")
+           "dvda_pcm_hip_diff_combine", "dvda_mlp_hip_index_graph_state",
+           "dvda_pcm_hip_energy", "dvda_pcm_hip_energy_workspace_words", "dvda_mlp_hip_pcm_energy",
+           "dvda_pcm_hip_energy_append", "dvda_pcm_hip_energy_total")
 
 CRC_TILE_BYTES = 16384      # DVDA_CRC_TILE_BYTES: the digest's tiles, aligned to the end of a stream's payload
 CRC_JOIN_TILES = 256        # DVDA_CRC_JOIN_TILES: tiles a join workgroup folds per turn of its loop
@@ -129,6 +131,25 @@ class Diff(ctypes.Structure):
         for k in cls._SCALARS:
             setattr(out, k, d[k])
         return out
+
+
+NRG_MIN_BLOCK, NRG_MAX_BLOCK = 64, 1 << 24      # DVDA_NRG_MIN_BLOCK / DVDA_NRG_MAX_BLOCK: the energy report's block length
+NRG_PIECE_FRAMES = 4096     # DVDA_NRG_PIECE_FRAMES: frames of one block a workgroup takes at most
+
+
+class EnergyBlock(ctypes.Structure):
+    """dvda_pcm_energy_block of include/dvda_mlp_hip.h"""
+    _fields_ = [("sq_lo", ctypes.c_uint64 * 8), ("sq_hi", ctypes.c_uint64 * 8), ("peak", ctypes.c_uint32 * 8),
+                ("frames", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return dict(sq_lo=[int(v) for v in self.sq_lo], sq_hi=[int(v) for v in self.sq_hi],
+                    peak=[int(v) for v in self.peak], frames=int(self.frames))
+
+    @classmethod
+    def from_dict(cls, d):
+        return cls((ctypes.c_uint64 * 8)(*d["sq_lo"]), (ctypes.c_uint64 * 8)(*d["sq_hi"]), (ctypes.c_uint32 * 8)(*d["peak"]),
+                   d["frames"], 0)
 
 
 ST_CONCEALED = 1 << 30          # DVDA_ST_CONCEALED: conceal mode, the stream was damaged (not in ST_BENIGN)
@@ -261,6 +282,15 @@ def lib():
         L.dvda_pcm_hip_compare.argtypes = [vp, u32, vp, vp, u32, vp, u32, ctypes.c_uint, u64, vp, vp, ctypes.c_size_t, vp]
         L.dvda_mlp_hip_pcm_compare.argtypes = [vp, vp, vp, vp, vp, u32, vp, ctypes.c_uint, ctypes.POINTER(Diff), u32, vp]
         L.dvda_pcm_hip_diff_combine.argtypes = [ctypes.POINTER(Diff), ctypes.POINTER(Diff), ctypes.POINTER(Diff)]
+        L.dvda_pcm_hip_energy_workspace_words.restype = ctypes.c_size_t
+        L.dvda_pcm_hip_energy_workspace_words.argtypes = [u32, u64, u32]
+        L.dvda_pcm_hip_energy.argtypes = [vp, u32, vp, u32, u32, vp, u64, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+        L.dvda_mlp_hip_pcm_energy.argtypes = [vp, vp, vp, vp, u32, ctypes.POINTER(EnergyBlock), u64, ctypes.POINTER(u64),
+                                              u32, vp]
+        L.dvda_pcm_hip_energy_append.argtypes = [ctypes.POINTER(EnergyBlock), ctypes.POINTER(u64), u64,
+                                                 ctypes.POINTER(EnergyBlock), u64, u32]
+        L.dvda_pcm_hip_energy_total.restype = None
+        L.dvda_pcm_hip_energy_total.argtypes = [ctypes.POINTER(EnergyBlock), u64, ctypes.POINTER(EnergyBlock)]
         _lib = L
     return _lib
 
@@ -417,6 +447,25 @@ class Context:
         _check(lib().dvda_mlp_hip_pcm_levels(self._h, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, bits, arr, n, stream),
                "dvda_mlp_hip_pcm_levels")
         return [arr[i].as_dict() for i in range(n)]
+
+    def pcm_energy(self, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, block_frames, n=None, stream=0, cap_blocks=None):
+        """dvda_mlp_hip_pcm_energy: per block of block_frames frames and channel the exact sum of squares and the peak
+        of every stream, computed on the device from the int32 PCM the last decode wrote -> one list of
+        EnergyBlock.as_dict() per stream; blocks.  cap_blocks: room for that many blocks in all (HipError ECAPACITY
+        when it is too small); default: the call asks first how many there are.  HipError (EINVAL) when the context's
+        layout is a WAV one."""
+        n = self.n_streams if n is None else n
+        first = (ctypes.c_uint64 * (n + 1))()
+        fn = lib().dvda_mlp_hip_pcm_energy
+        if cap_blocks is None:
+            rc = fn(self._h, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, block_frames, None, 0, first, n, stream)
+            if rc not in (0, -4):
+                _check(rc, "dvda_mlp_hip_pcm_energy")
+            cap_blocks = int(first[n])
+        arr = (EnergyBlock * max(cap_blocks, 1))()
+        _check(fn(self._h, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, block_frames, arr, cap_blocks, first, n, stream),
+               "dvda_mlp_hip_pcm_energy")
+        return [[arr[j].as_dict() for j in range(int(first[i]), int(first[i + 1]))] for i in range(n)]
 
     def pcm_compare(self, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, d_other, other_layout, other_desc, bits=0, n=None,
                     stream=None):
@@ -592,6 +641,98 @@ def diff_combine(a, b):
     return out.as_dict()
 
 
+def energy_nblocks(frames, block_frames, lead=None):
+    """blocks of a stream of `frames` frames on the grid (block_frames, lead): the rule of include/dvda_mlp_hip.h"""
+    lead = block_frames if lead is None else lead
+    if frames <= 0 or not 1 <= lead <= block_frames:
+        return 0
+    return 1 + -(-max(frames - lead, 0) // block_frames)
+
+
+def pcm_energy(d_pcm, layout, desc, block_frames, lead=None, max_total_frames=None, work=None, caps=None):
+    """dvda_pcm_hip_energy over torch tensors: d_pcm an int32 tensor on the device holding the streams in `layout`
+    (PCM_PLANAR or PCM_INTERLEAVED), desc a list of (off, stride, frames, channels) as dvda_pcm_crc_desc states them,
+    block_frames the grid's block length and lead the first block's length per stream (None: block_frames for all).
+    -> (d_blocks, first, d_nblocks): a uint8 device tensor [first[-1], sizeof(EnergyBlock)] in which stream i has room for
+    the blocks first[i] .. first[i + 1], that list, and an int64 device tensor of the streams' block counts
+    (energy_lists brings all of it to the host).  caps: room per stream (default: what each needs by energy_nblocks).
+    Only the kernels are asynchronous, on torch's current stream: like pcm_levels, this helper builds the descriptors on
+    the host, copies them to the device and allocates them, the results and -- when none is passed -- the workspace.
+    max_total_frames: bound on the sum of the frames (default: computed from desc); work: an int32 workspace tensor of
+    at least pcm_energy_workspace_words() elements."""
+    taken = [1 <= int(c) <= 8 and int(f) <= 1 << 40 for _, _, f, c in desc]
+    if max_total_frames is None:
+        max_total_frames = int(sum(int(d[2]) for d, ok in zip(desc, taken) if ok))
+    torch, n, d_desc, work, st = _report_args(d_pcm, desc, "the energy report", max_total_frames, work,
+                                              lambda k, total: lib().dvda_pcm_hip_energy_workspace_words(k, total,
+                                                                                                         block_frames))
+    dev = d_pcm.device
+    if caps is None:
+        caps = [energy_nblocks(int(d[2]), block_frames, None if lead is None else int(lead[i])) if ok else 0
+                for i, (d, ok) in enumerate(zip(desc, taken))]
+    first = [0]
+    for c in caps:
+        first.append(first[-1] + int(c))
+    arr = torch.tensor([first[:n] + [0], [int(c) for c in caps] + [0]], dtype=torch.int64).to(dev)
+    d_lead = None if lead is None else torch.tensor([int(v) for v in lead] + [0], dtype=torch.int32).to(dev)
+    d_blocks = torch.zeros((max(first[-1], 1), ctypes.sizeof(EnergyBlock)), dtype=torch.uint8, device=dev)
+    d_nblocks = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+    _check(lib().dvda_pcm_hip_energy(d_pcm.data_ptr(), layout, d_desc.data_ptr(), n, block_frames,
+                                     None if d_lead is None else d_lead.data_ptr(), max_total_frames, d_blocks.data_ptr(),
+                                     arr[0].data_ptr(), arr[1].data_ptr(), d_nblocks.data_ptr(), work.data_ptr(),
+                                     work.numel(), st), "dvda_pcm_hip_energy")
+    return d_blocks[:first[-1]], first, d_nblocks[:n]
+
+
+def pcm_energy_workspace_words(n, max_total_frames, block_frames):
+    return int(lib().dvda_pcm_hip_energy_workspace_words(n, max_total_frames, block_frames))
+
+
+def energy_lists(d_blocks, first, d_nblocks):
+    """pcm_energy's results -> (one list of EnergyBlock.as_dict() per stream: the blocks that were written, the block
+    counts as the device reports them) on the host (waits)"""
+    raw = np.ascontiguousarray(d_blocks.cpu().numpy())
+    counts = [int(v) for v in d_nblocks.cpu().numpy()]
+    out = []
+    for i, nb in enumerate(counts):
+        room = first[i + 1] - first[i]
+        out.append([EnergyBlock.from_buffer_copy(raw[first[i] + j].tobytes()).as_dict() for j in range(min(nb, room))])
+    return out, counts
+
+
+def _energy_array(blocks):
+    arr = (EnergyBlock * max(len(blocks), 1))()
+    for j, b in enumerate(blocks):
+        arr[j] = EnergyBlock.from_dict(b)
+    return arr
+
+
+def energy_append(track, piece, block_frames, cap=None):
+    """dvda_pcm_hip_energy_append: the blocks of a track (a list of EnergyBlock.as_dict()) with a piece's blocks joined
+    to them -> the new list; host arithmetic, needs no GPU.  cap: the room the track's array has (default: enough).
+    HipError EINVAL when the piece is not on the track's grid, ECAPACITY when cap is too small."""
+    cap = len(track) + len(piece) if cap is None else cap
+    arr = (EnergyBlock * max(cap, len(track), 1))()
+    for j, b in enumerate(track):
+        arr[j] = EnergyBlock.from_dict(b)
+    n = ctypes.c_uint64(len(track))
+    _check(lib().dvda_pcm_hip_energy_append(arr, ctypes.byref(n), cap, _energy_array(piece), len(piece), block_frames),
+           "dvda_pcm_hip_energy_append")
+    return [arr[j].as_dict() for j in range(int(n.value))]
+
+
+def energy_total(blocks):
+    """dvda_pcm_hip_energy_total: the blocks folded into one record (frames saturates at 2^32 - 1); needs no GPU"""
+    out = EnergyBlock()
+    lib().dvda_pcm_hip_energy_total(_energy_array(blocks), len(blocks), ctypes.byref(out))
+    return out.as_dict()
+
+
+def energy_sums(blocks):
+    """per block the eight sums of squares as Python ints (sq_hi << 64 | sq_lo)"""
+    return [[(int(h) << 64) | int(l) for l, h in zip(b["sq_lo"], b["sq_hi"])] for b in blocks]
+
+
 def crc_list(d_crc, d_nbytes):
     """pcm_crc32's tensors -> list of (crc, nbytes) on the host (waits)"""
     c = d_crc.cpu().numpy().view(np.uint32)
@@ -746,12 +887,14 @@ class PcmRegions:
 
 
 def decode_batch(ctx, batch, layout, attempts=1, capacity="report", decode=Context.decode, crc_bits=None, stream=None,
-                 levels=None, to_host=True):
+                 levels=None, to_host=True, energy=None):
     """The decode sequence, once: index; regions of standard length in `layout` (what ctx is set to); up to `attempts`
     rounds of decode, each after the first on regions grown to what DVDA_ST_OVERFLOW asked for and a new index; the
     digest at crc_bits if given; the host copy.  -> (pcm as cut_regions gives it, infos, digests or None)
     levels: a bit depth -- the level report at that depth too (Context.pcm_levels), appended: -> (pcm, infos, digests or
     None, reports)
+    energy: a block length -- the energy report on that grid too (Context.pcm_energy), appended behind whatever `levels`
+    appended (with energy alone: -> (pcm, infos, digests or None, blocks)): one list of blocks per stream
     capacity: what more major syncs than the context holds (sync patterns in payload count too) lead to -- "report":
     DVDA_ST_CAPACITY on the streams; "raise": HipError; a function: called with the count the index found, it returns
     the larger context the sequence goes on with (the caller's to close).
@@ -781,9 +924,12 @@ def decode_batch(ctx, batch, layout, attempts=1, capacity="report", decode=Conte
             break
     digests = ctx.pcm_crc32(*regions.ptrs, crc_bits, stream=st) if crc_bits else None
     pcm = regions.to_host(infos) if to_host else regions
+    more = ()
     if levels is not None:
-        return pcm, list(infos), digests, ctx.pcm_levels(*regions.ptrs, levels, stream=st)
-    return pcm, list(infos), digests
+        more += (ctx.pcm_levels(*regions.ptrs, levels, stream=st),)
+    if energy:
+        more += (ctx.pcm_energy(*regions.ptrs, energy, stream=st),)
+    return (pcm, list(infos), digests) + more
 
 
 def _context_for(ctx, batch, max_segments, lanes_per_segment, layout):
@@ -797,7 +943,7 @@ def _context_for(ctx, batch, max_segments, lanes_per_segment, layout):
 
 
 def decode_streams(streams, device=0, max_segments=None, lanes_per_segment=0, layout=PCM_PLANAR, ctx=None,
-                   presentation=PRESENT_FULL, crc32=False, crc_bits=24, levels=None):
+                   presentation=PRESENT_FULL, crc32=False, crc_bits=24, levels=None, energy=None):
     """Decodes a list of complete MLP byte streams on the GPU.
 
     Returns (pcm, infos): pcm[i] is an int32 array [channels, pcm_frames] in RIFF-WAVE
@@ -814,6 +960,8 @@ def decode_streams(streams, device=0, max_segments=None, lanes_per_segment=0, la
     computed on the device from the PCM where the decode wrote it (Context.pcm_crc32).
     levels=<bits> (16, 20 or 24): the level report of every stream at that nominal depth (Context.pcm_levels) is appended
     to the result: -> (pcm, infos, reports) or (pcm, infos, digests, reports).  layout must be an int32 one.
+    energy=<block_frames> (64 .. 2^24): the energy report of every stream on that block grid (Context.pcm_energy), one
+    list of blocks per stream, is appended behind all of the above.  layout must be an int32 one.
     """
     batch = Batch(streams, device)
     ctx, own = _context_for(ctx, batch, max_segments, lanes_per_segment, layout)
@@ -831,7 +979,8 @@ def decode_streams(streams, device=0, max_segments=None, lanes_per_segment=0, la
             ctx.set_presentation(presentation)
         # (int32 regions of r*c words, cut as [c, r], for any layout but PCM_INTERLEAVED)
         res = decode_batch(ctx, batch, layout if layout == PCM_INTERLEAVED else PCM_PLANAR, attempts=2,
-                           capacity=larger if own else "raise", crc_bits=crc_bits if crc32 else None, levels=levels)
+                           capacity=larger if own else "raise", crc_bits=crc_bits if crc32 else None, levels=levels,
+                           energy=energy)
         pcm, infos, digests = res[:3]
         return ((pcm, infos, digests) if crc32 else (pcm, infos)) + tuple(res[3:])
     finally:
@@ -840,7 +989,7 @@ def decode_streams(streams, device=0, max_segments=None, lanes_per_segment=0, la
 
 
 def decode_streams_concealed(streams, device=0, max_segments=None, lanes_per_segment=0, layout=PCM_PLANAR, init_fir=None,
-                             crc32=False, crc_bits=24, ctx=None, levels=None):
+                             crc32=False, crc_bits=24, ctx=None, levels=None, energy=None):
     """decode_streams in conceal mode (dvda_mlp_hip_set_conceal): a damaged stream comes out as kept PCM ++ silence ++
     PCM of a fresh decoder ++ ... instead of a non-benign status (include/dvda_mlp_hip.h states the rule).
 
@@ -852,6 +1001,7 @@ def decode_streams_concealed(streams, device=0, max_segments=None, lanes_per_seg
     depth of the WAV layout or at crc_bits for the int32 layouts (Context.pcm_crc32).
     levels=<bits>: the level report of every stream as it was handed out -- the concealed gaps are exact zeros -- is
     appended to the result (Context.pcm_levels; HipError for a WAV layout).
+    energy=<block_frames>: the energy report of every stream as it was handed out, behind that (Context.pcm_energy).
     `ctx`: a caller's Context to run on: its lane and layout settings are set to this call's, its presentation to
     PRESENT_FULL; conceal mode (and init_fir) are taken off it again when the call ends, however it ends.  It keeps its
     size: a batch it cannot hold raises."""
@@ -868,7 +1018,8 @@ def decode_streams_concealed(streams, device=0, max_segments=None, lanes_per_seg
             ctx.set_initial_fir(d_fir.data_ptr())
         # silence and a fresh decoder's access units can need more than the index's count, and then once more
         res = decode_batch(ctx, batch, layout, attempts=3, capacity="report" if own else "raise",
-                           crc_bits={PCM_WAV24: 24, PCM_WAV16: 16}.get(layout, crc_bits) if crc32 else None, levels=levels)
+                           crc_bits={PCM_WAV24: 24, PCM_WAV16: 16}.get(layout, crc_bits) if crc32 else None, levels=levels,
+                           energy=energy)
         pcm, infos, digests = res[:3]
         spans = [ctx.conceal_spans(i, batch.current_stream) for i in range(batch.n)]
         done = True
