@@ -145,6 +145,26 @@ void dvda_hip_set_energy(unsigned block_frames);
  * figure of dvda_hip_reader_memory. */
 int dvda_hip_reader_energy(const DVDA_Track_Reader *reader, struct dvda_pcm_energy_block *blocks, unsigned long long cap,
                            unsigned long long *n);
+/* bits_out != 0 (16, 20 or 24): track readers opened afterwards (per calling thread, read when the reader is opened,
+ * like dvda_hip_set_levels) deliver the track at that word length: every piece of int32 PCM is reduced where it lies on
+ * the device -- mode: DVDA_RQ_TRUNCATE, DVDA_RQ_ROUND or DVDA_RQ_TPDF with `seed`, and clamped to the output range; the
+ * contract is in dvda_mlp_hip.h, dvda_pcm_requant / dvda_pcm_hip_requantize -- with frame0 = the track's frames in front
+ * of the piece, so a track read whole and one read in windows are the same bytes.  Everything behind it describes what
+ * the reader hands out: the digest, the level and energy reports, the WAV payload, dvda_read; dvda_bits_per_sample()
+ * returns bits_out.  A reader that would decode straight into the WAV payload (dvda_hip_set_wav_output) decodes int32
+ * instead and is packed at bits_out afterwards.  Every reader: whole-track and windowed, MLP and raw PCM, the
+ * presentation.  A track whose depth is below bits_out is handed out as it is (the option is off for that reader); one
+ * whose depth equals bits_out is clamped and nothing else.  Out of scope: together with conceal mode (the stitch between
+ * two windows rewrites frames already handed over) -- such an open returns NULL, as does one with a bits_out or mode
+ * the reduction does not have.  0 (default): off, a reader launches and allocates exactly as without this call. */
+struct dvda_pcm_requant_report;
+void dvda_hip_set_requantize(unsigned bits_out, unsigned mode, unsigned long long seed);
+/* What the reduction counted: frames and, per channel, the values the clamp changed.  1: final for the track; 0: of what
+ * has been handed out so far (a windowed reader); -1: the reader does not reduce -- opened without the option, or the
+ * track's depth is below bits_out -- or it failed; nothing is written.  `out` may be NULL. */
+int dvda_hip_reader_requantized(const DVDA_Track_Reader *reader, struct dvda_pcm_requant_report *out);
+/* the depth the track has on the disc: dvda_bits_per_sample() unless the reader reduces the word length */
+unsigned dvda_hip_reader_source_bits(const DVDA_Track_Reader *reader);
 /* on != 0: MLP track readers opened afterwards (per calling thread, read when the reader is opened, like
  * dvda_hip_set_wav_output) conceal a damaged track instead of refusing it: the track comes out as
  *     kept PCM ++ silence ++ PCM of a fresh decoder from the next usable major sync ++ ...

@@ -743,6 +743,86 @@ int dvda_pcm_hip_energy_append(dvda_pcm_energy_block *track, uint64_t *n_track, 
                                const dvda_pcm_energy_block *piece, uint64_t n_piece, uint32_t block_frames);
 void dvda_pcm_hip_energy_total(const dvda_pcm_energy_block *blocks, uint64_t n, dvda_pcm_energy_block *out);
 
+/* ------------------------------------------------------------------ word-length reduction of the decoded PCM
+ * The first pass that writes PCM: a track delivered at a smaller word length -- 24-bit audio as a 16-bit file for a CD, a
+ * portable player, a preview -- made on the device while the samples are still there, truncated, rounded or dithered, and
+ * CLAMPED to the output range where write_signed would wrap (csrc/pcm_requant.h).  A 16-bit
+ * payload is half of what the 24-bit one moves to the host and a third of the int32 PCM.
+ *
+ * The contract; every figure exact.  s = bits_in - bits_out with bits_in, bits_out in {16, 20, 24} and bits_out <=
+ * bits_in, so s is 0, 4 or 8.  For the value v (any int32; the arithmetic as if in 64 bits) of channel c -- its position
+ * in the buffer, RIFF-WAVE order -- at absolute frame F = frame0 + f:
+ *   DVDA_RQ_TRUNCATE   q = v >> s (arithmetic shift: floor)
+ *   DVDA_RQ_ROUND      q = (v + 2^(s-1)) >> s
+ *   DVDA_RQ_TPDF       q = (v + 2^(s-1) + u1 - u2) >> s, u1 and u2 two s-bit uniforms: their difference is triangular
+ *                      over +-(2^s - 1), +-1 output LSB
+ *   s == 0             q = v in every mode: a pure clamp
+ * and the output is clamp(q, -2^(bits_out-1), 2^(bits_out-1) - 1); clipped[c] counts the values the clamp changed.
+ * The noise is a counter-based function of (seed, F, c), one 64-bit word per FOUR frames of a channel: with Q = F >> 2,
+ * j = F & 3, all arithmetic mod 2^64,
+ *   z = seed + 0x9E3779B97F4A7C15 * (8 Q + c + 1)
+ *   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z = z ^ (z >> 31)
+ *   field = (z >> (16 j)) & 0xFFFF;  u1 = field & (2^s - 1);  u2 = (field >> 8) & (2^s - 1)
+ * (z is output number 8 Q + c + 1 of splitmix64 seeded with `seed`).  frame0 is how a caller says "this piece starts at
+ * frame N of the track": a track requantized in one piece, in windows or on several devices is the same bytes.  The
+ * reports of two pieces join by adding `frames` and clipped[]; there is no combine function.
+ *
+ * Out of scope: noise shaping (error feedback is a serial nonlinear recurrence per channel), sample-rate conversion,
+ * auto-blanking of digital silence (TPDF on silence is noise of +-1 LSB, as it should be), float output, the streaming
+ * tier and dvda_mlp_hip_decode_multi.  The disc tier has it as dvda_hip_set_requantize (dvd-audio-hip.h). */
+#define DVDA_RQ_TRUNCATE 0u
+#define DVDA_RQ_ROUND    1u
+#define DVDA_RQ_TPDF     2u
+typedef struct dvda_pcm_requant {
+    uint32_t bits_in, bits_out;   /* 16, 20 or 24; bits_out <= bits_in */
+    uint32_t mode;                /* DVDA_RQ_* */
+    uint32_t reserved;            /* 0 */
+    uint64_t seed;                /* of the dither's noise (DVDA_RQ_TPDF) */
+} dvda_pcm_requant;               /* 24 bytes */
+typedef struct dvda_pcm_requant_report {
+    uint64_t frames;              /* PCM frames requantized */
+    uint64_t clipped[8];          /* per channel: values the clamp changed */
+} dvda_pcm_requant_report;        /* 72 bytes */
+
+/* The tier-free form.  Stream i: d_desc_in[i] in d_in (layout_in: DVDA_PCM_PLANAR or DVDA_PCM_INTERLEAVED) ->
+ * d_desc_out[i] in d_out, first absolute frame d_frame0[i] (a NULL array: 0 for every stream), report d_report[i]; device
+ * arrays, n entries.  layout_out: either int32 layout for any bits_out -- the values lie in the output range -- or
+ * DVDA_PCM_WAV16 when bits_out == 16 / DVDA_PCM_WAV24 when bits_out == 24: the payload exactly as dvda_mlp_hip_pack_wav
+ * would write it from the int32 result, from byte 4 * off on, frames * channels * bits_out / 8 bytes and not one more.
+ * A stream is not taken -- frames == 0 reported, nothing written -- when its input descriptor is one the reports do not
+ * take (channels outside 1..8, frames above 2^40) or its output descriptor has other frames / channels or a stride below
+ * its frames.  In place: d_out == d_in with the same int32 layout and the same descriptors is allowed and exact; any
+ * other overlap is the caller's error.  Enqueued on `stream`: no host wait, no allocation.  max_total_frames: a bound the
+ * host knows on the sum of the streams' frames; a stream whose tiles (DVDA_LVL_TILE_FRAMES frames, aligned to its start)
+ * fall outside it reports zeros, and its output region holds unspecified values inside its bounds and nothing outside
+ * them.  d_work: dvda_pcm_hip_requantize_workspace_words(n, max_total_frames) uint32 words, which need not be cleared;
+ * no atomics, the report is the same from run to run.  Either side's off may have any 4-byte alignment and a planar
+ * stride any parity: 16-byte accesses wherever memory allows them; nothing outside a stream's `frames` is read, nothing
+ * outside its output region written.  The arguments are judged first, on any machine -- DVDA_HIP_EINVAL: bits outside
+ * {16, 20, 24} or bits_out > bits_in, a mode above 2, reserved != 0, a WAV input layout, a WAV output layout of another
+ * depth than bits_out (or any for bits_out == 20), a null pointer other than d_frame0, work_words too small;
+ * DVDA_HIP_ECAPACITY: 2^31 tiles or more -- then the device: DVDA_HIP_ENODEV without one. */
+size_t dvda_pcm_hip_requantize_workspace_words(uint32_t n, uint64_t max_total_frames);
+int dvda_pcm_hip_requantize(const int32_t *d_in, uint32_t layout_in, const dvda_pcm_crc_desc *d_desc_in,
+                            int32_t *d_out, uint32_t layout_out, const dvda_pcm_crc_desc *d_desc_out,
+                            const uint64_t *d_frame0 /* or NULL */, uint32_t n, const dvda_pcm_requant *params /* host */,
+                            uint64_t max_total_frames, dvda_pcm_requant_report *d_report,
+                            uint32_t *d_work, size_t work_words, void *stream);
+
+/* behind dvda_mlp_hip_decode (blocks): the first n streams of the last decode requantized IN PLACE, d_pcm / d_out_off /
+ * d_out_stride as that decode got them, in the context's layout (DVDA_HIP_EINVAL when that is a WAV one); stream i starts
+ * at absolute frame host_frame0[i] (NULL: 0).  Frames and channels are what dvda_mlp_hip_stream_info reports; a stream
+ * that carries DVDA_ST_OVERFLOW is untouched and reports zeros.  Behind it dvda_mlp_hip_pcm_crc32(ctx, ..., bits_out),
+ * dvda_mlp_hip_pcm_levels and dvda_mlp_hip_pcm_energy see the requantized PCM. */
+int dvda_mlp_hip_pcm_requantize(dvda_mlp_hip_ctx *ctx, int32_t *d_pcm, const uint64_t *d_out_off, const uint64_t *d_out_stride,
+                                const dvda_pcm_requant *params, const uint64_t *host_frame0 /* or NULL */,
+                                dvda_pcm_requant_report *host_report, uint32_t n, void *stream);
+
+/* The contract above for one value: host arithmetic, needs no device -- the text the kernel compiles.  `frame` is the
+ * absolute frame.  *clipped (may be NULL) = 1 when the clamp changed the value, else 0; invalid params: returns 0 and
+ * sets *clipped = -1. */
+int32_t dvda_pcm_hip_requant_value(int32_t v, uint64_t frame, uint32_t channel, const dvda_pcm_requant *params, int *clipped);
+
 /* ------------------------------------------------------------------ tier B */
 /* The mlp.h mirror: same three calls, same meaning as reference src/mlp.h:29-42 /
  * src/mlp.c:265-354, with the reference's containers replaced by plain memory:

@@ -48,6 +48,8 @@ struct reader_opts {
     int levels;                 /* 1: ... and its level report is made there (dvda_hip_reader_levels) */
     int conceal;                /* 1: a damaged MLP track is concealed, not refused (dvda_hip_set_conceal) */
     unsigned energy;            /* != 0: ... and its energy report on a grid of that many frames (dvda_hip_reader_energy) */
+    unsigned rq_bits, rq_mode;  /* rq_bits != 0: every piece of int32 PCM is reduced to that many bits where it lies on the */
+    unsigned long long rq_seed; /*   device, in front of its reports (dvda_hip_set_requantize, dvda_hip_reader_requantized) */
 };
 static _Thread_local struct reader_opts t_opts;
 static _Thread_local int t_conceal_set;     /* dvda_hip_set_conceal() was called on this thread: DVDA_CONCEAL no longer counts */
@@ -57,6 +59,12 @@ void dvda_hip_set_presentation(int presentation) { t_opts.present = presentation
 void dvda_hip_set_digest(int on) { t_opts.digest = on != 0; }
 void dvda_hip_set_levels(int on) { t_opts.levels = on != 0; }
 void dvda_hip_set_energy(unsigned block_frames) { t_opts.energy = block_frames; }
+void dvda_hip_set_requantize(unsigned bits_out, unsigned mode, unsigned long long seed)
+{
+    t_opts.rq_bits = bits_out;
+    t_opts.rq_mode = mode;
+    t_opts.rq_seed = seed;
+}
 void dvda_hip_set_conceal(int on)
 {
     t_opts.conceal = on != 0;
@@ -79,7 +87,8 @@ static struct reader_opts opts_now(void)
 struct track_windows;               /* a long track read window by window (below) */
 
 /* The reports of a piece of PCM or of a track: the digest (dvda_hip_set_digest), the level report
- * (dvda_hip_set_levels) and the energy report (dvda_hip_set_energy).  Per report a state -- 0 off, 1 wanted and, once a
+ * (dvda_hip_set_levels), the energy report (dvda_hip_set_energy) and what the word-length reduction counted
+ * (dvda_hip_set_requantize).  Per report a state -- 0 off, 1 wanted and, once a
  * piece is through, made (a windowed track: joined over the windows handed out so far), -1 this reader has none -- and
  * its values.  The energy report's blocks are the record's own (rep_reset frees them): a piece's lie on the track's
  * grid, which is anchored at track frame 0, and join the track's when the piece is handed out. */
@@ -91,7 +100,28 @@ struct pcm_reports {
     uint32_t ng_block;          /* the grid's block length */
     dvda_pcm_energy_block *ng_blocks;
     uint64_t ng_n, ng_cap;
+    int rq;                     /* the word-length reduction: 0 also for a track whose depth is below bits_out */
+    dvda_pcm_requant rq_par;    /* (bits_in: set per piece from the track's depth) */
+    dvda_pcm_requant_report rq_rep;
 };
+
+/* the reports a reader opened with `o` wants */
+static void rep_want(struct pcm_reports *r, const struct reader_opts *o)
+{
+    r->dg = o->digest;
+    r->lv = o->levels;
+    r->ng = o->energy != 0;
+    r->ng_block = o->energy;
+    r->rq = o->rq_bits != 0;
+    r->rq_par.bits_in = r->rq_par.bits_out = o->rq_bits;
+    r->rq_par.mode = o->rq_mode;
+    r->rq_par.reserved = 0;
+    r->rq_par.seed = o->rq_seed;
+}
+
+/* does a reader opened with `o` reduce a track of `bits` bits?  (a track below bits_out is handed out as it is) */
+static int rq_applies(const struct reader_opts *o, unsigned bits) { return o->rq_bits != 0 && bits >= o->rq_bits; }
+static unsigned code_of_bits(unsigned bits) { return bits == 16 ? 0 : bits == 20 ? 1 : 2; }
 
 static void rep_reset(struct pcm_reports *r)
 {
@@ -104,6 +134,7 @@ struct DVDA_Track_Reader_s {
     struct track_windows *win;     /* != NULL: the track is decoded in windows of bounded size as it is read */
     unsigned bps_code[2], rate_code[2], assignment;
     unsigned channels, status;
+    unsigned src_bits;         /* != 0: the track's own depth, where the reader hands out fewer bits (dvda_hip_set_requantize) */
     uint64_t frames, served, stride;
     int interleaved;           /* MLP tracks: frame-major [frame][channel] = the dvda_read order;
                                   PCM tracks: planar [channel][stride]; RIFF-WAVE channel order */
@@ -268,6 +299,10 @@ static int64_t find_sync_dev(const uint8_t *d_bytes, uint64_t from, uint64_t siz
  * the track's, so the piece's first block has what is left of the block the track is in.  One block on the device holds
  * the descriptor, the results and the workspace, the largest one where several reports run: they run one behind the
  * other; the energy report's lead, counts and blocks lie behind the workspace.
+ * A reader that reduces the word length (have->rq > 0, bits at least its bits_out) does so HERE, first: the piece's int32
+ * PCM is requantized in place from `bits` to bits_out with frame0 = `before`, so a track read whole and read in windows
+ * is the same bytes, and every report behind it -- and every copy or pack the caller makes after this call -- sees the
+ * PCM the reader hands out, at bits_out.
  * Blocks; what it allocates it frees; allocates and launches nothing when there is nothing to make.  1 = ok. */
 static int piece_reports(struct pcm_reports *have, struct pcm_reports *out, int wav_payload, const int32_t *d_pcm,
                          uint32_t layout, unsigned bits, uint64_t stride, uint64_t frames, unsigned ch, uint64_t before)
@@ -278,6 +313,38 @@ static int piece_reports(struct pcm_reports *have, struct pcm_reports *out, int 
         dvda_pcm_levels levels;
     } res;
     const dvda_pcm_crc_desc desc = {0, stride, frames, ch, 0};
+    if (have->rq > 0 && bits < have->rq_par.bits_out)
+        have->rq = 0;
+    out->rq = have->rq;
+    out->rq_par = have->rq_par;
+    memset(&out->rq_rep, 0, sizeof(out->rq_rep));
+    if (have->rq > 0) {
+        struct {
+            dvda_pcm_crc_desc desc;
+            uint64_t frame0;
+            dvda_pcm_requant_report rep;
+        } blk = {desc, before, {0, {0}}};
+        dvda_pcm_requant par = have->rq_par;
+        const size_t rq_words = dvda_pcm_hip_requantize_workspace_words(1, frames);
+        uint8_t *dq = NULL;
+        par.bits_in = bits;
+        if (frames) {
+            if (!dev_alloc((void **)&dq, sizeof(blk) + rq_words * sizeof(uint32_t)))
+                return 0;
+            const int done =
+                hipMemcpy(dq, &blk, sizeof(blk), hipMemcpyHostToDevice) == hipSuccess &&
+                dvda_pcm_hip_requantize(d_pcm, layout, (const dvda_pcm_crc_desc *)dq, (int32_t *)d_pcm, layout,
+                                        (const dvda_pcm_crc_desc *)dq, (const uint64_t *)(dq + offsetof(__typeof__(blk), frame0)),
+                                        1, &par, frames, (dvda_pcm_requant_report *)(dq + offsetof(__typeof__(blk), rep)),
+                                        (uint32_t *)(dq + sizeof(blk)), rq_words, NULL) == DVDA_HIP_OK &&
+                hipMemcpy(&blk, dq, sizeof(blk), hipMemcpyDeviceToHost) == hipSuccess;
+            (void)hipFree(dq);
+            if (!done)
+                return 0;
+            out->rq_rep = blk.rep;
+        }
+        bits = have->rq_par.bits_out;
+    }
     const uint64_t payload = frames * ch * (bits / 8);
     if (have->dg > 0 && bits != 16 && bits != 24)
         have->dg = -1;
@@ -362,6 +429,11 @@ static void reports_join(struct pcm_reports *track, const struct pcm_reports *pi
     }
     if (track->lv > 0)
         dvda_pcm_hip_levels_combine(&track->levels, &piece->levels, &track->levels);
+    if (track->rq > 0) {
+        track->rq_rep.frames += piece->rq_rep.frames;
+        for (int c = 0; c < 8; c++)
+            track->rq_rep.clipped[c] += piece->rq_rep.clipped[c];
+    }
     if (track->ng > 0 && piece->ng_n) {
         /* (a piece that cannot be joined leaves a reader without the report: -1, as for one that was never made) */
         if (track->ng_n + piece->ng_n > track->ng_cap) {
@@ -608,10 +680,11 @@ static uint32_t layout_of(int wav_bits)
  * the payload dvda2wav would write -- interleaved, little-endian, write_signed at the stream's own bit depth -- and
  * nothing else, no int32 PCM and no separate packing pass (SURVEY 8(f-3) fused into the decode, DVDA_PCM_WAV24 /
  * WAV16): decided here, from the index's stream record, as 16, 24 or 0 (a depth that is decoded into int32 frames) and
- * then left alone.  Hands back the stream's record after the decode and the frames d_pcm has room for.  Its status is
+ * then left alone; a reader that reduces the word length (rq: its options, or NULL) decodes int32 frames, which the
+ * reduction works on: 0.  Hands back the stream's record after the decode and the frames d_pcm has room for.  Its status is
  * the caller's to judge.  1 = decoded, 0 = failure. */
 static int decode_stream(struct track_bufs *b, uint64_t len, const int32_t *fir, int *wav_bits,
-                         dvda_mlp_stream_info *info, uint64_t *stride_out)
+                         dvda_mlp_stream_info *info, uint64_t *stride_out, const struct reader_opts *rq)
 {
     if (dvda_mlp_hip_stream_info(b->ctx, info, 1, NULL) != DVDA_HIP_OK || info->channels == 0)
         return 0;
@@ -627,7 +700,7 @@ static int decode_stream(struct track_bufs *b, uint64_t len, const int32_t *fir,
         stride = 4;
     if (*wav_bits < 0) {
         const unsigned bits = bits_of(info->group0_bps);
-        *wav_bits = (bits == 16 || bits == 24) ? (int)bits : 0;
+        *wav_bits = (bits == 16 || bits == 24) && !(rq && rq_applies(rq, bits)) ? (int)bits : 0;
     }
     const unsigned wbits = (unsigned)*wav_bits;
     if (dvda_mlp_hip_set_pcm_layout(b->ctx, layout_of(*wav_bits)) != DVDA_HIP_OK)
@@ -729,7 +802,7 @@ static DVDA_Track_Reader *open_mlp(struct aob_set *aobs, const DVDA_Track *k, co
     if (!index_stream(&b, o, len, &n_seg))
         goto out;
     t_line(&t_mark, "context + index");
-    if (!decode_stream(&b, len, NULL, &wav_bits, &info, &stride))
+    if (!decode_stream(&b, len, NULL, &wav_bits, &info, &stride, o))
         goto out;
     t_line(&t_mark, "decode");
     /* the reference assert()s on a damaged stream; conceal mode hands it out composed (DVDA_ST_CONCEALED) */
@@ -754,13 +827,14 @@ static DVDA_Track_Reader *open_mlp(struct aob_set *aobs, const DVDA_Track *k, co
     if (!mlp_info_to_reader(r, &info, o->present))
         goto fail;
     /* before any copy to the host: the track as the decode left it on the device */
-    r->rep.dg = o->digest;
-    r->rep.lv = o->levels;
-    r->rep.ng = o->energy != 0;
-    r->rep.ng_block = o->energy;
+    rep_want(&r->rep, o);
     if (!piece_reports(&r->rep, &r->rep, wav_bits != 0, b.d_pcm, layout_of(wav_bits), bits_of(info.group0_bps), stride,
                        info.pcm_frames, info.channels, 0))
         goto fail;
+    if (r->rep.rq > 0) {
+        r->src_bits = bits_of(r->bps_code[0]);
+        r->bps_code[0] = code_of_bits(o->rq_bits);  /* what the reader hands out from here on */
+    }
     if (wav_bits) {
         r->d_wav = (uint8_t *)b.d_pcm;
         r->wav_bytes = r->frames * r->channels * ((unsigned)wav_bits / 8);
@@ -835,6 +909,7 @@ struct track_windows {
     /* a raw-PCM track read in windows (round 6): sectors decode independently of each other (src/pcm.c:149: whole chunks
        per packet), so a window is a run of sectors and nothing crosses a cut but the count of frames delivered so far */
     unsigned pcm_bits, pcm_channels;
+    unsigned pcm_out_bits;      /* the depth the reader hands out: pcm_bits, or what the word-length reduction leaves */
     uint64_t pcm_want;          /* the track's length in PCM frames (its PTS length); whole packets until it is covered */
     uint64_t pcm_done;
     uint8_t *pack_tmp;          /* host: a planar window packed for dvda_hip_reader_wav_next() on an int32 reader */
@@ -1360,7 +1435,7 @@ static int win_produce(struct track_windows *w, struct win_slot *out)
     /* ---- decode [0, cut) from the history the window before left (the payload or int32 frames: the bit depth is in
        the index's stream record, known before anything is decoded) */
     dvda_mlp_stream_info info;
-    if (!decode_stream(b, cut, w->have_fir ? w->fir : NULL, &w->wav_bits, &info, &stride))
+    if (!decode_stream(b, cut, w->have_fir ? w->fir : NULL, &w->wav_bits, &info, &stride, &w->opts))
         return 0;
     w->p_status |= info.status;
     if (info.status & ~(uint32_t)(DVDA_ST_BENIGN | (conceal ? DVDA_ST_CONCEALED : 0u)))
@@ -1448,15 +1523,17 @@ static int win_produce_pcm(struct track_windows *w, struct win_slot *out)
     w->started = 1;
     if (!final && (got < want || w->next >= w->aobs.total))
         final = 1;                               /* the files end inside the track */
-    /* (the planes as the un-swizzle left them: before packing and copy) */
-    if (!piece_reports(&w->rep, &out->rep, w->wav_bits != 0, b->d_pcm, DVDA_PCM_PLANAR, bits, stride, deliver, ch,
-                       w->rep_before))
+    /* (the planes as the un-swizzle left them: before packing and copy; a reader that reduces the word length has the
+       reports of its int32 PCM, as an MLP reader in its place has) */
+    if (!piece_reports(&w->rep, &out->rep, w->wav_bits != 0 && !rq_applies(&w->opts, bits), b->d_pcm, DVDA_PCM_PLANAR, bits,
+                       stride, deliver, ch, w->rep_before))
         return 0;
     w->rep_before += deliver;
     if (deliver && w->wav_bits) {
-        const size_t bytes = (size_t)deliver * ch * (bits / 8);
+        /* (at the depth the reader hands out: the track's, or what it was reduced to just now) */
+        const size_t bytes = (size_t)deliver * ch * (w->pcm_out_bits / 8);
         if (!bufs_dev_room(b, (void **)&b->d_stream, &b->cap_stream, bytes + 64) ||
-            dvda_mlp_hip_pack_wav(b->d_pcm, stride, ch, deliver, bits, b->d_stream, NULL) != DVDA_HIP_OK ||
+            dvda_mlp_hip_pack_wav(b->d_pcm, stride, ch, deliver, w->pcm_out_bits, b->d_stream, NULL) != DVDA_HIP_OK ||
             !slot_reserve(b, out, bytes) ||
             hipMemcpy(out->host, b->d_stream, bytes, hipMemcpyDeviceToHost) != hipSuccess)
             return 0;
@@ -1585,10 +1662,7 @@ static DVDA_Track_Reader *windows_new(const DVDA_Track *k, const struct reader_o
     r->interleaved = 1;
     w->produce = produce;
     w->opts = *o;
-    w->rep.dg = o->digest;
-    w->rep.lv = o->levels;
-    w->rep.ng = o->energy != 0;
-    w->rep.ng_block = o->energy;
+    rep_want(&w->rep, o);
     w->next = k->s.first;
     w->last = k->s.last >= k->s.first ? k->s.last : k->s.first;
     w->window = window_sectors();
@@ -1649,6 +1723,10 @@ static DVDA_Track_Reader *open_mlp_windowed(const DVDA_Track *k, const struct re
         reader_free(r);
         return NULL;
     }
+    if (rq_applies(o, bits_of(w->info.group0_bps))) {
+        r->src_bits = bits_of(w->info.group0_bps);
+        r->bps_code[0] = code_of_bits(o->rq_bits);
+    }
     return r;
 }
 
@@ -1688,12 +1766,13 @@ static DVDA_Track_Reader *open_pcm(struct aob_set *aobs, const DVDA_Track *k, co
     r->stride = stride;
     r->d_pcm = b.d_pcm;
     b.d_pcm = NULL;
-    r->rep.dg = o->digest;
-    r->rep.lv = o->levels;
-    r->rep.ng = o->energy != 0;
-    r->rep.ng_block = o->energy;
+    rep_want(&r->rep, o);
     if (!piece_reports(&r->rep, &r->rep, 0, r->d_pcm, DVDA_PCM_PLANAR, bits, stride, deliver, r->channels, 0))
         goto fail;
+    if (r->rep.rq > 0) {
+        r->src_bits = bits;
+        r->bps_code[0] = code_of_bits(o->rq_bits);
+    }
     goto done;
 fail:
     reader_free(r);
@@ -1719,9 +1798,12 @@ static DVDA_Track_Reader *open_pcm_windowed(const DVDA_Track *k, const uint8_t *
         return NULL;
     }
     w->pcm_bits = bits;
+    w->pcm_out_bits = rq_applies(o, bits) ? o->rq_bits : bits;
     w->pcm_channels = r->channels;
     w->pcm_want = pcm_track_frames(k, rate);
-    w->wav_bits = o->wav_output ? (int)bits : 0;
+    w->wav_bits = o->wav_output && w->pcm_out_bits != 20 ? (int)w->pcm_out_bits : 0;
+    r->src_bits = bits;
+    r->bps_code[0] = code_of_bits(w->pcm_out_bits);
     if (!windows_start(w)) {
         reader_free(r);
         return NULL;
@@ -1741,6 +1823,10 @@ static DVDA_Track_Reader *open_reader(const DVDA_Track *k, const struct reader_o
         return NULL;
     }
     if (hipSetDevice(o->device) != hipSuccess)
+        return NULL;
+    /* the word-length reduction: a depth and a mode it has; not together with conceal mode (the stitch between two
+       windows rewrites frames that were handed over, and reduced, already) */
+    if (o->rq_bits && ((o->rq_bits != 16 && o->rq_bits != 20 && o->rq_bits != 24) || o->rq_mode > DVDA_RQ_TPDF || o->conceal))
         return NULL;
     aob_open_all(&aobs, k->dir, k->titleset);
     if (aobs.n == 0 || k->s.first >= aobs.total)
@@ -1815,6 +1901,7 @@ void dvda_close_track_reader(DVDA_Track_Reader *r) { reader_free(r); }
 
 dvda_codec_t dvda_codec(const DVDA_Track_Reader *r) { return r->codec; }
 unsigned dvda_bits_per_sample(const DVDA_Track_Reader *r) { return bits_of(r->bps_code[0]); }
+unsigned dvda_hip_reader_source_bits(const DVDA_Track_Reader *r) { return r->src_bits ? r->src_bits : bits_of(r->bps_code[0]); }
 unsigned dvda_sample_rate(const DVDA_Track_Reader *r) { return rate_of(r->rate_code[0]); }
 unsigned dvda_channel_count(const DVDA_Track_Reader *r) { return channels_of(r->assignment); }
 unsigned dvda_hip_reader_status(const DVDA_Track_Reader *r)
@@ -1882,6 +1969,16 @@ int dvda_hip_reader_levels(const DVDA_Track_Reader *r, dvda_pcm_levels *out)
         return -1;
     if (out)
         *out = rep.levels;
+    return rc;
+}
+int dvda_hip_reader_requantized(const DVDA_Track_Reader *r, dvda_pcm_requant_report *out)
+{
+    struct pcm_reports rep;
+    const int rc = r ? reader_reports(r, &rep) : -1;
+    if (rc < 0 || rep.rq <= 0)
+        return -1;
+    if (out)
+        *out = rep.rq_rep;
     return rc;
 }
 int dvda_hip_reader_energy(const DVDA_Track_Reader *r, dvda_pcm_energy_block *blocks, unsigned long long cap,

@@ -1,5 +1,5 @@
 // pcm_report_run.h -- host side of the reports of decoded PCM, the digest (pcm_digest.h), the level report
-// (pcm_levels.h), the compare (pcm_compare.h) and the energy report (pcm_energy.h): what a report is to the driver, the one driver of the flat tile list (pcm_tiles.h), the one call that
+// (pcm_levels.h), the compare (pcm_compare.h), the energy report (pcm_energy.h) and the word-length reduction (pcm_requant.h): what a report is to the driver, the one driver of the flat tile list (pcm_tiles.h), the one call that
 // runs a report behind a decode on the context's own buffers, and the host arithmetic that joins two pieces' results.
 #pragma once
 #include <vector>
@@ -9,6 +9,7 @@
 #include "pcm_digest.h"
 #include "pcm_energy.h"
 #include "pcm_levels.h"
+#include "pcm_requant.h"
 
 // ---- a report, as the driver sees it: the unit its tiles are cut in and the words a tile leaves in the workspace, the
 //      layouts and depths it takes, where its results go, and its three launches
@@ -169,6 +170,57 @@ struct NrgReport {
     }
 };
 static_assert(sizeof(dvda_pcm_energy_block) == 168, "dvda_pcm_energy_block is 168 bytes");
+
+// The word-length reduction: the one report that also writes PCM.  The input is what the driver calls the PCM; the
+// output -- buffer, layout, descriptors -- the streams' first absolute frames and the parameters travel here.
+struct RqReport {
+    static constexpr uint32_t TILE = rq::TILE, TILE_WORDS = rq::REC, TILE_BLOCKS = rq::TILE_BLOCKS;        // unit: frames
+    dvda_pcm_requant_report *d_report;
+    int32_t *d_out;
+    uint32_t layout_out;
+    const dvda_pcm_crc_desc *d_desc_out;
+    const uint64_t *d_frame0;
+    const dvda_pcm_requant *params;         // (host)
+
+    static bool int32_layout(uint32_t layout) { return layout == DVDA_PCM_PLANAR || layout == DVDA_PCM_INTERLEAVED; }
+    bool layout_out_ok() const
+    {
+        return int32_layout(layout_out) || (layout_out == DVDA_PCM_WAV16 && params->bits_out == 16) ||
+               (layout_out == DVDA_PCM_WAV24 && params->bits_out == 24);
+    }
+    bool has_out() const { return d_report && d_out && d_desc_out && params && rq::params_ok(*params) && layout_out_ok(); }
+    static bool takes(uint32_t layout, unsigned) { return int32_layout(layout); }
+
+    void plan(hipStream_t st, const dvda_pcm_crc_desc *d_desc, uint32_t n, unsigned, uint32_t *cnt) const
+    {
+        hipLaunchKernelGGL(rq::k_rq_plan, dim3((n + 255) / 256), dim3(256), 0, st, d_desc, d_desc_out, n, cnt);
+    }
+    template <bool IN_PLANAR>
+    void tiles_in(dim3 grid, dim3 block, hipStream_t st, const int32_t *d_pcm, const dvda_pcm_crc_desc *d_desc, uint32_t n,
+                  const uint32_t *base, uint32_t *rec, uint32_t max_tiles) const
+    {
+        auto k = layout_out == DVDA_PCM_PLANAR        ? rq::k_rq_tiles<IN_PLANAR, rq::OUT_PLANAR>
+                 : layout_out == DVDA_PCM_INTERLEAVED ? rq::k_rq_tiles<IN_PLANAR, rq::OUT_FRAME_MAJOR>
+                 : layout_out == DVDA_PCM_WAV24       ? rq::k_rq_tiles<IN_PLANAR, rq::OUT_WAV24>
+                                                      : rq::k_rq_tiles<IN_PLANAR, rq::OUT_WAV16>;
+        hipLaunchKernelGGL(k, grid, block, 0, st, d_pcm, d_desc, d_out, d_desc_out, d_frame0, n, rq::par_of(*params), base,
+                           rec, max_tiles);
+    }
+    void tiles(dim3 grid, dim3 block, hipStream_t st, const int32_t *d_pcm, uint32_t layout, const dvda_pcm_crc_desc *d_desc,
+               uint32_t n, unsigned, const uint32_t *base, uint32_t *rec, uint32_t max_tiles) const
+    {
+        if (layout == DVDA_PCM_PLANAR)
+            tiles_in<true>(grid, block, st, d_pcm, d_desc, n, base, rec, max_tiles);
+        else
+            tiles_in<false>(grid, block, st, d_pcm, d_desc, n, base, rec, max_tiles);
+    }
+    void join(dim3 block, hipStream_t st, const dvda_pcm_crc_desc *d_desc, uint32_t n, unsigned, const uint32_t *base,
+              const uint32_t *rec, uint32_t max_tiles) const
+    {
+        hipLaunchKernelGGL(rq::k_rq_join, dim3(n), block, 0, st, d_desc, d_desc_out, n, base, rec, max_tiles, d_report);
+    }
+};
+static_assert(sizeof(dvda_pcm_requant) == 24 && sizeof(dvda_pcm_requant_report) == 72, "the requantizer's structs");
 
 // ---- the driver of the flat tile list
 // tiles the list can hold for n streams of max_total units in all: every stream has at most one ragged tile
@@ -583,4 +635,75 @@ extern "C" void dvda_pcm_hip_energy_total(const dvda_pcm_energy_block *blocks, u
     }
     r.frames = (uint32_t)frames;
     *out = r;
+}
+
+// ---- the word-length reduction
+extern "C" size_t dvda_pcm_hip_requantize_workspace_words(uint32_t n, uint64_t max_total_frames)
+{
+    return report_workspace_words<RqReport>(n, max_total_frames);
+}
+
+extern "C" int dvda_pcm_hip_requantize(const int32_t *d_in, uint32_t layout_in, const dvda_pcm_crc_desc *d_desc_in,
+                                       int32_t *d_out, uint32_t layout_out, const dvda_pcm_crc_desc *d_desc_out,
+                                       const uint64_t *d_frame0, uint32_t n, const dvda_pcm_requant *params,
+                                       uint64_t max_total_frames, dvda_pcm_requant_report *d_report, uint32_t *d_work,
+                                       size_t work_words, void *stream_)
+{
+    return report_run(RqReport{d_report, d_out, layout_out, d_desc_out, d_frame0, params}, d_in, layout_in, 0, d_desc_in, n,
+                      max_total_frames, d_work, work_words, stream_);
+}
+
+extern "C" int dvda_mlp_hip_pcm_requantize(dvda_mlp_hip_ctx *c, int32_t *d_pcm, const uint64_t *d_out_off,
+                                           const uint64_t *d_out_stride, const dvda_pcm_requant *params,
+                                           const uint64_t *host_frame0, dvda_pcm_requant_report *host_report, uint32_t n,
+                                           void *stream_)
+{
+    if (!c || !d_pcm || !d_out_off || !d_out_stride || !params || !host_report || !rq::params_ok(*params) ||
+        !RqReport::takes(c->set.pcm_layout, 0))
+        return DVDA_HIP_EINVAL;
+    std::vector<dvda_pcm_crc_desc> desc;
+    int rc = report_decode_descs(c, d_out_off, d_out_stride, &n, stream_, &desc);
+    if (rc || n == 0)
+        return rc;
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; i++)
+        total += PCMT_NOT_TAKEN(desc[i]) ? 0 : desc[i].frames;
+    // d_rep_out: the reports (9 words each) | frame0 [n]
+    constexpr size_t RW = sizeof(dvda_pcm_requant_report) / sizeof(uint64_t);
+    if ((rc = c->d_rep_desc.grow(n)) != 0 || (rc = c->d_rep_out.grow((RW + 1) * (size_t)n)) != 0 ||
+        (rc = c->d_rep_work.grow(report_workspace_words<RqReport>(n, total))) != 0)
+        return rc;
+    uint64_t *d_frame0 = nullptr;
+    HIP_TRY(hipMemcpy(c->d_rep_desc, desc.data(), (size_t)n * sizeof(dvda_pcm_crc_desc), hipMemcpyHostToDevice));
+    if (host_frame0) {
+        d_frame0 = c->d_rep_out + RW * (size_t)n;
+        HIP_TRY(hipMemcpy(d_frame0, host_frame0, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice));
+    }
+    const RqReport r{(dvda_pcm_requant_report *)(uint64_t *)c->d_rep_out, d_pcm, c->set.pcm_layout, c->d_rep_desc, d_frame0,
+                     params};
+    rc = report_run(r, d_pcm, c->set.pcm_layout, 0, c->d_rep_desc, n, total, c->d_rep_work, (size_t)c->d_rep_work.cap,
+                    stream_);
+    if (rc)
+        return rc;
+    hipStream_t st = (hipStream_t)stream_;
+    HIP_TRY(hipMemcpyAsync(host_report, r.d_report, (size_t)n * sizeof(dvda_pcm_requant_report), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DVDA_HIP_OK;
+}
+
+extern "C" int32_t dvda_pcm_hip_requant_value(int32_t v, uint64_t frame, uint32_t channel, const dvda_pcm_requant *params,
+                                              int *clipped)
+{
+    if (!params || !rq::params_ok(*params)) {
+        if (clipped)
+            *clipped = -1;
+        return 0;
+    }
+    const rq::Par p = rq::par_of(*params);
+    const uint64_t z = p.mode == DVDA_RQ_TPDF && p.s ? rq::noise_word(p.seed, frame >> 2, channel) : 0;
+    uint32_t cl = 0;
+    const int32_t q = rq::value(v, p, rq::noise_field(z, (uint32_t)frame & 3u), &cl);
+    if (clipped)
+        *clipped = (int)cl;
+    return q;
 }

@@ -26,7 +26,8 @@ EXPORTS = [
     "dvda_hip_reader_wav_next", "dvda_hip_reader_windowed", "dvda_hip_reader_memory", "dvda_hip_reader_failed",
     "dvda_hip_release_cached_buffers", "dvda_hip_set_presentation", "dvda_hip_open_track_reader_with",
     "dvda_hip_set_digest", "dvda_hip_reader_crc32", "dvda_hip_set_levels", "dvda_hip_reader_levels",
-    "dvda_hip_set_energy", "dvda_hip_reader_energy",
+    "dvda_hip_set_energy", "dvda_hip_reader_energy", "dvda_hip_set_requantize", "dvda_hip_reader_requantized",
+    "dvda_hip_reader_source_bits",
     "dvda_hip_set_conceal", "dvda_hip_reader_concealed", "dvda_hip_open_track_reader_concealing",
 ]
 
@@ -98,6 +99,12 @@ def lib():
         L.dvda_hip_reader_levels.argtypes = [vp, ctypes.POINTER(hipdec.Levels)]
         L.dvda_hip_set_energy.restype = None
         L.dvda_hip_set_energy.argtypes = [ctypes.c_uint]
+        L.dvda_hip_set_requantize.restype = None
+        L.dvda_hip_set_requantize.argtypes = [ctypes.c_uint, ctypes.c_uint, ctypes.c_ulonglong]
+        L.dvda_hip_reader_source_bits.restype = ctypes.c_uint
+        L.dvda_hip_reader_source_bits.argtypes = [vp]
+        L.dvda_hip_reader_requantized.restype = ctypes.c_int
+        L.dvda_hip_reader_requantized.argtypes = [vp, ctypes.POINTER(hipdec.RequantReport)]
         L.dvda_hip_reader_energy.restype = ctypes.c_int
         L.dvda_hip_reader_energy.argtypes = [vp, ctypes.POINTER(hipdec.EnergyBlock), ctypes.c_ulonglong,
                                              ctypes.POINTER(ctypes.c_ulonglong)]
@@ -138,7 +145,7 @@ def layout(audio_ts, titleset=1):
 
 
 def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0, fused=False, pieces=False,
-               presentation=0, digest=False, levels=False, conceal=None, energy=0):
+               presentation=0, digest=False, levels=False, conceal=None, energy=0, requant=None):
     """Decodes one track on the GPU.  Returns a dict: codec ("PCM"/"MLP"), bits, rate, channels,
     mask, status, and pcm = int32 [frames, channels] (interleaved, RIFF-WAVE order) read with
     dvda_read() in `chunk`-frame calls -- or, with wav=True, payload = the WAV data bytes packed
@@ -159,6 +166,11 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
     block length anchored at the track's first frame (dvda_hip_set_energy): info["energy"] = the track's blocks as
     hipdec.EnergyBlock.as_dict() gives them (None when the reader has none), and info["energy_states"] = what
     dvda_hip_reader_energy returned right after the open and at the end, info["energy_counts"] the block counts then.
+    requant=(bits_out, mode, seed): the reader delivers the track at bits_out bits (dvda_hip_set_requantize: reduced on
+    the device, hipdec.RQ_TRUNCATE / RQ_ROUND / RQ_TPDF with `seed`, clamped); info["bits"] is then bits_out and the PCM,
+    the payload and every report are of what the reader hands out.  info["requant"] = what the reduction counted as
+    hipdec.RequantReport.as_dict() gives it (None when the reader does not reduce: a track below bits_out), and
+    info["requant_states"] = what dvda_hip_reader_requantized returned right after the open and at the end.
     conceal=True: a damaged MLP track is concealed, not refused (dvda_hip_set_conceal): info["concealed"] = the spans as
     6-tuples (first_frame, frames, byte_off, byte_end, cause, flags) in track terms, and info["concealed_states"] = what
     dvda_hip_reader_concealed returned right after the open and at the end.  conceal=False says "off" explicitly; None
@@ -178,6 +190,8 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
         L.dvda_hip_set_digest(1 if digest else 0)
         L.dvda_hip_set_levels(1 if levels else 0)
         L.dvda_hip_set_energy(int(energy))
+        if requant is not None:
+            L.dvda_hip_set_requantize(int(requant[0]), int(requant[1]), int(requant[2]))
         try:
             r = L.dvda_hip_open_track_reader_concealing(k, device, 1 if (fused and wav) else 0, presentation,
                                                         -1 if conceal is None else int(bool(conceal))) if k else None
@@ -185,6 +199,7 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
             L.dvda_hip_set_digest(0)            # (read when the reader is opened: nothing is left behind)
             L.dvda_hip_set_levels(0)
             L.dvda_hip_set_energy(0)
+            L.dvda_hip_set_requantize(0, 0, 0)
         if not r:
             raise RuntimeError("track %d/%d/%d cannot be opened for reading" % (titleset, title, track))
         ch = L.dvda_channel_count(r)
@@ -200,6 +215,8 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
         n_blocks = ctypes.c_ulonglong()
         first_energy = L.dvda_hip_reader_energy(r, None, 0, ctypes.byref(n_blocks)) if energy else None
         first_blocks = int(n_blocks.value)
+        rq_report = hipdec.RequantReport()
+        first_rq = L.dvda_hip_reader_requantized(r, ctypes.byref(rq_report)) if requant is not None else None
         n_spans = ctypes.c_uint()
         first_spans = L.dvda_hip_reader_concealed(r, None, 0, ctypes.byref(n_spans)) if conceal else None
         if wav and pieces:
@@ -249,6 +266,11 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
                 arr = (hipdec.EnergyBlock * max(int(n_blocks.value), 1))()
                 L.dvda_hip_reader_energy(r, arr, n_blocks.value, ctypes.byref(n_blocks))
                 info["energy"] = [arr[j].as_dict() for j in range(int(n_blocks.value))]
+        if requant is not None:
+            state = L.dvda_hip_reader_requantized(r, ctypes.byref(rq_report))
+            info["requant_states"] = (first_rq, state)
+            info["requant"] = rq_report.as_dict() if state == 1 else None
+            info["source_bits"] = int(L.dvda_hip_reader_source_bits(r))
         if conceal:
             state = L.dvda_hip_reader_concealed(r, None, 0, ctypes.byref(n_spans))
             arr = (hipdec.ConcealSpan * max(int(n_spans.value), 1))()

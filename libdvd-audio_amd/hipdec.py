@@ -77,7 +77,9 @@ EXPORTS = ("dvda_mlp_hip_create", "dvda_mlp_hip_destroy", "dvda_mlp_hip_index", 
            "dvda_pcm_hip_compare", "dvda_pcm_hip_compare_workspace_words", "dvda_mlp_hip_pcm_compare",
            "dvda_pcm_hip_diff_combine", "dvda_mlp_hip_index_graph_state",
            "dvda_pcm_hip_energy", "dvda_pcm_hip_energy_workspace_words", "dvda_mlp_hip_pcm_energy",
-           "dvda_pcm_hip_energy_append", "dvda_pcm_hip_energy_total")
+           "dvda_pcm_hip_energy_append", "dvda_pcm_hip_energy_total",
+           "dvda_pcm_hip_requantize", "dvda_pcm_hip_requantize_workspace_words", "dvda_mlp_hip_pcm_requantize",
+           "dvda_pcm_hip_requant_value")
 
 CRC_TILE_BYTES = 16384      # DVDA_CRC_TILE_BYTES: the digest's tiles, aligned to the end of a stream's payload
 CRC_JOIN_TILES = 256        # DVDA_CRC_JOIN_TILES: tiles a join workgroup folds per turn of its loop
@@ -150,6 +152,34 @@ class EnergyBlock(ctypes.Structure):
     def from_dict(cls, d):
         return cls((ctypes.c_uint64 * 8)(*d["sq_lo"]), (ctypes.c_uint64 * 8)(*d["sq_hi"]), (ctypes.c_uint32 * 8)(*d["peak"]),
                    d["frames"], 0)
+
+
+RQ_TRUNCATE, RQ_ROUND, RQ_TPDF = 0, 1, 2        # DVDA_RQ_*: how the word-length reduction treats the bits it drops
+
+
+class Requant(ctypes.Structure):
+    """dvda_pcm_requant of include/dvda_mlp_hip.h"""
+    _fields_ = [("bits_in", ctypes.c_uint32), ("bits_out", ctypes.c_uint32), ("mode", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("seed", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return dict(bits_in=int(self.bits_in), bits_out=int(self.bits_out), mode=int(self.mode), seed=int(self.seed))
+
+    @classmethod
+    def from_dict(cls, d):
+        return cls(d["bits_in"], d["bits_out"], d["mode"], 0, d["seed"])
+
+
+class RequantReport(ctypes.Structure):
+    """dvda_pcm_requant_report of include/dvda_mlp_hip.h"""
+    _fields_ = [("frames", ctypes.c_uint64), ("clipped", ctypes.c_uint64 * 8)]
+
+    def as_dict(self):
+        return dict(frames=int(self.frames), clipped=[int(v) for v in self.clipped])
+
+    @classmethod
+    def from_dict(cls, d):
+        return cls(d["frames"], (ctypes.c_uint64 * 8)(*d["clipped"]))
 
 
 ST_CONCEALED = 1 << 30          # DVDA_ST_CONCEALED: conceal mode, the stream was damaged (not in ST_BENIGN)
@@ -291,6 +321,15 @@ def lib():
                                                  ctypes.POINTER(EnergyBlock), u64, u32]
         L.dvda_pcm_hip_energy_total.restype = None
         L.dvda_pcm_hip_energy_total.argtypes = [ctypes.POINTER(EnergyBlock), u64, ctypes.POINTER(EnergyBlock)]
+        L.dvda_pcm_hip_requantize_workspace_words.restype = ctypes.c_size_t
+        L.dvda_pcm_hip_requantize_workspace_words.argtypes = [u32, u64]
+        L.dvda_pcm_hip_requantize.argtypes = [vp, u32, vp, vp, u32, vp, vp, u32, ctypes.POINTER(Requant), u64, vp, vp,
+                                              ctypes.c_size_t, vp]
+        L.dvda_mlp_hip_pcm_requantize.argtypes = [vp, vp, vp, vp, ctypes.POINTER(Requant), ctypes.POINTER(u64),
+                                                  ctypes.POINTER(RequantReport), u32, vp]
+        L.dvda_pcm_hip_requant_value.restype = ctypes.c_int32
+        L.dvda_pcm_hip_requant_value.argtypes = [ctypes.c_int32, u64, u32, ctypes.POINTER(Requant),
+                                                 ctypes.POINTER(ctypes.c_int)]
         _lib = L
     return _lib
 
@@ -485,6 +524,19 @@ class Context:
         _check(lib().dvda_mlp_hip_pcm_compare(self._h, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, d_other.data_ptr(),
                                               other_layout, d_desc.data_ptr(), bits, arr, n, stream),
                "dvda_mlp_hip_pcm_compare")
+        return [arr[i].as_dict() for i in range(n)]
+
+    def pcm_requantize(self, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, bits_in, bits_out, mode=RQ_TPDF, seed=0,
+                       frame0=None, n=None, stream=0):
+        """dvda_mlp_hip_pcm_requantize: the int32 PCM the last decode wrote, reduced IN PLACE from bits_in to bits_out
+        (truncated, rounded or dithered; clamped) -> list of RequantReport.as_dict(); blocks.  frame0: per stream the
+        absolute frame it starts at (None: 0).  HipError (EINVAL) when the context's layout is a WAV one."""
+        n = self.n_streams if n is None else n
+        arr = (RequantReport * max(n, 1))()
+        f0 = None if frame0 is None else (ctypes.c_uint64 * max(n, 1))(*[int(f) for f in frame0][:n])
+        par = Requant(bits_in, bits_out, mode, 0, seed)
+        _check(lib().dvda_mlp_hip_pcm_requantize(self._h, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, ctypes.byref(par), f0,
+                                                 arr, n, stream), "dvda_mlp_hip_pcm_requantize")
         return [arr[i].as_dict() for i in range(n)]
 
     def decode_time(self):
@@ -731,6 +783,61 @@ def energy_total(blocks):
 def energy_sums(blocks):
     """per block the eight sums of squares as Python ints (sq_hi << 64 | sq_lo)"""
     return [[(int(h) << 64) | int(l) for l, h in zip(b["sq_lo"], b["sq_hi"])] for b in blocks]
+
+
+def pcm_requantize(d_in, layout_in, desc_in, bits_in, bits_out, mode=RQ_TPDF, seed=0, frame0=None, out=None,
+                   layout_out=None, desc_out=None, max_total_frames=None, work=None):
+    """dvda_pcm_hip_requantize over torch tensors: d_in an int32 tensor on the device holding the streams in layout_in
+    (PCM_PLANAR or PCM_INTERLEAVED), desc_in a list of (off, stride, frames, channels); every value reduced from bits_in to
+    bits_out bits (mode: RQ_TRUNCATE, RQ_ROUND, RQ_TPDF with `seed`) and clamped.  frame0: per stream the absolute frame
+    it starts at (None: 0).  out / layout_out / desc_out: where the result goes -- default: the input's layout and
+    descriptors in a fresh tensor of the same placement (a copy of d_in for an int32 layout, zeros for PCM_WAV16 /
+    PCM_WAV24); out=d_in with the same layout and descriptors works in place.  -> (d_out, d_report): the output tensor
+    and a uint8 device tensor [n, sizeof(RequantReport)] (requant_list brings it to the host).  Only the kernels are
+    asynchronous, on torch's current stream: like pcm_levels, this helper builds the descriptors on the host, copies
+    them to the device and allocates them, the results and -- when none is passed -- the workspace."""
+    layout_out = layout_in if layout_out is None else layout_out
+    desc_out = desc_in if desc_out is None else desc_out
+    if len(desc_out) != len(desc_in):
+        raise HipError("pcm_requantize: %d output descriptors for %d streams" % (len(desc_out), len(desc_in)))
+    if max_total_frames is None:
+        max_total_frames = int(sum(int(f) for _, _, f, c in desc_in if 1 <= int(c) <= 8 and int(f) <= 1 << 40))
+    torch, n, d_desc_in, work, st = _report_args(d_in, desc_in, "the word-length reduction", max_total_frames, work,
+                                                 lib().dvda_pcm_hip_requantize_workspace_words)
+    dev = d_in.device
+    if out is None:
+        out = d_in.clone() if layout_out in (PCM_PLANAR, PCM_INTERLEAVED) else torch.zeros_like(d_in)
+    d_desc_out = torch.from_numpy(_desc_records(desc_out).view(np.uint8).reshape(-1)).to(dev)
+    d_f0 = None if frame0 is None else torch.from_numpy(
+        np.array([int(f) for f in frame0] + [0], np.uint64).view(np.int64)).to(dev)
+    d_rep = torch.zeros((max(n, 1), ctypes.sizeof(RequantReport)), dtype=torch.uint8, device=dev)
+    par = Requant(bits_in, bits_out, mode, 0, seed)
+    _check(lib().dvda_pcm_hip_requantize(d_in.data_ptr(), layout_in, d_desc_in.data_ptr(), out.data_ptr(), layout_out,
+                                         d_desc_out.data_ptr(), None if d_f0 is None else d_f0.data_ptr(), n,
+                                         ctypes.byref(par), max_total_frames, d_rep.data_ptr(), work.data_ptr(),
+                                         work.numel(), st), "dvda_pcm_hip_requantize")
+    return out, d_rep[:n]
+
+
+def pcm_requantize_workspace_words(n, max_total_frames):
+    return int(lib().dvda_pcm_hip_requantize_workspace_words(n, max_total_frames))
+
+
+def requant_list(d_report):
+    """pcm_requantize's report tensor -> list of RequantReport.as_dict() on the host (waits)"""
+    raw = np.ascontiguousarray(d_report.cpu().numpy())
+    return [RequantReport.from_buffer_copy(raw[i].tobytes()).as_dict() for i in range(raw.shape[0])]
+
+
+def requant_value(v, frame, channel, bits_in, bits_out, mode=RQ_TPDF, seed=0):
+    """dvda_pcm_hip_requant_value: the word-length reduction of one value at absolute frame `frame` of channel `channel`
+    -> (value, 1 when the clamp changed it else 0); host arithmetic, needs no GPU.  HipError for invalid parameters"""
+    par = Requant(bits_in, bits_out, mode, 0, seed)
+    cl = ctypes.c_int(0)
+    q = lib().dvda_pcm_hip_requant_value(int(v), frame, channel, ctypes.byref(par), ctypes.byref(cl))
+    if cl.value < 0:
+        raise HipError("dvda_pcm_hip_requant_value: invalid parameters %r" % (par.as_dict(),))
+    return int(q), int(cl.value)
 
 
 def crc_list(d_crc, d_nbytes):
@@ -1129,6 +1236,75 @@ def decode_streams_wav(streams, bits, device=0, lanes_per_segment=0, presentatio
         return (out, infos, digests) if crc32 else (out, infos)
     finally:
         ctx.close()
+
+
+BITS_OF_CODE = {0: 16, 1: 20, 2: 24}      # the major sync's group-0 depth code
+
+
+def decode_streams_requantized(streams, bits_out, mode=RQ_TPDF, seed=0, device=0, layout=PCM_PLANAR, wav=False, ctx=None,
+                               presentation=PRESENT_FULL):
+    """Decodes complete MLP byte streams and reduces them to bits_out bits on the device (pcm_requantize: truncated,
+    rounded or dithered with `seed`, clamped), each from its own depth; streams of different depths run as one call per
+    depth.  -> (pcm, infos, reports): pcm[i] as decode_streams gives it (layout: PCM_PLANAR or PCM_INTERLEAVED), or with
+    wav=True (bits_out 16 or 24) the WAV payload as a uint8 array; reports[i] = RequantReport.as_dict().  A stream whose
+    depth is below bits_out comes out as decoded, reports[i] = None (wav=True: its payload at its own depth)."""
+    import torch
+    if layout not in (PCM_PLANAR, PCM_INTERLEAVED) or (wav and bits_out not in (16, 24)):
+        raise HipError("decode_streams_requantized: EINVAL (an int32 layout; a payload has 16 or 24 bits)")
+    batch = Batch(streams, device)
+    ctx, own = _context_for(ctx, batch, None, 0, layout)
+    made = [ctx]
+
+    def larger(found):
+        made[0].close()
+        made[0] = Context(device, batch.n, found + 64, 0, layout)
+        if presentation != PRESENT_FULL:
+            made[0].set_presentation(presentation)
+        return made[0]
+
+    try:
+        if presentation != PRESENT_FULL or not own:
+            ctx.set_presentation(presentation)
+        regions, infos, _ = decode_batch(ctx, batch, layout, attempts=2, capacity=larger if own else "raise", to_host=False)
+    finally:
+        if own:
+            made[0].close()
+    n = len(infos)
+    frames = [0 if inf.status & ST["OVERFLOW"] else min(int(inf.pcm_frames), r) for inf, r in zip(infos, regions.rows)]
+    desc = [(o, r, f, c) for o, r, f, c in zip(regions.out_off, regions.rows, frames, regions.channels)]
+    depth = [BITS_OF_CODE.get(int(inf.group0_bps), 0) for inf in infos]
+    wav_layout = PCM_WAV24 if bits_out == 24 else PCM_WAV16
+    d_wav = w_off = None
+    if wav:
+        w_off, words = region_layout(regions.rows, regions.channels, wav_layout)
+        d_wav = torch.zeros(words, dtype=torch.int32, device=regions.dev)
+    reports = [None] * n
+    for bits_in in sorted(set(depth)):
+        idx = [i for i in range(n) if depth[i] == bits_in and bits_in >= bits_out]
+        if not idx:
+            continue
+        sub = [desc[i] for i in idx]
+        if wav:
+            sub_out = [(w_off[i],) + desc[i][1:] for i in idx]
+            _, d_rep = pcm_requantize(regions.d_pcm, layout, sub, bits_in, bits_out, mode, seed, out=d_wav,
+                                      layout_out=wav_layout, desc_out=sub_out)
+        else:
+            _, d_rep = pcm_requantize(regions.d_pcm, layout, sub, bits_in, bits_out, mode, seed, out=regions.d_pcm)
+        for i, rep in zip(idx, requant_list(d_rep)):
+            reports[i] = rep
+    pcm = regions.to_host(infos)
+    if wav:
+        pay = cut_regions(d_wav.cpu().numpy(), w_off, regions.rows, regions.channels, frames, wav_layout)
+        for i in range(n):
+            if reports[i] is not None:
+                pcm[i] = pay[i]
+            elif depth[i] in (16, 24):      # as decoded: write_signed at its own depth
+                v = np.ascontiguousarray(pcm[i].T).reshape(-1).astype(np.int64)
+                w = (v & ((1 << (depth[i] - 1)) - 1)) | np.where(v < 0, 1 << (depth[i] - 1), 0)
+                pcm[i] = np.stack([(w >> (8 * k)) & 0xFF for k in range(depth[i] // 8)], 1).astype(np.uint8).reshape(-1)
+            else:
+                raise HipError("decode_streams_requantized: stream %d has %d bits: no WAV payload" % (i, depth[i]))
+    return pcm, list(infos), reports
 
 
 class MLPDecoder:

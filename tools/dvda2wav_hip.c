@@ -57,6 +57,10 @@ static double now_s(void)
     return ts.tv_sec + ts.tv_nsec * 1e-9;
 }
 
+/* -b / --dither / --seed: the word length every track is delivered at (0: its own), set once before any worker starts */
+static unsigned g_rq_bits, g_rq_mode = DVDA_RQ_TPDF;
+static unsigned long long g_rq_seed;
+
 static int extract(DVDA_Title *title, unsigned track_num, const char *dir, int device, int fused_wav, int stereo,
                    int crc, int conceal, unsigned titleset_num)
 {
@@ -75,6 +79,8 @@ static int extract(DVDA_Title *title, unsigned track_num, const char *dir, int d
     /* --conceal: a damaged MLP track is written with silence where the damage is, not refused (an explicit choice either
        way: the tool's option decides, not DVDA_CONCEAL in the environment) */
     dvda_hip_set_conceal(conceal);
+    /* -b: the reader reduces the track to that word length on the device; its depth is then the file's */
+    dvda_hip_set_requantize(g_rq_bits, g_rq_mode, g_rq_seed);
     DVDA_Track_Reader *r = dvda_hip_open_track_reader_with(track, device, fused_wav, stereo);
     if (!r) {
         fprintf(stderr, "*** Error: unable to open track %u for reading\n", track_num);
@@ -135,6 +141,20 @@ static int extract(DVDA_Title *title, unsigned track_num, const char *dir, int d
             printf("CRC32 %u %u %u %08x %llu\n", titleset_num, title_number, track_number, v, vb);
         else
             printf("CRC32 %u %u %u none 0\n", titleset_num, title_number, track_number);
+    }
+    if (ok && g_rq_bits) {
+        /* what the reduction did to the track just written: source depth, the file's depth, values the clamp changed */
+        struct dvda_pcm_requant_report rq;
+        if (dvda_hip_reader_requantized(r, &rq) == 1) {
+            unsigned long long clipped = 0;
+            for (int c = 0; c < 8; c++)
+                clipped += rq.clipped[c];
+            printf("REQUANT %u %u %u %u %u %llu\n", titleset_num, title_number, track_number, dvda_hip_reader_source_bits(r),
+                   bits, clipped);
+        } else {
+            printf("REQUANT %u %u %u %u %u none\n", titleset_num, title_number, track_number, dvda_hip_reader_source_bits(r),
+                   bits);
+        }
     }
     if (ok && conceal) {
         /* what was concealed of the track just written: one line per span */
@@ -228,6 +248,12 @@ static void usage(const char *prog)
            "  -K, --conceal             write a damaged MLP track with silence in place of the damage instead of failing\n"
            "                            on it; one line per concealed span on stdout: CONCEALED <titleset> <title> <track>\n"
            "                            <first_frame> <frames> <byte_off> <byte_end> <cause, hex> <flags>\n"
+           "  -b BITS, --bits=BITS      deliver every track at BITS bits (16 or 24): reduced on the GPU, clamped where the\n"
+           "                            plain payload would wrap; a track below BITS is written as it is.  One line per\n"
+           "                            track on stdout: REQUANT <titleset> <title> <track> <source bits> <file's bits>\n"
+           "                            <values clamped> (\"none\" for a track written as it is).  Not together with -K\n"
+           "      --dither=MODE         none | round | tpdf (default): truncate, round, or triangular dither of +-1 LSB\n"
+           "      --seed=N              seed of the dither's noise (default 0): the same seed gives the same file\n"
            "  -g N, --gpu=N             HIP device (default 0)\n"
            "  -D LIST, --devices=LIST   comma-separated HIP devices: one worker thread per entry takes tracks in turn\n"
            "                            (default: up to four workers on the device of -g)\n"
@@ -242,14 +268,15 @@ int main(int argc, char *argv[])
                                        {"gpu", required_argument, 0, 'g'},      {"help", no_argument, 0, 'h'},
                                        {"devices", required_argument, 0, 'D'},  {"stereo", no_argument, 0, '2'},
                                        {"crc", no_argument, 0, 'C'},            {"conceal", no_argument, 0, 'K'},
-                                       {0, 0, 0, 0}};
+                                       {"bits", required_argument, 0, 'b'},     {"dither", required_argument, 0, 1001},
+                                       {"seed", required_argument, 0, 1002},    {0, 0, 0, 0}};
     const char *audio_ts = NULL, *dir = ".", *cdrom = NULL;
     unsigned titleset_num = 1, title_num = 0, track_num = 0;
     int devices[64], n_devices = 0, one_device = 0, stereo = 0, crc = 0, conceal = 0;
     int c;
     if (getenv("DVDA_TOOL_TIMING"))
         fprintf(stderr, "timing: main at %.1f ms\n", now_s() * 1e3);
-    while ((c = getopt_long(argc, argv, "A:c:S:T:t:d:g:D:h2CK", longopts, NULL)) != -1) {
+    while ((c = getopt_long(argc, argv, "A:c:S:T:t:d:g:D:b:h2CK", longopts, NULL)) != -1) {
         switch (c) {
         case 'A': audio_ts = optarg; break;
         case 'c': cdrom = optarg; break;
@@ -265,6 +292,20 @@ int main(int argc, char *argv[])
         case '2': stereo = 1; break;
         case 'C': crc = 1; break;
         case 'K': conceal = 1; break;
+        case 'b': g_rq_bits = (unsigned)strtoul(optarg, NULL, 10); break;
+        case 1001:
+            if (!strcmp(optarg, "none"))
+                g_rq_mode = DVDA_RQ_TRUNCATE;
+            else if (!strcmp(optarg, "round"))
+                g_rq_mode = DVDA_RQ_ROUND;
+            else if (!strcmp(optarg, "tpdf"))
+                g_rq_mode = DVDA_RQ_TPDF;
+            else {
+                fprintf(stderr, "*** Error: --dither takes none, round or tpdf\n");
+                return 1;
+            }
+            break;
+        case 1002: g_rq_seed = strtoull(optarg, NULL, 0); break;
         case 'h': usage(argv[0]); return 0;
         default: return 1;
         }
@@ -272,6 +313,10 @@ int main(int argc, char *argv[])
     if (!audio_ts) {
         usage(argv[0]);
         return 0;
+    }
+    if (g_rq_bits && ((g_rq_bits != 16 && g_rq_bits != 24) || conceal)) {
+        fprintf(stderr, "*** Error: -b takes 16 or 24 (the depths a WAV payload has here), and not together with -K\n");
+        return 1;
     }
     /* (DVDA_NO_FUSED_WAV=1 in the environment brings the int32 decode + packing pass back, for comparison) */
     const int fused_wav = getenv("DVDA_NO_FUSED_WAV") == NULL;
