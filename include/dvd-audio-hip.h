@@ -165,6 +165,25 @@ void dvda_hip_set_requantize(unsigned bits_out, unsigned mode, unsigned long lon
 int dvda_hip_reader_requantized(const DVDA_Track_Reader *reader, struct dvda_pcm_requant_report *out);
 /* the depth the track has on the disc: dvda_bits_per_sample() unless the reader reduces the word length */
 unsigned dvda_hip_reader_source_bits(const DVDA_Track_Reader *reader);
+/* ratio 2 or 4: track readers opened afterwards (per calling thread, read when the reader is opened, like
+ * dvda_hip_set_requantize) deliver a track at its rate / ratio where that is 44 100, 48 000, 88 200 or 96 000 Hz: the
+ * decoded int32 PCM is decimated on the device into a second buffer at the track's depth -- the contract, an exact
+ * integer FIR with one rounding and a clamp, is in dvda_mlp_hip.h, dvda_pcm_hip_decimate -- and from there on the reader
+ * IS a track of ceil(F / ratio) frames at the lower rate: the word-length reduction (its frame0 counts output frames),
+ * the digest, the level and energy reports, the WAV payload, dvda_read, dvda_hip_reader_total_frames() and
+ * dvda_sample_rate() all describe the decimated track.  A reader that would decode straight into the WAV payload
+ * decodes int32 instead and is packed afterwards.  Any other track (48 kHz by 2, 96 kHz by 4) is handed out as it is.
+ * Whole-track readers only, MLP and raw PCM: a track the reader would take in windows makes the open return NULL, and so
+ * does the option together with conceal mode or a ratio other than 0, 2 and 4.  (dvda_pcm_decim_piece already carries
+ * what decimating window by window needs.)  0 (default): off, a reader launches and allocates exactly as without. */
+struct dvda_pcm_decim_report;
+void dvda_hip_set_decimate(unsigned ratio);
+/* 1: the reader decimates, *out (may be NULL) = what the pass counted (frames in and out, per channel the values the
+ * clamp changed); 0: it does not -- the option is off, the track's rate is not one it applies to, or `reader` is NULL;
+ * nothing is written */
+int dvda_hip_reader_decimated(const DVDA_Track_Reader *reader, struct dvda_pcm_decim_report *out);
+/* the rate the track has on the disc: dvda_sample_rate() unless the reader decimates; 0 for a NULL reader */
+unsigned dvda_hip_reader_source_rate(const DVDA_Track_Reader *reader);
 /* on != 0: MLP track readers opened afterwards (per calling thread, read when the reader is opened, like
  * dvda_hip_set_wav_output) conceal a damaged track instead of refusing it: the track comes out as
  *     kept PCM ++ silence ++ PCM of a fresh decoder from the next usable major sync ++ ...

@@ -767,9 +767,10 @@ void dvda_pcm_hip_energy_total(const dvda_pcm_energy_block *blocks, uint64_t n, 
  * frame N of the track": a track requantized in one piece, in windows or on several devices is the same bytes.  The
  * reports of two pieces join by adding `frames` and clipped[]; there is no combine function.
  *
- * Out of scope: noise shaping (error feedback is a serial nonlinear recurrence per channel), sample-rate conversion,
- * auto-blanking of digital silence (TPDF on silence is noise of +-1 LSB, as it should be), float output, the streaming
- * tier and dvda_mlp_hip_decode_multi.  The disc tier has it as dvda_hip_set_requantize (dvd-audio-hip.h). */
+ * Out of scope: noise shaping (error feedback is a serial nonlinear recurrence per channel), sample-rate conversion
+ * (but see the decimation by 2 or 4 below), auto-blanking of digital silence (TPDF on silence is noise of +-1 LSB, as it
+ * should be), float output, the streaming tier and dvda_mlp_hip_decode_multi.  The disc tier has it as
+ * dvda_hip_set_requantize (dvd-audio-hip.h). */
 #define DVDA_RQ_TRUNCATE 0u
 #define DVDA_RQ_ROUND    1u
 #define DVDA_RQ_TPDF     2u
@@ -822,6 +823,94 @@ int dvda_mlp_hip_pcm_requantize(dvda_mlp_hip_ctx *ctx, int32_t *d_pcm, const uin
  * absolute frame.  *clipped (may be NULL) = 1 when the clamp changed the value, else 0; invalid params: returns 0 and
  * sets *clipped = -1. */
 int32_t dvda_pcm_hip_requant_value(int32_t v, uint64_t frame, uint32_t channel, const dvda_pcm_requant *params, int *clipped);
+
+/* ------------------------------------------------------------------ decimation of the decoded PCM by 2 or 4
+ * DVD-Audio tracks run at 88.2 / 96 / 176.4 / 192 kHz; the file a CD, a player or a preview wants runs at 44.1 or 48 kHz,
+ * an integer reduction by 2 or 4 inside the format's two rate families.  Made on the device, the caller does not copy
+ * 4 bytes per sample at the high rate to the host in order to throw three quarters of them away (csrc/pcm_decim.h,
+ * DESIGN.md section 17).
+ *
+ * The contract; every figure exact.  Ratio D in {2, 4}.  One tap table per ratio, h_D[0 .. N_D - 1], int32, a committed
+ * constant (csrc/pcm_decim_taps.h; dvda_pcm_hip_decim_taps hands it out): N_2 = 191, N_4 = 383, H_D = (N_D - 1) / 2 = 95 /
+ * 191; symmetric, h[i] == h[N-1-i]; Q = 30 and sum h = 2^30 exactly, so the gain at DC is exactly 1; every tap at an
+ * offset from the centre that is a non-zero multiple of D is exactly 0 (a half-band / quarter-band filter).  Recipe of
+ * tools/make_decim_taps.py: 2 fc sinc(2 fc n) * kaiser(N, 12.0), fc = 0.5 / D, normalised, rint(h * 2^30), the sum's
+ * difference from 2^30 added to the centre tap -- but the library's truth is the committed integers.  sum |h| =
+ * 2 122 621 608 (D = 2) and 2 352 308 816 (D = 4); passband 0 .. 0.4535 fs_out within +-1.2e-5 dB, stopband from
+ * 0.5465 fs_out to the input Nyquist at -118.7 dB / -119.2 dB.  With sum |h| < 2.4e9 and |x| <= 2^31 the accumulator
+ * stays below 5.2e18 < 2^63 for ANY int32 input: the arithmetic is plain int64 and cannot overflow.
+ *
+ * For channel c and output frame M (absolute, on the track's grid), x[F][c] the input at absolute frame F:
+ *   acc     = sum_{k = -H .. H} h[H + k] * x[D M + k][c]                                   (int64)
+ *   y[M][c] = clamp((acc + 2^29) >> 30, -2^(bits-1), 2^(bits-1) - 1)     bits in {16, 20, 24}; the shift is arithmetic
+ * x[F] = 0 wherever the region does not hold F: in front of the track's first frame, behind its last one, beyond the
+ * context a piece brought.  clipped[c] counts the values the clamp changed (a band-limited version of full-scale
+ * material overshoots).  A track of F frames gives ceil(F / D) frames, M = 0 .. ceil(F / D) - 1.
+ *
+ * Pieces.  A stream may be a piece of a track: of the input descriptor's `frames` = before + own + after, the first
+ * `before` and the last `after` frames are context -- read, nothing produced for them -- and the own frames in between are
+ * the track's absolute frames [frame0, frame0 + own).  The piece's outputs are the M with frame0 <= D M < frame0 + own:
+ * dvda_pcm_hip_decim_out_frames(frame0, own, ratio) = ceil((frame0 + own) / D) - ceil(frame0 / D) of them (a host
+ * function; the kernels ask the same one; 0 for another ratio or frame0 / own above 2^62).  Only the H context frames
+ * nearest the own frames matter.  A piece whose context on each side is at least H frames, or reaches the track's end on
+ * that side, gives exactly the frames the whole track gives at those M; the reports of two pieces join by adding, there
+ * is no combine function.  d_piece == NULL: whole tracks, frame0 = 0, no context.  before + after > frames (or frame0
+ * above 2^62): the stream is not taken.
+ *
+ * Out of scope: conversion between the rate families (96 -> 44.1), upsampling, noise shaping, the WAV layouts on either
+ * side (requantize behind it writes them), in place, the streaming tier and dvda_mlp_hip_decode_multi.  The disc tier
+ * has it for tracks read whole: dvda_hip_set_decimate in dvd-audio-hip.h. */
+#define DVDA_DCM_TILE_FRAMES 1024u      /* OUTPUT frames of a tile; tiles are aligned to the stream's first output frame */
+typedef struct dvda_pcm_decim_piece {
+    uint64_t frame0;              /* absolute frame of the first own frame */
+    uint32_t before, after;       /* context frames in front of / behind the own frames */
+} dvda_pcm_decim_piece;           /* 16 bytes */
+typedef struct dvda_pcm_decim_report {
+    uint64_t frames_in;           /* own input frames */
+    uint64_t frames_out;          /* frames written */
+    uint64_t clipped[8];          /* per channel: values the clamp changed */
+} dvda_pcm_decim_report;          /* 80 bytes */
+
+/* The tier-free form.  Stream i: d_desc_in[i] in d_in (layout_in) -> d_desc_out[i] in d_out (layout_out), piece d_piece[i]
+ * (a NULL array: whole tracks), report d_report[i]; device arrays, n entries; each layout DVDA_PCM_PLANAR or
+ * DVDA_PCM_INTERLEAVED.  A stream is taken only when its input descriptor is one the reports take (channels 1..8, frames
+ * up to 2^40) and holds its context, and its output descriptor has the same channels, exactly out_frames frames and a
+ * stride >= frames; otherwise frames_in == frames_out == 0 is reported and nothing is written.  Out of place only; any
+ * overlap is the caller's error.  Enqueued on `stream`: no host wait, no allocation.  max_total_out_frames: a bound the
+ * host knows on the sum of the streams' OUTPUT frames; a stream whose tiles (DVDA_DCM_TILE_FRAMES output frames) fall
+ * outside it reports zeros, and its output region holds unspecified values inside its bounds and nothing outside them.
+ * d_work: dvda_pcm_hip_decimate_workspace_words(n, max_total_out_frames) uint32 words, which need not be cleared; no
+ * atomics, the report is the same from run to run.  Either side's off may have any 4-byte alignment and a planar stride
+ * any parity: 16-byte loads wherever memory allows them, 16-byte stores to an aligned planar output; nothing outside a
+ * region's `frames` is read, nothing outside the output region written.  The arguments are judged first, on any machine
+ * -- DVDA_HIP_EINVAL: a ratio other than 2 or 4, bits outside {16, 20, 24}, a WAV layout on either side, a null pointer
+ * other than d_piece, work_words too small; DVDA_HIP_ECAPACITY: 2^31 tiles or more -- then the device: DVDA_HIP_ENODEV
+ * without one. */
+size_t dvda_pcm_hip_decimate_workspace_words(uint32_t n, uint64_t max_total_out_frames);
+int dvda_pcm_hip_decimate(const int32_t *d_in, uint32_t layout_in, const dvda_pcm_crc_desc *d_desc_in,
+                          int32_t *d_out, uint32_t layout_out, const dvda_pcm_crc_desc *d_desc_out,
+                          const dvda_pcm_decim_piece *d_piece /* or NULL */, uint32_t n, uint32_t ratio, unsigned bits,
+                          uint64_t max_total_out_frames, dvda_pcm_decim_report *d_report,
+                          uint32_t *d_work, size_t work_words, void *stream);
+
+/* behind dvda_mlp_hip_decode (blocks): the first n streams of the last decode, whole tracks, d_pcm / d_out_off /
+ * d_out_stride as that decode got them, in the context's layout (DVDA_HIP_EINVAL when that is a WAV one), decimated into
+ * d_dst (layout_dst: either int32 layout): stream i to the dword offset host_dst_off[i] with the planar stride
+ * host_dst_stride[i] (host arrays; a stride below the stream's output frames: the stream is not taken).  Frames and
+ * channels are what dvda_mlp_hip_stream_info reports; a stream that carries DVDA_ST_OVERFLOW reports zeros and nothing
+ * is written for it. */
+int dvda_mlp_hip_pcm_decimate(dvda_mlp_hip_ctx *ctx, const int32_t *d_pcm, const uint64_t *d_out_off,
+                              const uint64_t *d_out_stride, uint32_t ratio, unsigned bits, int32_t *d_dst,
+                              uint32_t layout_dst, const uint64_t *host_dst_off, const uint64_t *host_dst_stride,
+                              dvda_pcm_decim_report *host_report, uint32_t n, void *stream);
+
+/* Host helpers; none needs a device.  taps: the committed table of `ratio`, *n (may be NULL) = its length; NULL and 0 for
+ * another ratio.  value: the contract above for one output value -- the text the kernel compiles -- from its window of
+ * 2 H + 1 input values, window[H] the one at D M; *clipped (may be NULL) = 1 when the clamp changed the value, else 0;
+ * an invalid ratio or depth or a NULL window: returns 0 and sets *clipped = -1. */
+const int32_t *dvda_pcm_hip_decim_taps(uint32_t ratio, uint32_t *n);
+uint64_t dvda_pcm_hip_decim_out_frames(uint64_t frame0, uint64_t own, uint32_t ratio);
+int32_t dvda_pcm_hip_decim_value(const int32_t *window, uint32_t ratio, unsigned bits, int *clipped);
 
 /* ------------------------------------------------------------------ tier B */
 /* The mlp.h mirror: same three calls, same meaning as reference src/mlp.h:29-42 /

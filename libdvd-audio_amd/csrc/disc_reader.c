@@ -50,6 +50,8 @@ struct reader_opts {
     unsigned energy;            /* != 0: ... and its energy report on a grid of that many frames (dvda_hip_reader_energy) */
     unsigned rq_bits, rq_mode;  /* rq_bits != 0: every piece of int32 PCM is reduced to that many bits where it lies on the */
     unsigned long long rq_seed; /*   device, in front of its reports (dvda_hip_set_requantize, dvda_hip_reader_requantized) */
+    unsigned dc_ratio;          /* != 0: a whole-track reader decimates the decoded PCM by 2 or 4 on the device, in front of
+                                   all of the above (dvda_hip_set_decimate, dvda_hip_reader_decimated) */
 };
 static _Thread_local struct reader_opts t_opts;
 static _Thread_local int t_conceal_set;     /* dvda_hip_set_conceal() was called on this thread: DVDA_CONCEAL no longer counts */
@@ -65,6 +67,7 @@ void dvda_hip_set_requantize(unsigned bits_out, unsigned mode, unsigned long lon
     t_opts.rq_mode = mode;
     t_opts.rq_seed = seed;
 }
+void dvda_hip_set_decimate(unsigned ratio) { t_opts.dc_ratio = ratio; }
 void dvda_hip_set_conceal(int on)
 {
     t_opts.conceal = on != 0;
@@ -123,6 +126,15 @@ static void rep_want(struct pcm_reports *r, const struct reader_opts *o)
 static int rq_applies(const struct reader_opts *o, unsigned bits) { return o->rq_bits != 0 && bits >= o->rq_bits; }
 static unsigned code_of_bits(unsigned bits) { return bits == 16 ? 0 : bits == 20 ? 1 : 2; }
 
+/* does a reader opened with `o` decimate a track whose rate has `rate_code`?  Only where rate / ratio is one of 44 100,
+ * 48 000, 88 200, 96 000: the codes count 0, 1, 2 = x1, x2, x4 inside a rate family (bit 3), so the quotient's code is
+ * rate_code - log2(ratio) where that is not negative.  Any other track is handed out as it is. */
+static unsigned dc_shift(const struct reader_opts *o) { return o->dc_ratio == 2 ? 1 : o->dc_ratio == 4 ? 2 : 0; }
+static int dc_applies(const struct reader_opts *o, unsigned rate_code)
+{
+    return dc_shift(o) != 0 && rate_of(rate_code) != 0 && (rate_code & 3) >= dc_shift(o);
+}
+
 static void rep_reset(struct pcm_reports *r)
 {
     free(r->ng_blocks);
@@ -135,6 +147,8 @@ struct DVDA_Track_Reader_s {
     unsigned bps_code[2], rate_code[2], assignment;
     unsigned channels, status;
     unsigned src_bits;         /* != 0: the track's own depth, where the reader hands out fewer bits (dvda_hip_set_requantize) */
+    unsigned src_rate;         /* != 0: the track's own rate, where the reader hands out a lower one (dvda_hip_set_decimate) */
+    dvda_pcm_decim_report dc_rep;      /* ... and what the decimation counted */
     uint64_t frames, served, stride;
     int interleaved;           /* MLP tracks: frame-major [frame][channel] = the dvda_read order;
                                   PCM tracks: planar [channel][stride]; RIFF-WAVE channel order */
@@ -450,6 +464,49 @@ static void reports_join(struct pcm_reports *track, const struct pcm_reports *pi
     }
 }
 
+/* A whole track decimated where it lies on the device (dvda_hip_set_decimate): `*frames` frames of `ch` channels at
+ * `bits` in `layout` (an int32 one) at *d_pcm, capacity *stride frames, go through dvda_pcm_hip_decimate as one whole
+ * track (no piece) into a second buffer in the same layout, which takes the place of the first: *d_pcm, *stride and
+ * *frames are then those of a track of ceil(frames / ratio) frames at the lower rate, and everything the reader does
+ * from here on -- requantize, the reports, the packing step, dvda_read -- sees that track.  One block on the device holds
+ * the two descriptors, the report and the workspace.  Blocks; the first buffer is freed.  1 = ok. */
+static int track_decimate(int32_t **d_pcm, uint32_t layout, unsigned bits, uint64_t *stride, uint64_t *frames, unsigned ch,
+                          unsigned ratio, dvda_pcm_decim_report *rep)
+{
+    const uint64_t out_frames = dvda_pcm_hip_decim_out_frames(0, *frames, ratio);
+    uint64_t out_stride = (out_frames + 3) & ~(uint64_t)3;
+    if (out_stride == 0)
+        out_stride = 4;
+    struct {
+        dvda_pcm_crc_desc in, out;
+        dvda_pcm_decim_report rep;
+    } blk = {{0, *stride, *frames, ch, 0}, {0, out_stride, out_frames, ch, 0}, {0, 0, {0}}};
+    const size_t words = dvda_pcm_hip_decimate_workspace_words(1, out_frames);
+    int32_t *d_out = NULL;
+    uint8_t *d = NULL;
+    int ok = dev_alloc((void **)&d_out, (size_t)out_stride * ch * sizeof(int32_t));
+    if (ok && out_frames) {
+        ok = dev_alloc((void **)&d, sizeof(blk) + words * sizeof(uint32_t)) &&
+             hipMemcpy(d, &blk, sizeof(blk), hipMemcpyHostToDevice) == hipSuccess &&
+             dvda_pcm_hip_decimate(*d_pcm, layout, (const dvda_pcm_crc_desc *)(d + offsetof(__typeof__(blk), in)), d_out,
+                                   layout, (const dvda_pcm_crc_desc *)(d + offsetof(__typeof__(blk), out)), NULL, 1, ratio,
+                                   bits, out_frames, (dvda_pcm_decim_report *)(d + offsetof(__typeof__(blk), rep)),
+                                   (uint32_t *)(d + sizeof(blk)), words, NULL) == DVDA_HIP_OK &&
+             hipMemcpy(&blk, d, sizeof(blk), hipMemcpyDeviceToHost) == hipSuccess && blk.rep.frames_out == out_frames;
+        (void)hipFree(d);
+    }
+    if (!ok) {
+        (void)hipFree(d_out);
+        return 0;
+    }
+    (void)hipFree(*d_pcm);
+    *d_pcm = d_out;
+    *stride = out_stride;
+    *frames = out_frames;
+    *rep = blk.rep;
+    return 1;
+}
+
 /* ------------------------------------------------------------------ the buffer set
  * Everything a track's decode works in.  The steps below fill and use it; who owns it decides how it is allocated:
  *   one batch (pinned == 0)  pageable sector buffer, device buffers of exactly the size in use, the whole set freed when
@@ -680,8 +737,8 @@ static uint32_t layout_of(int wav_bits)
  * the payload dvda2wav would write -- interleaved, little-endian, write_signed at the stream's own bit depth -- and
  * nothing else, no int32 PCM and no separate packing pass (SURVEY 8(f-3) fused into the decode, DVDA_PCM_WAV24 /
  * WAV16): decided here, from the index's stream record, as 16, 24 or 0 (a depth that is decoded into int32 frames) and
- * then left alone; a reader that reduces the word length (rq: its options, or NULL) decodes int32 frames, which the
- * reduction works on: 0.  Hands back the stream's record after the decode and the frames d_pcm has room for.  Its status is
+ * then left alone; a reader that reduces the word length or decimates (rq: its options, or NULL) decodes int32 frames,
+ * which those passes work on: 0.  Hands back the stream's record after the decode and the frames d_pcm has room for.  Its status is
  * the caller's to judge.  1 = decoded, 0 = failure. */
 static int decode_stream(struct track_bufs *b, uint64_t len, const int32_t *fir, int *wav_bits,
                          dvda_mlp_stream_info *info, uint64_t *stride_out, const struct reader_opts *rq)
@@ -700,7 +757,8 @@ static int decode_stream(struct track_bufs *b, uint64_t len, const int32_t *fir,
         stride = 4;
     if (*wav_bits < 0) {
         const unsigned bits = bits_of(info->group0_bps);
-        *wav_bits = (bits == 16 || bits == 24) && !(rq && rq_applies(rq, bits)) ? (int)bits : 0;
+        *wav_bits = (bits == 16 || bits == 24) && !(rq && (rq_applies(rq, bits) || dc_applies(rq, info->group0_rate)))
+                        ? (int)bits : 0;
     }
     const unsigned wbits = (unsigned)*wav_bits;
     if (dvda_mlp_hip_set_pcm_layout(b->ctx, layout_of(*wav_bits)) != DVDA_HIP_OK)
@@ -823,13 +881,23 @@ static DVDA_Track_Reader *open_mlp(struct aob_set *aobs, const DVDA_Track *k, co
     r->codec = DVDA_MLP;
     r->status = info.status;
     r->frames = info.pcm_frames;
-    r->stride = stride;
     if (!mlp_info_to_reader(r, &info, o->present))
         goto fail;
-    /* before any copy to the host: the track as the decode left it on the device */
+    if (dc_applies(o, info.group0_rate)) {
+        /* from here on the reader IS the shorter track at the lower rate (wav_bits == 0: decode_stream saw the option) */
+        if (wav_bits || !track_decimate(&b.d_pcm, DVDA_PCM_INTERLEAVED, bits_of(info.group0_bps), &stride, &r->frames,
+                                        info.channels, o->dc_ratio, &r->dc_rep))
+            goto fail;
+        b.cap_pcm = 0;
+        r->src_rate = rate_of(info.group0_rate);
+        r->rate_code[0] = info.group0_rate - dc_shift(o);
+        t_line(&t_mark, "decimate");
+    }
+    r->stride = stride;
+    /* before any copy to the host: the track as the decode (and the decimation) left it on the device */
     rep_want(&r->rep, o);
     if (!piece_reports(&r->rep, &r->rep, wav_bits != 0, b.d_pcm, layout_of(wav_bits), bits_of(info.group0_bps), stride,
-                       info.pcm_frames, info.channels, 0))
+                       r->frames, info.channels, 0))
         goto fail;
     if (r->rep.rq > 0) {
         r->src_bits = bits_of(r->bps_code[0]);
@@ -1719,7 +1787,12 @@ static DVDA_Track_Reader *open_mlp_windowed(const DVDA_Track *k, const struct re
     struct track_windows *w = r->win;
     w->wav_bits = o->wav_output ? -1 : 0;       /* (win_produce decides it from the first window's index) */
     /* (w->info is written once, by the first window that decodes: the producer thread only reads it) */
-    if (!windows_start(w) || !w->info.channels || !mlp_info_to_reader(r, &w->info, o->present)) {
+    /* (a track that would be decimated is not read in windows: a later change; dvda_pcm_decim_piece carries what it needs.
+       An MLP stream names its rate in its first major sync only, so the refusal comes after windows_start has decoded
+       the first window and started the producer thread -- work thrown away, on a path that ends in NULL either way; a
+       raw-PCM track's packet header has the rate, and open_pcm_windowed refuses before it starts anything) */
+    if (!windows_start(w) || !w->info.channels || !mlp_info_to_reader(r, &w->info, o->present) ||
+        dc_applies(o, w->info.group0_rate)) {
         reader_free(r);
         return NULL;
     }
@@ -1763,11 +1836,17 @@ static DVDA_Track_Reader *open_pcm(struct aob_set *aobs, const DVDA_Track *k, co
             break;                               /* (else the track spills over its sector range) */
     }
     r->frames = deliver;
-    r->stride = stride;
     r->d_pcm = b.d_pcm;
     b.d_pcm = NULL;
+    if (dc_applies(o, r->rate_code[0])) {
+        if (!track_decimate(&r->d_pcm, DVDA_PCM_PLANAR, bits, &stride, &r->frames, r->channels, o->dc_ratio, &r->dc_rep))
+            goto fail;
+        r->src_rate = rate;
+        r->rate_code[0] -= dc_shift(o);
+    }
+    r->stride = stride;
     rep_want(&r->rep, o);
-    if (!piece_reports(&r->rep, &r->rep, 0, r->d_pcm, DVDA_PCM_PLANAR, bits, stride, deliver, r->channels, 0))
+    if (!piece_reports(&r->rep, &r->rep, 0, r->d_pcm, DVDA_PCM_PLANAR, bits, stride, r->frames, r->channels, 0))
         goto fail;
     if (r->rep.rq > 0) {
         r->src_bits = bits;
@@ -1793,7 +1872,7 @@ static DVDA_Track_Reader *open_pcm_windowed(const DVDA_Track *k, const uint8_t *
     if (!r)
         return NULL;
     struct track_windows *w = r->win;
-    if (!pcm_params_to_reader(r, params, &bits, &rate)) {
+    if (!pcm_params_to_reader(r, params, &bits, &rate) || dc_applies(o, r->rate_code[0])) {
         reader_free(r);
         return NULL;
     }
@@ -1827,6 +1906,9 @@ static DVDA_Track_Reader *open_reader(const DVDA_Track *k, const struct reader_o
     /* the word-length reduction: a depth and a mode it has; not together with conceal mode (the stitch between two
        windows rewrites frames that were handed over, and reduced, already) */
     if (o->rq_bits && ((o->rq_bits != 16 && o->rq_bits != 20 && o->rq_bits != 24) || o->rq_mode > DVDA_RQ_TPDF || o->conceal))
+        return NULL;
+    /* the decimation: a ratio it has; not together with conceal mode */
+    if (o->dc_ratio && (!dc_shift(o) || o->conceal))
         return NULL;
     aob_open_all(&aobs, k->dir, k->titleset);
     if (aobs.n == 0 || k->s.first >= aobs.total)
@@ -1903,6 +1985,21 @@ dvda_codec_t dvda_codec(const DVDA_Track_Reader *r) { return r->codec; }
 unsigned dvda_bits_per_sample(const DVDA_Track_Reader *r) { return bits_of(r->bps_code[0]); }
 unsigned dvda_hip_reader_source_bits(const DVDA_Track_Reader *r) { return r->src_bits ? r->src_bits : bits_of(r->bps_code[0]); }
 unsigned dvda_sample_rate(const DVDA_Track_Reader *r) { return rate_of(r->rate_code[0]); }
+/* (the two accessors of the decimation take a NULL reader alike: no state, no rate) */
+unsigned dvda_hip_reader_source_rate(const DVDA_Track_Reader *r)
+{
+    if (!r)
+        return 0;
+    return r->src_rate ? r->src_rate : rate_of(r->rate_code[0]);
+}
+int dvda_hip_reader_decimated(const DVDA_Track_Reader *r, dvda_pcm_decim_report *out)
+{
+    if (!r || !r->src_rate)
+        return 0;
+    if (out)
+        *out = r->dc_rep;
+    return 1;
+}
 unsigned dvda_channel_count(const DVDA_Track_Reader *r) { return channels_of(r->assignment); }
 unsigned dvda_hip_reader_status(const DVDA_Track_Reader *r)
 {

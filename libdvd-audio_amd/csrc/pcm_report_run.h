@@ -1,11 +1,12 @@
 // pcm_report_run.h -- host side of the reports of decoded PCM, the digest (pcm_digest.h), the level report
-// (pcm_levels.h), the compare (pcm_compare.h), the energy report (pcm_energy.h) and the word-length reduction (pcm_requant.h): what a report is to the driver, the one driver of the flat tile list (pcm_tiles.h), the one call that
+// (pcm_levels.h), the compare (pcm_compare.h), the energy report (pcm_energy.h), the word-length reduction (pcm_requant.h) and the decimation (pcm_decim.h): what a report is to the driver, the one driver of the flat tile list (pcm_tiles.h), the one call that
 // runs a report behind a decode on the context's own buffers, and the host arithmetic that joins two pieces' results.
 #pragma once
 #include <vector>
 
 #include "mlp_ctx.h"
 #include "pcm_compare.h"
+#include "pcm_decim.h"
 #include "pcm_digest.h"
 #include "pcm_energy.h"
 #include "pcm_levels.h"
@@ -221,6 +222,52 @@ struct RqReport {
     }
 };
 static_assert(sizeof(dvda_pcm_requant) == 24 && sizeof(dvda_pcm_requant_report) == 72, "the requantizer's structs");
+
+// The decimation: the input is what the driver calls the PCM; the output -- buffer, layout, descriptors -- the pieces
+// and the ratio travel here.  Its unit is OUTPUT frames; the driver's `bits` is the depth the values are clamped to.
+struct DcReport {
+    static constexpr uint32_t TILE = dcm::TILE, TILE_WORDS = dcm::REC, TILE_BLOCKS = dcm::TILE_BLOCKS;     // unit: output frames
+    dvda_pcm_decim_report *d_report;
+    int32_t *d_out;
+    uint32_t layout_out;
+    const dvda_pcm_crc_desc *d_desc_out;
+    const dvda_pcm_decim_piece *d_piece;
+    uint32_t ratio;
+
+    static bool int32_layout(uint32_t layout) { return layout == DVDA_PCM_PLANAR || layout == DVDA_PCM_INTERLEAVED; }
+    bool has_out() const { return d_report && d_out && d_desc_out && dcm::ratio_ok(ratio) && int32_layout(layout_out); }
+    static bool takes(uint32_t layout, unsigned bits) { return int32_layout(layout) && dcm::depth_ok(bits); }
+
+    void plan(hipStream_t st, const dvda_pcm_crc_desc *d_desc, uint32_t n, unsigned, uint32_t *cnt) const
+    {
+        hipLaunchKernelGGL(dcm::k_dc_plan, dim3((n + 255) / 256), dim3(256), 0, st, d_desc, d_desc_out, d_piece, n, ratio, cnt);
+    }
+    template <uint32_t D>
+    void tiles_of(dim3 grid, dim3 block, hipStream_t st, const int32_t *d_pcm, uint32_t layout, const dvda_pcm_crc_desc *d_desc,
+                  uint32_t n, unsigned bits, const uint32_t *base, uint32_t *rec, uint32_t max_tiles) const
+    {
+        const bool pi = layout == DVDA_PCM_PLANAR, po = layout_out == DVDA_PCM_PLANAR;
+        auto k = pi ? (po ? dcm::k_dc_tiles<D, true, true> : dcm::k_dc_tiles<D, true, false>)
+                    : (po ? dcm::k_dc_tiles<D, false, true> : dcm::k_dc_tiles<D, false, false>);
+        hipLaunchKernelGGL(k, grid, block, 0, st, d_pcm, d_desc, d_out, d_desc_out, d_piece, n, (uint32_t)bits, base, rec,
+                           max_tiles);
+    }
+    void tiles(dim3 grid, dim3 block, hipStream_t st, const int32_t *d_pcm, uint32_t layout, const dvda_pcm_crc_desc *d_desc,
+               uint32_t n, unsigned bits, const uint32_t *base, uint32_t *rec, uint32_t max_tiles) const
+    {
+        if (ratio == 2)
+            tiles_of<2>(grid, block, st, d_pcm, layout, d_desc, n, bits, base, rec, max_tiles);
+        else
+            tiles_of<4>(grid, block, st, d_pcm, layout, d_desc, n, bits, base, rec, max_tiles);
+    }
+    void join(dim3 block, hipStream_t st, const dvda_pcm_crc_desc *d_desc, uint32_t n, unsigned, const uint32_t *base,
+              const uint32_t *rec, uint32_t max_tiles) const
+    {
+        hipLaunchKernelGGL(dcm::k_dc_join, dim3(n), block, 0, st, d_desc, d_desc_out, d_piece, n, ratio, base, rec, max_tiles,
+                           d_report);
+    }
+};
+static_assert(sizeof(dvda_pcm_decim_piece) == 16 && sizeof(dvda_pcm_decim_report) == 80, "the decimator's structs");
 
 // ---- the driver of the flat tile list
 // tiles the list can hold for n streams of max_total units in all: every stream has at most one ragged tile
@@ -706,4 +753,85 @@ extern "C" int32_t dvda_pcm_hip_requant_value(int32_t v, uint64_t frame, uint32_
     if (clipped)
         *clipped = (int)cl;
     return q;
+}
+
+// ---- the decimation
+extern "C" size_t dvda_pcm_hip_decimate_workspace_words(uint32_t n, uint64_t max_total_out_frames)
+{
+    return report_workspace_words<DcReport>(n, max_total_out_frames);
+}
+
+extern "C" int dvda_pcm_hip_decimate(const int32_t *d_in, uint32_t layout_in, const dvda_pcm_crc_desc *d_desc_in,
+                                     int32_t *d_out, uint32_t layout_out, const dvda_pcm_crc_desc *d_desc_out,
+                                     const dvda_pcm_decim_piece *d_piece, uint32_t n, uint32_t ratio, unsigned bits,
+                                     uint64_t max_total_out_frames, dvda_pcm_decim_report *d_report, uint32_t *d_work,
+                                     size_t work_words, void *stream_)
+{
+    return report_run(DcReport{d_report, d_out, layout_out, d_desc_out, d_piece, ratio}, d_in, layout_in, bits, d_desc_in, n,
+                      max_total_out_frames, d_work, work_words, stream_);
+}
+
+extern "C" int dvda_mlp_hip_pcm_decimate(dvda_mlp_hip_ctx *c, const int32_t *d_pcm, const uint64_t *d_out_off,
+                                         const uint64_t *d_out_stride, uint32_t ratio, unsigned bits, int32_t *d_dst,
+                                         uint32_t layout_dst, const uint64_t *host_dst_off, const uint64_t *host_dst_stride,
+                                         dvda_pcm_decim_report *host_report, uint32_t n, void *stream_)
+{
+    if (!c || !d_pcm || !d_out_off || !d_out_stride || !d_dst || !host_dst_off || !host_dst_stride || !host_report ||
+        !dcm::ratio_ok(ratio) || !DcReport::int32_layout(layout_dst) || !DcReport::takes(c->set.pcm_layout, bits))
+        return DVDA_HIP_EINVAL;
+    std::vector<dvda_pcm_crc_desc> desc;
+    int rc = report_decode_descs(c, d_out_off, d_out_stride, &n, stream_, &desc);
+    if (rc || n == 0)
+        return rc;
+    // the descriptors of both sides in one array: the input's [n], then the output's [n]
+    desc.resize(2 * (size_t)n);
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        dvda_pcm_crc_desc &o = desc[n + i];
+        o = desc[i];
+        o.off = host_dst_off[i];
+        o.stride = host_dst_stride[i];
+        o.frames = PCMT_NOT_TAKEN(desc[i]) ? 0 : dcm::out_frames(0, desc[i].frames, ratio);
+        total += o.frames;              // (an overflowed stream has no frames here: zeros reported, nothing written)
+    }
+    constexpr size_t RW = sizeof(dvda_pcm_decim_report) / sizeof(uint64_t);
+    if ((rc = c->d_rep_desc.grow(2 * (size_t)n)) != 0 || (rc = c->d_rep_out.grow(RW * (size_t)n)) != 0 ||
+        (rc = c->d_rep_work.grow(report_workspace_words<DcReport>(n, total))) != 0)
+        return rc;
+    HIP_TRY(hipMemcpy(c->d_rep_desc, desc.data(), 2 * (size_t)n * sizeof(dvda_pcm_crc_desc), hipMemcpyHostToDevice));
+    const dvda_pcm_crc_desc *d_in_desc = c->d_rep_desc;
+    const DcReport r{(dvda_pcm_decim_report *)(uint64_t *)c->d_rep_out, d_dst, layout_dst, d_in_desc + n, nullptr, ratio};
+    rc = report_run(r, d_pcm, c->set.pcm_layout, bits, d_in_desc, n, total, c->d_rep_work, (size_t)c->d_rep_work.cap, stream_);
+    if (rc)
+        return rc;
+    hipStream_t st = (hipStream_t)stream_;
+    HIP_TRY(hipMemcpyAsync(host_report, r.d_report, (size_t)n * sizeof(dvda_pcm_decim_report), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DVDA_HIP_OK;
+}
+
+extern "C" const int32_t *dvda_pcm_hip_decim_taps(uint32_t ratio, uint32_t *n)
+{
+    if (n)
+        *n = dcm::ratio_ok(ratio) ? dcm::taps_of(ratio) : 0u;
+    return ratio == 2 ? dcm::Taps<2>::h : ratio == 4 ? dcm::Taps<4>::h : nullptr;
+}
+
+extern "C" uint64_t dvda_pcm_hip_decim_out_frames(uint64_t frame0, uint64_t own, uint32_t ratio)
+{
+    return dcm::out_frames(frame0, own, ratio);
+}
+
+extern "C" int32_t dvda_pcm_hip_decim_value(const int32_t *window, uint32_t ratio, unsigned bits, int *clipped)
+{
+    if (!window || !dcm::ratio_ok(ratio) || !dcm::depth_ok(bits)) {
+        if (clipped)
+            *clipped = -1;
+        return 0;
+    }
+    uint32_t cl = 0;
+    const int32_t y = ratio == 2 ? dcm::value<2>(window, bits, &cl) : dcm::value<4>(window, bits, &cl);
+    if (clipped)
+        *clipped = (int)cl;
+    return y;
 }

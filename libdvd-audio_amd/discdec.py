@@ -27,7 +27,7 @@ EXPORTS = [
     "dvda_hip_release_cached_buffers", "dvda_hip_set_presentation", "dvda_hip_open_track_reader_with",
     "dvda_hip_set_digest", "dvda_hip_reader_crc32", "dvda_hip_set_levels", "dvda_hip_reader_levels",
     "dvda_hip_set_energy", "dvda_hip_reader_energy", "dvda_hip_set_requantize", "dvda_hip_reader_requantized",
-    "dvda_hip_reader_source_bits",
+    "dvda_hip_reader_source_bits", "dvda_hip_set_decimate", "dvda_hip_reader_decimated", "dvda_hip_reader_source_rate",
     "dvda_hip_set_conceal", "dvda_hip_reader_concealed", "dvda_hip_open_track_reader_concealing",
 ]
 
@@ -105,6 +105,12 @@ def lib():
         L.dvda_hip_reader_source_bits.argtypes = [vp]
         L.dvda_hip_reader_requantized.restype = ctypes.c_int
         L.dvda_hip_reader_requantized.argtypes = [vp, ctypes.POINTER(hipdec.RequantReport)]
+        L.dvda_hip_set_decimate.restype = None
+        L.dvda_hip_set_decimate.argtypes = [ctypes.c_uint]
+        L.dvda_hip_reader_decimated.restype = ctypes.c_int
+        L.dvda_hip_reader_decimated.argtypes = [vp, ctypes.POINTER(hipdec.DecimReport)]
+        L.dvda_hip_reader_source_rate.restype = ctypes.c_uint
+        L.dvda_hip_reader_source_rate.argtypes = [vp]
         L.dvda_hip_reader_energy.restype = ctypes.c_int
         L.dvda_hip_reader_energy.argtypes = [vp, ctypes.POINTER(hipdec.EnergyBlock), ctypes.c_ulonglong,
                                              ctypes.POINTER(ctypes.c_ulonglong)]
@@ -145,7 +151,7 @@ def layout(audio_ts, titleset=1):
 
 
 def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0, fused=False, pieces=False,
-               presentation=0, digest=False, levels=False, conceal=None, energy=0, requant=None):
+               presentation=0, digest=False, levels=False, conceal=None, energy=0, requant=None, decimate=0):
     """Decodes one track on the GPU.  Returns a dict: codec ("PCM"/"MLP"), bits, rate, channels,
     mask, status, and pcm = int32 [frames, channels] (interleaved, RIFF-WAVE order) read with
     dvda_read() in `chunk`-frame calls -- or, with wav=True, payload = the WAV data bytes packed
@@ -171,6 +177,12 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
     the payload and every report are of what the reader hands out.  info["requant"] = what the reduction counted as
     hipdec.RequantReport.as_dict() gives it (None when the reader does not reduce: a track below bits_out), and
     info["requant_states"] = what dvda_hip_reader_requantized returned right after the open and at the end.
+    decimate=2 or 4: the reader delivers the track at its rate / decimate where that is 44 100, 48 000, 88 200 or 96 000 Hz
+    (dvda_hip_set_decimate: filtered and decimated on the device, exact, clamped at the track's depth; whole-track
+    readers only -- a track read in windows cannot be opened); info["rate"] and info["frames"] are then those of the
+    decimated track, and the PCM, the payload, requant= and every report are of it.  info["decimate"] = what the pass
+    counted as hipdec.DecimReport.as_dict() gives it (None when the reader does not decimate: any other rate),
+    info["decimate_state"] = what dvda_hip_reader_decimated returned, info["source_rate"] = the rate on the disc.
     conceal=True: a damaged MLP track is concealed, not refused (dvda_hip_set_conceal): info["concealed"] = the spans as
     6-tuples (first_frame, frames, byte_off, byte_end, cause, flags) in track terms, and info["concealed_states"] = what
     dvda_hip_reader_concealed returned right after the open and at the end.  conceal=False says "off" explicitly; None
@@ -192,6 +204,7 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
         L.dvda_hip_set_energy(int(energy))
         if requant is not None:
             L.dvda_hip_set_requantize(int(requant[0]), int(requant[1]), int(requant[2]))
+        L.dvda_hip_set_decimate(int(decimate))
         try:
             r = L.dvda_hip_open_track_reader_concealing(k, device, 1 if (fused and wav) else 0, presentation,
                                                         -1 if conceal is None else int(bool(conceal))) if k else None
@@ -200,6 +213,7 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
             L.dvda_hip_set_levels(0)
             L.dvda_hip_set_energy(0)
             L.dvda_hip_set_requantize(0, 0, 0)
+            L.dvda_hip_set_decimate(0)
         if not r:
             raise RuntimeError("track %d/%d/%d cannot be opened for reading" % (titleset, title, track))
         ch = L.dvda_channel_count(r)
@@ -271,6 +285,12 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
             info["requant_states"] = (first_rq, state)
             info["requant"] = rq_report.as_dict() if state == 1 else None
             info["source_bits"] = int(L.dvda_hip_reader_source_bits(r))
+        if decimate:
+            dc_report = hipdec.DecimReport()
+            state = L.dvda_hip_reader_decimated(r, ctypes.byref(dc_report))
+            info["decimate_state"] = state
+            info["decimate"] = dc_report.as_dict() if state == 1 else None
+            info["source_rate"] = int(L.dvda_hip_reader_source_rate(r))
         if conceal:
             state = L.dvda_hip_reader_concealed(r, None, 0, ctypes.byref(n_spans))
             arr = (hipdec.ConcealSpan * max(int(n_spans.value), 1))()

@@ -79,7 +79,9 @@ EXPORTS = ("dvda_mlp_hip_create", "dvda_mlp_hip_destroy", "dvda_mlp_hip_index", 
            "dvda_pcm_hip_energy", "dvda_pcm_hip_energy_workspace_words", "dvda_mlp_hip_pcm_energy",
            "dvda_pcm_hip_energy_append", "dvda_pcm_hip_energy_total",
            "dvda_pcm_hip_requantize", "dvda_pcm_hip_requantize_workspace_words", "dvda_mlp_hip_pcm_requantize",
-           "dvda_pcm_hip_requant_value")
+           "dvda_pcm_hip_requant_value",
+           "dvda_pcm_hip_decimate", "dvda_pcm_hip_decimate_workspace_words", "dvda_mlp_hip_pcm_decimate",
+           "dvda_pcm_hip_decim_taps", "dvda_pcm_hip_decim_out_frames", "dvda_pcm_hip_decim_value")
 
 CRC_TILE_BYTES = 16384      # DVDA_CRC_TILE_BYTES: the digest's tiles, aligned to the end of a stream's payload
 CRC_JOIN_TILES = 256        # DVDA_CRC_JOIN_TILES: tiles a join workgroup folds per turn of its loop
@@ -180,6 +182,27 @@ class RequantReport(ctypes.Structure):
     @classmethod
     def from_dict(cls, d):
         return cls(d["frames"], (ctypes.c_uint64 * 8)(*d["clipped"]))
+
+
+DCM_TILE_FRAMES = 1024      # DVDA_DCM_TILE_FRAMES: OUTPUT frames of the decimator's tiles, aligned to a stream's first output frame
+DECIM_RATES = (44100, 48000, 88200, 96000)      # the rates decode_streams_decimated hands out
+
+
+class DecimPiece(ctypes.Structure):
+    """dvda_pcm_decim_piece of include/dvda_mlp_hip.h"""
+    _fields_ = [("frame0", ctypes.c_uint64), ("before", ctypes.c_uint32), ("after", ctypes.c_uint32)]
+
+
+class DecimReport(ctypes.Structure):
+    """dvda_pcm_decim_report of include/dvda_mlp_hip.h"""
+    _fields_ = [("frames_in", ctypes.c_uint64), ("frames_out", ctypes.c_uint64), ("clipped", ctypes.c_uint64 * 8)]
+
+    def as_dict(self):
+        return dict(frames_in=int(self.frames_in), frames_out=int(self.frames_out), clipped=[int(v) for v in self.clipped])
+
+    @classmethod
+    def from_dict(cls, d):
+        return cls(d["frames_in"], d["frames_out"], (ctypes.c_uint64 * 8)(*d["clipped"]))
 
 
 ST_CONCEALED = 1 << 30          # DVDA_ST_CONCEALED: conceal mode, the stream was damaged (not in ST_BENIGN)
@@ -330,6 +353,18 @@ def lib():
         L.dvda_pcm_hip_requant_value.restype = ctypes.c_int32
         L.dvda_pcm_hip_requant_value.argtypes = [ctypes.c_int32, u64, u32, ctypes.POINTER(Requant),
                                                  ctypes.POINTER(ctypes.c_int)]
+        L.dvda_pcm_hip_decimate_workspace_words.restype = ctypes.c_size_t
+        L.dvda_pcm_hip_decimate_workspace_words.argtypes = [u32, u64]
+        L.dvda_pcm_hip_decimate.argtypes = [vp, u32, vp, vp, u32, vp, vp, u32, u32, ctypes.c_uint, u64, vp, vp,
+                                            ctypes.c_size_t, vp]
+        L.dvda_mlp_hip_pcm_decimate.argtypes = [vp, vp, vp, vp, u32, ctypes.c_uint, vp, u32, ctypes.POINTER(u64),
+                                                ctypes.POINTER(u64), ctypes.POINTER(DecimReport), u32, vp]
+        L.dvda_pcm_hip_decim_taps.restype = ctypes.POINTER(ctypes.c_int32)
+        L.dvda_pcm_hip_decim_taps.argtypes = [u32, ctypes.POINTER(u32)]
+        L.dvda_pcm_hip_decim_out_frames.restype = u64
+        L.dvda_pcm_hip_decim_out_frames.argtypes = [u64, u64, u32]
+        L.dvda_pcm_hip_decim_value.restype = ctypes.c_int32
+        L.dvda_pcm_hip_decim_value.argtypes = [vp, u32, ctypes.c_uint, ctypes.POINTER(ctypes.c_int)]
         _lib = L
     return _lib
 
@@ -537,6 +572,20 @@ class Context:
         par = Requant(bits_in, bits_out, mode, 0, seed)
         _check(lib().dvda_mlp_hip_pcm_requantize(self._h, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, ctypes.byref(par), f0,
                                                  arr, n, stream), "dvda_mlp_hip_pcm_requantize")
+        return [arr[i].as_dict() for i in range(n)]
+
+    def pcm_decimate(self, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, ratio, bits, d_dst_ptr, layout_dst, dst_off,
+                     dst_stride, n=None, stream=0):
+        """dvda_mlp_hip_pcm_decimate: the int32 PCM the last decode wrote, whole tracks, decimated by `ratio` (2 or 4) and
+        clamped to `bits` into the device buffer at d_dst_ptr in layout_dst (PCM_PLANAR or PCM_INTERLEAVED): stream i to
+        the int32 word dst_off[i], planar stride dst_stride[i] (host lists) -> list of DecimReport.as_dict(); blocks.
+        HipError (EINVAL) when the context's layout is a WAV one."""
+        n = self.n_streams if n is None else n
+        arr = (DecimReport * max(n, 1))()
+        off = (ctypes.c_uint64 * max(n, 1))(*[int(v) for v in dst_off][:n])
+        stride = (ctypes.c_uint64 * max(n, 1))(*[int(v) for v in dst_stride][:n])
+        _check(lib().dvda_mlp_hip_pcm_decimate(self._h, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, ratio, bits, d_dst_ptr,
+                                               layout_dst, off, stride, arr, n, stream), "dvda_mlp_hip_pcm_decimate")
         return [arr[i].as_dict() for i in range(n)]
 
     def decode_time(self):
@@ -838,6 +887,106 @@ def requant_value(v, frame, channel, bits_in, bits_out, mode=RQ_TPDF, seed=0):
     if cl.value < 0:
         raise HipError("dvda_pcm_hip_requant_value: invalid parameters %r" % (par.as_dict(),))
     return int(q), int(cl.value)
+
+
+def decim_taps(ratio):
+    """dvda_pcm_hip_decim_taps: the committed tap table of `ratio` as an int32 array (a copy); needs no GPU.  HipError
+    for a ratio other than 2 or 4"""
+    n = ctypes.c_uint32(0)
+    p = lib().dvda_pcm_hip_decim_taps(ratio, ctypes.byref(n))
+    if not p or not n.value:
+        raise HipError("dvda_pcm_hip_decim_taps: no table for ratio %r" % (ratio,))
+    return np.ctypeslib.as_array(p, (int(n.value),)).astype(np.int32)
+
+
+def decim_out_frames(frame0, own, ratio):
+    """dvda_pcm_hip_decim_out_frames: output frames of the absolute frames [frame0, frame0 + own); needs no GPU"""
+    return int(lib().dvda_pcm_hip_decim_out_frames(frame0, own, ratio))
+
+
+def decim_value(window, ratio, bits):
+    """dvda_pcm_hip_decim_value: one output value from its window of 2 H + 1 input values -> (value, 1 when the clamp
+    changed it else 0); host arithmetic, needs no GPU.  HipError for an invalid ratio or depth or a window of another
+    length"""
+    w = np.ascontiguousarray(window, np.int32)
+    if ratio not in (2, 4) or w.shape != (96 * ratio - 1,):
+        raise HipError("dvda_pcm_hip_decim_value: a window of %s values for ratio %r" % (w.shape, ratio))
+    cl = ctypes.c_int(0)
+    y = lib().dvda_pcm_hip_decim_value(w.ctypes.data, ratio, bits, ctypes.byref(cl))
+    if cl.value < 0:
+        raise HipError("dvda_pcm_hip_decim_value: invalid parameters (ratio %r, bits %r)" % (ratio, bits))
+    return int(y), int(cl.value)
+
+
+def _piece_records(pieces):
+    """a list of (frame0, before, after) -> the dvda_pcm_decim_piece records (one at least)"""
+    rec = np.zeros(max(len(pieces), 1), np.dtype([("frame0", "<u8"), ("before", "<u4"), ("after", "<u4")]))
+    for i, (frame0, before, after) in enumerate(pieces):
+        rec[i] = (frame0, before, after)
+    return rec
+
+
+def decim_desc_out(desc_in, ratio, pieces=None):
+    """the output descriptors pcm_decimate makes when none are passed: per stream its output frames (0 for a stream the
+    pass does not take), the input's channels, the regions end to end with the stride = the frames, which serves either
+    int32 layout -> (desc_out, words)"""
+    out, pos = [], 0
+    for i, (_, _, frames, ch) in enumerate(desc_in):
+        frame0, before, after = pieces[i] if pieces is not None else (0, 0, 0)
+        ok = 1 <= int(ch) <= 8 and int(frames) <= 1 << 40 and before + after <= int(frames)
+        f = decim_out_frames(frame0, int(frames) - before - after, ratio) if ok else 0
+        out.append((pos, f, f, int(ch)))
+        pos += f * int(ch) if ok else 0
+    return out, max(pos, 1)
+
+
+def pcm_decimate(d_in, layout_in, desc_in, ratio, bits, pieces=None, out=None, layout_out=None, desc_out=None,
+                 max_total_out_frames=None, work=None):
+    """dvda_pcm_hip_decimate over torch tensors: d_in an int32 tensor on the device holding the streams in layout_in
+    (PCM_PLANAR or PCM_INTERLEAVED), desc_in a list of (off, stride, frames, channels); every stream decimated by `ratio`
+    (2 or 4), the values clamped to `bits`.  pieces: per stream (frame0, before, after) as dvda_pcm_decim_piece states
+    them (None: whole tracks).  out / layout_out / desc_out: where the result goes -- default: the input's layout, the
+    regions end to end in a fresh zeroed tensor (decim_desc_out).  -> (d_out, desc_out, d_report): the output tensor, its
+    descriptors and a uint8 device tensor [n, sizeof(DecimReport)] (decim_list brings it to the host).  Only the kernels
+    are asynchronous, on torch's current stream: like pcm_levels, this helper builds the descriptors on the host, copies
+    them to the device and allocates them, the results and -- when none is passed -- the workspace."""
+    layout_out = layout_in if layout_out is None else layout_out
+    if pieces is not None and len(pieces) != len(desc_in):
+        raise HipError("pcm_decimate: %d pieces for %d streams" % (len(pieces), len(desc_in)))
+    words = None
+    if desc_out is None:
+        desc_out, words = decim_desc_out(desc_in, ratio, pieces)
+    if len(desc_out) != len(desc_in):
+        raise HipError("pcm_decimate: %d output descriptors for %d streams" % (len(desc_out), len(desc_in)))
+    if max_total_out_frames is None:
+        max_total_out_frames = int(sum(int(f) for _, _, f, c in desc_out if 1 <= int(c) <= 8 and int(f) <= 1 << 40))
+    torch, n, d_desc_in, work, st = _report_args(d_in, desc_in, "the decimation", max_total_out_frames, work,
+                                                 lib().dvda_pcm_hip_decimate_workspace_words)
+    dev = d_in.device
+    if out is None:
+        if words is None:
+            words = max([int(o) + int(r) * int(c) for o, r, f, c in desc_out] + [1])
+        out = torch.zeros(words, dtype=torch.int32, device=dev)
+    d_desc_out = torch.from_numpy(_desc_records(desc_out).view(np.uint8).reshape(-1)).to(dev)
+    d_piece = None if pieces is None else torch.from_numpy(_piece_records(pieces).view(np.uint8).reshape(-1)).to(dev)
+    d_rep = torch.zeros((max(n, 1), ctypes.sizeof(DecimReport)), dtype=torch.uint8, device=dev)
+    _check(lib().dvda_pcm_hip_decimate(d_in.data_ptr(), layout_in, d_desc_in.data_ptr(), out.data_ptr(), layout_out,
+                                       d_desc_out.data_ptr(), None if d_piece is None else d_piece.data_ptr(), n, ratio,
+                                       bits, max_total_out_frames, d_rep.data_ptr(), work.data_ptr(), work.numel(), st),
+           "dvda_pcm_hip_decimate")
+    return out, desc_out, d_rep[:n]
+
+
+def pcm_decimate_workspace_words(n, max_total_out_frames):
+    """dvda_pcm_hip_decimate_workspace_words: the uint32 words of workspace pcm_decimate needs for n streams whose
+    OUTPUT frames sum to at most max_total_out_frames (what `work` must hold when the caller passes one); needs no GPU"""
+    return int(lib().dvda_pcm_hip_decimate_workspace_words(n, max_total_out_frames))
+
+
+def decim_list(d_report):
+    """pcm_decimate's report tensor -> list of DecimReport.as_dict() on the host (waits)"""
+    raw = np.ascontiguousarray(d_report.cpu().numpy())
+    return [DecimReport.from_buffer_copy(raw[i].tobytes()).as_dict() for i in range(raw.shape[0])]
 
 
 def crc_list(d_crc, d_nbytes):
@@ -1305,6 +1454,67 @@ def decode_streams_requantized(streams, bits_out, mode=RQ_TPDF, seed=0, device=0
             else:
                 raise HipError("decode_streams_requantized: stream %d has %d bits: no WAV payload" % (i, depth[i]))
     return pcm, list(infos), reports
+
+
+RATE_OF_CODE = {0: 48000, 1: 96000, 2: 192000, 8: 44100, 9: 88200, 10: 176400}    # the major sync's group-0 rate code
+
+
+def decode_streams_decimated(streams, ratio, device=0, layout=PCM_PLANAR, ctx=None, presentation=PRESENT_FULL):
+    """Decodes complete MLP byte streams and decimates them by `ratio` (2 or 4) on the device (pcm_decimate), each
+    clamped at its own depth; streams of different depths run as one call per depth.  -> (pcm, rates, infos, reports):
+    pcm[i] int32 [channels, ceil(frames / ratio)] as decode_streams gives it, rates[i] the new rate in Hz, reports[i] =
+    DecimReport.as_dict().  ValueError when a stream's rate / ratio is not 44 100, 48 000, 88 200 or 96 000 Hz: judged
+    from the index's stream records, before anything is decoded.  A stream
+    whose region the decode could not fill (DVDA_ST_OVERFLOW) comes out empty with a report of zeros."""
+    if layout not in (PCM_PLANAR, PCM_INTERLEAVED) or ratio not in (2, 4):
+        raise HipError("decode_streams_decimated: EINVAL (an int32 layout, a ratio of 2 or 4)")
+    batch = Batch(streams, device)
+    ctx, own = _context_for(ctx, batch, None, 0, layout)
+    made = [ctx]
+    rates = []
+
+    def larger(found):
+        made[0].close()
+        made[0] = Context(device, batch.n, found + 64, 0, layout)
+        if presentation != PRESENT_FULL:
+            made[0].set_presentation(presentation)
+        return made[0]
+
+    def decode(c, *args):
+        # the rates are the index's: a batch that cannot be divided costs no decode
+        del rates[:]
+        for i, inf in enumerate(c.stream_info(stream=args[-1])):
+            rate = RATE_OF_CODE.get(int(inf.group0_rate), 0)
+            if rate % ratio or rate // ratio not in DECIM_RATES:
+                raise ValueError("decode_streams_decimated: stream %d runs at %d Hz: no %d Hz output" % (i, rate, rate // ratio))
+            rates.append(rate // ratio)
+        return Context.decode(c, *args)
+
+    try:
+        if presentation != PRESENT_FULL or not own:
+            ctx.set_presentation(presentation)
+        regions, infos, _ = decode_batch(ctx, batch, layout, attempts=2, capacity=larger if own else "raise", decode=decode,
+                                         to_host=False)
+    finally:
+        if own:
+            made[0].close()
+    n = len(infos)
+    frames = [0 if inf.status & ST["OVERFLOW"] else min(int(inf.pcm_frames), r) for inf, r in zip(infos, regions.rows)]
+    desc = [(o, r, f, c) for o, r, f, c in zip(regions.out_off, regions.rows, frames, regions.channels)]
+    depth = [BITS_OF_CODE.get(int(inf.group0_bps), 0) for inf in infos]
+    desc_out, words = decim_desc_out(desc, ratio)
+    import torch
+    d_out = torch.zeros(words, dtype=torch.int32, device=regions.dev)
+    reports = [None] * n
+    for bits in sorted(set(depth)):
+        idx = [i for i in range(n) if depth[i] == bits]
+        _, _, d_rep = pcm_decimate(regions.d_pcm, layout, [desc[i] for i in idx], ratio, bits, out=d_out, layout_out=layout,
+                                   desc_out=[desc_out[i] for i in idx])
+        for i, rep in zip(idx, decim_list(d_rep)):
+            reports[i] = rep
+    pcm = cut_regions(d_out.cpu().numpy(), [d[0] for d in desc_out], [d[1] for d in desc_out], regions.channels,
+                      [d[2] for d in desc_out], layout)
+    return pcm, rates, list(infos), reports
 
 
 class MLPDecoder:

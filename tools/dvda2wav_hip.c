@@ -60,6 +60,8 @@ static double now_s(void)
 /* -b / --dither / --seed: the word length every track is delivered at (0: its own), set once before any worker starts */
 static unsigned g_rq_bits, g_rq_mode = DVDA_RQ_TPDF;
 static unsigned long long g_rq_seed;
+/* -r: the rate every track is delivered at where its own is 1, 2 or 4 times that (0: its own) */
+static unsigned g_rate;
 
 static int extract(DVDA_Title *title, unsigned track_num, const char *dir, int device, int fused_wav, int stereo,
                    int crc, int conceal, unsigned titleset_num)
@@ -81,7 +83,34 @@ static int extract(DVDA_Title *title, unsigned track_num, const char *dir, int d
     dvda_hip_set_conceal(conceal);
     /* -b: the reader reduces the track to that word length on the device; its depth is then the file's */
     dvda_hip_set_requantize(g_rq_bits, g_rq_mode, g_rq_seed);
+    /* -r: the reader decimates the track by its rate / RATE on the device.  The rate is the stream's own and is known once
+       a reader is open: the first one is opened by 2 (96 -> 48, 88.2 -> 44.1: the common case; a track that cannot be
+       divided by 2 comes as it is), and where that did not give RATE the track is opened again, by 4 or as it is.  A
+       track long enough to be read in windows is refused by 2: it is opened as it is to learn its rate, and fails only
+       where it really needs a ratio */
+    dvda_hip_set_decimate(g_rate ? 2 : 0);
     DVDA_Track_Reader *r = dvda_hip_open_track_reader_with(track, device, fused_wav, stereo);
+    if (g_rate && (!r || dvda_sample_rate(r) != g_rate)) {
+        const int refused = !r;
+        if (refused) {
+            dvda_hip_set_decimate(0);
+            r = dvda_hip_open_track_reader_with(track, device, fused_wav, stereo);
+        }
+        const unsigned src = dvda_hip_reader_source_rate(r);
+        const unsigned ratio = src == 2 * g_rate ? 2 : src == 4 * g_rate ? 4 : 0;
+        if (r && src != g_rate && !ratio)
+            fprintf(stderr, "*** Warning: track %u runs at %u Hz, which is not 1, 2 or 4 times %u: written as it is\n", track_num,
+                    src, g_rate);
+        if (r && (ratio || dvda_hip_reader_decimated(r, NULL) == 1)) {
+            dvda_close_track_reader(r);
+            dvda_hip_set_decimate(ratio);
+            r = refused && ratio == 2 ? NULL : dvda_hip_open_track_reader_with(track, device, fused_wav, stereo);
+            if (!r && refused)
+                fprintf(stderr, "*** Error: track %u runs at %u Hz and is read in windows: -r cannot divide it by %u\n", track_num,
+                        src, ratio);
+        }
+    }
+    dvda_hip_set_decimate(0);
     if (!r) {
         fprintf(stderr, "*** Error: unable to open track %u for reading\n", track_num);
         dvda_close_track(track);
@@ -154,6 +183,20 @@ static int extract(DVDA_Title *title, unsigned track_num, const char *dir, int d
         } else {
             printf("REQUANT %u %u %u %u %u none\n", titleset_num, title_number, track_number, dvda_hip_reader_source_bits(r),
                    bits);
+        }
+    }
+    if (ok && g_rate) {
+        /* what the decimation did to the track just written: the rate on the disc, the file's rate, values the clamp changed */
+        struct dvda_pcm_decim_report dc;
+        if (dvda_hip_reader_decimated(r, &dc) == 1) {
+            unsigned long long clipped = 0;
+            for (int c = 0; c < 8; c++)
+                clipped += dc.clipped[c];
+            printf("DECIMATE %u %u %u %u %u %llu\n", titleset_num, title_number, track_number, dvda_hip_reader_source_rate(r),
+                   rate, clipped);
+        } else {
+            printf("DECIMATE %u %u %u %u %u none\n", titleset_num, title_number, track_number, dvda_hip_reader_source_rate(r),
+                   rate);
         }
     }
     if (ok && conceal) {
@@ -254,6 +297,14 @@ static void usage(const char *prog)
            "                            <values clamped> (\"none\" for a track written as it is).  Not together with -K\n"
            "      --dither=MODE         none | round | tpdf (default): truncate, round, or triangular dither of +-1 LSB\n"
            "      --seed=N              seed of the dither's noise (default 0): the same seed gives the same file\n"
+           "  -r RATE, --rate=RATE      deliver every track at RATE Hz (44100, 48000, 88200 or 96000) where its own rate is\n"
+           "                            2 or 4 times that: filtered and decimated on the GPU, exact, clamped at the track's\n"
+           "                            depth; any other track is written as it is, with a warning unless it runs at RATE.\n"
+           "                            One line per track on stdout: DECIMATE <titleset> <title> <track> <source rate>\n"
+           "                            <file's rate> <values clamped> (\"none\" for a track written as it is).  Composes\n"
+           "                            with -b / --dither (the reduction follows the decimation).  Whole-track readers\n"
+           "                            only: a track long enough to be read in windows fails where it would have to be\n"
+           "                            decimated, and is written as it is where not.  Not together with -K\n"
            "  -g N, --gpu=N             HIP device (default 0)\n"
            "  -D LIST, --devices=LIST   comma-separated HIP devices: one worker thread per entry takes tracks in turn\n"
            "                            (default: up to four workers on the device of -g)\n"
@@ -269,14 +320,15 @@ int main(int argc, char *argv[])
                                        {"devices", required_argument, 0, 'D'},  {"stereo", no_argument, 0, '2'},
                                        {"crc", no_argument, 0, 'C'},            {"conceal", no_argument, 0, 'K'},
                                        {"bits", required_argument, 0, 'b'},     {"dither", required_argument, 0, 1001},
-                                       {"seed", required_argument, 0, 1002},    {0, 0, 0, 0}};
+                                       {"seed", required_argument, 0, 1002},    {"rate", required_argument, 0, 'r'},
+                                       {0, 0, 0, 0}};
     const char *audio_ts = NULL, *dir = ".", *cdrom = NULL;
     unsigned titleset_num = 1, title_num = 0, track_num = 0;
     int devices[64], n_devices = 0, one_device = 0, stereo = 0, crc = 0, conceal = 0;
     int c;
     if (getenv("DVDA_TOOL_TIMING"))
         fprintf(stderr, "timing: main at %.1f ms\n", now_s() * 1e3);
-    while ((c = getopt_long(argc, argv, "A:c:S:T:t:d:g:D:b:h2CK", longopts, NULL)) != -1) {
+    while ((c = getopt_long(argc, argv, "A:c:S:T:t:d:g:D:b:r:h2CK", longopts, NULL)) != -1) {
         switch (c) {
         case 'A': audio_ts = optarg; break;
         case 'c': cdrom = optarg; break;
@@ -305,6 +357,7 @@ int main(int argc, char *argv[])
                 return 1;
             }
             break;
+        case 'r': g_rate = (unsigned)strtoul(optarg, NULL, 10); break;
         case 1002: g_rq_seed = strtoull(optarg, NULL, 0); break;
         case 'h': usage(argv[0]); return 0;
         default: return 1;
@@ -316,6 +369,10 @@ int main(int argc, char *argv[])
     }
     if (g_rq_bits && ((g_rq_bits != 16 && g_rq_bits != 24) || conceal)) {
         fprintf(stderr, "*** Error: -b takes 16 or 24 (the depths a WAV payload has here), and not together with -K\n");
+        return 1;
+    }
+    if (g_rate && ((g_rate != 44100 && g_rate != 48000 && g_rate != 88200 && g_rate != 96000) || conceal)) {
+        fprintf(stderr, "*** Error: -r takes 44100, 48000, 88200 or 96000, and not together with -K\n");
         return 1;
     }
     /* (DVDA_NO_FUSED_WAV=1 in the environment brings the int32 decode + packing pass back, for comparison) */
