@@ -19,8 +19,11 @@
 //                                  two passes, k_chain_filter in place on the planes and k_chain_rematrix behind it.)
 //
 // k_chain_plan + a 3-channel scan + k_chain_lists lay out the workspaces and list the deferred segments and
-// the chain heads.  Streams with non-standard timing, IIR taps or restart headers inside a frame go to the
-// sequential pass instead (ST_TIMING / ST_SEQ, mlp_decode.h).
+// the chain heads.  Streams with non-standard timing or restart headers inside a frame go to the sequential pass
+// instead (ST_TIMING / ST_SEQ, mlp_decode.h).  IIR taps do not: a segment with a block that runs them is decoded here,
+// frame by frame (seg_meta bit 9: slow_step of k_chain_fused, the IIR branch of k_chain_filter) -- observed on the
+// IIR | CHAINED row of tests/chain_cases.py, whose segments come out CHAINED | GENERAL in both forms; only a segment
+// whose IIR words do not fit its block records is handed on (ST_SEQ, mlp_decode.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -64,8 +67,8 @@ __device__ __forceinline__ uint32_t chain_n_seg(const ChainArgs &a)
     return n > a.max_seg ? a.max_seg : n;
 }
 
-// is segment i one the chain passes decode?  (flagged by the fast pass, free of errors, standard timing)
-__device__ __forceinline__ bool chain_deferred(const ChainArgs &a, uint32_t i)
+// is segment i one the fast pass left to the passes behind it?  (flagged, free of errors, standard timing)
+__device__ __forceinline__ bool chain_flagged(const ChainArgs &a, uint32_t i)
 {
     const SegRec r = a.seg[i];
     if ((r.flags & (SEG_DEAD | ST_FATAL_INDEX)) || r.nframes == 0)
@@ -74,6 +77,25 @@ __device__ __forceinline__ bool chain_deferred(const ChainArgs &a, uint32_t i)
     if (!(ss & ST_CHAIN) || (ss & ~ST_INFO))
         return false;
     return (a.streams[r.stream].status & (ST_TIMING | ST_SEQ)) == 0;
+}
+
+// ... whose first PCM frame lies behind the end of the caller's region: nothing of it can be stored, and the segment in
+// front of it may have no history to hand on -- a lane of the fast pass stops where its region ends (mlp_decode.h), so a
+// chain that started behind it found "nothing to continue from" and reported DVDA_ST_ENVELOPE on a stream that was
+// merely too long for its buffer.  Such a segment is not decoded: k_chain_plan counts its frames (rows = the size
+// needed) and reports DVDA_ST_OVERFLOW.
+__device__ __forceinline__ bool chain_past_capacity(const ChainArgs &a, uint32_t i)
+{
+    const SegRec r = a.seg[i];
+    const StreamRec sr = a.streams[r.stream];
+    const uint64_t row0 = (uint64_t)(a.seg_fbase[i] - a.seg_fbase[sr.first_seg]) * rows_per_au((sr.sync >> 8) & 0xF);
+    return row0 >= a.out_stride[r.stream];
+}
+
+// is segment i one the chain passes decode?
+__device__ __forceinline__ bool chain_deferred(const ChainArgs &a, uint32_t i)
+{
+    return chain_flagged(a, i) && !chain_past_capacity(a, i);
 }
 
 __device__ __forceinline__ uint32_t chain_prev_live(const ChainArgs &a, uint32_t i, uint32_t first)
@@ -109,6 +131,11 @@ __global__ __launch_bounds__(256) void k_chain_plan(ChainArgs a)
             head = p == i || !chain_deferred(a, p);
         }
         v.z = head ? 1u : 0u;
+    } else if (chain_flagged(a, i)) {
+        // wholly behind the end of the caller's region (chain_past_capacity): taken care of here
+        const SegRec r = a.seg[i];
+        a.seg_rows[i] = (r.nframes - r.ndrop) * rows_per_au((a.streams[r.stream].sync >> 8) & 0xF);
+        atomicOr(&a.seg_status[i], ST_OVERFLOW | ST_GENERAL);
     }
     a.plan[i] = v;
 }

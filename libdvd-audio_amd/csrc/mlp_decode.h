@@ -3098,7 +3098,10 @@ __global__ __launch_bounds__(DEC_THREADS, 2) void k_decode(DecodeArgs a)
             const uint64_t edge = out_stride < row_limit ? out_stride : row_limit;
             if (edge > row0)
                 room0 = edge - row0 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)(edge - row0);
-            a.seg_rows[segi] = room0 - room;
+            // (a lane that stopped where the caller's region ends reports the size needed -- the segment's standard
+            //  length, it is below row_limit --, as the cooperative kernel and the passes behind this one do)
+            const uint32_t std_rows = (sr.nframes - sr.ndrop) * rpa;
+            a.seg_rows[segi] = ((status & ST_OVERFLOW) && std_rows > room0 - room) ? std_rows : room0 - room;
         }
     }
 }
