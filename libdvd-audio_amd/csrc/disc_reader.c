@@ -269,6 +269,24 @@ static int dev_alloc(void **p, size_t bytes)
     return hipMalloc(p, bytes ? bytes : 16) == hipSuccess;
 }
 
+/* One block on the device for the calls of a pass or of several: a host struct -- the head: descriptors, parameters,
+ * results -- and `more` bytes behind it, the passes' workspace first.  Open allocates the block at *d and copies the head
+ * up; DEV_AT is where a member of the head lies on the device; close copies the head back down where the calls between
+ * the two went well (`ok`), and frees the block.  1 = ok. */
+#define DEV_AT(d, head, member) ((void *)((d) + offsetof(__typeof__(head), member)))
+
+static int dev_block_open(uint8_t **d, const void *head, size_t head_bytes, size_t more)
+{
+    return dev_alloc((void **)d, head_bytes + more) && hipMemcpy(*d, head, head_bytes, hipMemcpyHostToDevice) == hipSuccess;
+}
+
+static int dev_block_close(uint8_t *d, void *head, size_t head_bytes, int ok)
+{
+    ok = ok && hipMemcpy(head, d, head_bytes, hipMemcpyDeviceToHost) == hipSuccess;
+    (void)hipFree(d);
+    return ok;
+}
+
 /* offset of the first major-sync pattern (bytes +4..+7 = F8 72 6F BB) at or after `from` whose
  * 8 bytes lie inside [0, size), or -1 (find_major_sync, src/dvd-audio.c:1250-1285) */
 static int64_t find_sync(const uint8_t *b, uint64_t from, uint64_t size)
@@ -310,9 +328,9 @@ static int64_t find_sync_dev(const uint8_t *d_bytes, uint64_t from, uint64_t siz
  * this reader has is decided here and nowhere else: a digest at 16 and 24 bits, a level report at 16, 20 and 24 bits of
  * int32 PCM, an energy report of int32 PCM at a block length the report takes -- a reader that hands out the WAV payload
  * (wav_payload) has neither of the two.  `before`: the track's frames in front of the piece: the energy report's grid is
- * the track's, so the piece's first block has what is left of the block the track is in.  One block on the device holds
- * the descriptor, the results and the workspace, the largest one where several reports run: they run one behind the
- * other; the energy report's lead, counts and blocks lie behind the workspace.
+ * the track's, so the piece's first block has what is left of the block the track is in.  One block on the device
+ * (dev_block) holds the head -- the descriptor, the results, the energy report's lead and counts -- and the workspace, the
+ * largest one where several reports run: they run one behind the other; the energy report's blocks lie behind it.
  * A reader that reduces the word length (have->rq > 0, bits at least its bits_out) does so HERE, first: the piece's int32
  * PCM is requantized in place from `bits` to bits_out with frame0 = `before`, so a track read whole and read in windows
  * is the same bytes, and every report behind it -- and every copy or pack the caller makes after this call -- sees the
@@ -321,12 +339,8 @@ static int64_t find_sync_dev(const uint8_t *d_bytes, uint64_t from, uint64_t siz
 static int piece_reports(struct pcm_reports *have, struct pcm_reports *out, int wav_payload, const int32_t *d_pcm,
                          uint32_t layout, unsigned bits, uint64_t stride, uint64_t frames, unsigned ch, uint64_t before)
 {
-    struct {
-        uint64_t bytes;
-        uint32_t crc, pad;
-        dvda_pcm_levels levels;
-    } res;
     const dvda_pcm_crc_desc desc = {0, stride, frames, ch, 0};
+    uint8_t *d = NULL;
     if (have->rq > 0 && bits < have->rq_par.bits_out)
         have->rq = 0;
     out->rq = have->rq;
@@ -337,25 +351,19 @@ static int piece_reports(struct pcm_reports *have, struct pcm_reports *out, int 
             dvda_pcm_crc_desc desc;
             uint64_t frame0;
             dvda_pcm_requant_report rep;
-        } blk = {desc, before, {0, {0}}};
+        } rq = {desc, before, {0, {0}}};
         dvda_pcm_requant par = have->rq_par;
         const size_t rq_words = dvda_pcm_hip_requantize_workspace_words(1, frames);
-        uint8_t *dq = NULL;
         par.bits_in = bits;
         if (frames) {
-            if (!dev_alloc((void **)&dq, sizeof(blk) + rq_words * sizeof(uint32_t)))
+            const int done = dev_block_open(&d, &rq, sizeof(rq), rq_words * sizeof(uint32_t)) &&
+                             dvda_pcm_hip_requantize(d_pcm, layout, DEV_AT(d, rq, desc), (int32_t *)d_pcm, layout,
+                                                     DEV_AT(d, rq, desc), DEV_AT(d, rq, frame0), 1, &par, frames,
+                                                     DEV_AT(d, rq, rep), (uint32_t *)(d + sizeof(rq)), rq_words,
+                                                     NULL) == DVDA_HIP_OK;
+            if (!dev_block_close(d, &rq, sizeof(rq), done))
                 return 0;
-            const int done =
-                hipMemcpy(dq, &blk, sizeof(blk), hipMemcpyHostToDevice) == hipSuccess &&
-                dvda_pcm_hip_requantize(d_pcm, layout, (const dvda_pcm_crc_desc *)dq, (int32_t *)d_pcm, layout,
-                                        (const dvda_pcm_crc_desc *)dq, (const uint64_t *)(dq + offsetof(__typeof__(blk), frame0)),
-                                        1, &par, frames, (dvda_pcm_requant_report *)(dq + offsetof(__typeof__(blk), rep)),
-                                        (uint32_t *)(dq + sizeof(blk)), rq_words, NULL) == DVDA_HIP_OK &&
-                hipMemcpy(&blk, dq, sizeof(blk), hipMemcpyDeviceToHost) == hipSuccess;
-            (void)hipFree(dq);
-            if (!done)
-                return 0;
-            out->rq_rep = blk.rep;
+            out->rq_rep = rq.rep;
         }
         bits = have->rq_par.bits_out;
     }
@@ -373,14 +381,18 @@ static int piece_reports(struct pcm_reports *have, struct pcm_reports *out, int 
     const size_t w_ng = ng ? dvda_pcm_hip_energy_workspace_words(1, frames, nrg_b) : 0;
     const size_t w_two = w_dg > w_lv ? w_dg : w_lv;
     const size_t words = w_two > w_ng ? w_two : w_ng;
-    /* the energy report: { lead, -, off, cap, nblocks } and the piece's blocks */
+    /* the energy report: its lead (the kernels read the low word), off, cap, nblocks; its blocks lie behind the workspace */
     const uint32_t lead = ng ? nrg_b - (uint32_t)(before % nrg_b) : 0;
     const uint64_t ng_n = !ng || !frames ? 0 : 1 + ((frames > lead ? frames - lead : 0) + nrg_b - 1) / nrg_b;
-    const uint64_t ng_head[4] = {lead, 0, ng_n, 0};
-    const size_t ng_at = (sizeof(desc) + sizeof(res) + words * sizeof(uint32_t) + 7) & ~(size_t)7;
-    const size_t ng_bytes = ng ? sizeof(ng_head) + (size_t)ng_n * sizeof(dvda_pcm_energy_block) : 0;
+    struct {
+        dvda_pcm_crc_desc desc;
+        uint64_t bytes;
+        uint32_t crc, pad;
+        dvda_pcm_levels levels;
+        uint64_t ng_lead, ng_off, ng_cap, ng_got;
+    } res = {desc, 0, 0, 0, {0}, lead, 0, ng_n, 0};
+    const size_t ng_at = (words * sizeof(uint32_t) + 7) & ~(size_t)7;
     dvda_pcm_energy_block *ng_blocks = NULL;
-    uint8_t *d = NULL;
     out->dg = have->dg;
     out->lv = have->lv;
     out->ng = have->ng;
@@ -395,42 +407,30 @@ static int piece_reports(struct pcm_reports *have, struct pcm_reports *out, int 
         return 1;                                /* (the reports of no frames are zeros, and no blocks) */
     if (ng && (ng_blocks = malloc((size_t)ng_n * sizeof(*ng_blocks))) == NULL)
         return 0;
-    if (!dev_alloc((void **)&d, ng ? ng_at + ng_bytes : sizeof(desc) + sizeof(res) + words * sizeof(uint32_t))) {
-        free(ng_blocks);
-        return 0;
-    }
-    uint8_t *d_res = d + sizeof(desc);
-    uint32_t *d_work = (uint32_t *)(d_res + sizeof(res));
-    uint64_t *d_ng = (uint64_t *)(d + ng_at);    /* (only where the energy report runs) */
-    uint64_t ng_got = 0;
-    const int ok =
-        hipMemcpy(d, &desc, sizeof(desc), hipMemcpyHostToDevice) == hipSuccess &&
-        (!dg || dvda_pcm_hip_crc32(d_pcm, layout, bits, (const dvda_pcm_crc_desc *)d, 1, payload,
-                                   (uint32_t *)(d_res + offsetof(__typeof__(res), crc)), (uint64_t *)d_res, d_work, words,
-                                   NULL) == DVDA_HIP_OK) &&
-        (!lv || dvda_pcm_hip_levels(d_pcm, layout, bits, (const dvda_pcm_crc_desc *)d, 1, frames,
-                                    (dvda_pcm_levels *)(d_res + offsetof(__typeof__(res), levels)), d_work, words,
-                                    NULL) == DVDA_HIP_OK) &&
-        hipMemcpy(&res, d_res, sizeof(res), hipMemcpyDeviceToHost) == hipSuccess &&
-        (!ng || (hipMemcpy(d_ng, ng_head, sizeof(ng_head), hipMemcpyHostToDevice) == hipSuccess &&
-                 dvda_pcm_hip_energy(d_pcm, layout, (const dvda_pcm_crc_desc *)d, 1, nrg_b, (const uint32_t *)d_ng, frames,
-                                     (dvda_pcm_energy_block *)(d_ng + 4), d_ng + 1, d_ng + 2, d_ng + 3, d_work, words,
-                                     NULL) == DVDA_HIP_OK &&
-                 hipMemcpy(&ng_got, d_ng + 3, sizeof(ng_got), hipMemcpyDeviceToHost) == hipSuccess && ng_got == ng_n &&
-                 hipMemcpy(ng_blocks, d_ng + 4, (size_t)ng_n * sizeof(*ng_blocks), hipMemcpyDeviceToHost) == hipSuccess));
-    (void)hipFree(d);
+    int ok = dev_block_open(&d, &res, sizeof(res), ng ? ng_at + (size_t)ng_n * sizeof(*ng_blocks) : words * sizeof(uint32_t));
+    uint32_t *d_work = (uint32_t *)(d + sizeof(res));
+    dvda_pcm_energy_block *d_blocks = (dvda_pcm_energy_block *)((uint8_t *)d_work + ng_at);     /* (only where it runs) */
+    ok = ok &&
+         (!dg || dvda_pcm_hip_crc32(d_pcm, layout, bits, DEV_AT(d, res, desc), 1, payload, DEV_AT(d, res, crc),
+                                    DEV_AT(d, res, bytes), d_work, words, NULL) == DVDA_HIP_OK) &&
+         (!lv || dvda_pcm_hip_levels(d_pcm, layout, bits, DEV_AT(d, res, desc), 1, frames, DEV_AT(d, res, levels), d_work,
+                                     words, NULL) == DVDA_HIP_OK) &&
+         (!ng || (dvda_pcm_hip_energy(d_pcm, layout, DEV_AT(d, res, desc), 1, nrg_b, DEV_AT(d, res, ng_lead), frames, d_blocks,
+                                      DEV_AT(d, res, ng_off), DEV_AT(d, res, ng_cap), DEV_AT(d, res, ng_got), d_work, words,
+                                      NULL) == DVDA_HIP_OK &&
+                  hipMemcpy(ng_blocks, d_blocks, (size_t)ng_n * sizeof(*ng_blocks), hipMemcpyDeviceToHost) == hipSuccess));
+    ok = dev_block_close(d, &res, sizeof(res), ok) && (!ng || res.ng_got == ng_n);
     if (ok && ng) {
         out->ng_blocks = ng_blocks;
         out->ng_n = out->ng_cap = ng_n;
     } else {
         free(ng_blocks);
     }
-    if (ok && dg) {
+    if (ok) {                                    /* (zeros where a report did not run) */
         out->crc = res.crc;
         out->bytes = res.bytes;
-    }
-    if (ok && lv)
         out->levels = res.levels;
+    }
     return ok;
 }
 
@@ -486,14 +486,10 @@ static int track_decimate(int32_t **d_pcm, uint32_t layout, unsigned bits, uint6
     uint8_t *d = NULL;
     int ok = dev_alloc((void **)&d_out, (size_t)out_stride * ch * sizeof(int32_t));
     if (ok && out_frames) {
-        ok = dev_alloc((void **)&d, sizeof(blk) + words * sizeof(uint32_t)) &&
-             hipMemcpy(d, &blk, sizeof(blk), hipMemcpyHostToDevice) == hipSuccess &&
-             dvda_pcm_hip_decimate(*d_pcm, layout, (const dvda_pcm_crc_desc *)(d + offsetof(__typeof__(blk), in)), d_out,
-                                   layout, (const dvda_pcm_crc_desc *)(d + offsetof(__typeof__(blk), out)), NULL, 1, ratio,
-                                   bits, out_frames, (dvda_pcm_decim_report *)(d + offsetof(__typeof__(blk), rep)),
-                                   (uint32_t *)(d + sizeof(blk)), words, NULL) == DVDA_HIP_OK &&
-             hipMemcpy(&blk, d, sizeof(blk), hipMemcpyDeviceToHost) == hipSuccess && blk.rep.frames_out == out_frames;
-        (void)hipFree(d);
+        ok = dev_block_open(&d, &blk, sizeof(blk), words * sizeof(uint32_t)) &&
+             dvda_pcm_hip_decimate(*d_pcm, layout, DEV_AT(d, blk, in), d_out, layout, DEV_AT(d, blk, out), NULL, 1, ratio, bits,
+                                   out_frames, DEV_AT(d, blk, rep), (uint32_t *)(d + sizeof(blk)), words, NULL) == DVDA_HIP_OK;
+        ok = dev_block_close(d, &blk, sizeof(blk), ok) && blk.rep.frames_out == out_frames;
     }
     if (!ok) {
         (void)hipFree(d_out);
@@ -504,6 +500,32 @@ static int track_decimate(int32_t **d_pcm, uint32_t layout, unsigned bits, uint6
     *stride = out_stride;
     *frames = out_frames;
     *rep = blk.rep;
+    return 1;
+}
+
+/* What a whole-track reader, MLP or raw PCM, does with its track once it lies decoded on the device -- r->frames frames of
+ * r->channels channels at the depth and rate of r's codes in `layout` at *d_pcm, capacity `stride` -- before any copy to
+ * the host: the decimation where it applies (from there on the reader IS the shorter track at the lower rate), then the
+ * reports the options want of the track as that left it, the word-length reduction among them: the reader hands out
+ * bits_out bits from there on.  1 = ok. */
+static int track_passes(DVDA_Track_Reader *r, const struct reader_opts *o, int32_t **d_pcm, uint32_t layout, int wav_payload,
+                        uint64_t stride)
+{
+    const unsigned bits = bits_of(r->bps_code[0]);
+    r->stride = stride;
+    if (dc_applies(o, r->rate_code[0])) {
+        if (!track_decimate(d_pcm, layout, bits, &r->stride, &r->frames, r->channels, o->dc_ratio, &r->dc_rep))
+            return 0;
+        r->src_rate = rate_of(r->rate_code[0]);
+        r->rate_code[0] -= dc_shift(o);
+    }
+    rep_want(&r->rep, o);
+    if (!piece_reports(&r->rep, &r->rep, wav_payload, *d_pcm, layout, bits, r->stride, r->frames, r->channels, 0))
+        return 0;
+    if (r->rep.rq > 0) {
+        r->src_bits = bits;
+        r->bps_code[0] = code_of_bits(o->rq_bits);
+    }
     return 1;
 }
 
@@ -883,25 +905,13 @@ static DVDA_Track_Reader *open_mlp(struct aob_set *aobs, const DVDA_Track *k, co
     r->frames = info.pcm_frames;
     if (!mlp_info_to_reader(r, &info, o->present))
         goto fail;
-    if (dc_applies(o, info.group0_rate)) {
-        /* from here on the reader IS the shorter track at the lower rate (wav_bits == 0: decode_stream saw the option) */
-        if (wav_bits || !track_decimate(&b.d_pcm, DVDA_PCM_INTERLEAVED, bits_of(info.group0_bps), &stride, &r->frames,
-                                        info.channels, o->dc_ratio, &r->dc_rep))
-            goto fail;
-        b.cap_pcm = 0;
-        r->src_rate = rate_of(info.group0_rate);
-        r->rate_code[0] = info.group0_rate - dc_shift(o);
-        t_line(&t_mark, "decimate");
-    }
-    r->stride = stride;
-    /* before any copy to the host: the track as the decode (and the decimation) left it on the device */
-    rep_want(&r->rep, o);
-    if (!piece_reports(&r->rep, &r->rep, wav_bits != 0, b.d_pcm, layout_of(wav_bits), bits_of(info.group0_bps), stride,
-                       r->frames, info.channels, 0))
+    /* (a track that is decimated has int32 PCM: decode_stream saw the option) */
+    if ((wav_bits && dc_applies(o, info.group0_rate)) ||
+        !track_passes(r, o, &b.d_pcm, layout_of(wav_bits), wav_bits != 0, stride))
         goto fail;
-    if (r->rep.rq > 0) {
-        r->src_bits = bits_of(r->bps_code[0]);
-        r->bps_code[0] = code_of_bits(o->rq_bits);  /* what the reader hands out from here on */
+    if (r->src_rate) {
+        b.cap_pcm = 0;          /* (b.d_pcm is the decimation's buffer) */
+        t_line(&t_mark, "decimate + reports");
     }
     if (wav_bits) {
         r->d_wav = (uint8_t *)b.d_pcm;
@@ -1838,20 +1848,8 @@ static DVDA_Track_Reader *open_pcm(struct aob_set *aobs, const DVDA_Track *k, co
     r->frames = deliver;
     r->d_pcm = b.d_pcm;
     b.d_pcm = NULL;
-    if (dc_applies(o, r->rate_code[0])) {
-        if (!track_decimate(&r->d_pcm, DVDA_PCM_PLANAR, bits, &stride, &r->frames, r->channels, o->dc_ratio, &r->dc_rep))
-            goto fail;
-        r->src_rate = rate;
-        r->rate_code[0] -= dc_shift(o);
-    }
-    r->stride = stride;
-    rep_want(&r->rep, o);
-    if (!piece_reports(&r->rep, &r->rep, 0, r->d_pcm, DVDA_PCM_PLANAR, bits, stride, r->frames, r->channels, 0))
+    if (!track_passes(r, o, &r->d_pcm, DVDA_PCM_PLANAR, 0, stride))
         goto fail;
-    if (r->rep.rq > 0) {
-        r->src_bits = bits;
-        r->bps_code[0] = code_of_bits(o->rq_bits);
-    }
     goto done;
 fail:
     reader_free(r);

@@ -123,12 +123,12 @@ struct dvda_mlp_hip_ctx {
     DevBuf<uint32_t> d_brec;
     DevBuf<uint32_t> d_frec;
     uint32_t iir_lanes;
-    // dvda_mlp_hip_pcm_crc32 / dvda_mlp_hip_pcm_levels / dvda_mlp_hip_pcm_compare (pcm_report_run.h): grown on first use,
-    // and the same three for every report.  What one report left in them is the next one's to overwrite: a report reads
+    // the six dvda_mlp_hip_pcm_* calls (pcm_report_run.h, report_of_decode): grown on first use, and the same three for
+    // every report.  What one report left in them is the next one's to overwrite: a report reads
     // no word of the workspace or the result block that the same call has not stored (the tests named
     // test_poisoned_workspace and test_deterministic_on_a_poisoned_workspace pin that).
-    DevBuf<dvda_pcm_crc_desc> d_rep_desc;   // [streams]
-    DevBuf<uint64_t> d_rep_out;         // the results, laid out by the report (CrcReport::in / LvlReport::in / CmpReport::in)
+    DevBuf<dvda_pcm_crc_desc> d_rep_desc;   // [streams], and behind them the descriptors a report stages of its own
+    DevBuf<uint64_t> d_rep_out;         // the results and what a report lays behind them (its stage() / bind())
     DevBuf<uint32_t> d_rep_work;
     DecodeSettings set;
     // call state

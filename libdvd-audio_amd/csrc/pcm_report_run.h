@@ -1,7 +1,8 @@
-// pcm_report_run.h -- host side of the reports of decoded PCM, the digest (pcm_digest.h), the level report
-// (pcm_levels.h), the compare (pcm_compare.h), the energy report (pcm_energy.h), the word-length reduction (pcm_requant.h) and the decimation (pcm_decim.h): what a report is to the driver, the one driver of the flat tile list (pcm_tiles.h), the one call that
-// runs a report behind a decode on the context's own buffers, and the host arithmetic that joins two pieces' results.
+// pcm_report_run.h -- host side of the six passes over decoded PCM (pcm_digest.h, pcm_levels.h, pcm_compare.h, pcm_energy.h,
+// pcm_requant.h, pcm_decim.h): what a report is to the driver, the one driver of the flat tile list (pcm_tiles.h), the one
+// call that runs a report behind a decode on the context's buffers, and the host arithmetic that joins two pieces' results.
 #pragma once
+#include <algorithm>
 #include <vector>
 
 #include "mlp_ctx.h"
@@ -12,8 +13,30 @@
 #include "pcm_levels.h"
 #include "pcm_requant.h"
 
+static inline bool int32_layout(uint32_t layout) { return layout == DVDA_PCM_PLANAR || layout == DVDA_PCM_INTERLEAVED; }
+
+// What a report behind a decode lays into the context's buffers (report_of_decode, below), as its stage() states it on
+// the host: the uint64 words it wants in d_rep_out -- its results first; none: nothing to run -- and what is uploaded
+// into the last of them.
+using Descs = std::vector<dvda_pcm_crc_desc>;
+struct ReportStage {
+    size_t out_words = 0;
+    std::vector<uint64_t> behind;
+
+    int want(size_t words)
+    {
+        out_words = words;
+        return DVDA_HIP_OK;
+    }
+};
+
 // ---- a report, as the driver sees it: the unit its tiles are cut in and the words a tile leaves in the workspace, the
-//      layouts and depths it takes, where its results go, and its three launches
+//      layouts and depths it takes, where its results go, and its three launches.  Behind a decode it also states
+//        units(d, bits)       what a descriptor adds to the bound on its list;
+//        stage(desc, n, &s)   on the host: `s`; descriptors of its own behind the n of `desc` (uploaded with them); a
+//                             verdict of its own as the return code;
+//        bind(...)            on the device: where its results, what it staged and the descriptors lie.
+//      What a report needs of the host for that travels in its last members ("(host)": the driver never reads them).
 struct CrcReport {
     static constexpr uint32_t TILE = crc::TILE, TILE_WORDS = 1, TILE_BLOCKS = crc::TILE_BLOCKS;    // unit: payload bytes
     uint32_t *d_crc;
@@ -25,10 +48,10 @@ struct CrcReport {
         return layout <= DVDA_PCM_WAV16 && (bits == 16 || bits == 24) && !(layout == DVDA_PCM_WAV24 && bits != 24) &&
                !(layout == DVDA_PCM_WAV16 && bits != 16);
     }
-    static uint64_t units(const dvda_pcm_crc_desc &d, unsigned bits) { return d.frames * d.channels * (bits / 8); }
+    uint64_t units(const dvda_pcm_crc_desc &d, unsigned bits) const { return d.frames * d.channels * (bits / 8); }
     // the results of n streams in one block of uint64 words: the byte counts, then the digests
-    static size_t out_words(uint32_t n) { return (size_t)n + ((size_t)n + 1) / 2; }
-    static CrcReport in(uint64_t *d_out, uint32_t n) { return CrcReport{(uint32_t *)(d_out + n), d_out}; }
+    int stage(Descs &, uint32_t n, ReportStage *s) const { return s->want(n + ((size_t)n + 1) / 2); }
+    void bind(uint64_t *d_out, uint64_t *, const dvda_pcm_crc_desc *, uint32_t n) { *this = {(uint32_t *)(d_out + n), d_out}; }
 
     void plan(hipStream_t st, const dvda_pcm_crc_desc *d_desc, uint32_t n, unsigned bits, uint32_t *cnt) const
     {
@@ -61,13 +84,10 @@ struct LvlReport {
     dvda_pcm_levels *d_levels;
 
     bool has_out() const { return d_levels != nullptr; }
-    static bool takes(uint32_t layout, unsigned bits)
-    {
-        return (bits == 16 || bits == 20 || bits == 24) && (layout == DVDA_PCM_PLANAR || layout == DVDA_PCM_INTERLEAVED);
-    }
-    static uint64_t units(const dvda_pcm_crc_desc &d, unsigned) { return d.frames; }
-    static size_t out_words(uint32_t n) { return (size_t)n * (sizeof(dvda_pcm_levels) / sizeof(uint64_t)); }
-    static LvlReport in(uint64_t *d_out, uint32_t) { return LvlReport{(dvda_pcm_levels *)d_out}; }
+    static bool takes(uint32_t layout, unsigned bits) { return (bits == 16 || bits == 20 || bits == 24) && int32_layout(layout); }
+    uint64_t units(const dvda_pcm_crc_desc &d, unsigned) const { return d.frames; }
+    int stage(Descs &, uint32_t n, ReportStage *s) const { return s->want((size_t)n * (sizeof(dvda_pcm_levels) / 8)); }
+    void bind(uint64_t *d_out, uint64_t *, const dvda_pcm_crc_desc *, uint32_t) { d_levels = (dvda_pcm_levels *)d_out; }
 
     void plan(hipStream_t st, const dvda_pcm_crc_desc *d_desc, uint32_t n, unsigned, uint32_t *cnt) const
     {
@@ -99,16 +119,15 @@ struct CmpReport {
     uint32_t layout_b;
     const dvda_pcm_crc_desc *d_desc_b;
 
-    static bool int32_layout(uint32_t layout) { return layout == DVDA_PCM_PLANAR || layout == DVDA_PCM_INTERLEAVED; }
     bool has_out() const { return d_diff && d_b && d_desc_b && int32_layout(layout_b); }
     static bool takes(uint32_t layout, unsigned bits)
     {
         return (bits == 0 || bits == 16 || bits == 20 || bits == 24) && int32_layout(layout);
     }
     // (side A's frames: at least what the pair compares)
-    static uint64_t units(const dvda_pcm_crc_desc &d, unsigned) { return d.frames; }
-    static size_t out_words(uint32_t n) { return (size_t)n * (sizeof(dvda_pcm_diff) / sizeof(uint64_t)); }
-    CmpReport in(uint64_t *d_out, uint32_t) const { return CmpReport{(dvda_pcm_diff *)d_out, d_b, layout_b, d_desc_b}; }
+    uint64_t units(const dvda_pcm_crc_desc &d, unsigned) const { return d.frames; }
+    int stage(Descs &, uint32_t n, ReportStage *s) const { return s->want((size_t)n * (sizeof(dvda_pcm_diff) / 8)); }
+    void bind(uint64_t *d_out, uint64_t *, const dvda_pcm_crc_desc *, uint32_t) { d_diff = (dvda_pcm_diff *)d_out; }
 
     void plan(hipStream_t st, const dvda_pcm_crc_desc *d_desc, uint32_t n, unsigned, uint32_t *cnt) const
     {
@@ -139,14 +158,44 @@ struct NrgReport {
     dvda_pcm_energy_block *d_blocks;
     const uint64_t *d_block_off, *d_block_cap;
     uint64_t *d_nblocks;
+    uint64_t cap_blocks;            // (host) the blocks the caller has room for, and where it is told each stream's first
+    uint64_t *host_first;
 
     static bool block_ok(uint32_t b) { return b >= DVDA_NRG_MIN_BLOCK && b <= DVDA_NRG_MAX_BLOCK; }
     bool has_out() const { return block_ok(block_frames) && d_blocks && d_block_off && d_block_cap && d_nblocks; }
-    static bool takes(uint32_t layout, unsigned) { return layout == DVDA_PCM_PLANAR || layout == DVDA_PCM_INTERLEAVED; }
+    static bool takes(uint32_t layout, unsigned) { return int32_layout(layout); }
     // every block has at most one ragged piece, and a stream at most frames / B + 2 blocks
     uint64_t max_tiles(uint32_t n, uint64_t max_total) const
     {
         return max_total / nrg::PIECE + max_total / block_frames + 2ull * n;
+    }
+    uint64_t units(const dvda_pcm_crc_desc &d, unsigned) const { return PCMT_NOT_TAKEN(d) ? 0 : d.frames; }
+    // The streams back to back: what each needs is known on the host (every grid starts at its stream's first frame), so
+    // the verdict falls here: host_first is filled, or ECAPACITY carries the count in host_first[n], and no blocks is OK.
+    // d_rep_out: the blocks (21 words each) | off [n] | cap [n] | nblocks [n]
+    int stage(Descs &desc, uint32_t n, ReportStage *s) const
+    {
+        std::vector<uint64_t> first((size_t)n + 1);
+        for (uint32_t i = 0; i < n; i++)
+            first[i + 1] = first[i] + nrg::grid_of(desc[i], block_frames, block_frames).blocks();
+        if (first[n] > cap_blocks) {
+            host_first[n] = first[n];
+            return DVDA_HIP_ECAPACITY;
+        }
+        std::copy(first.begin(), first.end(), host_first);
+        s->behind = std::vector<uint64_t>(3 * (size_t)n);
+        for (uint32_t i = 0; i < n; i++) {
+            s->behind[i] = first[i];
+            s->behind[n + i] = first[i + 1] - first[i];
+        }
+        return s->want(first[n] ? first[n] * (sizeof(dvda_pcm_energy_block) / 8) + 3 * (uint64_t)n : 0);
+    }
+    void bind(uint64_t *d_out, uint64_t *d_behind, const dvda_pcm_crc_desc *, uint32_t n)
+    {
+        d_blocks = (dvda_pcm_energy_block *)d_out;
+        d_block_off = d_behind;
+        d_block_cap = d_behind + n;
+        d_nblocks = d_behind + 2 * (size_t)n;
     }
 
     void plan(hipStream_t st, const dvda_pcm_crc_desc *d_desc, uint32_t n, unsigned, uint32_t *cnt) const
@@ -182,8 +231,22 @@ struct RqReport {
     const dvda_pcm_crc_desc *d_desc_out;
     const uint64_t *d_frame0;
     const dvda_pcm_requant *params;         // (host)
+    const uint64_t *host_frame0;            // (host) behind a decode: the streams' first frames, or none
 
-    static bool int32_layout(uint32_t layout) { return layout == DVDA_PCM_PLANAR || layout == DVDA_PCM_INTERLEAVED; }
+    uint64_t units(const dvda_pcm_crc_desc &d, unsigned) const { return PCMT_NOT_TAKEN(d) ? 0 : d.frames; }
+    // d_rep_out: the reports (9 words each) | frame0 [n]; in place: the output's descriptors are the input's
+    int stage(Descs &, uint32_t n, ReportStage *s) const
+    {
+        if (host_frame0)
+            s->behind.assign(host_frame0, host_frame0 + n);
+        return s->want((sizeof(dvda_pcm_requant_report) / 8 + 1) * (size_t)n);
+    }
+    void bind(uint64_t *d_out_, uint64_t *d_behind, const dvda_pcm_crc_desc *d_desc, uint32_t)
+    {
+        d_report = (dvda_pcm_requant_report *)d_out_;
+        d_desc_out = d_desc;
+        d_frame0 = d_behind;
+    }
     bool layout_out_ok() const
     {
         return int32_layout(layout_out) || (layout_out == DVDA_PCM_WAV16 && params->bits_out == 16) ||
@@ -233,8 +296,31 @@ struct DcReport {
     const dvda_pcm_crc_desc *d_desc_out;
     const dvda_pcm_decim_piece *d_piece;
     uint32_t ratio;
+    const uint64_t *host_off, *host_stride;     // (host) behind a decode: where the output's regions lie
 
-    static bool int32_layout(uint32_t layout) { return layout == DVDA_PCM_PLANAR || layout == DVDA_PCM_INTERLEAVED; }
+    // (an overflowed stream has no frames here: zeros reported, nothing written)
+    uint64_t units(const dvda_pcm_crc_desc &d, unsigned) const
+    {
+        return PCMT_NOT_TAKEN(d) ? 0 : dcm::out_frames(0, d.frames, ratio);
+    }
+    // the descriptors of both sides in one array: the input's [n], then the output's [n]
+    int stage(Descs &desc, uint32_t n, ReportStage *s) const
+    {
+        desc.resize(2 * (size_t)n);
+        for (uint32_t i = 0; i < n; i++) {
+            dvda_pcm_crc_desc &o = desc[n + i];
+            o = desc[i];
+            o.off = host_off[i];
+            o.stride = host_stride[i];
+            o.frames = units(desc[i], 0);
+        }
+        return s->want((size_t)n * (sizeof(dvda_pcm_decim_report) / 8));
+    }
+    void bind(uint64_t *d_out_, uint64_t *, const dvda_pcm_crc_desc *d_desc, uint32_t n)
+    {
+        d_report = (dvda_pcm_decim_report *)d_out_;
+        d_desc_out = d_desc + n;
+    }
     bool has_out() const { return d_report && d_out && d_desc_out && dcm::ratio_ok(ratio) && int32_layout(layout_out); }
     static bool takes(uint32_t layout, unsigned bits) { return int32_layout(layout) && dcm::depth_ok(bits); }
 
@@ -270,23 +356,9 @@ struct DcReport {
 static_assert(sizeof(dvda_pcm_decim_piece) == 16 && sizeof(dvda_pcm_decim_report) == 80, "the decimator's structs");
 
 // ---- the driver of the flat tile list
-// tiles the list can hold for n streams of max_total units in all: every stream has at most one ragged tile
-template <class R>
-static inline uint64_t report_max_tiles(uint32_t n, uint64_t max_total)
-{
-    return max_total / R::TILE + n;
-}
-
-// workspace (uint32 words): tiles per stream [n + 1] | their exclusive scan [n + 1] | block sums of the scan | what the
-// tiles leave
-template <class R>
-static inline size_t report_workspace_words(uint32_t n, uint64_t max_total)
-{
-    return 2 * ((size_t)n + 1) + ((size_t)n + 1023) / 1024 + 2 + (size_t)report_max_tiles<R>(n, max_total) * R::TILE_WORDS;
-}
-
-// ... for a report `r` that may supply its own bound, max_tiles(n, max_total), from what it carries (the energy report's
-// pieces depend on its block length); a report without one has the bound above
+// tiles the list can hold for n streams of max_total units in all: every stream has at most one ragged tile -- unless the
+// report `r` supplies its own bound, max_tiles(n, max_total), from what it carries (the energy report's pieces depend on
+// its block length, and on nothing else of it)
 template <class R>
 static inline auto report_max_tiles(const R &r, uint32_t n, uint64_t max_total, int) -> decltype(r.max_tiles(n, max_total))
 {
@@ -295,8 +367,11 @@ static inline auto report_max_tiles(const R &r, uint32_t n, uint64_t max_total, 
 template <class R>
 static inline uint64_t report_max_tiles(const R &, uint32_t n, uint64_t max_total, long)
 {
-    return report_max_tiles<R>(n, max_total);
+    return max_total / R::TILE + n;
 }
+
+// workspace (uint32 words): tiles per stream [n + 1] | their exclusive scan [n + 1] | block sums of the scan | what the
+// tiles leave
 template <class R>
 static inline size_t report_workspace_words(const R &r, uint32_t n, uint64_t max_total)
 {
@@ -380,33 +455,53 @@ static int report_decode_descs(dvda_mlp_hip_ctx *c, const uint64_t *d_out_off, c
 }
 
 // The report of the first n (clamped to the batch; 0: nothing to do) streams of the context's last decode, on the
-// context's buffers: the descriptors copied up, then the report, enqueued on `stream_`.  *r: where the results lie on
-// the device; the caller copies them down and waits.  Blocks for the descriptors.
+// context's buffers: the report's stage on the host, the buffers grown to it, the descriptors -- and what the report laid
+// behind its results -- copied up, the report bound to where all of it lies, then its run, enqueued on `stream_`.  *r:
+// where the results lie on the device; the caller copies them down and waits (report_down).  *n_io: 0 where there is
+// nothing to copy down -- no streams, or a stage that wants no words.  Blocks for the descriptors.
 template <class R>
 static int report_of_decode(dvda_mlp_hip_ctx *c, const int32_t *d_pcm, const uint64_t *d_out_off,
                             const uint64_t *d_out_stride, unsigned bits, uint32_t *n_io, void *stream_, R *r)
 {
-    std::vector<dvda_pcm_crc_desc> desc;
+    Descs desc;
+    ReportStage s;
     int rc = report_decode_descs(c, d_out_off, d_out_stride, n_io, stream_, &desc);
     const uint32_t n = *n_io;
-    if (rc || n == 0)
+    if (rc || (rc = r->stage(desc, n, &s)) != 0 || s.out_words == 0) {
+        *n_io = 0;
         return rc;
+    }
     uint64_t total = 0;
     for (uint32_t i = 0; i < n; i++)
-        total += R::units(desc[i], bits);
-    if ((rc = c->d_rep_desc.grow(n)) != 0 || (rc = c->d_rep_out.grow(R::out_words(n))) != 0 ||
-        (rc = c->d_rep_work.grow(report_workspace_words<R>(n, total))) != 0)
+        total += r->units(desc[i], bits);
+    if ((rc = c->d_rep_desc.grow(desc.size())) != 0 || (rc = c->d_rep_out.grow(s.out_words)) != 0 ||
+        (rc = c->d_rep_work.grow(report_workspace_words(*r, n, total))) != 0)
         return rc;
-    HIP_TRY(hipMemcpy(c->d_rep_desc, desc.data(), (size_t)n * sizeof(dvda_pcm_crc_desc), hipMemcpyHostToDevice));
-    *r = r->in(c->d_rep_out, n);            // (a report that carries more than its results keeps it)
+    uint64_t *d_behind = s.behind.empty() ? nullptr : c->d_rep_out + (s.out_words - s.behind.size());
+    HIP_TRY(hipMemcpy(c->d_rep_desc, desc.data(), desc.size() * sizeof(dvda_pcm_crc_desc), hipMemcpyHostToDevice));
+    if (d_behind)
+        HIP_TRY(hipMemcpy(d_behind, s.behind.data(), s.behind.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    r->bind(c->d_rep_out, d_behind, c->d_rep_desc, n);
     return report_run(*r, d_pcm, c->set.pcm_layout, bits, c->d_rep_desc, n, total, c->d_rep_work,
                       (size_t)c->d_rep_work.cap, stream_);
+}
+
+// ... and the results copied down behind it on its stream (a second array where the report has two), and the wait
+static int report_down(void *stream_, void *host, const void *dev, size_t bytes, void *host2 = nullptr,
+                       const void *dev2 = nullptr, size_t bytes2 = 0)
+{
+    hipStream_t st = (hipStream_t)stream_;
+    HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
+    if (host2)
+        HIP_TRY(hipMemcpyAsync(host2, dev2, bytes2, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DVDA_HIP_OK;
 }
 
 // ---- the digest
 extern "C" size_t dvda_pcm_hip_crc32_workspace_words(uint32_t n, uint64_t max_total_bytes)
 {
-    return report_workspace_words<CrcReport>(n, max_total_bytes);
+    return report_workspace_words(CrcReport{}, n, max_total_bytes);
 }
 
 extern "C" int dvda_pcm_hip_crc32(const int32_t *d_pcm, uint32_t layout, unsigned bits, const dvda_pcm_crc_desc *d_desc,
@@ -427,11 +522,8 @@ extern "C" int dvda_mlp_hip_pcm_crc32(dvda_mlp_hip_ctx *c, const int32_t *d_pcm,
     const int rc = report_of_decode(c, d_pcm, d_out_off, d_out_stride, bits, &n, stream_, &r);
     if (rc || n == 0)
         return rc;
-    hipStream_t st = (hipStream_t)stream_;
-    HIP_TRY(hipMemcpyAsync(host_crc, r.d_crc, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(host_nbytes, r.d_nbytes, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return DVDA_HIP_OK;
+    return report_down(stream_, host_crc, r.d_crc, (size_t)n * sizeof(uint32_t), host_nbytes, r.d_nbytes,
+                       (size_t)n * sizeof(uint64_t));
 }
 
 extern "C" uint32_t dvda_pcm_hip_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b)
@@ -444,7 +536,7 @@ extern "C" uint32_t dvda_pcm_hip_crc32_combine(uint32_t crc_a, uint32_t crc_b, u
 // ---- the level report
 extern "C" size_t dvda_pcm_hip_levels_workspace_words(uint32_t n, uint64_t max_total_frames)
 {
-    return report_workspace_words<LvlReport>(n, max_total_frames);
+    return report_workspace_words(LvlReport{}, n, max_total_frames);
 }
 
 extern "C" int dvda_pcm_hip_levels(const int32_t *d_pcm, uint32_t layout, unsigned bits, const dvda_pcm_crc_desc *d_desc,
@@ -464,10 +556,7 @@ extern "C" int dvda_mlp_hip_pcm_levels(dvda_mlp_hip_ctx *c, const int32_t *d_pcm
     const int rc = report_of_decode(c, d_pcm, d_out_off, d_out_stride, bits, &n, stream_, &r);
     if (rc || n == 0)
         return rc;
-    hipStream_t st = (hipStream_t)stream_;
-    HIP_TRY(hipMemcpyAsync(host_levels, r.d_levels, (size_t)n * sizeof(dvda_pcm_levels), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return DVDA_HIP_OK;
+    return report_down(stream_, host_levels, r.d_levels, (size_t)n * sizeof(dvda_pcm_levels));
 }
 
 extern "C" void dvda_pcm_hip_levels_combine(const dvda_pcm_levels *a_, const dvda_pcm_levels *b_, dvda_pcm_levels *out)
@@ -493,7 +582,7 @@ extern "C" void dvda_pcm_hip_levels_combine(const dvda_pcm_levels *a_, const dvd
 // ---- the compare
 extern "C" size_t dvda_pcm_hip_compare_workspace_words(uint32_t n, uint64_t max_total_frames)
 {
-    return report_workspace_words<CmpReport>(n, max_total_frames);
+    return report_workspace_words(CmpReport{}, n, max_total_frames);
 }
 
 extern "C" int dvda_pcm_hip_compare(const int32_t *d_a, uint32_t layout_a, const dvda_pcm_crc_desc *d_desc_a,
@@ -512,15 +601,12 @@ extern "C" int dvda_mlp_hip_pcm_compare(dvda_mlp_hip_ctx *c, const int32_t *d_pc
 {
     CmpReport r{nullptr, d_other, other_layout, d_other_desc};
     if (!c || !d_pcm || !d_out_off || !d_out_stride || !host_diff || !d_other || !d_other_desc ||
-        !CmpReport::int32_layout(other_layout) || !CmpReport::takes(c->set.pcm_layout, bits))
+        !int32_layout(other_layout) || !CmpReport::takes(c->set.pcm_layout, bits))
         return DVDA_HIP_EINVAL;
     const int rc = report_of_decode(c, d_pcm, d_out_off, d_out_stride, bits, &n, stream_, &r);
     if (rc || n == 0)
         return rc;
-    hipStream_t st = (hipStream_t)stream_;
-    HIP_TRY(hipMemcpyAsync(host_diff, r.d_diff, (size_t)n * sizeof(dvda_pcm_diff), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return DVDA_HIP_OK;
+    return report_down(stream_, host_diff, r.d_diff, (size_t)n * sizeof(dvda_pcm_diff));
 }
 
 extern "C" int dvda_pcm_hip_diff_combine(const dvda_pcm_diff *a_, const dvda_pcm_diff *b_, dvda_pcm_diff *out)
@@ -561,7 +647,7 @@ extern "C" size_t dvda_pcm_hip_energy_workspace_words(uint32_t n, uint64_t max_t
 {
     if (!NrgReport::block_ok(block_frames))
         return 0;
-    return report_workspace_words(NrgReport{block_frames, nullptr, nullptr, nullptr, nullptr, nullptr}, n, max_total_frames);
+    return report_workspace_words(NrgReport{block_frames}, n, max_total_frames);
 }
 
 extern "C" int dvda_pcm_hip_energy(const int32_t *d_pcm, uint32_t layout, const dvda_pcm_crc_desc *d_desc, uint32_t n,
@@ -581,52 +667,11 @@ extern "C" int dvda_mlp_hip_pcm_energy(dvda_mlp_hip_ctx *c, const int32_t *d_pcm
     if (!c || !d_pcm || !d_out_off || !d_out_stride || !host_first || (!host_blocks && cap_blocks) ||
         !NrgReport::block_ok(block_frames) || !NrgReport::takes(c->set.pcm_layout, 0))
         return DVDA_HIP_EINVAL;
-    std::vector<dvda_pcm_crc_desc> desc;
-    int rc = report_decode_descs(c, d_out_off, d_out_stride, &n, stream_, &desc);
-    if (rc)
+    NrgReport r{block_frames, nullptr, nullptr, nullptr, nullptr, nullptr, cap_blocks, host_first};
+    const int rc = report_of_decode(c, d_pcm, d_out_off, d_out_stride, 0, &n, stream_, &r);
+    if (rc || n == 0)
         return rc;
-    // the streams back to back: what each needs is known here (every grid starts at its stream's first frame)
-    std::vector<uint64_t> first((size_t)n + 1), arr(3 * (size_t)n);
-    uint64_t total = 0, blocks = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        first[i] = blocks;
-        blocks += nrg::grid_of(desc[i], block_frames, block_frames).blocks();
-        total += PCMT_NOT_TAKEN(desc[i]) ? 0 : desc[i].frames;
-    }
-    first[n] = blocks;
-    if (blocks > cap_blocks) {
-        host_first[n] = blocks;
-        return DVDA_HIP_ECAPACITY;
-    }
-    for (uint32_t i = 0; i <= n; i++)
-        host_first[i] = first[i];
-    if (n == 0 || blocks == 0)
-        return DVDA_HIP_OK;
-    // d_rep_out: the blocks (21 words each) | off [n] | cap [n] | nblocks [n]
-    constexpr size_t BW = sizeof(dvda_pcm_energy_block) / sizeof(uint64_t);
-    NrgReport r{block_frames, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if ((rc = c->d_rep_desc.grow(n)) != 0 || (rc = c->d_rep_out.grow(blocks * BW + 3 * (uint64_t)n)) != 0 ||
-        (rc = c->d_rep_work.grow(report_workspace_words(r, n, total))) != 0)
-        return rc;
-    for (uint32_t i = 0; i < n; i++) {
-        arr[i] = first[i];
-        arr[n + i] = first[i + 1] - first[i];
-        arr[2 * (size_t)n + i] = 0;
-    }
-    uint64_t *d_arr = c->d_rep_out + blocks * BW;
-    HIP_TRY(hipMemcpy(c->d_rep_desc, desc.data(), (size_t)n * sizeof(dvda_pcm_crc_desc), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_arr, arr.data(), arr.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-    r.d_blocks = (dvda_pcm_energy_block *)(uint64_t *)c->d_rep_out;
-    r.d_block_off = d_arr;
-    r.d_block_cap = d_arr + n;
-    r.d_nblocks = d_arr + 2 * (size_t)n;
-    rc = report_run(r, d_pcm, c->set.pcm_layout, 0, c->d_rep_desc, n, total, c->d_rep_work, (size_t)c->d_rep_work.cap, stream_);
-    if (rc)
-        return rc;
-    hipStream_t st = (hipStream_t)stream_;
-    HIP_TRY(hipMemcpyAsync(host_blocks, r.d_blocks, (size_t)blocks * sizeof(dvda_pcm_energy_block), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return DVDA_HIP_OK;
+    return report_down(stream_, host_blocks, r.d_blocks, (size_t)host_first[n] * sizeof(dvda_pcm_energy_block));
 }
 
 static inline void nrg_add(dvda_pcm_energy_block *t, const dvda_pcm_energy_block &p)
@@ -687,7 +732,7 @@ extern "C" void dvda_pcm_hip_energy_total(const dvda_pcm_energy_block *blocks, u
 // ---- the word-length reduction
 extern "C" size_t dvda_pcm_hip_requantize_workspace_words(uint32_t n, uint64_t max_total_frames)
 {
-    return report_workspace_words<RqReport>(n, max_total_frames);
+    return report_workspace_words(RqReport{}, n, max_total_frames);
 }
 
 extern "C" int dvda_pcm_hip_requantize(const int32_t *d_in, uint32_t layout_in, const dvda_pcm_crc_desc *d_desc_in,
@@ -708,34 +753,11 @@ extern "C" int dvda_mlp_hip_pcm_requantize(dvda_mlp_hip_ctx *c, int32_t *d_pcm, 
     if (!c || !d_pcm || !d_out_off || !d_out_stride || !params || !host_report || !rq::params_ok(*params) ||
         !RqReport::takes(c->set.pcm_layout, 0))
         return DVDA_HIP_EINVAL;
-    std::vector<dvda_pcm_crc_desc> desc;
-    int rc = report_decode_descs(c, d_out_off, d_out_stride, &n, stream_, &desc);
+    RqReport r{nullptr, d_pcm, c->set.pcm_layout, nullptr, nullptr, params, host_frame0};
+    const int rc = report_of_decode(c, d_pcm, d_out_off, d_out_stride, 0, &n, stream_, &r);
     if (rc || n == 0)
         return rc;
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; i++)
-        total += PCMT_NOT_TAKEN(desc[i]) ? 0 : desc[i].frames;
-    // d_rep_out: the reports (9 words each) | frame0 [n]
-    constexpr size_t RW = sizeof(dvda_pcm_requant_report) / sizeof(uint64_t);
-    if ((rc = c->d_rep_desc.grow(n)) != 0 || (rc = c->d_rep_out.grow((RW + 1) * (size_t)n)) != 0 ||
-        (rc = c->d_rep_work.grow(report_workspace_words<RqReport>(n, total))) != 0)
-        return rc;
-    uint64_t *d_frame0 = nullptr;
-    HIP_TRY(hipMemcpy(c->d_rep_desc, desc.data(), (size_t)n * sizeof(dvda_pcm_crc_desc), hipMemcpyHostToDevice));
-    if (host_frame0) {
-        d_frame0 = c->d_rep_out + RW * (size_t)n;
-        HIP_TRY(hipMemcpy(d_frame0, host_frame0, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice));
-    }
-    const RqReport r{(dvda_pcm_requant_report *)(uint64_t *)c->d_rep_out, d_pcm, c->set.pcm_layout, c->d_rep_desc, d_frame0,
-                     params};
-    rc = report_run(r, d_pcm, c->set.pcm_layout, 0, c->d_rep_desc, n, total, c->d_rep_work, (size_t)c->d_rep_work.cap,
-                    stream_);
-    if (rc)
-        return rc;
-    hipStream_t st = (hipStream_t)stream_;
-    HIP_TRY(hipMemcpyAsync(host_report, r.d_report, (size_t)n * sizeof(dvda_pcm_requant_report), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return DVDA_HIP_OK;
+    return report_down(stream_, host_report, r.d_report, (size_t)n * sizeof(dvda_pcm_requant_report));
 }
 
 extern "C" int32_t dvda_pcm_hip_requant_value(int32_t v, uint64_t frame, uint32_t channel, const dvda_pcm_requant *params,
@@ -758,7 +780,7 @@ extern "C" int32_t dvda_pcm_hip_requant_value(int32_t v, uint64_t frame, uint32_
 // ---- the decimation
 extern "C" size_t dvda_pcm_hip_decimate_workspace_words(uint32_t n, uint64_t max_total_out_frames)
 {
-    return report_workspace_words<DcReport>(n, max_total_out_frames);
+    return report_workspace_words(DcReport{}, n, max_total_out_frames);
 }
 
 extern "C" int dvda_pcm_hip_decimate(const int32_t *d_in, uint32_t layout_in, const dvda_pcm_crc_desc *d_desc_in,
@@ -777,37 +799,13 @@ extern "C" int dvda_mlp_hip_pcm_decimate(dvda_mlp_hip_ctx *c, const int32_t *d_p
                                          dvda_pcm_decim_report *host_report, uint32_t n, void *stream_)
 {
     if (!c || !d_pcm || !d_out_off || !d_out_stride || !d_dst || !host_dst_off || !host_dst_stride || !host_report ||
-        !dcm::ratio_ok(ratio) || !DcReport::int32_layout(layout_dst) || !DcReport::takes(c->set.pcm_layout, bits))
+        !dcm::ratio_ok(ratio) || !int32_layout(layout_dst) || !DcReport::takes(c->set.pcm_layout, bits))
         return DVDA_HIP_EINVAL;
-    std::vector<dvda_pcm_crc_desc> desc;
-    int rc = report_decode_descs(c, d_out_off, d_out_stride, &n, stream_, &desc);
+    DcReport r{nullptr, d_dst, layout_dst, nullptr, nullptr, ratio, host_dst_off, host_dst_stride};
+    const int rc = report_of_decode(c, d_pcm, d_out_off, d_out_stride, bits, &n, stream_, &r);
     if (rc || n == 0)
         return rc;
-    // the descriptors of both sides in one array: the input's [n], then the output's [n]
-    desc.resize(2 * (size_t)n);
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        dvda_pcm_crc_desc &o = desc[n + i];
-        o = desc[i];
-        o.off = host_dst_off[i];
-        o.stride = host_dst_stride[i];
-        o.frames = PCMT_NOT_TAKEN(desc[i]) ? 0 : dcm::out_frames(0, desc[i].frames, ratio);
-        total += o.frames;              // (an overflowed stream has no frames here: zeros reported, nothing written)
-    }
-    constexpr size_t RW = sizeof(dvda_pcm_decim_report) / sizeof(uint64_t);
-    if ((rc = c->d_rep_desc.grow(2 * (size_t)n)) != 0 || (rc = c->d_rep_out.grow(RW * (size_t)n)) != 0 ||
-        (rc = c->d_rep_work.grow(report_workspace_words<DcReport>(n, total))) != 0)
-        return rc;
-    HIP_TRY(hipMemcpy(c->d_rep_desc, desc.data(), 2 * (size_t)n * sizeof(dvda_pcm_crc_desc), hipMemcpyHostToDevice));
-    const dvda_pcm_crc_desc *d_in_desc = c->d_rep_desc;
-    const DcReport r{(dvda_pcm_decim_report *)(uint64_t *)c->d_rep_out, d_dst, layout_dst, d_in_desc + n, nullptr, ratio};
-    rc = report_run(r, d_pcm, c->set.pcm_layout, bits, d_in_desc, n, total, c->d_rep_work, (size_t)c->d_rep_work.cap, stream_);
-    if (rc)
-        return rc;
-    hipStream_t st = (hipStream_t)stream_;
-    HIP_TRY(hipMemcpyAsync(host_report, r.d_report, (size_t)n * sizeof(dvda_pcm_decim_report), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return DVDA_HIP_OK;
+    return report_down(stream_, host_report, r.d_report, (size_t)n * sizeof(dvda_pcm_decim_report));
 }
 
 extern "C" const int32_t *dvda_pcm_hip_decim_taps(uint32_t ratio, uint32_t *n)

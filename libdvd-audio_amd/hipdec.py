@@ -4,6 +4,7 @@ torch is used for what it is good at here -- device memory and streams; every
 compute step is the HIP library.  There is no CPU fallback: a missing library,
 a missing GPU or a HIP error raises.
 """
+import contextlib
 import ctypes
 
 import numpy as np
@@ -87,6 +88,23 @@ CRC_TILE_BYTES = 16384      # DVDA_CRC_TILE_BYTES: the digest's tiles, aligned t
 CRC_JOIN_TILES = 256        # DVDA_CRC_JOIN_TILES: tiles a join workgroup folds per turn of its loop
 
 
+class _Record(ctypes.Structure):
+    """A result or parameter struct of include/dvda_mlp_hip.h whose dict form follows from its _fields_: a scalar is an
+    int, an array a list of int, a field named `reserved` is left out (and zero on the way back)."""
+
+    def as_dict(self):
+        out = {}
+        for k, t in self._fields_:
+            if k != "reserved":
+                v = getattr(self, k)
+                out[k] = [int(e) for e in v] if issubclass(t, ctypes.Array) else int(v)
+        return out
+
+    @classmethod
+    def from_dict(cls, d):
+        return cls(**{k: t(*d[k]) if issubclass(t, ctypes.Array) else d[k] for k, t in cls._fields_ if k != "reserved"})
+
+
 class CrcDesc(ctypes.Structure):
     """dvda_pcm_crc_desc of include/dvda_mlp_hip.h"""
     _fields_ = [("off", ctypes.c_uint64), ("stride", ctypes.c_uint64), ("frames", ctypes.c_uint64),
@@ -95,93 +113,47 @@ class CrcDesc(ctypes.Structure):
 LVL_TILE_FRAMES = 4096      # DVDA_LVL_TILE_FRAMES: the level report's tiles, aligned to the start of a stream
 
 
-class Levels(ctypes.Structure):
+class Levels(_Record):
     """dvda_pcm_levels of include/dvda_mlp_hip.h"""
     _fields_ = [("frames", ctypes.c_uint64), ("lead_silent", ctypes.c_uint64), ("trail_silent", ctypes.c_uint64),
                 ("sum", ctypes.c_int64 * 8), ("over", ctypes.c_uint64 * 8), ("min", ctypes.c_int32 * 8),
                 ("max", ctypes.c_int32 * 8)]
-
-    def as_dict(self):
-        return dict(frames=int(self.frames), lead_silent=int(self.lead_silent), trail_silent=int(self.trail_silent),
-                    sum=[int(v) for v in self.sum], over=[int(v) for v in self.over], min=[int(v) for v in self.min],
-                    max=[int(v) for v in self.max])
-
-    @classmethod
-    def from_dict(cls, d):
-        return cls(d["frames"], d["lead_silent"], d["trail_silent"], (ctypes.c_int64 * 8)(*d["sum"]),
-                   (ctypes.c_uint64 * 8)(*d["over"]), (ctypes.c_int32 * 8)(*d["min"]), (ctypes.c_int32 * 8)(*d["max"]))
 
 
 CMP_TILE_FRAMES = 4096      # DVDA_CMP_TILE_FRAMES: the compare's tiles, aligned to the start of a stream pair
 CMP_SHAPE = 1               # DVDA_CMP_SHAPE: nothing was compared, the two descriptors do not go together
 
 
-class Diff(ctypes.Structure):
+class Diff(_Record):
     """dvda_pcm_diff of include/dvda_mlp_hip.h"""
     _fields_ = [("frames_a", ctypes.c_uint64), ("frames_b", ctypes.c_uint64), ("compared", ctypes.c_uint64),
                 ("diff_frames", ctypes.c_uint64), ("first_diff", ctypes.c_uint64), ("diff_end", ctypes.c_uint64),
                 ("runs", ctypes.c_uint64), ("diff_values", ctypes.c_uint64 * 8), ("max_abs", ctypes.c_uint32 * 8),
                 ("channels", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
-    _SCALARS = ("frames_a", "frames_b", "compared", "diff_frames", "first_diff", "diff_end", "runs", "channels", "flags")
-
-    def as_dict(self):
-        d = {k: int(getattr(self, k)) for k in self._SCALARS}
-        d.update(diff_values=[int(v) for v in self.diff_values], max_abs=[int(v) for v in self.max_abs])
-        return d
-
-    @classmethod
-    def from_dict(cls, d):
-        out = cls(diff_values=(ctypes.c_uint64 * 8)(*d["diff_values"]), max_abs=(ctypes.c_uint32 * 8)(*d["max_abs"]))
-        for k in cls._SCALARS:
-            setattr(out, k, d[k])
-        return out
 
 
 NRG_MIN_BLOCK, NRG_MAX_BLOCK = 64, 1 << 24      # DVDA_NRG_MIN_BLOCK / DVDA_NRG_MAX_BLOCK: the energy report's block length
 NRG_PIECE_FRAMES = 4096     # DVDA_NRG_PIECE_FRAMES: frames of one block a workgroup takes at most
 
 
-class EnergyBlock(ctypes.Structure):
+class EnergyBlock(_Record):
     """dvda_pcm_energy_block of include/dvda_mlp_hip.h"""
     _fields_ = [("sq_lo", ctypes.c_uint64 * 8), ("sq_hi", ctypes.c_uint64 * 8), ("peak", ctypes.c_uint32 * 8),
                 ("frames", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
-
-    def as_dict(self):
-        return dict(sq_lo=[int(v) for v in self.sq_lo], sq_hi=[int(v) for v in self.sq_hi],
-                    peak=[int(v) for v in self.peak], frames=int(self.frames))
-
-    @classmethod
-    def from_dict(cls, d):
-        return cls((ctypes.c_uint64 * 8)(*d["sq_lo"]), (ctypes.c_uint64 * 8)(*d["sq_hi"]), (ctypes.c_uint32 * 8)(*d["peak"]),
-                   d["frames"], 0)
 
 
 RQ_TRUNCATE, RQ_ROUND, RQ_TPDF = 0, 1, 2        # DVDA_RQ_*: how the word-length reduction treats the bits it drops
 
 
-class Requant(ctypes.Structure):
+class Requant(_Record):
     """dvda_pcm_requant of include/dvda_mlp_hip.h"""
     _fields_ = [("bits_in", ctypes.c_uint32), ("bits_out", ctypes.c_uint32), ("mode", ctypes.c_uint32),
                 ("reserved", ctypes.c_uint32), ("seed", ctypes.c_uint64)]
 
-    def as_dict(self):
-        return dict(bits_in=int(self.bits_in), bits_out=int(self.bits_out), mode=int(self.mode), seed=int(self.seed))
 
-    @classmethod
-    def from_dict(cls, d):
-        return cls(d["bits_in"], d["bits_out"], d["mode"], 0, d["seed"])
-
-
-class RequantReport(ctypes.Structure):
+class RequantReport(_Record):
     """dvda_pcm_requant_report of include/dvda_mlp_hip.h"""
     _fields_ = [("frames", ctypes.c_uint64), ("clipped", ctypes.c_uint64 * 8)]
-
-    def as_dict(self):
-        return dict(frames=int(self.frames), clipped=[int(v) for v in self.clipped])
-
-    @classmethod
-    def from_dict(cls, d):
-        return cls(d["frames"], (ctypes.c_uint64 * 8)(*d["clipped"]))
 
 
 DCM_TILE_FRAMES = 1024      # DVDA_DCM_TILE_FRAMES: OUTPUT frames of the decimator's tiles, aligned to a stream's first output frame
@@ -193,16 +165,9 @@ class DecimPiece(ctypes.Structure):
     _fields_ = [("frame0", ctypes.c_uint64), ("before", ctypes.c_uint32), ("after", ctypes.c_uint32)]
 
 
-class DecimReport(ctypes.Structure):
+class DecimReport(_Record):
     """dvda_pcm_decim_report of include/dvda_mlp_hip.h"""
     _fields_ = [("frames_in", ctypes.c_uint64), ("frames_out", ctypes.c_uint64), ("clipped", ctypes.c_uint64 * 8)]
-
-    def as_dict(self):
-        return dict(frames_in=int(self.frames_in), frames_out=int(self.frames_out), clipped=[int(v) for v in self.clipped])
-
-    @classmethod
-    def from_dict(cls, d):
-        return cls(d["frames_in"], d["frames_out"], (ctypes.c_uint64 * 8)(*d["clipped"]))
 
 
 ST_CONCEALED = 1 << 30          # DVDA_ST_CONCEALED: conceal mode, the stream was damaged (not in ST_BENIGN)
@@ -512,15 +477,19 @@ class Context:
                                             nbytes.ctypes.data, n, stream), "dvda_mlp_hip_pcm_crc32")
         return [(int(c), int(b)) for c, b in zip(crc, nbytes)]
 
+    def _records(self, name, cls, n, stream, *args):
+        """what the pcm_* calls have in common: lib().<name>(context, *args, room for n records of cls, n, stream),
+        checked -> list of cls.as_dict()"""
+        arr = (cls * max(n, 1))()
+        _check(getattr(lib(), name)(self._h, *args, arr, n, stream), name)
+        return [arr[i].as_dict() for i in range(n)]
+
     def pcm_levels(self, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, bits, n=None, stream=0):
         """dvda_mlp_hip_pcm_levels: the level report of every stream at nominal depth `bits` (16, 20 or 24), computed on
         the device from the int32 PCM the last decode wrote -> list of Levels.as_dict(); blocks.  HipError (EINVAL) when
         the context's layout is a WAV one."""
         n = self.n_streams if n is None else n
-        arr = (Levels * max(n, 1))()
-        _check(lib().dvda_mlp_hip_pcm_levels(self._h, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, bits, arr, n, stream),
-               "dvda_mlp_hip_pcm_levels")
-        return [arr[i].as_dict() for i in range(n)]
+        return self._records("dvda_mlp_hip_pcm_levels", Levels, n, stream, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, bits)
 
     def pcm_energy(self, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, block_frames, n=None, stream=0, cap_blocks=None):
         """dvda_mlp_hip_pcm_energy: per block of block_frames frames and channel the exact sum of squares and the peak
@@ -554,12 +523,9 @@ class Context:
             raise HipError("pcm_compare: %d descriptors for %d streams" % (len(other_desc), n))
         if stream is None:
             stream = torch.cuda.current_stream(d_other.device).cuda_stream
-        d_desc = torch.from_numpy(_desc_records(other_desc[:n]).view(np.uint8).reshape(-1)).to(d_other.device)
-        arr = (Diff * max(n, 1))()
-        _check(lib().dvda_mlp_hip_pcm_compare(self._h, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, d_other.data_ptr(),
-                                              other_layout, d_desc.data_ptr(), bits, arr, n, stream),
-               "dvda_mlp_hip_pcm_compare")
-        return [arr[i].as_dict() for i in range(n)]
+        d_desc = _to_device(_desc_records(other_desc[:n]), d_other.device)
+        return self._records("dvda_mlp_hip_pcm_compare", Diff, n, stream, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr,
+                             d_other.data_ptr(), other_layout, d_desc.data_ptr(), bits)
 
     def pcm_requantize(self, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, bits_in, bits_out, mode=RQ_TPDF, seed=0,
                        frame0=None, n=None, stream=0):
@@ -567,12 +533,10 @@ class Context:
         (truncated, rounded or dithered; clamped) -> list of RequantReport.as_dict(); blocks.  frame0: per stream the
         absolute frame it starts at (None: 0).  HipError (EINVAL) when the context's layout is a WAV one."""
         n = self.n_streams if n is None else n
-        arr = (RequantReport * max(n, 1))()
         f0 = None if frame0 is None else (ctypes.c_uint64 * max(n, 1))(*[int(f) for f in frame0][:n])
         par = Requant(bits_in, bits_out, mode, 0, seed)
-        _check(lib().dvda_mlp_hip_pcm_requantize(self._h, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, ctypes.byref(par), f0,
-                                                 arr, n, stream), "dvda_mlp_hip_pcm_requantize")
-        return [arr[i].as_dict() for i in range(n)]
+        return self._records("dvda_mlp_hip_pcm_requantize", RequantReport, n, stream, d_pcm_ptr, d_out_off_ptr,
+                             d_out_stride_ptr, ctypes.byref(par), f0)
 
     def pcm_decimate(self, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, ratio, bits, d_dst_ptr, layout_dst, dst_off,
                      dst_stride, n=None, stream=0):
@@ -581,12 +545,10 @@ class Context:
         the int32 word dst_off[i], planar stride dst_stride[i] (host lists) -> list of DecimReport.as_dict(); blocks.
         HipError (EINVAL) when the context's layout is a WAV one."""
         n = self.n_streams if n is None else n
-        arr = (DecimReport * max(n, 1))()
         off = (ctypes.c_uint64 * max(n, 1))(*[int(v) for v in dst_off][:n])
         stride = (ctypes.c_uint64 * max(n, 1))(*[int(v) for v in dst_stride][:n])
-        _check(lib().dvda_mlp_hip_pcm_decimate(self._h, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, ratio, bits, d_dst_ptr,
-                                               layout_dst, off, stride, arr, n, stream), "dvda_mlp_hip_pcm_decimate")
-        return [arr[i].as_dict() for i in range(n)]
+        return self._records("dvda_mlp_hip_pcm_decimate", DecimReport, n, stream, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr,
+                             ratio, bits, d_dst_ptr, layout_dst, off, stride)
 
     def decode_time(self):
         """mean device ms of a whole decode call (all passes); call before kernel_time(), which resets the ring"""
@@ -616,6 +578,24 @@ def _desc_records(desc):
     return rec
 
 
+def _to_device(rec, dev):
+    """a numpy array of records (_desc_records, _piece_records) -> its bytes on `dev` (the host waits for the copy)"""
+    import torch
+    return torch.from_numpy(rec.view(np.uint8).reshape(-1)).to(dev)
+
+
+def _result_tensor(cls, n, dev):
+    """room on `dev` for n records of cls (one at least, so that it has an address), zeroed: uint8 [max(n, 1), sizeof(cls)]"""
+    import torch
+    return torch.zeros((max(n, 1), ctypes.sizeof(cls)), dtype=torch.uint8, device=dev)
+
+
+def _record_list(cls, d_records):
+    """a uint8 device tensor [n, sizeof(cls)] -> list of cls.as_dict() on the host (waits)"""
+    raw = np.ascontiguousarray(d_records.cpu().numpy())
+    return [cls.from_buffer_copy(raw[i].tobytes()).as_dict() for i in range(raw.shape[0])]
+
+
 def _report_args(d_pcm, desc, what, max_total, work, workspace_words):
     """What pcm_crc32 and pcm_levels hand their C entry point besides the results: the dvda_pcm_crc_desc records of `desc`
     on d_pcm's device (the host waits for that copy), the workspace (`work`, or one allocated here from
@@ -625,11 +605,9 @@ def _report_args(d_pcm, desc, what, max_total, work, workspace_words):
         raise HipError("no GPU visible to torch: %s is HIP-only" % what)
     dev = d_pcm.device
     n = len(desc)
-    rec = _desc_records(desc)
     if work is None:
         work = torch.empty(int(workspace_words(n, max_total)), dtype=torch.int32, device=dev)
-    d_desc = torch.from_numpy(rec.view(np.uint8).reshape(-1)).to(dev)
-    return torch, n, d_desc, work, torch.cuda.current_stream(dev).cuda_stream
+    return torch, n, _to_device(_desc_records(desc), dev), work, torch.cuda.current_stream(dev).cuda_stream
 
 
 def pcm_crc32(d_pcm, layout, bits, desc, max_total_bytes=None, work=None):
@@ -678,7 +656,7 @@ def pcm_levels(d_pcm, layout, bits, desc, max_total_frames=None, work=None):
         max_total_frames = int(sum(int(f) for _, _, f, c in desc if 1 <= int(c) <= 8))
     torch, n, d_desc, work, st = _report_args(d_pcm, desc, "the level report", max_total_frames, work,
                                               lib().dvda_pcm_hip_levels_workspace_words)
-    d_out = torch.zeros((max(n, 1), ctypes.sizeof(Levels)), dtype=torch.uint8, device=d_pcm.device)
+    d_out = _result_tensor(Levels, n, d_pcm.device)
     _check(lib().dvda_pcm_hip_levels(d_pcm.data_ptr(), layout, bits, d_desc.data_ptr(), n, max_total_frames,
                                      d_out.data_ptr(), work.data_ptr(), work.numel(), st), "dvda_pcm_hip_levels")
     return d_out[:n]
@@ -690,8 +668,7 @@ def pcm_levels_workspace_words(n, max_total_frames):
 
 def levels_list(d_levels):
     """pcm_levels' tensor -> list of Levels.as_dict() on the host (waits)"""
-    raw = np.ascontiguousarray(d_levels.cpu().numpy())
-    return [Levels.from_buffer_copy(raw[i].tobytes()).as_dict() for i in range(raw.shape[0])]
+    return _record_list(Levels, d_levels)
 
 
 def _compared(da, db):
@@ -715,8 +692,8 @@ def pcm_compare(d_a, layout_a, desc_a, d_b, layout_b, desc_b, bits=0, max_total_
         max_total_frames = int(sum(_compared(a, b) for a, b in zip(desc_a, desc_b)))
     torch, n, d_desc_a, work, st = _report_args(d_a, desc_a, "the PCM compare", max_total_frames, work,
                                                 lib().dvda_pcm_hip_compare_workspace_words)
-    d_desc_b = torch.from_numpy(_desc_records(desc_b).view(np.uint8).reshape(-1)).to(d_a.device)
-    d_out = torch.zeros((max(n, 1), ctypes.sizeof(Diff)), dtype=torch.uint8, device=d_a.device)
+    d_desc_b = _to_device(_desc_records(desc_b), d_a.device)
+    d_out = _result_tensor(Diff, n, d_a.device)
     _check(lib().dvda_pcm_hip_compare(d_a.data_ptr(), layout_a, d_desc_a.data_ptr(), d_b.data_ptr(), layout_b,
                                       d_desc_b.data_ptr(), n, bits, max_total_frames, d_out.data_ptr(), work.data_ptr(),
                                       work.numel(), st), "dvda_pcm_hip_compare")
@@ -729,8 +706,7 @@ def pcm_compare_workspace_words(n, max_total_frames):
 
 def diff_list(d_diff):
     """pcm_compare's tensor -> list of Diff.as_dict() on the host (waits)"""
-    raw = np.ascontiguousarray(d_diff.cpu().numpy())
-    return [Diff.from_buffer_copy(raw[i].tobytes()).as_dict() for i in range(raw.shape[0])]
+    return _record_list(Diff, d_diff)
 
 
 def diff_combine(a, b):
@@ -776,7 +752,7 @@ def pcm_energy(d_pcm, layout, desc, block_frames, lead=None, max_total_frames=No
         first.append(first[-1] + int(c))
     arr = torch.tensor([first[:n] + [0], [int(c) for c in caps] + [0]], dtype=torch.int64).to(dev)
     d_lead = None if lead is None else torch.tensor([int(v) for v in lead] + [0], dtype=torch.int32).to(dev)
-    d_blocks = torch.zeros((max(first[-1], 1), ctypes.sizeof(EnergyBlock)), dtype=torch.uint8, device=dev)
+    d_blocks = _result_tensor(EnergyBlock, first[-1], dev)
     d_nblocks = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
     _check(lib().dvda_pcm_hip_energy(d_pcm.data_ptr(), layout, d_desc.data_ptr(), n, block_frames,
                                      None if d_lead is None else d_lead.data_ptr(), max_total_frames, d_blocks.data_ptr(),
@@ -856,10 +832,10 @@ def pcm_requantize(d_in, layout_in, desc_in, bits_in, bits_out, mode=RQ_TPDF, se
     dev = d_in.device
     if out is None:
         out = d_in.clone() if layout_out in (PCM_PLANAR, PCM_INTERLEAVED) else torch.zeros_like(d_in)
-    d_desc_out = torch.from_numpy(_desc_records(desc_out).view(np.uint8).reshape(-1)).to(dev)
+    d_desc_out = _to_device(_desc_records(desc_out), dev)
     d_f0 = None if frame0 is None else torch.from_numpy(
         np.array([int(f) for f in frame0] + [0], np.uint64).view(np.int64)).to(dev)
-    d_rep = torch.zeros((max(n, 1), ctypes.sizeof(RequantReport)), dtype=torch.uint8, device=dev)
+    d_rep = _result_tensor(RequantReport, n, dev)
     par = Requant(bits_in, bits_out, mode, 0, seed)
     _check(lib().dvda_pcm_hip_requantize(d_in.data_ptr(), layout_in, d_desc_in.data_ptr(), out.data_ptr(), layout_out,
                                          d_desc_out.data_ptr(), None if d_f0 is None else d_f0.data_ptr(), n,
@@ -874,8 +850,7 @@ def pcm_requantize_workspace_words(n, max_total_frames):
 
 def requant_list(d_report):
     """pcm_requantize's report tensor -> list of RequantReport.as_dict() on the host (waits)"""
-    raw = np.ascontiguousarray(d_report.cpu().numpy())
-    return [RequantReport.from_buffer_copy(raw[i].tobytes()).as_dict() for i in range(raw.shape[0])]
+    return _record_list(RequantReport, d_report)
 
 
 def requant_value(v, frame, channel, bits_in, bits_out, mode=RQ_TPDF, seed=0):
@@ -967,9 +942,9 @@ def pcm_decimate(d_in, layout_in, desc_in, ratio, bits, pieces=None, out=None, l
         if words is None:
             words = max([int(o) + int(r) * int(c) for o, r, f, c in desc_out] + [1])
         out = torch.zeros(words, dtype=torch.int32, device=dev)
-    d_desc_out = torch.from_numpy(_desc_records(desc_out).view(np.uint8).reshape(-1)).to(dev)
-    d_piece = None if pieces is None else torch.from_numpy(_piece_records(pieces).view(np.uint8).reshape(-1)).to(dev)
-    d_rep = torch.zeros((max(n, 1), ctypes.sizeof(DecimReport)), dtype=torch.uint8, device=dev)
+    d_desc_out = _to_device(_desc_records(desc_out), dev)
+    d_piece = None if pieces is None else _to_device(_piece_records(pieces), dev)
+    d_rep = _result_tensor(DecimReport, n, dev)
     _check(lib().dvda_pcm_hip_decimate(d_in.data_ptr(), layout_in, d_desc_in.data_ptr(), out.data_ptr(), layout_out,
                                        d_desc_out.data_ptr(), None if d_piece is None else d_piece.data_ptr(), n, ratio,
                                        bits, max_total_out_frames, d_rep.data_ptr(), work.data_ptr(), work.numel(), st),
@@ -985,8 +960,7 @@ def pcm_decimate_workspace_words(n, max_total_out_frames):
 
 def decim_list(d_report):
     """pcm_decimate's report tensor -> list of DecimReport.as_dict() on the host (waits)"""
-    raw = np.ascontiguousarray(d_report.cpu().numpy())
-    return [DecimReport.from_buffer_copy(raw[i].tobytes()).as_dict() for i in range(raw.shape[0])]
+    return _record_list(DecimReport, d_report)
 
 
 def crc_list(d_crc, d_nbytes):
@@ -1198,6 +1172,38 @@ def _context_for(ctx, batch, max_segments, lanes_per_segment, layout):
     return ctx, False
 
 
+@contextlib.contextmanager
+def _call_context(ctx, batch, max_segments, lanes_per_segment, layout, presentation):
+    """The context a decode_streams* call runs on, for a `with`: the caller's, set to this call's lanes, layout and
+    presentation, or one of the call's own, which the decode sequence may replace by a larger one and which is closed when
+    the block ends, however it ends.  -> (ctx, capacity) as decode_batch takes them."""
+    ctx, own = _context_for(ctx, batch, max_segments, lanes_per_segment, layout)
+    made = [ctx]
+
+    def larger(found):
+        made[0].close()
+        made[0] = Context(batch.dev.index, batch.n, found + 64, lanes_per_segment, layout)
+        if presentation != PRESENT_FULL:
+            made[0].set_presentation(presentation)
+        return made[0]
+
+    try:
+        if presentation != PRESENT_FULL or not own:
+            ctx.set_presentation(presentation)
+        yield ctx, larger if own else "raise"
+    finally:
+        if own:
+            made[0].close()
+
+
+def _decoded_lists(infos, regions):
+    """what the passes behind a decode need of it, per stream -> (frames: those its region holds, 0 for a stream with
+    DVDA_ST_OVERFLOW; desc: (off, stride, frames, channels); depth: its bits, 0 for a code that has none)"""
+    frames = [0 if inf.status & ST["OVERFLOW"] else min(int(inf.pcm_frames), r) for inf, r in zip(infos, regions.rows)]
+    desc = [(o, r, f, c) for o, r, f, c in zip(regions.out_off, regions.rows, frames, regions.channels)]
+    return frames, desc, [BITS_OF_CODE.get(int(inf.group0_bps), 0) for inf in infos]
+
+
 def decode_streams(streams, device=0, max_segments=None, lanes_per_segment=0, layout=PCM_PLANAR, ctx=None,
                    presentation=PRESENT_FULL, crc32=False, crc_bits=24, levels=None, energy=None):
     """Decodes a list of complete MLP byte streams on the GPU.
@@ -1220,28 +1226,12 @@ def decode_streams(streams, device=0, max_segments=None, lanes_per_segment=0, la
     list of blocks per stream, is appended behind all of the above.  layout must be an int32 one.
     """
     batch = Batch(streams, device)
-    ctx, own = _context_for(ctx, batch, max_segments, lanes_per_segment, layout)
-    made = [ctx]
-
-    def larger(found):
-        made[0].close()
-        made[0] = Context(device, batch.n, found + 64, lanes_per_segment, layout)
-        if presentation != PRESENT_FULL:
-            made[0].set_presentation(presentation)
-        return made[0]
-
-    try:
-        if presentation != PRESENT_FULL or not own:
-            ctx.set_presentation(presentation)
+    with _call_context(ctx, batch, max_segments, lanes_per_segment, layout, presentation) as (ctx, capacity):
         # (int32 regions of r*c words, cut as [c, r], for any layout but PCM_INTERLEAVED)
-        res = decode_batch(ctx, batch, layout if layout == PCM_INTERLEAVED else PCM_PLANAR, attempts=2,
-                           capacity=larger if own else "raise", crc_bits=crc_bits if crc32 else None, levels=levels,
-                           energy=energy)
+        res = decode_batch(ctx, batch, layout if layout == PCM_INTERLEAVED else PCM_PLANAR, attempts=2, capacity=capacity,
+                           crc_bits=crc_bits if crc32 else None, levels=levels, energy=energy)
         pcm, infos, digests = res[:3]
         return ((pcm, infos, digests) if crc32 else (pcm, infos)) + tuple(res[3:])
-    finally:
-        if own:
-            made[0].close()
 
 
 def decode_streams_concealed(streams, device=0, max_segments=None, lanes_per_segment=0, layout=PCM_PLANAR, init_fir=None,
@@ -1401,27 +1391,10 @@ def decode_streams_requantized(streams, bits_out, mode=RQ_TPDF, seed=0, device=0
     if layout not in (PCM_PLANAR, PCM_INTERLEAVED) or (wav and bits_out not in (16, 24)):
         raise HipError("decode_streams_requantized: EINVAL (an int32 layout; a payload has 16 or 24 bits)")
     batch = Batch(streams, device)
-    ctx, own = _context_for(ctx, batch, None, 0, layout)
-    made = [ctx]
-
-    def larger(found):
-        made[0].close()
-        made[0] = Context(device, batch.n, found + 64, 0, layout)
-        if presentation != PRESENT_FULL:
-            made[0].set_presentation(presentation)
-        return made[0]
-
-    try:
-        if presentation != PRESENT_FULL or not own:
-            ctx.set_presentation(presentation)
-        regions, infos, _ = decode_batch(ctx, batch, layout, attempts=2, capacity=larger if own else "raise", to_host=False)
-    finally:
-        if own:
-            made[0].close()
+    with _call_context(ctx, batch, None, 0, layout, presentation) as (ctx, capacity):
+        regions, infos, _ = decode_batch(ctx, batch, layout, attempts=2, capacity=capacity, to_host=False)
     n = len(infos)
-    frames = [0 if inf.status & ST["OVERFLOW"] else min(int(inf.pcm_frames), r) for inf, r in zip(infos, regions.rows)]
-    desc = [(o, r, f, c) for o, r, f, c in zip(regions.out_off, regions.rows, frames, regions.channels)]
-    depth = [BITS_OF_CODE.get(int(inf.group0_bps), 0) for inf in infos]
+    frames, desc, depth = _decoded_lists(infos, regions)
     wav_layout = PCM_WAV24 if bits_out == 24 else PCM_WAV16
     d_wav = w_off = None
     if wav:
@@ -1469,16 +1442,7 @@ def decode_streams_decimated(streams, ratio, device=0, layout=PCM_PLANAR, ctx=No
     if layout not in (PCM_PLANAR, PCM_INTERLEAVED) or ratio not in (2, 4):
         raise HipError("decode_streams_decimated: EINVAL (an int32 layout, a ratio of 2 or 4)")
     batch = Batch(streams, device)
-    ctx, own = _context_for(ctx, batch, None, 0, layout)
-    made = [ctx]
     rates = []
-
-    def larger(found):
-        made[0].close()
-        made[0] = Context(device, batch.n, found + 64, 0, layout)
-        if presentation != PRESENT_FULL:
-            made[0].set_presentation(presentation)
-        return made[0]
 
     def decode(c, *args):
         # the rates are the index's: a batch that cannot be divided costs no decode
@@ -1490,18 +1454,10 @@ def decode_streams_decimated(streams, ratio, device=0, layout=PCM_PLANAR, ctx=No
             rates.append(rate // ratio)
         return Context.decode(c, *args)
 
-    try:
-        if presentation != PRESENT_FULL or not own:
-            ctx.set_presentation(presentation)
-        regions, infos, _ = decode_batch(ctx, batch, layout, attempts=2, capacity=larger if own else "raise", decode=decode,
-                                         to_host=False)
-    finally:
-        if own:
-            made[0].close()
+    with _call_context(ctx, batch, None, 0, layout, presentation) as (ctx, capacity):
+        regions, infos, _ = decode_batch(ctx, batch, layout, attempts=2, capacity=capacity, decode=decode, to_host=False)
     n = len(infos)
-    frames = [0 if inf.status & ST["OVERFLOW"] else min(int(inf.pcm_frames), r) for inf, r in zip(infos, regions.rows)]
-    desc = [(o, r, f, c) for o, r, f, c in zip(regions.out_off, regions.rows, frames, regions.channels)]
-    depth = [BITS_OF_CODE.get(int(inf.group0_bps), 0) for inf in infos]
+    _, desc, depth = _decoded_lists(infos, regions)
     desc_out, words = decim_desc_out(desc, ratio)
     import torch
     d_out = torch.zeros(words, dtype=torch.int32, device=regions.dev)

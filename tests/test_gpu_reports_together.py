@@ -1,6 +1,7 @@
 """The PCM digest and the level report side by side (csrc/pcm_report_run.h, csrc/disc_reader.c piece_reports): on a context
 they share one descriptor array, one result block and one workspace, and the disc tier makes both of a piece in one block
-on the device -- so each must come out as it does alone, whatever the other left behind.  Every comparison is exact."""
+on the device -- so each must come out as it does alone, whatever the other left behind.  The same holds of all six passes
+behind a decode, which share one staging path (report_of_decode).  Every comparison is exact."""
 import ctypes
 import tempfile
 import zlib
@@ -8,7 +9,12 @@ import zlib
 import numpy as np
 import pytest
 
+from tests import compare_model as cm
+from tests import decimate_model as dm
+from tests import digest_model as dgm
+from tests import energy_model as em
 from tests import levels_model as lm
+from tests import requant_model as rm
 from tests.test_disc_api import _titles
 from tests.test_gpu_digest_disc import window_sectors
 
@@ -61,6 +67,69 @@ def test_interleaved_on_one_context(pkg, oracle, layout):
         assert [p.shape for p in pcm] == [(2, f)] and f == 3 * AU
         assert ctx.pcm_crc32(*out.ptrs, 24, stream=st) == _digests(oracle, pcm, 24)
         assert ctx.pcm_levels(*out.ptrs, 24, stream=st) == [lm.levels(pcm[0], 24)]
+    finally:
+        ctx.close()
+
+
+def _six_passes(hd, ctx, out, st, pcm, infos):
+    """Every Context.pcm_* call on one decoded batch, interleaved: energy (B = 64), digest 24, decimate by 2 into a second
+    tensor, levels 24, compare against a clone with one value changed, requantize 24 -> 16 in place, digest 16, levels 16,
+    energy -- each exactly its model's of the host copy of the PCM as it was at that point"""
+    import torch
+    lay, n = out.layout, len(pcm)
+
+    def energy(now):
+        assert ctx.pcm_energy(*out.ptrs, 64, stream=st) == [em.energy_fast(p, 64) for p in now]
+
+    def digest(now, bits):
+        want = [(zlib.crc32(dgm.wav_payload(p, bits)), p.size * (bits // 8)) for p in now]
+        assert ctx.pcm_crc32(*out.ptrs, bits, stream=st) == want
+
+    energy(pcm)
+    digest(pcm, 24)
+    desc = [(o, r, p.shape[1], c) for o, r, p, c in zip(out.out_off, out.rows, pcm, out.channels)]
+    desc_low, words = hd.decim_desc_out(desc, 2)
+    d_low = torch.full((words,), 0x5A5A5A5A, dtype=torch.int32, device=out.dev)
+    low = [dm.decimate_np(p, hd.decim_taps(2), 2, 24) for p in pcm]
+    assert ctx.pcm_decimate(*out.ptrs, 2, 24, d_low.data_ptr(), lay, [d[0] for d in desc_low], [d[1] for d in desc_low],
+                            stream=st) == [dm.report(p.shape[1], w.shape[1], cl) for p, (w, cl) in zip(pcm, low)]
+    got = hd.cut_regions(d_low.cpu().numpy(), *[[d[k] for d in desc_low] for k in (0, 1)], out.channels,
+                         [d[2] for d in desc_low], lay)
+    assert all(np.array_equal(g, w) for g, (w, _) in zip(got, low))
+    assert ctx.pcm_levels(*out.ptrs, 24, stream=st) == [lm.levels(p, 24) for p in pcm]
+    # side B: the decode's buffer with the last stream's value at (channel 1, frame 70) one higher
+    other, c, f = [p.copy() for p in pcm], 1, 70
+    other[-1][c, f] += 1
+    d_other = out.d_pcm.clone()
+    d_other[out.out_off[-1] + (f * out.channels[-1] + c if lay == hd.PCM_INTERLEAVED else c * out.rows[-1] + f)] += 1
+    diffs = ctx.pcm_compare(*out.ptrs, d_other, lay, desc, 0, stream=st)
+    assert diffs == [cm.diff(a, b, 0) for a, b in zip(pcm, other)] and [d["diff_frames"] for d in diffs] == [0] * (n - 1) + [1]
+    frame0 = [3, 0, 2 ** 40 - 5][:n]
+    want = [rm.requant_np(p, 24, 16, rm.TPDF, 77, f0) for p, f0 in zip(pcm, frame0)]
+    assert ctx.pcm_requantize(*out.ptrs, 24, 16, hd.RQ_TPDF, seed=77, frame0=frame0, stream=st) == \
+        [rm.report(p.shape[1], cl) for p, (_, cl) in zip(pcm, want)]
+    pcm16 = out.to_host(infos)
+    assert all(np.array_equal(a, w) for a, (w, _) in zip(pcm16, want))
+    digest(pcm16, 16)
+    assert ctx.pcm_levels(*out.ptrs, 16, stream=st) == [lm.levels(p, 16) for p in pcm16]
+    energy(pcm16)
+
+
+@pytest.mark.parametrize("layout", ["planar", "interleaved"])
+def test_all_six_passes_on_one_context(pkg, layout):
+    """the six passes share one staging path and one result block with six different layouts: each comes out as it does
+    alone, and a one-stream batch behind the longer one shows nothing stale"""
+    hd, syn = pkg.hipdec, pkg.synth
+    lay = {"planar": hd.PCM_PLANAR, "interleaved": hd.PCM_INTERLEAVED}[layout]
+    streams = [syn.stream(syn.make_cfg(assignment=a, rate_code=1, n_substreams=1, n_aus=n), 40 + i)[0]
+               for i, (a, n) in enumerate([(1, 1), (1, 60), (12, 60)])]
+    short = syn.stream(syn.make_cfg(assignment=1, rate_code=1, n_substreams=1, n_aus=3), 50)[0]
+    ctx = hd.Context(0, 3, 4096, 0, lay)
+    try:
+        for batch, shapes in ((streams, [(2, AU), (2, 60 * AU), (6, 60 * AU)]), ([short], [(2, 3 * AU)])):
+            out, st, pcm = _decode(hd, ctx, batch, lay)
+            assert [p.shape for p in pcm] == shapes
+            _six_passes(hd, ctx, out, st, pcm, ctx.stream_info(stream=st))
     finally:
         ctx.close()
 
