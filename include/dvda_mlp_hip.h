@@ -190,6 +190,11 @@ int dvda_mlp_hip_decode_async(dvda_mlp_hip_ctx *ctx, int32_t *d_pcm, const uint6
  *            a fresh decoder (zero FIR / IIR history, no parameters carried) -- the PCM the reference returns for the
  *            bytes from that sync on.  Damage behind it: the same again (at most 4 decode rounds; what is still
  *            damaged after the last is concealed whole)
+ *   reach    the first round is the caller's decode; each of the three behind it decodes the ranges planned so far.  A
+ *            plan holds 16 ranges, the last of them open to the stream's end and planned again after its own decode.  So
+ *            with damage that the units' checks locate a stream keeps 45 ranges, and a 46th when nothing behind it is
+ *            damaged; what lies behind is one span with DVDA_CONCEAL_ROUNDS.  Damage behind a resume point that only the
+ *            range's own decode finds (no check data) costs that range one round more
  *   silence  g = (t_r - t_k - n_k) mod 65536 PCM frames between the last kept unit (16-bit input timing t_k, n_k
  *            frames) and the resume unit (t_r), plus 65536 w, w >= 0 the integer that brings the span's bytes per
  *            frame closest to the stream's mean over its kept ranges; 0 frames in front of the first usable major

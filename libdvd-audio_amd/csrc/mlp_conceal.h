@@ -20,6 +20,9 @@ namespace mlp {
 // first block continues the FIR history (DVDA_ST_CHAINED) reads history the reference never had there; it is decoded
 // with zero history, as the oracle decodes it, and that is what conceal mode hands out
 constexpr uint32_t CONCEAL_DAMAGE = 0x1FDu | (1u << 16);
+// what the fast pass leaves to the sequential pass, which decodes a stream in order and stops at its first damage: behind
+// that damage such a segment's status is all there is, and a damaged unit can be what made the segment look so
+constexpr uint32_t CONCEAL_DEFERRED = (1u << 17) | (1u << 25);      // DVDA_ST_TIMING | DVDA_ST_SEQ
 constexpr uint32_t CONCEAL_MAX_RANGES = 16;     // kept ranges one plan holds; a stream with more is planned again
                                                 // from the last one in the next round
 constexpr uint32_t CONCEAL_MAX_WALK = 1u << 20; // access units one walk over a damaged segment checks at most
@@ -206,7 +209,10 @@ __global__ __launch_bounds__(64) void k_conceal_plan(const uint8_t *__restrict__
                 nxt++;
             const uint64_t lim = (nxt < n_cand && seg[nxt].stream == s) ? seg[nxt].off : s_end;
             const uint32_t st = (seg_status[h] | r.flags) & ~SEG_DEAD;
-            const bool damaged = fresh ? (st & CONCEAL_DAMAGE & ~(1u << 0)) != 0 : (st & CONCEAL_DAMAGE) != 0;
+            // (behind damage the units of a segment left to the sequential pass are checked like those of one that reports
+            //  damage: CONCEAL_DEFERRED)
+            const bool damaged = fresh ? (st & ((CONCEAL_DAMAGE & ~(1u << 0)) | CONCEAL_DEFERRED)) != 0
+                                       : (st & CONCEAL_DAMAGE) != 0;
             if (damaged) {
                 uint64_t p = r.off;
                 uint32_t fail = 0;

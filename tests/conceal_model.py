@@ -16,6 +16,9 @@ import numpy as np
 ORA_DAMAGE = 0x1FD          # oracle status bits that mark damage (all but SYNC_CHANGE and ENVELOPE: a fresh decoder at a
                             # major sync that continues the FIR history is outside the reference's envelope, not damaged)
 LEADING, TRAILING = 1, 2    # DVDA_CONCEAL_* span flags
+ROUNDS = 4                  # DVDA_CONCEAL_ROUNDS: the span holds a range still damaged after the last decode round
+LIMITS = (16, 4)            # (CONCEAL_MAX_RANGES, CONCEAL_ROUNDS) of csrc/mlp_conceal.h: tests/test_conceal_cases_model.py
+                            # holds them to the headers
 SYNC_PARAMS = 0x00FFFFFF
 
 
@@ -129,10 +132,55 @@ def chain(D, a):
     return out, p
 
 
-def kept_ranges(D, nch, rows_per_au, oracle, cap=None):
-    """-> list of (a, b, frames, t_first, t_end): the kept byte ranges of D under the rule"""
+def range_end(D, r, nch, oracle, cap, fresh=False):
+    """-> where the range that a decoder opens at the usable major sync r of D ends (len(D): it runs to the end).
+    fresh=False: the rule -- in front of the first unit whose own checks fail, or, when the oracle stops at a unit in front
+    of that one, at the major sync of that unit's segment.  fresh=True: what k_conceal_plan can say of a range behind
+    damage before the range has been decoded by itself -- the units' own checks only."""
+    offs, chain_end = chain(D, r)
+    S = u8(D, r + 20) >> 4
+
+    def bad(e):
+        return oracle.decode(D[r:e], nch, cap)[2] & ORA_DAMAGE
+
+    unframed = chain_end + 4 <= len(D) and au_size(D, chain_end) < 4     # not a cut tail: a broken header
+    if not fresh and not unframed and not bad(chain_end):
+        # (the oracle verifies every unit's check data: nothing to look for unit by unit)
+        u_c = None
+    else:
+        # the first unit whose own framing / check data fails
+        u_c = next((k for k, o in enumerate(offs) if unit_check(D, o, S)), None)
+    if u_c is None and unframed:
+        u_c = len(offs)
+        offs = offs + [chain_end]
+    ends = offs[1:u_c + 1] if u_c is not None else offs[1:] + [chain_end]
+    # the first unit the oracle's decode fails on in front of it (the oracle drops a failing unit and goes on:
+    # the shortest failing prefix says which one)
+    u_d = None
+    if not fresh and ends and bad(ends[-1]):
+        lo, hi = 0, len(ends) - 1
+        while lo < hi:
+            mid = (lo + hi) // 2
+            if bad(ends[mid]):
+                hi = mid
+            else:
+                lo = mid + 1
+        u_d = lo
+    if u_d is not None and (u_c is None or u_d < u_c):
+        # nothing the unit says: its segment (from the major sync in front of it) is damaged whole
+        return max(o for o in offs[:u_d + 1] if is_sync(D, o))
+    if u_c is not None:
+        return offs[u_c]                        # the unit itself is damaged
+    return len(D)
+
+
+def kept_ranges(D, nch, rows_per_au, oracle, cap=None, limits=None):
+    """-> list of (a, b, frames, t_first, t_end): the kept byte ranges of D under the rule
+    limits=(max_ranges, rounds): only those the library's plan and rounds reach (limited_ranges), without their flags"""
     D = np.asarray(D, np.uint8)
     cap = cap or (len(D) + 4096) * 2
+    if limits is not None:
+        return [r[:5] for r in limited_ranges(D, nch, oracle, cap, limits)[0]]
     syncs = sync_offsets(D)
     if not syncs:
         return []
@@ -142,42 +190,7 @@ def kept_ranges(D, nch, rows_per_au, oracle, cap=None):
         r = next((p for p in syncs if p >= bound and can_resume(D, p, want)), None)
         if r is None:
             return out
-        offs, chain_end = chain(D, r)
-        S = u8(D, r + 20) >> 4
-
-        def bad(e):
-            return oracle.decode(D[r:e], nch, cap)[2] & ORA_DAMAGE
-
-        unframed = chain_end + 4 <= len(D) and au_size(D, chain_end) < 4     # not a cut tail: a broken header
-        if not unframed and not bad(chain_end):
-            # (the oracle verifies every unit's check data: nothing to look for unit by unit)
-            u_c = None
-        else:
-            # the first unit whose own framing / check data fails
-            u_c = next((k for k, o in enumerate(offs) if unit_check(D, o, S)), None)
-        if u_c is None and unframed:
-            u_c = len(offs)
-            offs = offs + [chain_end]
-        ends = offs[1:u_c + 1] if u_c is not None else offs[1:] + [chain_end]
-        # the first unit the oracle's decode fails on in front of it (the oracle drops a failing unit and goes on:
-        # the shortest failing prefix says which one)
-        u_d = None
-        if ends and bad(ends[-1]):
-            lo, hi = 0, len(ends) - 1
-            while lo < hi:
-                mid = (lo + hi) // 2
-                if bad(ends[mid]):
-                    hi = mid
-                else:
-                    lo = mid + 1
-            u_d = lo
-        if u_d is not None and (u_c is None or u_d < u_c):
-            # nothing the unit says: its segment (from the major sync in front of it) is damaged whole
-            kept_end = max(o for o in offs[:u_d + 1] if is_sync(D, o))
-        elif u_c is not None:
-            kept_end = offs[u_c]                    # the unit itself is damaged
-        else:
-            kept_end = len(D)
+        kept_end = range_end(D, r, nch, oracle, cap)
         if kept_end > r:
             # behind the range's last unit: its first unit's input timing + the PCM frames the range decodes to
             _, frames, _ = oracle.decode(D[r:kept_end], nch, cap)
@@ -185,6 +198,91 @@ def kept_ranges(D, nch, rows_per_au, oracle, cap=None):
         if kept_end >= len(D):
             return out
         bound = kept_end + 2
+
+
+def plan(P, nch, oracle, cap, max_ranges):
+    """k_conceal_plan on a piece P (a caller's stream, or a range decoded again as a stream of its own) whose decode
+    reported damage -> [(a, b)] relative to P.  A range that opens at the piece's first byte was decoded with the state a
+    fresh decoder has there: the whole rule ends it.  A range behind damage was not (`fresh` in the kernel): only its
+    units' own checks end it, and its decode is judged in the next round.  The plan's last slot is an open range to the
+    piece's end.
+    (The kernel checks the units of a segment only when the segment's decode status gives a reason: a damage bit, or that
+    the fast pass left it to the sequential pass, which never got there.  The model checks every unit; the two agree as
+    long as a unit that fails its checks makes its segment report one or the other, and the GPU file's 50 isolated flips
+    hold the library to that: a flip can make a unit's timing look non-standard, DVDA_ST_TIMING alone.)"""
+    syncs = sync_offsets(P)
+    if not syncs:
+        return []
+    want = packed_sync(P, syncs[0])
+    out, bound = [], 0
+    while True:
+        r = next((p for p in syncs if p >= bound and can_resume(P, p, want)), None)
+        if r is None:
+            return out
+        if len(out) + 1 == max_ranges:
+            return out + [(r, len(P))]
+        kept_end = range_end(P, r, nch, oracle, cap, fresh=r != 0)
+        if kept_end > r:
+            out.append((r, kept_end))
+        if kept_end >= len(P):
+            return out
+        bound = kept_end + 2
+
+
+def limited_ranges(D, nch, oracle, cap, limits):
+    """The rule as conceal_run reaches it -> ([(a, b, frames, t_first, t_end, flags)], tail_flags); flags: the
+    DVDA_CONCEAL_* flags of the span in front of the range beyond LEADING / TRAILING, tail_flags: of the span behind the
+    last one.
+
+    Round 0 plans the stream (plan: at most max_ranges - 1 closed ranges and one open one).  Each of the rounds 1 ..
+    rounds - 1 decodes every range not yet known to be clean as a stream of its own; a clean one is kept; a damaged one
+    is planned again (the same plan, on the range) and its ranges go into the next round -- except in the last round,
+    where nothing is planned any more: the damaged range is concealed whole, and the span it falls into carries ROUNDS.
+
+    How far that reaches, for D isolated damages that the units' own checks locate (every plan is final then): the
+    unlimited rule keeps D + 1 ranges.  Round 0 plans ranges 0 .. 14 closed and range 15 open; round 1 decodes those 16,
+    the open one is damaged when D > 15 and is planned again: 15 .. 29 closed, 30 open; round 2 decodes those 16 and
+    plans 30 .. 44 closed, 45 open; round 3, the last, decodes those 16 and plans nothing.  So rounds 1 .. 3 keep
+    (max_ranges - 1) * (rounds - 1) = 45 closed ranges, and the open range of round 3 is kept only when it is clean,
+    which is when it is the stream's last range: D + 1 <= 46.  D <= 14 needs no open range at all, D = 15 has a clean
+    open range in round 1, D = 16 .. 30 need round 2 (30: clean open range), D = 31 .. 45 round 3 (45: clean open
+    range), D >= 46 leaves everything from range 45's first byte on as one TRAILING | ROUNDS span.
+
+    A range behind damage that holds damage its units' checks do not locate costs a round of its own: the plan passes
+    over it, the range's own decode finds it, and the range is planned again."""
+    max_ranges, rounds = limits
+    items = [[a, b, 0, 0] for a, b in plan(D, nch, oracle, cap, max_ranges)]      # a, b, state (1: clean), flags
+    tail_flags = 0
+    for rnd in range(1, rounds):
+        if all(it[2] for it in items):
+            break
+        nv, carry = [], 0
+        for a, b, state, flags in items:
+            flags |= carry
+            carry = 0
+            if state:
+                nv.append([a, b, 1, flags])
+            elif not oracle.decode(D[a:b], nch, cap)[2] & ORA_DAMAGE:
+                nv.append([a, b, 1, flags])
+            elif rnd + 1 == rounds:
+                carry = flags | ROUNDS
+            else:
+                sub = plan(D[a:b], nch, oracle, cap, max_ranges)
+                nv += [[a + x, a + y, 0, flags if k == 0 else 0] for k, (x, y) in enumerate(sub)]
+        tail_flags |= carry
+        items = nv
+    out = []
+    for a, b, state, flags in items:
+        assert state, "a range no round decoded"
+        frames = oracle.decode(D[a:b], nch, cap)[1]
+        out.append((a, b, frames, au_timing(D, a), (au_timing(D, a) + frames) & 0xFFFF, flags))
+    return out, tail_flags
+
+
+def kept_units(D, R):
+    """access units in the kept ranges R of D: what mlp_frames counts in conceal mode"""
+    D = np.asarray(D, np.uint8)
+    return sum(len(chain(D[r[0]:r[1]], 0)[0]) for r in R)
 
 
 def gap_frames(B, g, m):
@@ -201,30 +299,36 @@ def gap_frames(B, g, m):
     return best[0]
 
 
-def conceal(D, nch, rows_per_au, oracle, cap=None):
-    """-> (pcm int32 [nch, frames], spans [(first_frame, frames, byte_off, byte_end, flags)]) under the rule"""
+def conceal(D, nch, rows_per_au, oracle, cap=None, limits=None):
+    """-> (pcm int32 [nch, frames], spans [(first_frame, frames, byte_off, byte_end, flags)]) under the rule
+    limits=(max_ranges, rounds), the library's LIMITS: under the rule as far as its plans and rounds reach it
+    (limited_ranges) -- what no round decoded clean is concealed, its span carries ROUNDS, and the mean bytes per frame
+    is that of the ranges kept"""
     D = np.asarray(D, np.uint8)
     cap = cap or (len(D) + 4096) * 2
-    R = kept_ranges(D, nch, rows_per_au, oracle, cap)
+    if limits is None:
+        R, tail_flags = [r + (0,) for r in kept_ranges(D, nch, rows_per_au, oracle, cap)], 0
+    else:
+        R, tail_flags = limited_ranges(D, nch, oracle, cap, limits)
     if not R:
-        return np.zeros((nch, 0), np.int32), [(0, 0, 0, len(D), LEADING | TRAILING)]
-    K = sum(b - a for a, b, _, _, _ in R)
-    F = sum(f for _, _, f, _, _ in R)
+        return np.zeros((nch, 0), np.int32), [(0, 0, 0, len(D), LEADING | TRAILING | tail_flags)]
+    K = sum(r[1] - r[0] for r in R)
+    F = sum(r[2] for r in R)
     m = K / F if K and F else 0.0
     parts, spans, pos = [], [], 0
-    for k, (a, b, f, t_first, _) in enumerate(R):
+    for k, (a, b, f, t_first, _, flags) in enumerate(R):
         if k == 0:
             if a > 0:
-                spans.append((0, 0, 0, a, LEADING))
+                spans.append((0, 0, 0, a, LEADING | flags))
         else:
             pb, pt_end = R[k - 1][1], R[k - 1][4]
             G = gap_frames(a - pb, (t_first - pt_end) & 0xFFFF, m)
-            spans.append((pos, G, pb, a, 0))
+            spans.append((pos, G, pb, a, flags))
             parts.append(np.zeros((nch, G), np.int32))
             pos += G
         pcm, _, _ = oracle.decode(D[a:b], nch, cap)
         parts.append(pcm)
         pos += f
     if R[-1][1] < len(D):
-        spans.append((pos, 0, R[-1][1], len(D), TRAILING))
+        spans.append((pos, 0, R[-1][1], len(D), TRAILING | tail_flags))
     return np.concatenate(parts, axis=1), spans
