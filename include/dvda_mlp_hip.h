@@ -293,6 +293,19 @@ int dvda_mlp_hip_set_presentation(dvda_mlp_hip_ctx *ctx, uint32_t presentation);
 /* Device time (ms) of the strip kernels of the last dvda_mlp_hip_index under DVDA_PRESENT_SUBSTREAM0, the source bytes
  * they walked and the bytes of the presentation streams they wrote (blocks until they have run). */
 int dvda_mlp_hip_present_time(dvda_mlp_hip_ctx *ctx, double *ms, uint64_t *bytes_in, uint64_t *bytes_out);
+/* Diagnostic: the presentation buffer of the last dvda_mlp_hip_index under DVDA_PRESENT_SUBSTREAM0, read back to the host
+ * (blocks on `stream`; changes nothing in the context).  Every argument but ctx may be NULL / 0:
+ *   offsets, lengths   [n] (n clamped to the streams of the index): where presentation stream i starts in the buffer
+ *                      (a multiple of 16: the running sum of the lengths in front of it, each rounded up to 16) and its
+ *                      length in bytes -- 0 for a stream that has no presentation
+ *   readable           bytes of the buffer the call hands out: what the second index is told to scan (the source's
+ *                      total_bytes rounded up to 16, plus 16 per stream) and the 64 bytes behind it that it may read.
+ *                      All of them behind the end of a stream -- the padding up to the next stream's start, and
+ *                      everything behind the last stream -- are zero
+ *   bytes              [count]: bytes [first, first + count) of the buffer; first + count > readable: DVDA_HIP_EINVAL
+ * DVDA_HIP_ESTATE unless the context is indexed under DVDA_PRESENT_SUBSTREAM0. */
+int dvda_mlp_hip_present_read(dvda_mlp_hip_ctx *ctx, uint64_t *offsets, uint64_t *lengths, uint32_t n, uint64_t *readable,
+                              uint8_t *bytes, uint64_t first, uint64_t count, void *stream);
 
 /* Sizes the workspaces of the passes behind the fast pass ahead of time (they only ever grow): chain passes for
  * `chain_segments` deferred segments holding `chain_pcm_frames` PCM frames in all (for titles whose restart points

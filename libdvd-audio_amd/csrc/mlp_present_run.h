@@ -120,6 +120,33 @@ extern "C" int dvda_mlp_hip_present_time(dvda_mlp_hip_ctx *c, double *ms, uint64
     return DVDA_HIP_OK;
 }
 
+// diagnostic: the presentation buffer as the second index reads it (the ranges it was given, and the bytes up to what it
+// scans plus the 64 behind that); copies only, no state of the context touched
+extern "C" int dvda_mlp_hip_present_read(dvda_mlp_hip_ctx *c, uint64_t *offsets, uint64_t *lengths, uint32_t n,
+                                         uint64_t *readable, uint8_t *bytes, uint64_t first, uint64_t count, void *stream_)
+{
+    if (!c)
+        return DVDA_HIP_EINVAL;
+    if (!pp_inner(c) || !c->indexed)
+        return DVDA_HIP_ESTATE;
+    const uint64_t limit = c->pp.bound + 64;
+    if (first > limit || count > limit - first || (count && !bytes))
+        return DVDA_HIP_EINVAL;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream_));
+    if (n > c->n_streams)
+        n = c->n_streams;
+    if (offsets && n)
+        HIP_TRY(hipMemcpy(offsets, c->pp.d_off64, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (lengths && n)
+        HIP_TRY(hipMemcpy(lengths, c->pp.d_len64, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (readable)
+        *readable = limit;
+    if (count)
+        HIP_TRY(hipMemcpy(bytes, c->pp.d_bytes + first, (size_t)count, hipMemcpyDeviceToHost));
+    return DVDA_HIP_OK;
+}
+
 // host copies of what the getters map with (once per index call; the caller has waited for `stream`)
 static int present_map(dvda_mlp_hip_ctx *c)
 {

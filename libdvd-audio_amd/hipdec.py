@@ -70,7 +70,7 @@ EXPORTS = ("dvda_mlp_hip_create", "dvda_mlp_hip_destroy", "dvda_mlp_hip_index", 
            "dvda_mlp_hip_shard", "dvda_mlp_hip_create_multi", "dvda_mlp_hip_destroy_multi",
            "dvda_mlp_hip_multi_devices", "dvda_mlp_hip_decode_multi", "dvda_mlp_hip_multi_device_time",
            "dvda_mlp_hip_set_conceal", "dvda_mlp_hip_conceal_spans", "dvda_mlp_hip_conceal_edges",
-           "dvda_mlp_hip_set_presentation", "dvda_mlp_hip_present_time",
+           "dvda_mlp_hip_set_presentation", "dvda_mlp_hip_present_time", "dvda_mlp_hip_present_read",
            "dvda_pcm_hip_crc32", "dvda_pcm_hip_crc32_workspace_words", "dvda_mlp_hip_pcm_crc32",
            "dvda_pcm_hip_crc32_combine",
            "dvda_pcm_hip_levels", "dvda_pcm_hip_levels_workspace_words", "dvda_mlp_hip_pcm_levels",
@@ -279,6 +279,7 @@ def lib():
         L.dvda_mlp_hip_segment_info.argtypes = [vp, u32, ctypes.POINTER(SegmentInfo), vp]
         L.dvda_mlp_hip_present_time.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(u64),
                                                 ctypes.POINTER(u64)]
+        L.dvda_mlp_hip_present_read.argtypes = [vp, vp, vp, u32, ctypes.POINTER(u64), vp, u64, u64, vp]
         L.dvda_mlp_hip_set_initial_fir.argtypes = [vp, vp]
         L.dvda_mlp_hip_segment_fir.argtypes = [vp, u32, vp, vp]
         L.dvda_mlp_hip_conceal_spans.argtypes = [vp, u32, ctypes.POINTER(ConcealSpan), u32, ctypes.POINTER(u32), vp]
@@ -414,6 +415,23 @@ class Context:
         _check(lib().dvda_mlp_hip_present_time(self._h, ctypes.byref(ms), ctypes.byref(a), ctypes.byref(b)),
                "dvda_mlp_hip_present_time")
         return float(ms.value), int(a.value), int(b.value)
+
+    def present_read(self, first=0, count=None, stream=0):
+        """dvda_mlp_hip_present_read (diagnostic): the presentation buffer of the last index under PRESENT_SUBSTREAM0 ->
+        (offsets, lengths: uint64 arrays per stream; readable: bytes of the buffer the call hands out; bytes
+        [first, first + count) of it as a uint8 array, count=None: up to `readable`).  Blocks on `stream`; HipError
+        (ESTATE) unless the context is indexed under the mode."""
+        n = self.n_streams
+        offs, lens = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        readable = ctypes.c_uint64()
+        fn = lib().dvda_mlp_hip_present_read
+        _check(fn(self._h, offs.ctypes.data, lens.ctypes.data, n, ctypes.byref(readable), None, 0, 0, stream),
+               "dvda_mlp_hip_present_read")
+        if count is None:
+            count = int(readable.value) - first
+        data = np.zeros(max(count, 0), np.uint8)
+        _check(fn(self._h, None, None, 0, None, data.ctypes.data, first, count, stream), "dvda_mlp_hip_present_read")
+        return offs, lens, int(readable.value), data
 
     def index(self, d_bytes_ptr, total_bytes, d_off_ptr, d_len_ptr, n_streams, stream=0):
         self.n_streams = n_streams
