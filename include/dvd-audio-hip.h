@@ -178,12 +178,27 @@ unsigned dvda_hip_reader_source_bits(const DVDA_Track_Reader *reader);
  * what decimating window by window needs.)  0 (default): off, a reader launches and allocates exactly as without. */
 struct dvda_pcm_decim_report;
 void dvda_hip_set_decimate(unsigned ratio);
-/* 1: the reader decimates, *out (may be NULL) = what the pass counted (frames in and out, per channel the values the
- * clamp changed); 0: it does not -- the option is off, the track's rate is not one it applies to, or `reader` is NULL;
- * nothing is written */
+/* 1: the reader decimates (also: as the first stage of dvda_hip_set_resample), *out (may be NULL) = what the pass
+ * counted (frames in and out, per channel the values the clamp changed); 0: it does not -- the option is off, the
+ * track's rate is not one it applies to, or `reader` is NULL; nothing is written */
 int dvda_hip_reader_decimated(const DVDA_Track_Reader *reader, struct dvda_pcm_decim_report *out);
-/* the rate the track has on the disc: dvda_sample_rate() unless the reader decimates; 0 for a NULL reader */
+/* the rate the track has on the disc: dvda_sample_rate() unless the reader decimates or resamples; 0 for a NULL reader */
 unsigned dvda_hip_reader_source_rate(const DVDA_Track_Reader *reader);
+/* rate 44100: track readers opened afterwards (per calling thread, read when the reader is opened, like
+ * dvda_hip_set_decimate) deliver a 48 / 96 / 192 kHz track at 44 100 Hz: the decoded int32 PCM is decimated by rate /
+ * 48 000 where that is above 1 (dvda_pcm_hip_decimate, at the track's depth), then resampled by 147 / 160 into a new
+ * buffer (dvda_pcm_hip_resample: the contract, an exact integer polyphase FIR with one rounding and a clamp at the track's
+ * depth, is in dvda_mlp_hip.h), and from there on the reader IS the 44.1 kHz track of ceil(147 F / 160) frames for the
+ * word-length reduction, the reports, the WAV payload, dvda_read, dvda_hip_reader_total_frames() and dvda_sample_rate()
+ * (44 100); dvda_hip_reader_source_rate() gives the disc's rate.  Any other track (the 44.1 kHz family) is handed out as
+ * it is.  Whole-track readers only, MLP and raw PCM: the open returns NULL for a track the reader would take in windows,
+ * in conceal mode, together with a non-zero dvda_hip_set_decimate, and for any value but 0 and 44100.  0 (default): off. */
+void dvda_hip_set_resample(unsigned rate);
+/* 1: the reader resamples, *out (may be NULL) = what the 48 -> 44.1 kHz pass counted (frames in at 48 kHz and out, per
+ * channel the values the clamp changed) -- where the track ran at 96 / 192 kHz, dvda_hip_reader_decimated gives the stage
+ * in front of it; 0: it does not -- the option is off, the track's rate is not one it applies to, or `reader` is NULL;
+ * nothing is written */
+int dvda_hip_reader_resampled(const DVDA_Track_Reader *reader, struct dvda_pcm_decim_report *out);
 /* on != 0: MLP track readers opened afterwards (per calling thread, read when the reader is opened, like
  * dvda_hip_set_wav_output) conceal a damaged track instead of refusing it: the track comes out as
  *     kept PCM ++ silence ++ PCM of a fresh decoder from the next usable major sync ++ ...

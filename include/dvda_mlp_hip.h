@@ -786,8 +786,8 @@ void dvda_pcm_hip_energy_total(const dvda_pcm_energy_block *blocks, uint64_t n, 
  * reports of two pieces join by adding `frames` and clipped[]; there is no combine function.
  *
  * Out of scope: noise shaping (error feedback is a serial nonlinear recurrence per channel), sample-rate conversion
- * (but see the decimation by 2 or 4 below), auto-blanking of digital silence (TPDF on silence is noise of +-1 LSB, as it
- * should be), float output, the streaming tier and dvda_mlp_hip_decode_multi.  The disc tier has it as
+ * (but see the decimation by 2 or 4 and the 48 -> 44.1 kHz resampler below), auto-blanking of digital silence (TPDF on
+ * silence is noise of +-1 LSB, as it should be), float output, the streaming tier and dvda_mlp_hip_decode_multi.  The disc tier has it as
  * dvda_hip_set_requantize (dvd-audio-hip.h). */
 #define DVDA_RQ_TRUNCATE 0u
 #define DVDA_RQ_ROUND    1u
@@ -875,9 +875,10 @@ int32_t dvda_pcm_hip_requant_value(int32_t v, uint64_t frame, uint32_t channel, 
  * is no combine function.  d_piece == NULL: whole tracks, frame0 = 0, no context.  before + after > frames (or frame0
  * above 2^62): the stream is not taken.
  *
- * Out of scope: conversion between the rate families (96 -> 44.1), upsampling, noise shaping, the WAV layouts on either
- * side (requantize behind it writes them), in place, the streaming tier and dvda_mlp_hip_decode_multi.  The disc tier
- * has it for tracks read whole: dvda_hip_set_decimate in dvd-audio-hip.h. */
+ * Out of scope: upsampling, noise shaping, the WAV layouts on either side (requantize behind it writes them), in place,
+ * the streaming tier and dvda_mlp_hip_decode_multi.  Between the rate families there is one step, 48 -> 44.1 kHz:
+ * dvda_pcm_hip_resample below (96 -> 44.1 is this pass by 2, then that one).  The disc tier has it for tracks read whole:
+ * dvda_hip_set_decimate in dvd-audio-hip.h. */
 #define DVDA_DCM_TILE_FRAMES 1024u      /* OUTPUT frames of a tile; tiles are aligned to the stream's first output frame */
 typedef struct dvda_pcm_decim_piece {
     uint64_t frame0;              /* absolute frame of the first own frame */
@@ -929,6 +930,82 @@ int dvda_mlp_hip_pcm_decimate(dvda_mlp_hip_ctx *ctx, const int32_t *d_pcm, const
 const int32_t *dvda_pcm_hip_decim_taps(uint32_t ratio, uint32_t *n);
 uint64_t dvda_pcm_hip_decim_out_frames(uint64_t frame0, uint64_t own, uint32_t ratio);
 int32_t dvda_pcm_hip_decim_value(const int32_t *window, uint32_t ratio, unsigned bits, int *clipped);
+
+/* ------------------------------------------------------------------ 48 kHz to 44.1 kHz: the resampler
+ * The decimation above stays inside a rate family; a CD runs at 44.1 kHz and most DVD-Audio discs sit in the 48 / 96 /
+ * 192 kHz family.  This pass crosses: 48 000 Hz in, 44 100 Hz out, ratio L / M = 147 / 160 and no other (96 / 192 kHz:
+ * decimate by 2 / 4 first).  Made on the device (csrc/pcm_resample.h).
+ *
+ * The contract; every figure exact.  One table g[147][96], int32, Q30, a committed constant (csrc/pcm_resample_taps.h;
+ * dvda_pcm_hip_resample_taps hands it out): 147 phases of 96 taps.  Recipe of tools/make_resample_taps.py:
+ * h_c(t) = (147/160) sinc((147/160) t) * I0(12 sqrt(1 - (t/48)^2)) / I0(12), t in input samples; g[p][i] =
+ * h_c(i - 47 - p/147); every phase normalised to sum 1, rint(. * 2^30), the phase's difference from 2^30 added to that
+ * phase's largest tap -- but the library's truth is the committed integers.  Every phase sums to exactly 2^30, so the gain
+ * at DC is exactly 1 at every output frame; g[147 - p][i] == g[p][95 - i] for p = 1 .. 146; from an FFT of the integers
+ * over the whole 147-times oversampled prototype, images included: passband 0 .. 0.4535 fs_out within +1.2e-5 / -0.9e-5 dB,
+ * stopband from 0.5465 fs_out upward at -118.2 dB (the decimator's class); the largest per-phase sum |g| is
+ * 2 561 819 644 < 2^32, so with |x| <= 2^31 |acc| + 2^29 < 2^63 for ANY int32 input: the arithmetic is plain int64 and
+ * cannot overflow.
+ *
+ * For channel c and output frame m (absolute, on the track's output grid), x[F][c] the input at absolute frame F:
+ *   q       = (160 m) div 147,   p = (160 m) mod 147
+ *   acc     = sum_{i = 0 .. 95} g[p][i] * x[q - 47 + i][c]                                (int64)
+ *   y[m][c] = clamp((acc + 2^29) >> 30, -2^(bits-1), 2^(bits-1) - 1)     bits in {16, 20, 24}; the shift is arithmetic
+ * x[F] = 0 wherever the region does not hold F: in front of the track's first frame, behind its last one, beyond the
+ * context a piece brought.  clipped[c] counts the values the clamp changed.  A track of F frames gives ceil(147 F / 160)
+ * frames.
+ *
+ * Pieces: dvda_pcm_decim_piece and dvda_pcm_decim_report as they are above.  A piece's outputs are the m with
+ * frame0 <= (160 m) div 147 < frame0 + own: dvda_pcm_hip_resample_out_frames(frame0, own) = ceil(147 (frame0 + own) / 160)
+ * - ceil(147 frame0 / 160) of them (a host function; the kernels ask the same one; 0 for frame0 / own above 2^62), and
+ * the pieces of a track add up to the track's ceil(147 F / 160).  Only the 47 context frames in front of the own frames
+ * and the 48 behind them matter.  A piece whose context on each side is at least 48 frames, or reaches the track's end on
+ * that side, gives exactly the frames the whole track gives at those m; the reports of two pieces join by adding.
+ * d_piece == NULL: whole tracks, frame0 = 0, no context.  before + after > frames (or frame0 above 2^62): the stream is
+ * not taken.
+ *
+ * Out of scope: any other ratio (upsampling, 44.1 -> 48, 96 -> 44.1 in one step), noise shaping, the WAV layouts on
+ * either side (requantize behind it writes them), in place, the streaming tier and dvda_mlp_hip_decode_multi.  The disc
+ * tier has it for tracks read whole: dvda_hip_set_resample in dvd-audio-hip.h. */
+#define DVDA_RSM_TILE_FRAMES 9408u      /* OUTPUT frames of a tile, 64 * 147; tiles are aligned to the stream's first output frame */
+
+/* The tier-free form, with the decimator's shapes.  Stream i: d_desc_in[i] in d_in (layout_in) -> d_desc_out[i] in d_out
+ * (layout_out), piece d_piece[i] (a NULL array: whole tracks), report d_report[i]; device arrays, n entries; each layout
+ * DVDA_PCM_PLANAR or DVDA_PCM_INTERLEAVED.  A stream is taken only when its input descriptor is one the reports take
+ * (channels 1..8, frames up to 2^40) and holds its context, and its output descriptor has the same channels, exactly
+ * out_frames frames and a stride >= frames; otherwise frames_in == frames_out == 0 is reported and nothing is written.
+ * Out of place only; any overlap is the caller's error.  Enqueued on `stream`: no host wait, no allocation.
+ * max_total_out_frames: a bound the host knows on the sum of the streams' OUTPUT frames; a stream whose tiles
+ * (DVDA_RSM_TILE_FRAMES output frames) fall outside it reports zeros, and its output region holds unspecified values
+ * inside its bounds and nothing outside them.  d_work: dvda_pcm_hip_resample_workspace_words(n, max_total_out_frames)
+ * uint32 words, which need not be cleared; no atomics, the report is the same from run to run.  Either side's off may
+ * have any 4-byte alignment and a planar stride any parity; nothing outside a region's `frames` is read, nothing outside
+ * the output region written.  The arguments are judged first, on any machine -- DVDA_HIP_EINVAL: bits outside {16, 20,
+ * 24}, a WAV layout on either side, a null pointer other than d_piece, work_words too small; DVDA_HIP_ECAPACITY: 2^31
+ * tiles or more -- then the device: DVDA_HIP_ENODEV without one. */
+size_t dvda_pcm_hip_resample_workspace_words(uint32_t n, uint64_t max_total_out_frames);
+int dvda_pcm_hip_resample(const int32_t *d_in, uint32_t layout_in, const dvda_pcm_crc_desc *d_desc_in,
+                          int32_t *d_out, uint32_t layout_out, const dvda_pcm_crc_desc *d_desc_out,
+                          const dvda_pcm_decim_piece *d_piece /* or NULL */, uint32_t n, unsigned bits,
+                          uint64_t max_total_out_frames, dvda_pcm_decim_report *d_report,
+                          uint32_t *d_work, size_t work_words, void *stream);
+
+/* behind dvda_mlp_hip_decode (blocks): as dvda_mlp_hip_pcm_decimate, the first n streams of the last decode, whole
+ * tracks taken as 48 kHz, resampled into d_dst (layout_dst: either int32 layout): stream i to the dword offset
+ * host_dst_off[i] with the planar stride host_dst_stride[i] (host arrays; a stride below the stream's output frames: the
+ * stream is not taken).  A stream that carries DVDA_ST_OVERFLOW reports zeros and nothing is written for it. */
+int dvda_mlp_hip_pcm_resample(dvda_mlp_hip_ctx *ctx, const int32_t *d_pcm, const uint64_t *d_out_off,
+                              const uint64_t *d_out_stride, unsigned bits, int32_t *d_dst, uint32_t layout_dst,
+                              const uint64_t *host_dst_off, const uint64_t *host_dst_stride,
+                              dvda_pcm_decim_report *host_report, uint32_t n, void *stream);
+
+/* Host helpers; none needs a device.  taps: the committed table, row p at [96 p .. 96 p + 95]; *phases / *taps (either
+ * may be NULL) = 147 / 96.  value: the contract above for one output value -- the text the kernel compiles -- from its
+ * window of 96 input values, window[47] the one at q, and its phase p; *clipped (may be NULL) = 1 when the clamp changed
+ * the value, else 0; a phase above 146, an invalid depth or a NULL window: returns 0 and sets *clipped = -1. */
+const int32_t *dvda_pcm_hip_resample_taps(uint32_t *phases, uint32_t *taps);
+uint64_t dvda_pcm_hip_resample_out_frames(uint64_t frame0, uint64_t own);
+int32_t dvda_pcm_hip_resample_value(const int32_t *window, uint32_t phase, unsigned bits, int *clipped);
 
 /* ------------------------------------------------------------------ tier B */
 /* The mlp.h mirror: same three calls, same meaning as reference src/mlp.h:29-42 /

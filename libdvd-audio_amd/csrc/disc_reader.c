@@ -52,6 +52,8 @@ struct reader_opts {
     unsigned long long rq_seed; /*   device, in front of its reports (dvda_hip_set_requantize, dvda_hip_reader_requantized) */
     unsigned dc_ratio;          /* != 0: a whole-track reader decimates the decoded PCM by 2 or 4 on the device, in front of
                                    all of the above (dvda_hip_set_decimate, dvda_hip_reader_decimated) */
+    unsigned rs_rate;           /* != 0 (44100): a whole-track reader brings a 48 / 96 / 192 kHz track to 44.1 kHz on the device,
+                                   in the decimation's place (dvda_hip_set_resample, dvda_hip_reader_resampled) */
 };
 static _Thread_local struct reader_opts t_opts;
 static _Thread_local int t_conceal_set;     /* dvda_hip_set_conceal() was called on this thread: DVDA_CONCEAL no longer counts */
@@ -68,6 +70,7 @@ void dvda_hip_set_requantize(unsigned bits_out, unsigned mode, unsigned long lon
     t_opts.rq_seed = seed;
 }
 void dvda_hip_set_decimate(unsigned ratio) { t_opts.dc_ratio = ratio; }
+void dvda_hip_set_resample(unsigned rate) { t_opts.rs_rate = rate; }
 void dvda_hip_set_conceal(int on)
 {
     t_opts.conceal = on != 0;
@@ -135,6 +138,13 @@ static int dc_applies(const struct reader_opts *o, unsigned rate_code)
     return dc_shift(o) != 0 && rate_of(rate_code) != 0 && (rate_code & 3) >= dc_shift(o);
 }
 
+/* does a reader opened with `o` resample a track whose rate has `rate_code`?  The 48 kHz family (bit 3 clear): 48 kHz as
+ * it is, 96 / 192 kHz decimated by 2 / 4 first.  Any other track is handed out as it is. */
+static int rs_applies(const struct reader_opts *o, unsigned rate_code)
+{
+    return o->rs_rate == 44100 && rate_of(rate_code) != 0 && !(rate_code & 8);
+}
+
 static void rep_reset(struct pcm_reports *r)
 {
     free(r->ng_blocks);
@@ -147,8 +157,10 @@ struct DVDA_Track_Reader_s {
     unsigned bps_code[2], rate_code[2], assignment;
     unsigned channels, status;
     unsigned src_bits;         /* != 0: the track's own depth, where the reader hands out fewer bits (dvda_hip_set_requantize) */
-    unsigned src_rate;         /* != 0: the track's own rate, where the reader hands out a lower one (dvda_hip_set_decimate) */
-    dvda_pcm_decim_report dc_rep;      /* ... and what the decimation counted */
+    unsigned src_rate;         /* != 0: the track's own rate, where the reader hands out a lower one (dvda_hip_set_decimate,
+                                  dvda_hip_set_resample) */
+    int dc_done, rs_done;      /* the track went through the decimation / the resampler */
+    dvda_pcm_decim_report dc_rep, rs_rep;      /* ... and what each counted */
     uint64_t frames, served, stride;
     int interleaved;           /* MLP tracks: frame-major [frame][channel] = the dvda_read order;
                                   PCM tracks: planar [channel][stride]; RIFF-WAVE channel order */
@@ -473,7 +485,9 @@ static void reports_join(struct pcm_reports *track, const struct pcm_reports *pi
 static int track_decimate(int32_t **d_pcm, uint32_t layout, unsigned bits, uint64_t *stride, uint64_t *frames, unsigned ch,
                           unsigned ratio, dvda_pcm_decim_report *rep)
 {
-    const uint64_t out_frames = dvda_pcm_hip_decim_out_frames(0, *frames, ratio);
+    /* (ratio 0: the same steps around dvda_pcm_hip_resample, 48 kHz to 44.1 kHz: dvda_hip_set_resample) */
+    const uint64_t out_frames = ratio ? dvda_pcm_hip_decim_out_frames(0, *frames, ratio)
+                                      : dvda_pcm_hip_resample_out_frames(0, *frames);
     uint64_t out_stride = (out_frames + 3) & ~(uint64_t)3;
     if (out_stride == 0)
         out_stride = 4;
@@ -481,14 +495,19 @@ static int track_decimate(int32_t **d_pcm, uint32_t layout, unsigned bits, uint6
         dvda_pcm_crc_desc in, out;
         dvda_pcm_decim_report rep;
     } blk = {{0, *stride, *frames, ch, 0}, {0, out_stride, out_frames, ch, 0}, {0, 0, {0}}};
-    const size_t words = dvda_pcm_hip_decimate_workspace_words(1, out_frames);
+    const size_t words = ratio ? dvda_pcm_hip_decimate_workspace_words(1, out_frames)
+                               : dvda_pcm_hip_resample_workspace_words(1, out_frames);
     int32_t *d_out = NULL;
     uint8_t *d = NULL;
     int ok = dev_alloc((void **)&d_out, (size_t)out_stride * ch * sizeof(int32_t));
     if (ok && out_frames) {
         ok = dev_block_open(&d, &blk, sizeof(blk), words * sizeof(uint32_t)) &&
-             dvda_pcm_hip_decimate(*d_pcm, layout, DEV_AT(d, blk, in), d_out, layout, DEV_AT(d, blk, out), NULL, 1, ratio, bits,
-                                   out_frames, DEV_AT(d, blk, rep), (uint32_t *)(d + sizeof(blk)), words, NULL) == DVDA_HIP_OK;
+             (ratio ? dvda_pcm_hip_decimate(*d_pcm, layout, DEV_AT(d, blk, in), d_out, layout, DEV_AT(d, blk, out), NULL, 1,
+                                            ratio, bits, out_frames, DEV_AT(d, blk, rep), (uint32_t *)(d + sizeof(blk)), words,
+                                            NULL)
+                    : dvda_pcm_hip_resample(*d_pcm, layout, DEV_AT(d, blk, in), d_out, layout, DEV_AT(d, blk, out), NULL, 1,
+                                            bits, out_frames, DEV_AT(d, blk, rep), (uint32_t *)(d + sizeof(blk)), words,
+                                            NULL)) == DVDA_HIP_OK;
         ok = dev_block_close(d, &blk, sizeof(blk), ok) && blk.rep.frames_out == out_frames;
     }
     if (!ok) {
@@ -513,9 +532,23 @@ static int track_passes(DVDA_Track_Reader *r, const struct reader_opts *o, int32
 {
     const unsigned bits = bits_of(r->bps_code[0]);
     r->stride = stride;
-    if (dc_applies(o, r->rate_code[0])) {
+    if (rs_applies(o, r->rate_code[0])) {
+        /* 96 / 192 kHz: by 2 / 4 to 48 kHz at the track's depth first; then 48 kHz to 44.1 kHz into a new buffer */
+        const unsigned shift = r->rate_code[0] & 3;
+        if (shift) {
+            if (!track_decimate(d_pcm, layout, bits, &r->stride, &r->frames, r->channels, 1u << shift, &r->dc_rep))
+                return 0;
+            r->dc_done = 1;
+        }
+        if (!track_decimate(d_pcm, layout, bits, &r->stride, &r->frames, r->channels, 0, &r->rs_rep))
+            return 0;
+        r->rs_done = 1;
+        r->src_rate = rate_of(r->rate_code[0]);
+        r->rate_code[0] = 8;            /* 44 100 Hz */
+    } else if (dc_applies(o, r->rate_code[0])) {
         if (!track_decimate(d_pcm, layout, bits, &r->stride, &r->frames, r->channels, o->dc_ratio, &r->dc_rep))
             return 0;
+        r->dc_done = 1;
         r->src_rate = rate_of(r->rate_code[0]);
         r->rate_code[0] -= dc_shift(o);
     }
@@ -779,7 +812,7 @@ static int decode_stream(struct track_bufs *b, uint64_t len, const int32_t *fir,
         stride = 4;
     if (*wav_bits < 0) {
         const unsigned bits = bits_of(info->group0_bps);
-        *wav_bits = (bits == 16 || bits == 24) && !(rq && (rq_applies(rq, bits) || dc_applies(rq, info->group0_rate)))
+        *wav_bits = (bits == 16 || bits == 24) && !(rq && (rq_applies(rq, bits) || dc_applies(rq, info->group0_rate) || rs_applies(rq, info->group0_rate)))
                         ? (int)bits : 0;
     }
     const unsigned wbits = (unsigned)*wav_bits;
@@ -906,7 +939,7 @@ static DVDA_Track_Reader *open_mlp(struct aob_set *aobs, const DVDA_Track *k, co
     if (!mlp_info_to_reader(r, &info, o->present))
         goto fail;
     /* (a track that is decimated has int32 PCM: decode_stream saw the option) */
-    if ((wav_bits && dc_applies(o, info.group0_rate)) ||
+    if ((wav_bits && (dc_applies(o, info.group0_rate) || rs_applies(o, info.group0_rate))) ||
         !track_passes(r, o, &b.d_pcm, layout_of(wav_bits), wav_bits != 0, stride))
         goto fail;
     if (r->src_rate) {
@@ -1802,7 +1835,7 @@ static DVDA_Track_Reader *open_mlp_windowed(const DVDA_Track *k, const struct re
        the first window and started the producer thread -- work thrown away, on a path that ends in NULL either way; a
        raw-PCM track's packet header has the rate, and open_pcm_windowed refuses before it starts anything) */
     if (!windows_start(w) || !w->info.channels || !mlp_info_to_reader(r, &w->info, o->present) ||
-        dc_applies(o, w->info.group0_rate)) {
+        dc_applies(o, w->info.group0_rate) || rs_applies(o, w->info.group0_rate)) {
         reader_free(r);
         return NULL;
     }
@@ -1870,7 +1903,7 @@ static DVDA_Track_Reader *open_pcm_windowed(const DVDA_Track *k, const uint8_t *
     if (!r)
         return NULL;
     struct track_windows *w = r->win;
-    if (!pcm_params_to_reader(r, params, &bits, &rate) || dc_applies(o, r->rate_code[0])) {
+    if (!pcm_params_to_reader(r, params, &bits, &rate) || dc_applies(o, r->rate_code[0]) || rs_applies(o, r->rate_code[0])) {
         reader_free(r);
         return NULL;
     }
@@ -1907,6 +1940,9 @@ static DVDA_Track_Reader *open_reader(const DVDA_Track *k, const struct reader_o
         return NULL;
     /* the decimation: a ratio it has; not together with conceal mode */
     if (o->dc_ratio && (!dc_shift(o) || o->conceal))
+        return NULL;
+    /* the resampler: the one rate it makes; not together with conceal mode or the decimation */
+    if (o->rs_rate && (o->rs_rate != 44100 || o->conceal || o->dc_ratio))
         return NULL;
     aob_open_all(&aobs, k->dir, k->titleset);
     if (aobs.n == 0 || k->s.first >= aobs.total)
@@ -1992,10 +2028,18 @@ unsigned dvda_hip_reader_source_rate(const DVDA_Track_Reader *r)
 }
 int dvda_hip_reader_decimated(const DVDA_Track_Reader *r, dvda_pcm_decim_report *out)
 {
-    if (!r || !r->src_rate)
+    if (!r || !r->dc_done)
         return 0;
     if (out)
         *out = r->dc_rep;
+    return 1;
+}
+int dvda_hip_reader_resampled(const DVDA_Track_Reader *r, dvda_pcm_decim_report *out)
+{
+    if (!r || !r->rs_done)
+        return 0;
+    if (out)
+        *out = r->rs_rep;
     return 1;
 }
 unsigned dvda_channel_count(const DVDA_Track_Reader *r) { return channels_of(r->assignment); }

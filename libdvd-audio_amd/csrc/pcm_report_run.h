@@ -1,5 +1,5 @@
-// pcm_report_run.h -- host side of the six passes over decoded PCM (pcm_digest.h, pcm_levels.h, pcm_compare.h, pcm_energy.h,
-// pcm_requant.h, pcm_decim.h): what a report is to the driver, the one driver of the flat tile list (pcm_tiles.h), the one
+// pcm_report_run.h -- host side of the seven passes over decoded PCM (pcm_digest.h, pcm_levels.h, pcm_compare.h, pcm_energy.h,
+// pcm_requant.h, pcm_decim.h, pcm_resample.h): what a report is to the driver, the one driver of the flat tile list (pcm_tiles.h), the one
 // call that runs a report behind a decode on the context's buffers, and the host arithmetic that joins two pieces' results.
 #pragma once
 #include <algorithm>
@@ -12,6 +12,7 @@
 #include "pcm_energy.h"
 #include "pcm_levels.h"
 #include "pcm_requant.h"
+#include "pcm_resample.h"
 
 static inline bool int32_layout(uint32_t layout) { return layout == DVDA_PCM_PLANAR || layout == DVDA_PCM_INTERLEAVED; }
 
@@ -354,6 +355,61 @@ struct DcReport {
     }
 };
 static_assert(sizeof(dvda_pcm_decim_piece) == 16 && sizeof(dvda_pcm_decim_report) == 80, "the decimator's structs");
+
+// The resampler, 48 kHz to 44.1 kHz: the decimator's shape without a ratio.  Its unit is OUTPUT frames; the driver's
+// `bits` is the depth the values are clamped to.
+struct RsReport {
+    static constexpr uint32_t TILE = rsm::TILE, TILE_WORDS = rsm::REC, TILE_BLOCKS = rsm::TILE_BLOCKS;     // unit: output frames
+    dvda_pcm_decim_report *d_report;
+    int32_t *d_out;
+    uint32_t layout_out;
+    const dvda_pcm_crc_desc *d_desc_out;
+    const dvda_pcm_decim_piece *d_piece;
+    const uint64_t *host_off, *host_stride;     // (host) behind a decode: where the output's regions lie
+
+    // (an overflowed stream has no frames here: zeros reported, nothing written)
+    uint64_t units(const dvda_pcm_crc_desc &d, unsigned) const { return PCMT_NOT_TAKEN(d) ? 0 : rsm::out_frames(0, d.frames); }
+    // the descriptors of both sides in one array: the input's [n], then the output's [n]
+    int stage(Descs &desc, uint32_t n, ReportStage *s) const
+    {
+        desc.resize(2 * (size_t)n);
+        for (uint32_t i = 0; i < n; i++) {
+            dvda_pcm_crc_desc &o = desc[n + i];
+            o = desc[i];
+            o.off = host_off[i];
+            o.stride = host_stride[i];
+            o.frames = units(desc[i], 0);
+        }
+        return s->want((size_t)n * (sizeof(dvda_pcm_decim_report) / 8));
+    }
+    void bind(uint64_t *d_out_, uint64_t *, const dvda_pcm_crc_desc *d_desc, uint32_t n)
+    {
+        d_report = (dvda_pcm_decim_report *)d_out_;
+        d_desc_out = d_desc + n;
+    }
+    bool has_out() const { return d_report && d_out && d_desc_out && int32_layout(layout_out); }
+    static bool takes(uint32_t layout, unsigned bits) { return int32_layout(layout) && rsm::depth_ok(bits); }
+
+    void plan(hipStream_t st, const dvda_pcm_crc_desc *d_desc, uint32_t n, unsigned, uint32_t *cnt) const
+    {
+        hipLaunchKernelGGL(rsm::k_rs_plan, dim3((n + 255) / 256), dim3(256), 0, st, d_desc, d_desc_out, d_piece, n, cnt);
+    }
+    void tiles(dim3 grid, dim3 block, hipStream_t st, const int32_t *d_pcm, uint32_t layout, const dvda_pcm_crc_desc *d_desc,
+               uint32_t n, unsigned bits, const uint32_t *base, uint32_t *rec, uint32_t max_tiles) const
+    {
+        const bool pi = layout == DVDA_PCM_PLANAR, po = layout_out == DVDA_PCM_PLANAR;
+        auto k = pi ? (po ? rsm::k_rs_tiles<true, true> : rsm::k_rs_tiles<true, false>)
+                    : (po ? rsm::k_rs_tiles<false, true> : rsm::k_rs_tiles<false, false>);
+        hipLaunchKernelGGL(k, grid, block, 0, st, d_pcm, d_desc, d_out, d_desc_out, d_piece, n, (uint32_t)bits, base, rec,
+                           max_tiles);
+    }
+    void join(dim3 block, hipStream_t st, const dvda_pcm_crc_desc *d_desc, uint32_t n, unsigned, const uint32_t *base,
+              const uint32_t *rec, uint32_t max_tiles) const
+    {
+        hipLaunchKernelGGL(rsm::k_rs_join, dim3(n), block, 0, st, d_desc, d_desc_out, d_piece, n, base, rec, max_tiles,
+                           d_report);
+    }
+};
 
 // ---- the driver of the flat tile list
 // tiles the list can hold for n streams of max_total units in all: every stream has at most one ragged tile -- unless the
@@ -829,6 +885,62 @@ extern "C" int32_t dvda_pcm_hip_decim_value(const int32_t *window, uint32_t rati
     }
     uint32_t cl = 0;
     const int32_t y = ratio == 2 ? dcm::value<2>(window, bits, &cl) : dcm::value<4>(window, bits, &cl);
+    if (clipped)
+        *clipped = (int)cl;
+    return y;
+}
+
+// ---- the resampler
+extern "C" size_t dvda_pcm_hip_resample_workspace_words(uint32_t n, uint64_t max_total_out_frames)
+{
+    return report_workspace_words(RsReport{}, n, max_total_out_frames);
+}
+
+extern "C" int dvda_pcm_hip_resample(const int32_t *d_in, uint32_t layout_in, const dvda_pcm_crc_desc *d_desc_in,
+                                     int32_t *d_out, uint32_t layout_out, const dvda_pcm_crc_desc *d_desc_out,
+                                     const dvda_pcm_decim_piece *d_piece, uint32_t n, unsigned bits,
+                                     uint64_t max_total_out_frames, dvda_pcm_decim_report *d_report, uint32_t *d_work,
+                                     size_t work_words, void *stream_)
+{
+    return report_run(RsReport{d_report, d_out, layout_out, d_desc_out, d_piece}, d_in, layout_in, bits, d_desc_in, n,
+                      max_total_out_frames, d_work, work_words, stream_);
+}
+
+extern "C" int dvda_mlp_hip_pcm_resample(dvda_mlp_hip_ctx *c, const int32_t *d_pcm, const uint64_t *d_out_off,
+                                         const uint64_t *d_out_stride, unsigned bits, int32_t *d_dst, uint32_t layout_dst,
+                                         const uint64_t *host_dst_off, const uint64_t *host_dst_stride,
+                                         dvda_pcm_decim_report *host_report, uint32_t n, void *stream_)
+{
+    if (!c || !d_pcm || !d_out_off || !d_out_stride || !d_dst || !host_dst_off || !host_dst_stride || !host_report ||
+        !int32_layout(layout_dst) || !RsReport::takes(c->set.pcm_layout, bits))
+        return DVDA_HIP_EINVAL;
+    RsReport r{nullptr, d_dst, layout_dst, nullptr, nullptr, host_dst_off, host_dst_stride};
+    const int rc = report_of_decode(c, d_pcm, d_out_off, d_out_stride, bits, &n, stream_, &r);
+    if (rc || n == 0)
+        return rc;
+    return report_down(stream_, host_report, r.d_report, (size_t)n * sizeof(dvda_pcm_decim_report));
+}
+
+extern "C" const int32_t *dvda_pcm_hip_resample_taps(uint32_t *phases, uint32_t *taps)
+{
+    if (phases)
+        *phases = rsm::PHASES;
+    if (taps)
+        *taps = rsm::TAPS;
+    return &rsm::Table::g[0][0];
+}
+
+extern "C" uint64_t dvda_pcm_hip_resample_out_frames(uint64_t frame0, uint64_t own) { return rsm::out_frames(frame0, own); }
+
+extern "C" int32_t dvda_pcm_hip_resample_value(const int32_t *window, uint32_t phase, unsigned bits, int *clipped)
+{
+    if (!window || phase >= rsm::PHASES || !rsm::depth_ok(bits)) {
+        if (clipped)
+            *clipped = -1;
+        return 0;
+    }
+    uint32_t cl = 0;
+    const int32_t y = rsm::value(window, phase, bits, &cl);
     if (clipped)
         *clipped = (int)cl;
     return y;

@@ -28,6 +28,7 @@ EXPORTS = [
     "dvda_hip_set_digest", "dvda_hip_reader_crc32", "dvda_hip_set_levels", "dvda_hip_reader_levels",
     "dvda_hip_set_energy", "dvda_hip_reader_energy", "dvda_hip_set_requantize", "dvda_hip_reader_requantized",
     "dvda_hip_reader_source_bits", "dvda_hip_set_decimate", "dvda_hip_reader_decimated", "dvda_hip_reader_source_rate",
+    "dvda_hip_set_resample", "dvda_hip_reader_resampled",
     "dvda_hip_set_conceal", "dvda_hip_reader_concealed", "dvda_hip_open_track_reader_concealing",
 ]
 
@@ -109,6 +110,10 @@ def lib():
         L.dvda_hip_set_decimate.argtypes = [ctypes.c_uint]
         L.dvda_hip_reader_decimated.restype = ctypes.c_int
         L.dvda_hip_reader_decimated.argtypes = [vp, ctypes.POINTER(hipdec.DecimReport)]
+        L.dvda_hip_set_resample.restype = None
+        L.dvda_hip_set_resample.argtypes = [ctypes.c_uint]
+        L.dvda_hip_reader_resampled.restype = ctypes.c_int
+        L.dvda_hip_reader_resampled.argtypes = [vp, ctypes.POINTER(hipdec.DecimReport)]
         L.dvda_hip_reader_source_rate.restype = ctypes.c_uint
         L.dvda_hip_reader_source_rate.argtypes = [vp]
         L.dvda_hip_reader_energy.restype = ctypes.c_int
@@ -151,7 +156,8 @@ def layout(audio_ts, titleset=1):
 
 
 def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0, fused=False, pieces=False,
-               presentation=0, digest=False, levels=False, conceal=None, energy=0, requant=None, decimate=0):
+               presentation=0, digest=False, levels=False, conceal=None, energy=0, requant=None, decimate=0,
+               resample=0):
     """Decodes one track on the GPU.  Returns a dict: codec ("PCM"/"MLP"), bits, rate, channels,
     mask, status, and pcm = int32 [frames, channels] (interleaved, RIFF-WAVE order) read with
     dvda_read() in `chunk`-frame calls -- or, with wav=True, payload = the WAV data bytes packed
@@ -183,6 +189,13 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
     decimated track, and the PCM, the payload, requant= and every report are of it.  info["decimate"] = what the pass
     counted as hipdec.DecimReport.as_dict() gives it (None when the reader does not decimate: any other rate),
     info["decimate_state"] = what dvda_hip_reader_decimated returned, info["source_rate"] = the rate on the disc.
+    resample=44100: the reader delivers a 48 / 96 / 192 kHz track at 44 100 Hz (dvda_hip_set_resample: decimated by 2 / 4
+    where the rate asks for it, then resampled by 147 / 160 on the device, exact, clamped at the track's depth;
+    whole-track readers only, not together with decimate= or conceal=); info["rate"] and info["frames"] are then those of
+    the 44.1 kHz track, and the PCM, the payload, requant= and every report are of it.  info["resample"] = what the
+    48 -> 44.1 kHz pass counted as hipdec.DecimReport.as_dict() gives it (None when the reader does not resample: the
+    44.1 kHz family), info["resample_state"] = what dvda_hip_reader_resampled returned, info["resample_decimate"] = the
+    report of the decimation in front of it (None: there was none), info["source_rate"] = the rate on the disc.
     conceal=True: a damaged MLP track is concealed, not refused (dvda_hip_set_conceal): info["concealed"] = the spans as
     6-tuples (first_frame, frames, byte_off, byte_end, cause, flags) in track terms, and info["concealed_states"] = what
     dvda_hip_reader_concealed returned right after the open and at the end.  conceal=False says "off" explicitly; None
@@ -205,6 +218,7 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
         if requant is not None:
             L.dvda_hip_set_requantize(int(requant[0]), int(requant[1]), int(requant[2]))
         L.dvda_hip_set_decimate(int(decimate))
+        L.dvda_hip_set_resample(int(resample))
         try:
             r = L.dvda_hip_open_track_reader_concealing(k, device, 1 if (fused and wav) else 0, presentation,
                                                         -1 if conceal is None else int(bool(conceal))) if k else None
@@ -214,6 +228,7 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
             L.dvda_hip_set_energy(0)
             L.dvda_hip_set_requantize(0, 0, 0)
             L.dvda_hip_set_decimate(0)
+            L.dvda_hip_set_resample(0)
         if not r:
             raise RuntimeError("track %d/%d/%d cannot be opened for reading" % (titleset, title, track))
         ch = L.dvda_channel_count(r)
@@ -290,6 +305,13 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
             state = L.dvda_hip_reader_decimated(r, ctypes.byref(dc_report))
             info["decimate_state"] = state
             info["decimate"] = dc_report.as_dict() if state == 1 else None
+            info["source_rate"] = int(L.dvda_hip_reader_source_rate(r))
+        if resample:
+            rs_report, dc_report = hipdec.DecimReport(), hipdec.DecimReport()
+            state = L.dvda_hip_reader_resampled(r, ctypes.byref(rs_report))
+            info["resample_state"] = state
+            info["resample"] = rs_report.as_dict() if state == 1 else None
+            info["resample_decimate"] = dc_report.as_dict() if L.dvda_hip_reader_decimated(r, ctypes.byref(dc_report)) == 1 else None
             info["source_rate"] = int(L.dvda_hip_reader_source_rate(r))
         if conceal:
             state = L.dvda_hip_reader_concealed(r, None, 0, ctypes.byref(n_spans))

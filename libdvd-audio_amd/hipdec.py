@@ -82,7 +82,9 @@ EXPORTS = ("dvda_mlp_hip_create", "dvda_mlp_hip_destroy", "dvda_mlp_hip_index", 
            "dvda_pcm_hip_requantize", "dvda_pcm_hip_requantize_workspace_words", "dvda_mlp_hip_pcm_requantize",
            "dvda_pcm_hip_requant_value",
            "dvda_pcm_hip_decimate", "dvda_pcm_hip_decimate_workspace_words", "dvda_mlp_hip_pcm_decimate",
-           "dvda_pcm_hip_decim_taps", "dvda_pcm_hip_decim_out_frames", "dvda_pcm_hip_decim_value")
+           "dvda_pcm_hip_decim_taps", "dvda_pcm_hip_decim_out_frames", "dvda_pcm_hip_decim_value",
+           "dvda_pcm_hip_resample", "dvda_pcm_hip_resample_workspace_words", "dvda_mlp_hip_pcm_resample",
+           "dvda_pcm_hip_resample_taps", "dvda_pcm_hip_resample_out_frames", "dvda_pcm_hip_resample_value")
 
 CRC_TILE_BYTES = 16384      # DVDA_CRC_TILE_BYTES: the digest's tiles, aligned to the end of a stream's payload
 CRC_JOIN_TILES = 256        # DVDA_CRC_JOIN_TILES: tiles a join workgroup folds per turn of its loop
@@ -158,6 +160,11 @@ class RequantReport(_Record):
 
 DCM_TILE_FRAMES = 1024      # DVDA_DCM_TILE_FRAMES: OUTPUT frames of the decimator's tiles, aligned to a stream's first output frame
 DECIM_RATES = (44100, 48000, 88200, 96000)      # the rates decode_streams_decimated hands out
+
+
+RSM_TILE_FRAMES = 9408      # DVDA_RSM_TILE_FRAMES: OUTPUT frames of the resampler's tiles (64 * 147), aligned as the decimator's
+RSM_PHASES, RSM_TAPS = 147, 96      # the resampler's table: 48 000 Hz * 147 / 160 = 44 100 Hz
+RESAMPLE_RATE = 44100       # the one rate decode_streams_resampled hands out
 
 
 class DecimPiece(ctypes.Structure):
@@ -331,6 +338,18 @@ def lib():
         L.dvda_pcm_hip_decim_out_frames.argtypes = [u64, u64, u32]
         L.dvda_pcm_hip_decim_value.restype = ctypes.c_int32
         L.dvda_pcm_hip_decim_value.argtypes = [vp, u32, ctypes.c_uint, ctypes.POINTER(ctypes.c_int)]
+        L.dvda_pcm_hip_resample_workspace_words.restype = ctypes.c_size_t
+        L.dvda_pcm_hip_resample_workspace_words.argtypes = [u32, u64]
+        L.dvda_pcm_hip_resample.argtypes = [vp, u32, vp, vp, u32, vp, vp, u32, ctypes.c_uint, u64, vp, vp, ctypes.c_size_t,
+                                            vp]
+        L.dvda_mlp_hip_pcm_resample.argtypes = [vp, vp, vp, vp, ctypes.c_uint, vp, u32, ctypes.POINTER(u64),
+                                                ctypes.POINTER(u64), vp, u32, vp]
+        L.dvda_pcm_hip_resample_taps.restype = ctypes.POINTER(ctypes.c_int32)
+        L.dvda_pcm_hip_resample_taps.argtypes = [ctypes.POINTER(u32), ctypes.POINTER(u32)]
+        L.dvda_pcm_hip_resample_out_frames.restype = u64
+        L.dvda_pcm_hip_resample_out_frames.argtypes = [u64, u64]
+        L.dvda_pcm_hip_resample_value.restype = ctypes.c_int32
+        L.dvda_pcm_hip_resample_value.argtypes = [vp, u32, ctypes.c_uint, ctypes.POINTER(ctypes.c_int)]
         _lib = L
     return _lib
 
@@ -567,6 +586,18 @@ class Context:
         stride = (ctypes.c_uint64 * max(n, 1))(*[int(v) for v in dst_stride][:n])
         return self._records("dvda_mlp_hip_pcm_decimate", DecimReport, n, stream, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr,
                              ratio, bits, d_dst_ptr, layout_dst, off, stride)
+
+    def pcm_resample(self, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, bits, d_dst_ptr, layout_dst, dst_off, dst_stride,
+                     n=None, stream=0):
+        """dvda_mlp_hip_pcm_resample: the int32 PCM the last decode wrote, whole tracks taken as 48 kHz, resampled to
+        44.1 kHz and clamped to `bits` into the device buffer at d_dst_ptr in layout_dst (PCM_PLANAR or PCM_INTERLEAVED):
+        stream i to the int32 word dst_off[i], planar stride dst_stride[i] (host lists) -> list of
+        DecimReport.as_dict(); blocks.  HipError (EINVAL) when the context's layout is a WAV one."""
+        n = self.n_streams if n is None else n
+        off = (ctypes.c_uint64 * max(n, 1))(*[int(v) for v in dst_off][:n])
+        stride = (ctypes.c_uint64 * max(n, 1))(*[int(v) for v in dst_stride][:n])
+        return self._records("dvda_mlp_hip_pcm_resample", DecimReport, n, stream, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr,
+                             bits, d_dst_ptr, layout_dst, off, stride)
 
     def decode_time(self):
         """mean device ms of a whole decode call (all passes); call before kernel_time(), which resets the ring"""
@@ -979,6 +1010,86 @@ def pcm_decimate_workspace_words(n, max_total_out_frames):
 def decim_list(d_report):
     """pcm_decimate's report tensor -> list of DecimReport.as_dict() on the host (waits)"""
     return _record_list(DecimReport, d_report)
+
+
+def resample_taps():
+    """dvda_pcm_hip_resample_taps: the committed table g[147][96] as an int32 array (a copy); needs no GPU"""
+    ph, tp = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    p = lib().dvda_pcm_hip_resample_taps(ctypes.byref(ph), ctypes.byref(tp))
+    return np.ctypeslib.as_array(p, (int(ph.value), int(tp.value))).astype(np.int32)
+
+
+def resample_out_frames(frame0, own):
+    """dvda_pcm_hip_resample_out_frames: output frames of the absolute frames [frame0, frame0 + own); needs no GPU"""
+    return int(lib().dvda_pcm_hip_resample_out_frames(frame0, own))
+
+
+def resample_value(window, phase, bits):
+    """dvda_pcm_hip_resample_value: one output value of phase `phase` from its window of 96 input values -> (value, 1 when
+    the clamp changed it else 0); host arithmetic, needs no GPU.  HipError for an invalid phase or depth or a window of
+    another length"""
+    w = np.ascontiguousarray(window, np.int32)
+    if w.shape != (RSM_TAPS,):
+        raise HipError("dvda_pcm_hip_resample_value: a window of %s values" % (w.shape,))
+    cl = ctypes.c_int(0)
+    y = lib().dvda_pcm_hip_resample_value(w.ctypes.data, phase, bits, ctypes.byref(cl))
+    if cl.value < 0:
+        raise HipError("dvda_pcm_hip_resample_value: invalid parameters (phase %r, bits %r)" % (phase, bits))
+    return int(y), int(cl.value)
+
+
+def resample_desc_out(desc_in, pieces=None):
+    """the output descriptors pcm_resample makes when none are passed, as decim_desc_out -> (desc_out, words)"""
+    out, pos = [], 0
+    for i, (_, _, frames, ch) in enumerate(desc_in):
+        frame0, before, after = pieces[i] if pieces is not None else (0, 0, 0)
+        ok = 1 <= int(ch) <= 8 and int(frames) <= 1 << 40 and before + after <= int(frames)
+        f = resample_out_frames(frame0, int(frames) - before - after) if ok else 0
+        out.append((pos, f, f, int(ch)))
+        pos += f * int(ch) if ok else 0
+    return out, max(pos, 1)
+
+
+def pcm_resample(d_in, layout_in, desc_in, bits, pieces=None, out=None, layout_out=None, desc_out=None,
+                 max_total_out_frames=None, work=None):
+    """dvda_pcm_hip_resample over torch tensors, with pcm_decimate's shapes: d_in an int32 tensor on the device holding
+    the streams in layout_in (PCM_PLANAR or PCM_INTERLEAVED), desc_in a list of (off, stride, frames, channels); every
+    stream taken as 48 kHz and resampled to 44.1 kHz, the values clamped to `bits`.  pieces: per stream (frame0, before,
+    after) (None: whole tracks).  out / layout_out / desc_out: where the result goes -- default: the input's layout, the
+    regions end to end in a fresh zeroed tensor (resample_desc_out).  -> (d_out, desc_out, d_report): the output tensor,
+    its descriptors and a uint8 device tensor [n, sizeof(DecimReport)] (decim_list brings it to the host).  Only the
+    kernels are asynchronous, on torch's current stream."""
+    layout_out = layout_in if layout_out is None else layout_out
+    if pieces is not None and len(pieces) != len(desc_in):
+        raise HipError("pcm_resample: %d pieces for %d streams" % (len(pieces), len(desc_in)))
+    words = None
+    if desc_out is None:
+        desc_out, words = resample_desc_out(desc_in, pieces)
+    if len(desc_out) != len(desc_in):
+        raise HipError("pcm_resample: %d output descriptors for %d streams" % (len(desc_out), len(desc_in)))
+    if max_total_out_frames is None:
+        max_total_out_frames = int(sum(int(f) for _, _, f, c in desc_out if 1 <= int(c) <= 8 and int(f) <= 1 << 40))
+    torch, n, d_desc_in, work, st = _report_args(d_in, desc_in, "the resampler", max_total_out_frames, work,
+                                                 lib().dvda_pcm_hip_resample_workspace_words)
+    dev = d_in.device
+    if out is None:
+        if words is None:
+            words = max([int(o) + int(r) * int(c) for o, r, f, c in desc_out] + [1])
+        out = torch.zeros(words, dtype=torch.int32, device=dev)
+    d_desc_out = _to_device(_desc_records(desc_out), dev)
+    d_piece = None if pieces is None else _to_device(_piece_records(pieces), dev)
+    d_rep = _result_tensor(DecimReport, n, dev)
+    _check(lib().dvda_pcm_hip_resample(d_in.data_ptr(), layout_in, d_desc_in.data_ptr(), out.data_ptr(), layout_out,
+                                       d_desc_out.data_ptr(), None if d_piece is None else d_piece.data_ptr(), n, bits,
+                                       max_total_out_frames, d_rep.data_ptr(), work.data_ptr(), work.numel(), st),
+           "dvda_pcm_hip_resample")
+    return out, desc_out, d_rep[:n]
+
+
+def pcm_resample_workspace_words(n, max_total_out_frames):
+    """dvda_pcm_hip_resample_workspace_words: the uint32 words of workspace pcm_resample needs for n streams whose
+    OUTPUT frames sum to at most max_total_out_frames; needs no GPU"""
+    return int(lib().dvda_pcm_hip_resample_workspace_words(n, max_total_out_frames))
 
 
 def crc_list(d_crc, d_nbytes):
@@ -1489,6 +1600,62 @@ def decode_streams_decimated(streams, ratio, device=0, layout=PCM_PLANAR, ctx=No
     pcm = cut_regions(d_out.cpu().numpy(), [d[0] for d in desc_out], [d[1] for d in desc_out], regions.channels,
                       [d[2] for d in desc_out], layout)
     return pcm, rates, list(infos), reports
+
+
+def decode_streams_resampled(streams, rate=RESAMPLE_RATE, device=0, layout=PCM_PLANAR, ctx=None, presentation=PRESENT_FULL):
+    """Decodes complete MLP byte streams and brings each to `rate` = 44 100 Hz on the device, by its own rate: 44.1 kHz as
+    it is; 88.2 / 176.4 kHz decimated by 2 / 4 (pcm_decimate); 48 kHz resampled (pcm_resample); 96 / 192 kHz decimated
+    by 2 / 4 into an intermediate buffer at the stream's depth, then resampled -- by definition the composition of the
+    two passes.  Each stream is clamped at its own depth.  -> (pcm, infos, reports): pcm[i] int32 [channels, frames at
+    44.1 kHz], reports[i] = dict(decimate=DecimReport.as_dict() or None, resample=DecimReport.as_dict() or None).
+    ValueError for any other `rate`."""
+    if rate != RESAMPLE_RATE:
+        raise ValueError("decode_streams_resampled: %r Hz: only %d Hz is made" % (rate, RESAMPLE_RATE))
+    if layout not in (PCM_PLANAR, PCM_INTERLEAVED):
+        raise HipError("decode_streams_resampled: EINVAL (an int32 layout)")
+    import torch
+    batch = Batch(streams, device)
+    with _call_context(ctx, batch, None, 0, layout, presentation) as (ctx, capacity):
+        regions, infos, _ = decode_batch(ctx, batch, layout, attempts=2, capacity=capacity, to_host=False)
+    n = len(infos)
+    _, desc, depth = _decoded_lists(infos, regions)
+    src = [RATE_OF_CODE.get(int(inf.group0_rate), 0) for inf in infos]
+    ratio = [{44100: 1, 48000: 1, 88200: 2, 96000: 2, 176400: 4, 192000: 4}.get(r, 0) for r in src]
+    cross = [r in (48000, 96000, 192000) for r in src]
+    for i in range(n):
+        if not ratio[i]:
+            raise ValueError("decode_streams_resampled: stream %d runs at %d Hz: no %d Hz output" % (i, src[i], rate))
+    reports = [dict(decimate=None, resample=None) for _ in range(n)]
+    # stage 1: decimate by 2 / 4 where the rate asks for it; `cur` is where each stream lies after it
+    cur = [(regions.d_pcm, desc[i]) for i in range(n)]
+    for D in (2, 4):
+        for bits in sorted(set(depth)):
+            idx = [i for i in range(n) if ratio[i] == D and depth[i] == bits]
+            if not idx:
+                continue
+            d_mid, desc_mid, d_rep = pcm_decimate(regions.d_pcm, layout, [desc[i] for i in idx], D, bits)
+            for i, dm, rep in zip(idx, desc_mid, decim_list(d_rep)):
+                cur[i] = (d_mid, dm)
+                reports[i]["decimate"] = rep
+    # stage 2: 48 kHz to 44.1 kHz, one call per buffer and depth
+    for key in sorted(set((id(cur[i][0]), depth[i]) for i in range(n) if cross[i])):
+        idx = [i for i in range(n) if cross[i] and (id(cur[i][0]), depth[i]) == key]
+        d_out, desc_out, d_rep = pcm_resample(cur[idx[0]][0], layout, [cur[i][1] for i in idx], key[1])
+        for i, do, rep in zip(idx, desc_out, decim_list(d_rep)):
+            cur[i] = (d_out, do)
+            reports[i]["resample"] = rep
+    pcm = []
+    for i in range(n):
+        buf, (off, stride, frames, ch) = cur[i]
+        if frames == 0 or ch == 0:
+            pcm.append(np.zeros((int(ch), 0), np.int32))
+            continue
+        host = buf[off:off + max(stride, frames) * ch].cpu().numpy()
+        if layout == PCM_PLANAR:
+            pcm.append(np.stack([host[c * stride:c * stride + frames] for c in range(ch)]).astype(np.int32))
+        else:
+            pcm.append(np.ascontiguousarray(host[:frames * ch].reshape(frames, ch).T).astype(np.int32))
+    return pcm, list(infos), reports
 
 
 class MLPDecoder:

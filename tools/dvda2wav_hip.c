@@ -62,6 +62,8 @@ static unsigned g_rq_bits, g_rq_mode = DVDA_RQ_TPDF;
 static unsigned long long g_rq_seed;
 /* -r: the rate every track is delivered at where its own is 1, 2 or 4 times that (0: its own) */
 static unsigned g_rate;
+/* --resample: with -r 44100, a 48 / 96 / 192 kHz track is resampled to 44.1 kHz */
+static int g_resample;
 
 static int extract(DVDA_Title *title, unsigned track_num, const char *dir, int device, int fused_wav, int stereo,
                    int crc, int conceal, unsigned titleset_num)
@@ -98,7 +100,8 @@ static int extract(DVDA_Title *title, unsigned track_num, const char *dir, int d
         }
         const unsigned src = dvda_hip_reader_source_rate(r);
         const unsigned ratio = src == 2 * g_rate ? 2 : src == 4 * g_rate ? 4 : 0;
-        if (r && src != g_rate && !ratio)
+        /* (--resample takes the 48 kHz family below) */
+        if (r && src != g_rate && !ratio && !(g_resample && (src == 48000 || src == 96000 || src == 192000)))
             fprintf(stderr, "*** Warning: track %u runs at %u Hz, which is not 1, 2 or 4 times %u: written as it is\n", track_num,
                     src, g_rate);
         if (r && (ratio || dvda_hip_reader_decimated(r, NULL) == 1)) {
@@ -111,6 +114,20 @@ static int extract(DVDA_Title *title, unsigned track_num, const char *dir, int d
         }
     }
     dvda_hip_set_decimate(0);
+    /* --resample: a track that came out at its own rate in the 48 kHz family is opened once more, resampled */
+    if (g_resample && r && dvda_sample_rate(r) != g_rate && dvda_hip_reader_decimated(r, NULL) != 1) {
+        const unsigned src = dvda_sample_rate(r);
+        if (src == 48000 || src == 96000 || src == 192000) {
+            const int windowed = dvda_hip_reader_windowed(r);
+            dvda_close_track_reader(r);
+            dvda_hip_set_resample(g_rate);
+            r = windowed ? NULL : dvda_hip_open_track_reader_with(track, device, fused_wav, stereo);
+            dvda_hip_set_resample(0);
+            if (!r)
+                fprintf(stderr, "*** Error: track %u runs at %u Hz%s: --resample cannot bring it to %u\n", track_num, src,
+                        windowed ? " and is read in windows" : "", g_rate);
+        }
+    }
     if (!r) {
         fprintf(stderr, "*** Error: unable to open track %u for reading\n", track_num);
         dvda_close_track(track);
@@ -196,6 +213,22 @@ static int extract(DVDA_Title *title, unsigned track_num, const char *dir, int d
                    rate, clipped);
         } else {
             printf("DECIMATE %u %u %u %u %u none\n", titleset_num, title_number, track_number, dvda_hip_reader_source_rate(r),
+                   rate);
+        }
+    }
+    if (ok && g_resample) {
+        /* what the resampler did to the track just written: the rate on the disc, the file's rate, values the clamps changed
+           (those of the decimation in front of it included) */
+        struct dvda_pcm_decim_report rs, dc;
+        if (dvda_hip_reader_resampled(r, &rs) == 1) {
+            unsigned long long clipped = 0;
+            const int staged = dvda_hip_reader_decimated(r, &dc) == 1;
+            for (int c = 0; c < 8; c++)
+                clipped += rs.clipped[c] + (staged ? dc.clipped[c] : 0);
+            printf("RESAMPLE %u %u %u %u %u %llu\n", titleset_num, title_number, track_number, dvda_hip_reader_source_rate(r),
+                   rate, clipped);
+        } else {
+            printf("RESAMPLE %u %u %u %u %u none\n", titleset_num, title_number, track_number, dvda_hip_reader_source_rate(r),
                    rate);
         }
     }
@@ -305,6 +338,11 @@ static void usage(const char *prog)
            "                            with -b / --dither (the reduction follows the decimation).  Whole-track readers\n"
            "                            only: a track long enough to be read in windows fails where it would have to be\n"
            "                            decimated, and is written as it is where not.  Not together with -K\n"
+           "      --resample            with -r 44100: a 48, 96 or 192 kHz track is brought to 44100 Hz too (decimated by 2 or\n"
+           "                            4 where its rate asks for it, then resampled by 147 / 160 on the GPU, exact, clamped\n"
+           "                            at the track's depth).  One line per track on stdout: RESAMPLE <titleset> <title>\n"
+           "                            <track> <source rate> <file's rate> <values clamped> (\"none\" for a track that was\n"
+           "                            not resampled).  Whole-track readers only\n"
            "  -g N, --gpu=N             HIP device (default 0)\n"
            "  -D LIST, --devices=LIST   comma-separated HIP devices: one worker thread per entry takes tracks in turn\n"
            "                            (default: up to four workers on the device of -g)\n"
@@ -321,6 +359,7 @@ int main(int argc, char *argv[])
                                        {"crc", no_argument, 0, 'C'},            {"conceal", no_argument, 0, 'K'},
                                        {"bits", required_argument, 0, 'b'},     {"dither", required_argument, 0, 1001},
                                        {"seed", required_argument, 0, 1002},    {"rate", required_argument, 0, 'r'},
+                                       {"resample", no_argument, 0, 1003},
                                        {0, 0, 0, 0}};
     const char *audio_ts = NULL, *dir = ".", *cdrom = NULL;
     unsigned titleset_num = 1, title_num = 0, track_num = 0;
@@ -359,6 +398,7 @@ int main(int argc, char *argv[])
             break;
         case 'r': g_rate = (unsigned)strtoul(optarg, NULL, 10); break;
         case 1002: g_rq_seed = strtoull(optarg, NULL, 0); break;
+        case 1003: g_resample = 1; break;
         case 'h': usage(argv[0]); return 0;
         default: return 1;
         }
@@ -373,6 +413,10 @@ int main(int argc, char *argv[])
     }
     if (g_rate && ((g_rate != 44100 && g_rate != 48000 && g_rate != 88200 && g_rate != 96000) || conceal)) {
         fprintf(stderr, "*** Error: -r takes 44100, 48000, 88200 or 96000, and not together with -K\n");
+        return 1;
+    }
+    if (g_resample && g_rate != 44100) {
+        fprintf(stderr, "*** Error: --resample goes with -r 44100\n");
         return 1;
     }
     /* (DVDA_NO_FUSED_WAV=1 in the environment brings the int32 decode + packing pass back, for comparison) */
