@@ -1,7 +1,7 @@
 """The PCM digest and the level report side by side (csrc/pcm_report_run.h, csrc/disc_reader.c piece_reports): on a context
 they share one descriptor array, one result block and one workspace, and the disc tier makes both of a piece in one block
-on the device -- so each must come out as it does alone, whatever the other left behind.  The same holds of all six passes
-behind a decode, which share one staging path (report_of_decode).  Every comparison is exact."""
+on the device -- so each must come out as it does alone, whatever the other left behind.  The same holds of all seven
+passes behind a decode, which share one staging path (report_of_decode).  Every comparison is exact."""
 import ctypes
 import tempfile
 import zlib
@@ -15,6 +15,7 @@ from tests import digest_model as dgm
 from tests import energy_model as em
 from tests import levels_model as lm
 from tests import requant_model as rm
+from tests import resample_model as rsm
 from tests.test_disc_api import _titles
 from tests.test_gpu_digest_disc import window_sectors
 
@@ -71,12 +72,25 @@ def test_interleaved_on_one_context(pkg, oracle, layout):
         ctx.close()
 
 
-def _six_passes(hd, ctx, out, st, pcm, infos):
+def _seven_passes(hd, ctx, out, st, pcm, infos):
     """Every Context.pcm_* call on one decoded batch, interleaved: energy (B = 64), digest 24, decimate by 2 into a second
-    tensor, levels 24, compare against a clone with one value changed, requantize 24 -> 16 in place, digest 16, levels 16,
-    energy -- each exactly its model's of the host copy of the PCM as it was at that point"""
+    tensor, resample into a third, levels 24, compare against a clone with one value changed, requantize 24 -> 16 in
+    place, resample again, digest 16, levels 16, energy -- each exactly its model's of the host copy of the PCM as it was
+    at that point"""
     import torch
     lay, n = out.layout, len(pcm)
+    table = hd.resample_taps()
+
+    def resample(now, bits):
+        """(the resampler stages output descriptors of its own behind the caller's, as the decimator does)"""
+        desc_rs, words = hd.resample_desc_out(desc)
+        d_rs = torch.full((words,), 0x5A5A5A5A, dtype=torch.int32, device=out.dev)
+        want = [rsm.resample_np(p, table, bits) for p in now]
+        assert ctx.pcm_resample(*out.ptrs, bits, d_rs.data_ptr(), lay, [d[0] for d in desc_rs], [d[1] for d in desc_rs],
+                                stream=st) == [rsm.report(p.shape[1], w.shape[1], cl) for p, (w, cl) in zip(now, want)]
+        got = hd.cut_regions(d_rs.cpu().numpy(), *[[d[k] for d in desc_rs] for k in (0, 1)], out.channels,
+                             [d[2] for d in desc_rs], lay)
+        assert all(np.array_equal(g, w) for g, (w, _) in zip(got, want))
 
     def energy(now):
         assert ctx.pcm_energy(*out.ptrs, 64, stream=st) == [em.energy_fast(p, 64) for p in now]
@@ -96,6 +110,7 @@ def _six_passes(hd, ctx, out, st, pcm, infos):
     got = hd.cut_regions(d_low.cpu().numpy(), *[[d[k] for d in desc_low] for k in (0, 1)], out.channels,
                          [d[2] for d in desc_low], lay)
     assert all(np.array_equal(g, w) for g, (w, _) in zip(got, low))
+    resample(pcm, 24)
     assert ctx.pcm_levels(*out.ptrs, 24, stream=st) == [lm.levels(p, 24) for p in pcm]
     # side B: the decode's buffer with the last stream's value at (channel 1, frame 70) one higher
     other, c, f = [p.copy() for p in pcm], 1, 70
@@ -110,15 +125,16 @@ def _six_passes(hd, ctx, out, st, pcm, infos):
         [rm.report(p.shape[1], cl) for p, (_, cl) in zip(pcm, want)]
     pcm16 = out.to_host(infos)
     assert all(np.array_equal(a, w) for a, (w, _) in zip(pcm16, want))
+    resample(pcm16, 16)
     digest(pcm16, 16)
     assert ctx.pcm_levels(*out.ptrs, 16, stream=st) == [lm.levels(p, 16) for p in pcm16]
     energy(pcm16)
 
 
 @pytest.mark.parametrize("layout", ["planar", "interleaved"])
-def test_all_six_passes_on_one_context(pkg, layout):
-    """the six passes share one staging path and one result block with six different layouts: each comes out as it does
-    alone, and a one-stream batch behind the longer one shows nothing stale"""
+def test_all_seven_passes_on_one_context(pkg, layout):
+    """the seven passes share one staging path and one result block with seven different layouts: each comes out as it
+    does alone, and a one-stream batch behind the longer one shows nothing stale"""
     hd, syn = pkg.hipdec, pkg.synth
     lay = {"planar": hd.PCM_PLANAR, "interleaved": hd.PCM_INTERLEAVED}[layout]
     streams = [syn.stream(syn.make_cfg(assignment=a, rate_code=1, n_substreams=1, n_aus=n), 40 + i)[0]
@@ -129,7 +145,7 @@ def test_all_six_passes_on_one_context(pkg, layout):
         for batch, shapes in ((streams, [(2, AU), (2, 60 * AU), (6, 60 * AU)]), ([short], [(2, 3 * AU)])):
             out, st, pcm = _decode(hd, ctx, batch, lay)
             assert [p.shape for p in pcm] == shapes
-            _six_passes(hd, ctx, out, st, pcm, ctx.stream_info(stream=st))
+            _seven_passes(hd, ctx, out, st, pcm, ctx.stream_info(stream=st))
     finally:
         ctx.close()
 
