@@ -199,6 +199,26 @@ void dvda_hip_set_resample(unsigned rate);
  * in front of it; 0: it does not -- the option is off, the track's rate is not one it applies to, or `reader` is NULL;
  * nothing is written */
 int dvda_hip_reader_resampled(const DVDA_Track_Reader *reader, struct dvda_pcm_decim_report *out);
+/* out_channels 1 or 2: track readers opened afterwards (per calling thread, read when the reader is opened, like
+ * dvda_hip_set_decimate) deliver a track of any other channel count mixed to that many channels: the decoded int32 PCM
+ * goes through dvda_pcm_hip_mix with the default matrix of the track's channel assignment (dvda_pcm_hip_mix_matrix of
+ * dvda_pcm_hip_speaker_mask(assignment) with `flags`, DVDA_MIX_*: the contract is in dvda_mlp_hip.h) at the track's depth
+ * into a new buffer, FIRST -- in front of the decimation, the resampler, the word-length reduction and the reports, which
+ * all see the mixed track; every stage rounds and clamps, so this order is part of the contract.  From there on the
+ * reader IS the 1- or 2-channel track: dvda_channel_count() gives out_channels, dvda_riff_wave_channel_mask() FL | FR
+ * (mono: FC), dvda_hip_reader_source_channels() the disc's count.  A track that already has out_channels channels -- a
+ * stereo presentation through dvda_hip_set_presentation(1) too -- is handed out untouched.  Whole-track readers only, MLP
+ * and raw PCM: the open returns NULL for a track the reader would take in windows, in conceal mode, for out_channels above
+ * 2, unknown flags, and for flags whose matrix the kernels do not take (dvda_pcm_hip_mix_valid: DVDA_MIX_UNITY on 5.0 /
+ * 5.1).  0 (default): off. */
+struct dvda_pcm_mix_report;
+void dvda_hip_set_downmix(unsigned out_channels, unsigned flags);
+/* 1: the reader mixes, *out (may be NULL) = what the pass counted (frames, per OUTPUT channel the values the clamp
+ * changed); 0: it does not -- the option is off, the track has out_channels channels already, or `reader` is NULL; nothing
+ * is written */
+int dvda_hip_reader_downmixed(const DVDA_Track_Reader *reader, struct dvda_pcm_mix_report *out);
+/* the channels the track has on the disc: dvda_channel_count() unless the reader mixes; 0 for a NULL reader */
+unsigned dvda_hip_reader_source_channels(const DVDA_Track_Reader *reader);
 /* on != 0: MLP track readers opened afterwards (per calling thread, read when the reader is opened, like
  * dvda_hip_set_wav_output) conceal a damaged track instead of refusing it: the track comes out as
  *     kept PCM ++ silence ++ PCM of a fresh decoder from the next usable major sync ++ ...

@@ -1007,6 +1007,105 @@ const int32_t *dvda_pcm_hip_resample_taps(uint32_t *phases, uint32_t *taps);
 uint64_t dvda_pcm_hip_resample_out_frames(uint64_t frame0, uint64_t own);
 int32_t dvda_pcm_hip_resample_value(const int32_t *window, uint32_t phase, unsigned bits, int *clipped);
 
+/* ------------------------------------------------------------------ channel mix: multichannel PCM to stereo or mono
+ * The passes above make a 24-bit 96 kHz track a 16-bit 44.1 kHz one; the file a CD, a portable player or a preview
+ * takes has two channels as well, and a one-substream multichannel MLP title or a raw-PCM multichannel track carries no
+ * stereo mix of its own (dvda_mlp_hip_set_presentation covers only titles that do).  This pass folds the channels on
+ * the device (csrc/pcm_mix.h): out_channels rows of Q30 coefficients over in_channels inputs.  It
+ * is the first pass whose output has another channel count than its input.
+ *
+ * The contract; every figure exact.  For frame f and output channel o, x[f][c] ANY int32, channels in RIFF-WAVE order
+ * as they lie in the buffer:
+ *   acc     = sum_{c < in_channels} coef[o][c] * x[f][c]                                   (int64)
+ *   y[f][o] = clamp((acc + 2^29) >> 30, -2^(bits-1), 2^(bits-1) - 1)     bits in {16, 20, 24}; the shift is arithmetic
+ * clipped[o] counts the values the clamp changed.
+ *
+ * Validity: a matrix is valid when both channel counts lie in 1..8 and every used row has sum_c |coef[o][c]| <= 2^31
+ * (c < in_channels; entries outside [out_channels)[in_channels) are ignored).  Then for any int32 input |x| <= 2^31, so
+ * |acc| <= sum_c |coef[o][c]| * 2^31 <= 2^62 and |acc + 2^29| <= 2^62 + 2^29 < 2^63: the arithmetic is plain int64 and
+ * cannot overflow.  A stream whose matrix is invalid, or whose channel counts do not match its descriptors, is not
+ * taken: frames == 0 is reported and nothing is written.
+ *
+ * The pass is pointwise in the frame: a track mixed whole, in pieces or on several devices gives the same bytes, with
+ * no context frames, and the reports of pieces join by adding their fields.  With 2^30 on the diagonal the output is
+ * the input for values inside `bits`; rows can also express a permutation or the extraction of one channel.
+ *
+ * The default matrices (dvda_pcm_hip_mix_matrix) are Q30 integers: ONE = 2^30, A = 759250125 = rint(2^30 / sqrt 2),
+ * HALF = 2^29.  Stereo rows (L, R): FL -> L: ONE; FR -> R: ONE; FC -> both: A; BL -> L: A; BR -> R: A; BC -> both: HALF;
+ * LFE -> 0, or both: A with DVDA_MIX_LFE.  The mono row is wL + wR per channel.
+ *   DVDA_MIX_NORMALIZED (0, the default): S = the larger of the two row sums (mono: the row's sum), coef = (w << 30) div S
+ *     with ONE S for both rows, which keeps the balance.  Input inside `bits` can then never clip: every coef >= 0 and
+ *     floor((w << 30) / S) summed over a row is <= (sum w) * 2^30 / S <= 2^30, so with |x| <= 2^(bits-1)
+ *     |acc| <= 2^30 * 2^(bits-1); and acc <= 2^30 * (2^(bits-1) - 1) on the positive side, so (acc + 2^29) >> 30 lies in
+ *     [-2^(bits-1), 2^(bits-1) - 1].
+ *   DVDA_MIX_UNITY: the weights as they are (mono: (wL + wR) >> 1): the fronts at gain 1, and the clamp counts the overs.
+ *     Where a row's weights sum above 2^31 -- FL + FC + BL is 2^30 (1 + sqrt 2) -- the matrix made is not a valid one and
+ *     a stream given it is not taken: ask dvda_pcm_hip_mix_valid.
+ *
+ * Out of scope: the disc's own downmix coefficient table (a caller who has it passes it as a dvda_pcm_mix), upmixing
+ * rules (though out > in is a valid matrix), float or per-frame gains, dither (requantize behind it dithers), the WAV
+ * layouts on either side, in place, the streaming tier and dvda_mlp_hip_decode_multi. */
+#define DVDA_MIX_NORMALIZED 0u
+#define DVDA_MIX_UNITY      1u
+#define DVDA_MIX_LFE        2u
+
+typedef struct dvda_pcm_mix {
+    uint32_t in_channels;     /* 1..8; must equal the input descriptor's channels  */
+    uint32_t out_channels;    /* 1..8; must equal the output descriptor's channels */
+    int32_t  coef[8][8];      /* coef[o][c], Q30; entries outside [out)[in) are ignored */
+} dvda_pcm_mix;               /* 264 bytes */
+typedef struct dvda_pcm_mix_report {
+    uint64_t frames;          /* PCM frames mixed */
+    uint64_t clipped[8];      /* per OUTPUT channel: values the clamp changed */
+} dvda_pcm_mix_report;        /* 72 bytes */
+
+/* The tier-free form.  Stream i: d_desc_in[i] in d_in (layout_in) -> d_desc_out[i] in d_out (layout_out) through the
+ * matrix d_mix[i], report d_report[i]; device arrays, n entries; each layout DVDA_PCM_PLANAR or DVDA_PCM_INTERLEAVED.
+ * The matrices lie on the device, so the kernels judge them: a stream is taken only when its input descriptor is one
+ * the reports take (channels 1..8, frames up to 2^40), its matrix is valid with in_channels == the input's channels and
+ * out_channels == the output descriptor's channels, and the output descriptor says exactly the input's frames and a
+ * stride >= frames; otherwise frames == 0 is reported and nothing is written.  Out of place only; any overlap of input
+ * and output regions is the caller's error.  Enqueued on `stream`: no host wait, no allocation.  max_total_frames: a
+ * bound the host knows on the sum of the streams' frames; a stream whose tiles (DVDA_LVL_TILE_FRAMES frames, aligned to
+ * its start) fall outside it reports zeros, and its output region holds unspecified values inside its bounds and nothing
+ * outside them.  d_work: dvda_pcm_hip_mix_workspace_words(n, max_total_frames) uint32 words, which need not be cleared;
+ * no atomics, the report is the same from run to run.  Either side's off may have any 4-byte alignment and a planar
+ * stride any parity; nothing outside a region's `frames` is read, nothing outside the output region written.  The
+ * arguments are judged first, on any machine -- DVDA_HIP_EINVAL: bits outside {16, 20, 24}, a WAV layout on either
+ * side, a null pointer, work_words too small; DVDA_HIP_ECAPACITY: 2^31 tiles or more -- then the device:
+ * DVDA_HIP_ENODEV without one. */
+size_t dvda_pcm_hip_mix_workspace_words(uint32_t n, uint64_t max_total_frames);
+int dvda_pcm_hip_mix(const int32_t *d_in, uint32_t layout_in, const dvda_pcm_crc_desc *d_desc_in,
+                     int32_t *d_out, uint32_t layout_out, const dvda_pcm_crc_desc *d_desc_out,
+                     const dvda_pcm_mix *d_mix, uint32_t n, unsigned bits, uint64_t max_total_frames,
+                     dvda_pcm_mix_report *d_report, uint32_t *d_work, size_t work_words, void *stream);
+
+/* behind dvda_mlp_hip_decode (blocks): the first n streams of the last decode mixed into d_out, in the context's layout
+ * on both sides (a WAV layout: DVDA_HIP_EINVAL): stream i through host_mix[i] (a host array of n matrices) to the dword
+ * offset d_mix_off[i] with the planar stride d_mix_stride[i] (device arrays, as d_out_off / d_out_stride are; a stride
+ * below the stream's frames: the stream is not taken).  Frames and channels are what dvda_mlp_hip_stream_info reports;
+ * a matrix whose in_channels differs from that is a stream not taken.  A stream that carries DVDA_ST_OVERFLOW reports
+ * zeros and nothing is written for it. */
+int dvda_mlp_hip_pcm_mix(dvda_mlp_hip_ctx *ctx, const int32_t *d_pcm, const uint64_t *d_out_off, const uint64_t *d_out_stride,
+                         int32_t *d_out, const uint64_t *d_mix_off, const uint64_t *d_mix_stride,
+                         const dvda_pcm_mix *host_mix, unsigned bits, dvda_pcm_mix_report *host_report, uint32_t n,
+                         void *stream);
+
+/* Host helpers; none needs a device.
+ * speaker_mask: the RIFF-WAVE speaker mask of DVD-Audio channel assignment 0..20 (what dvda_riff_wave_channel_mask of
+ *   the disc tier answers: the table lives here), 0 for any other assignment.
+ * mix_matrix: the default matrix above for a buffer whose channel c is the c-th set bit of speaker_mask, ascending, to
+ *   out_channels = 1 or 2, flags = DVDA_MIX_NORMALIZED or DVDA_MIX_UNITY, | DVDA_MIX_LFE.  DVDA_HIP_EINVAL for a zero mask,
+ *   bits outside 0x13F (FL FR FC LFE BL BR BC), out_channels outside {1, 2}, unknown flags or a NULL `out`.
+ * mix_valid: 1 when the matrix is valid as stated above, else 0 (NULL: 0).
+ * mix_value: the contract above for one output value -- the text the kernel compiles -- from the frame's in_channels
+ *   values x; *clipped (may be NULL) = 1 when the clamp changed the value, else 0; an invalid matrix or depth, o >=
+ *   out_channels or a NULL pointer: returns 0 and sets *clipped = -1. */
+unsigned dvda_pcm_hip_speaker_mask(unsigned assignment);
+int dvda_pcm_hip_mix_matrix(unsigned speaker_mask, uint32_t out_channels, uint32_t flags, dvda_pcm_mix *out);
+int dvda_pcm_hip_mix_valid(const dvda_pcm_mix *m);
+int32_t dvda_pcm_hip_mix_value(const int32_t *x, const dvda_pcm_mix *m, uint32_t o, unsigned bits, int *clipped);
+
 /* ------------------------------------------------------------------ tier B */
 /* The mlp.h mirror: same three calls, same meaning as reference src/mlp.h:29-42 /
  * src/mlp.c:265-354, with the reference's containers replaced by plain memory:

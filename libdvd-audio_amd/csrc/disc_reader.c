@@ -54,6 +54,9 @@ struct reader_opts {
                                    all of the above (dvda_hip_set_decimate, dvda_hip_reader_decimated) */
     unsigned rs_rate;           /* != 0 (44100): a whole-track reader brings a 48 / 96 / 192 kHz track to 44.1 kHz on the device,
                                    in the decimation's place (dvda_hip_set_resample, dvda_hip_reader_resampled) */
+    unsigned mx_ch, mx_flags;   /* mx_ch != 0 (1, 2): a whole-track reader mixes a track of another channel count to that many
+                                   channels on the device, in front of all of the above (dvda_hip_set_downmix,
+                                   dvda_hip_reader_downmixed) */
 };
 static _Thread_local struct reader_opts t_opts;
 static _Thread_local int t_conceal_set;     /* dvda_hip_set_conceal() was called on this thread: DVDA_CONCEAL no longer counts */
@@ -71,6 +74,11 @@ void dvda_hip_set_requantize(unsigned bits_out, unsigned mode, unsigned long lon
 }
 void dvda_hip_set_decimate(unsigned ratio) { t_opts.dc_ratio = ratio; }
 void dvda_hip_set_resample(unsigned rate) { t_opts.rs_rate = rate; }
+void dvda_hip_set_downmix(unsigned out_channels, unsigned flags)
+{
+    t_opts.mx_ch = out_channels;
+    t_opts.mx_flags = flags;
+}
 void dvda_hip_set_conceal(int on)
 {
     t_opts.conceal = on != 0;
@@ -145,6 +153,10 @@ static int rs_applies(const struct reader_opts *o, unsigned rate_code)
     return o->rs_rate == 44100 && rate_of(rate_code) != 0 && !(rate_code & 8);
 }
 
+/* does a reader opened with `o` mix a track of `channels` channels?  (a track that has out_channels already -- a stereo
+ * presentation too -- is handed out as it is) */
+static int mx_applies(const struct reader_opts *o, unsigned channels) { return o->mx_ch != 0 && channels != o->mx_ch; }
+
 static void rep_reset(struct pcm_reports *r)
 {
     free(r->ng_blocks);
@@ -160,6 +172,8 @@ struct DVDA_Track_Reader_s {
     unsigned src_rate;         /* != 0: the track's own rate, where the reader hands out a lower one (dvda_hip_set_decimate,
                                   dvda_hip_set_resample) */
     int dc_done, rs_done;      /* the track went through the decimation / the resampler */
+    unsigned src_channels;     /* != 0: the track's own channel count, where the reader hands out the mix (dvda_hip_set_downmix) */
+    dvda_pcm_mix_report mx_rep;    /* ... and what the mix counted */
     dvda_pcm_decim_report dc_rep, rs_rep;      /* ... and what each counted */
     uint64_t frames, served, stride;
     int interleaved;           /* MLP tracks: frame-major [frame][channel] = the dvda_read order;
@@ -522,16 +536,71 @@ static int track_decimate(int32_t **d_pcm, uint32_t layout, unsigned bits, uint6
     return 1;
 }
 
+/* A whole track mixed where it lies on the device (dvda_hip_set_downmix), by track_decimate's steps: `frames` frames of
+ * *ch channels (the channels of `mask`, ascending) at `bits` in `layout` at *d_pcm, capacity *stride frames, go through
+ * dvda_pcm_hip_mix with the default matrix of `mask` into a second buffer in the same layout, which takes the place of
+ * the first: the reader is the track of out_ch channels from here on.  One block on the device holds the two descriptors,
+ * the matrix, the report and the workspace.  Blocks; the first buffer is freed.  1 = ok. */
+static int track_mix(int32_t **d_pcm, uint32_t layout, unsigned bits, uint64_t *stride, uint64_t frames, unsigned *ch,
+                     unsigned mask, unsigned out_ch, unsigned flags, dvda_pcm_mix_report *rep)
+{
+    uint64_t out_stride = (frames + 3) & ~(uint64_t)3;
+    if (out_stride == 0)
+        out_stride = 4;
+    struct {
+        dvda_pcm_crc_desc in, out;
+        dvda_pcm_mix mix;
+        dvda_pcm_mix_report rep;
+    } blk;
+    memset(&blk, 0, sizeof(blk));
+    blk.in = (dvda_pcm_crc_desc){0, *stride, frames, *ch, 0};
+    blk.out = (dvda_pcm_crc_desc){0, out_stride, frames, out_ch, 0};
+    /* (a matrix the kernels would not take -- DVDA_MIX_UNITY rows above 2^31 -- or a mask of other channels: no reader) */
+    if (dvda_pcm_hip_mix_matrix(mask, out_ch, flags, &blk.mix) != DVDA_HIP_OK || !dvda_pcm_hip_mix_valid(&blk.mix) ||
+        blk.mix.in_channels != *ch)
+        return 0;
+    const size_t words = dvda_pcm_hip_mix_workspace_words(1, frames);
+    int32_t *d_out = NULL;
+    uint8_t *d = NULL;
+    int ok = dev_alloc((void **)&d_out, (size_t)out_stride * out_ch * sizeof(int32_t));
+    if (ok && frames) {
+        ok = dev_block_open(&d, &blk, sizeof(blk), words * sizeof(uint32_t)) &&
+             dvda_pcm_hip_mix(*d_pcm, layout, DEV_AT(d, blk, in), d_out, layout, DEV_AT(d, blk, out), DEV_AT(d, blk, mix), 1,
+                              bits, frames, DEV_AT(d, blk, rep), (uint32_t *)(d + sizeof(blk)), words, NULL) == DVDA_HIP_OK;
+        ok = dev_block_close(d, &blk, sizeof(blk), ok) && blk.rep.frames == frames;
+    }
+    if (!ok) {
+        (void)hipFree(d_out);
+        return 0;
+    }
+    (void)hipFree(*d_pcm);
+    *d_pcm = d_out;
+    *stride = out_stride;
+    *ch = out_ch;
+    *rep = blk.rep;
+    return 1;
+}
+
 /* What a whole-track reader, MLP or raw PCM, does with its track once it lies decoded on the device -- r->frames frames of
  * r->channels channels at the depth and rate of r's codes in `layout` at *d_pcm, capacity `stride` -- before any copy to
- * the host: the decimation where it applies (from there on the reader IS the shorter track at the lower rate), then the
- * reports the options want of the track as that left it, the word-length reduction among them: the reader hands out
- * bits_out bits from there on.  1 = ok. */
+ * the host: FIRST the channel mix where it applies (dvda_hip_set_downmix: r->channels and r->stride are the mixed
+ * track's from there on, r->src_channels the disc's), then the decimation or the resampler where they apply (from there
+ * on the reader IS the shorter track at the lower rate), then the reports the options want of the track as that left
+ * it, the word-length reduction among them: the reader hands out bits_out bits from there on.  Every stage rounds and
+ * clamps, so this order is part of the contract.  1 = ok. */
 static int track_passes(DVDA_Track_Reader *r, const struct reader_opts *o, int32_t **d_pcm, uint32_t layout, int wav_payload,
                         uint64_t stride)
 {
     const unsigned bits = bits_of(r->bps_code[0]);
     r->stride = stride;
+    /* the channel mix first, at the track's depth: every stage rounds and clamps, so the order is part of the contract */
+    if (mx_applies(o, r->channels)) {
+        const unsigned src = r->channels;
+        if (!track_mix(d_pcm, layout, bits, &r->stride, r->frames, &r->channels, dvda_pcm_hip_speaker_mask(r->assignment),
+                       o->mx_ch, o->mx_flags, &r->mx_rep))
+            return 0;
+        r->src_channels = src;
+    }
     if (rs_applies(o, r->rate_code[0])) {
         /* 96 / 192 kHz: by 2 / 4 to 48 kHz at the track's depth first; then 48 kHz to 44.1 kHz into a new buffer */
         const unsigned shift = r->rate_code[0] & 3;
@@ -812,7 +881,8 @@ static int decode_stream(struct track_bufs *b, uint64_t len, const int32_t *fir,
         stride = 4;
     if (*wav_bits < 0) {
         const unsigned bits = bits_of(info->group0_bps);
-        *wav_bits = (bits == 16 || bits == 24) && !(rq && (rq_applies(rq, bits) || dc_applies(rq, info->group0_rate) || rs_applies(rq, info->group0_rate)))
+        *wav_bits = (bits == 16 || bits == 24) && !(rq && (rq_applies(rq, bits) || dc_applies(rq, info->group0_rate) ||
+                                                           rs_applies(rq, info->group0_rate) || mx_applies(rq, info->channels)))
                         ? (int)bits : 0;
     }
     const unsigned wbits = (unsigned)*wav_bits;
@@ -939,11 +1009,11 @@ static DVDA_Track_Reader *open_mlp(struct aob_set *aobs, const DVDA_Track *k, co
     if (!mlp_info_to_reader(r, &info, o->present))
         goto fail;
     /* (a track that is decimated has int32 PCM: decode_stream saw the option) */
-    if ((wav_bits && (dc_applies(o, info.group0_rate) || rs_applies(o, info.group0_rate))) ||
+    if ((wav_bits && (dc_applies(o, info.group0_rate) || rs_applies(o, info.group0_rate) || mx_applies(o, r->channels))) ||
         !track_passes(r, o, &b.d_pcm, layout_of(wav_bits), wav_bits != 0, stride))
         goto fail;
-    if (r->src_rate) {
-        b.cap_pcm = 0;          /* (b.d_pcm is the decimation's buffer) */
+    if (r->src_rate || r->src_channels) {
+        b.cap_pcm = 0;          /* (b.d_pcm is the decimation's buffer, or the mix's) */
         t_line(&t_mark, "decimate + reports");
     }
     if (wav_bits) {
@@ -1835,7 +1905,7 @@ static DVDA_Track_Reader *open_mlp_windowed(const DVDA_Track *k, const struct re
        the first window and started the producer thread -- work thrown away, on a path that ends in NULL either way; a
        raw-PCM track's packet header has the rate, and open_pcm_windowed refuses before it starts anything) */
     if (!windows_start(w) || !w->info.channels || !mlp_info_to_reader(r, &w->info, o->present) ||
-        dc_applies(o, w->info.group0_rate) || rs_applies(o, w->info.group0_rate)) {
+        dc_applies(o, w->info.group0_rate) || rs_applies(o, w->info.group0_rate) || mx_applies(o, r->channels)) {
         reader_free(r);
         return NULL;
     }
@@ -1903,7 +1973,8 @@ static DVDA_Track_Reader *open_pcm_windowed(const DVDA_Track *k, const uint8_t *
     if (!r)
         return NULL;
     struct track_windows *w = r->win;
-    if (!pcm_params_to_reader(r, params, &bits, &rate) || dc_applies(o, r->rate_code[0]) || rs_applies(o, r->rate_code[0])) {
+    if (!pcm_params_to_reader(r, params, &bits, &rate) || dc_applies(o, r->rate_code[0]) || rs_applies(o, r->rate_code[0]) ||
+        mx_applies(o, r->channels)) {
         reader_free(r);
         return NULL;
     }
@@ -1943,6 +2014,9 @@ static DVDA_Track_Reader *open_reader(const DVDA_Track *k, const struct reader_o
         return NULL;
     /* the resampler: the one rate it makes; not together with conceal mode or the decimation */
     if (o->rs_rate && (o->rs_rate != 44100 || o->conceal || o->dc_ratio))
+        return NULL;
+    /* the channel mix: one or two channels, flags it has; not together with conceal mode */
+    if (o->mx_ch && (o->mx_ch > 2 || (o->mx_flags & ~(DVDA_MIX_UNITY | DVDA_MIX_LFE)) || o->conceal))
         return NULL;
     aob_open_all(&aobs, k->dir, k->titleset);
     if (aobs.n == 0 || k->s.first >= aobs.total)
@@ -2042,7 +2116,21 @@ int dvda_hip_reader_resampled(const DVDA_Track_Reader *r, dvda_pcm_decim_report 
         *out = r->rs_rep;
     return 1;
 }
-unsigned dvda_channel_count(const DVDA_Track_Reader *r) { return channels_of(r->assignment); }
+unsigned dvda_channel_count(const DVDA_Track_Reader *r) { return r->src_channels ? r->channels : channels_of(r->assignment); }
+unsigned dvda_hip_reader_source_channels(const DVDA_Track_Reader *r)
+{
+    if (!r)
+        return 0;
+    return r->src_channels ? r->src_channels : r->channels;
+}
+int dvda_hip_reader_downmixed(const DVDA_Track_Reader *r, dvda_pcm_mix_report *out)
+{
+    if (!r || !r->src_channels)
+        return 0;
+    if (out)
+        *out = r->mx_rep;
+    return 1;
+}
 unsigned dvda_hip_reader_status(const DVDA_Track_Reader *r)
 {
     if (!r->win)
@@ -2182,15 +2270,10 @@ int dvda_hip_reader_memory(const DVDA_Track_Reader *r, unsigned long long *host_
 
 unsigned dvda_riff_wave_channel_mask(const DVDA_Track_Reader *r)
 {
-    /* speaker bits per channel assignment (src/dvd-audio.c:693-755) */
-    enum { FL = 0x1, FR = 0x2, FC = 0x4, LF = 0x8, BL = 0x10, BR = 0x20, BC = 0x100 };
-    static const unsigned mask[21] = {
-        FC, FL | FR, FL | FR | BC, FL | FR | BL | BR, FL | FR | LF, FL | FR | LF | BC, FL | FR | LF | BL | BR,
-        FL | FR | FC, FL | FR | FC | BC, FL | FR | FC | BL | BR, FL | FR | FC | LF, FL | FR | FC | LF | BC,
-        FL | FR | FC | LF | BL | BR, FL | FR | FC | BC, FL | FR | FC | BL | BR, FL | FR | FC | LF,
-        FL | FR | FC | LF | BC, FL | FR | FC | LF | BL | BR, FL | FR | BL | BR | LF, FL | FR | BL | BR | FC,
-        FL | FR | BL | BR | FC | LF};
-    return r->assignment < 21 ? mask[r->assignment] : 0;
+    /* speaker bits per channel assignment (src/dvd-audio.c:693-755): the table the default mix matrices are made from */
+    if (r->src_channels)
+        return r->channels == 1 ? 0x4u : 0x3u;      /* the mix: FC, or FL | FR */
+    return dvda_pcm_hip_speaker_mask(r->assignment);
 }
 
 unsigned dvda_read(DVDA_Track_Reader *r, unsigned pcm_frames, int buffer[])

@@ -16,7 +16,8 @@
 // Host code beside the core, each in a header included here: hip_ws.h (owning buffers and handles), mlp_ctx.h (the
 // context), mlp_conceal_run.h, mlp_present_run.h (the two modes), mlp_stepper.h (streaming tier), mlp_tiers.h (raw PCM,
 // demux, WAV payload), pcm_report_run.h (the reports of the decoded PCM: its CRC-32, its levels, its compare with another buffer,
-// its energy, its reduction to a smaller word length, its decimation by 2 or 4, and 48 kHz resampled to 44.1 kHz).
+// its energy, its reduction to a smaller word length, its decimation by 2 or 4, 48 kHz resampled to 44.1 kHz, and its
+// channel mix).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>

@@ -1,7 +1,9 @@
-// pcm_report_run.h -- host side of the seven passes over decoded PCM (pcm_digest.h, pcm_levels.h, pcm_compare.h, pcm_energy.h,
-// pcm_requant.h, pcm_decim.h, pcm_resample.h): what a report is to the driver, the one driver of the flat tile list (pcm_tiles.h), the one
+// pcm_report_run.h -- host side of the eight passes over decoded PCM (pcm_digest.h, pcm_levels.h, pcm_compare.h, pcm_energy.h,
+// pcm_requant.h, pcm_decim.h, pcm_resample.h, pcm_mix.h): what a report is to the driver, the one driver of the flat tile list (pcm_tiles.h), the one
 // call that runs a report behind a decode on the context's buffers, and the host arithmetic that joins two pieces' results.
 #pragma once
+#include <string.h>
+
 #include <algorithm>
 #include <vector>
 
@@ -11,6 +13,7 @@
 #include "pcm_digest.h"
 #include "pcm_energy.h"
 #include "pcm_levels.h"
+#include "pcm_mix.h"
 #include "pcm_requant.h"
 #include "pcm_resample.h"
 
@@ -410,6 +413,69 @@ struct RsReport {
                            d_report);
     }
 };
+
+// The channel mix: the input is what the driver calls the PCM; the output -- buffer, layout, descriptors -- and the
+// matrices (a device array, so the kernels judge them) travel here.  Its unit is frames; the driver's `bits` is the depth
+// the values are clamped to.
+struct MixReport {
+    static constexpr uint32_t TILE = mix::TILE, TILE_WORDS = mix::REC, TILE_BLOCKS = mix::TILE_BLOCKS;     // unit: frames
+    dvda_pcm_mix_report *d_report;
+    int32_t *d_out;
+    uint32_t layout_out;
+    const dvda_pcm_crc_desc *d_desc_out;
+    const dvda_pcm_mix *d_mix;
+    const uint64_t *host_off, *host_stride;     // (host) behind a decode: where the output's regions lie
+    const dvda_pcm_mix *host_mix;               // (host) ... and the streams' matrices
+
+    // (an overflowed stream has no frames here: zeros reported, nothing written)
+    uint64_t units(const dvda_pcm_crc_desc &d, unsigned) const { return PCMT_NOT_TAKEN(d) ? 0 : d.frames; }
+    // the descriptors of both sides in one array: the input's [n], then the output's [n], which say the matrix's output
+    // channels.  d_rep_out: the reports (9 words each) | the matrices (33 words each)
+    int stage(Descs &desc, uint32_t n, ReportStage *s) const
+    {
+        desc.resize(2 * (size_t)n);
+        for (uint32_t i = 0; i < n; i++) {
+            dvda_pcm_crc_desc &o = desc[n + i];
+            o = desc[i];
+            o.off = host_off[i];
+            o.stride = host_stride[i];
+            o.channels = host_mix[i].out_channels;
+        }
+        constexpr size_t W = sizeof(dvda_pcm_mix) / 8;
+        s->behind.resize(W * n);
+        memcpy(s->behind.data(), host_mix, sizeof(dvda_pcm_mix) * (size_t)n);
+        return s->want((sizeof(dvda_pcm_mix_report) / 8 + W) * (size_t)n);
+    }
+    void bind(uint64_t *d_out_, uint64_t *d_behind, const dvda_pcm_crc_desc *d_desc, uint32_t n)
+    {
+        d_report = (dvda_pcm_mix_report *)d_out_;
+        d_desc_out = d_desc + n;
+        d_mix = (const dvda_pcm_mix *)d_behind;
+    }
+    bool has_out() const { return d_report && d_out && d_desc_out && d_mix && int32_layout(layout_out); }
+    static bool takes(uint32_t layout, unsigned bits) { return int32_layout(layout) && mix::depth_ok(bits); }
+
+    void plan(hipStream_t st, const dvda_pcm_crc_desc *d_desc, uint32_t n, unsigned, uint32_t *cnt) const
+    {
+        hipLaunchKernelGGL(mix::k_mix_plan, dim3((n + 255) / 256), dim3(256), 0, st, d_desc, d_desc_out, d_mix, n, cnt);
+    }
+    void tiles(dim3 grid, dim3 block, hipStream_t st, const int32_t *d_pcm, uint32_t layout, const dvda_pcm_crc_desc *d_desc,
+               uint32_t n, unsigned bits, const uint32_t *base, uint32_t *rec, uint32_t max_tiles) const
+    {
+        const bool pi = layout == DVDA_PCM_PLANAR, po = layout_out == DVDA_PCM_PLANAR;
+        auto k = pi ? (po ? mix::k_mix_tiles<true, true> : mix::k_mix_tiles<true, false>)
+                    : (po ? mix::k_mix_tiles<false, true> : mix::k_mix_tiles<false, false>);
+        hipLaunchKernelGGL(k, grid, block, 0, st, d_pcm, d_desc, d_out, d_desc_out, d_mix, n, (uint32_t)bits, base, rec,
+                           max_tiles);
+    }
+    void join(dim3 block, hipStream_t st, const dvda_pcm_crc_desc *d_desc, uint32_t n, unsigned, const uint32_t *base,
+              const uint32_t *rec, uint32_t max_tiles) const
+    {
+        hipLaunchKernelGGL(mix::k_mix_join, dim3(n), block, 0, st, d_desc, d_desc_out, d_mix, n, base, rec, max_tiles,
+                           d_report);
+    }
+};
+static_assert(sizeof(dvda_pcm_mix) == 264 && sizeof(dvda_pcm_mix_report) == 72, "the mix's structs");
 
 // ---- the driver of the flat tile list
 // tiles the list can hold for n streams of max_total units in all: every stream has at most one ragged tile -- unless the
@@ -941,6 +1007,130 @@ extern "C" int32_t dvda_pcm_hip_resample_value(const int32_t *window, uint32_t p
     }
     uint32_t cl = 0;
     const int32_t y = rsm::value(window, phase, bits, &cl);
+    if (clipped)
+        *clipped = (int)cl;
+    return y;
+}
+
+// ---- the channel mix
+extern "C" size_t dvda_pcm_hip_mix_workspace_words(uint32_t n, uint64_t max_total_frames)
+{
+    return report_workspace_words(MixReport{}, n, max_total_frames);
+}
+
+extern "C" int dvda_pcm_hip_mix(const int32_t *d_in, uint32_t layout_in, const dvda_pcm_crc_desc *d_desc_in, int32_t *d_out,
+                                uint32_t layout_out, const dvda_pcm_crc_desc *d_desc_out, const dvda_pcm_mix *d_mix,
+                                uint32_t n, unsigned bits, uint64_t max_total_frames, dvda_pcm_mix_report *d_report,
+                                uint32_t *d_work, size_t work_words, void *stream_)
+{
+    return report_run(MixReport{d_report, d_out, layout_out, d_desc_out, d_mix}, d_in, layout_in, bits, d_desc_in, n,
+                      max_total_frames, d_work, work_words, stream_);
+}
+
+extern "C" int dvda_mlp_hip_pcm_mix(dvda_mlp_hip_ctx *c, const int32_t *d_pcm, const uint64_t *d_out_off,
+                                    const uint64_t *d_out_stride, int32_t *d_out, const uint64_t *d_mix_off,
+                                    const uint64_t *d_mix_stride, const dvda_pcm_mix *host_mix, unsigned bits,
+                                    dvda_pcm_mix_report *host_report, uint32_t n, void *stream_)
+{
+    if (!c || !d_pcm || !d_out_off || !d_out_stride || !d_out || !d_mix_off || !d_mix_stride || !host_mix || !host_report ||
+        !MixReport::takes(c->set.pcm_layout, bits))
+        return DVDA_HIP_EINVAL;
+    if (!c->indexed)
+        return DVDA_HIP_ESTATE;
+    if (n > c->n_streams)
+        n = c->n_streams;
+    if (n == 0)
+        return DVDA_HIP_OK;
+    // where the output's regions lie, on the host: the stage writes them into the output's descriptors
+    std::vector<uint64_t> off(n), stride(n);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpy(off.data(), d_mix_off, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(stride.data(), d_mix_stride, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    MixReport r{nullptr, d_out, c->set.pcm_layout, nullptr, nullptr, off.data(), stride.data(), host_mix};
+    const int rc = report_of_decode(c, d_pcm, d_out_off, d_out_stride, bits, &n, stream_, &r);
+    if (rc || n == 0)
+        return rc;
+    return report_down(stream_, host_report, r.d_report, (size_t)n * sizeof(dvda_pcm_mix_report));
+}
+
+extern "C" unsigned dvda_pcm_hip_speaker_mask(unsigned assignment)
+{
+    // speaker bits per DVD-Audio channel assignment, the channels of a buffer in ascending order of their bits
+    enum { FL = 0x1, FR = 0x2, FC = 0x4, LF = 0x8, BL = 0x10, BR = 0x20, BC = 0x100 };
+    static const unsigned mask[21] = {
+        FC, FL | FR, FL | FR | BC, FL | FR | BL | BR, FL | FR | LF, FL | FR | LF | BC, FL | FR | LF | BL | BR,
+        FL | FR | FC, FL | FR | FC | BC, FL | FR | FC | BL | BR, FL | FR | FC | LF, FL | FR | FC | LF | BC,
+        FL | FR | FC | LF | BL | BR, FL | FR | FC | BC, FL | FR | FC | BL | BR, FL | FR | FC | LF,
+        FL | FR | FC | LF | BC, FL | FR | FC | LF | BL | BR, FL | FR | BL | BR | LF, FL | FR | BL | BR | FC,
+        FL | FR | BL | BR | FC | LF};
+    return assignment < 21 ? mask[assignment] : 0;
+}
+
+extern "C" int dvda_pcm_hip_mix_matrix(unsigned speaker_mask, uint32_t out_channels, uint32_t flags, dvda_pcm_mix *out)
+{
+    constexpr int64_t ONE = 1ll << 30, A = 759250125, HALF = 1ll << 29;
+    if (!out || speaker_mask == 0 || (speaker_mask & ~0x13Fu) || (out_channels != 1 && out_channels != 2) ||
+        (flags & ~(DVDA_MIX_UNITY | DVDA_MIX_LFE)))
+        return DVDA_HIP_EINVAL;
+    const int64_t lfe = (flags & DVDA_MIX_LFE) ? A : 0;
+    // the weights of the buffer's channels, the c-th set bit of the mask being channel c
+    int64_t w[2][8] = {};
+    uint32_t in = 0;
+    for (unsigned bit = 0; bit < 9; bit++) {
+        if (!(speaker_mask >> bit & 1u))
+            continue;
+        int64_t l = 0, r = 0;
+        switch (1u << bit) {
+        case 0x1: l = ONE; break;
+        case 0x2: r = ONE; break;
+        case 0x4: l = r = A; break;
+        case 0x8: l = r = lfe; break;
+        case 0x10: l = A; break;
+        case 0x20: r = A; break;
+        case 0x100: l = r = HALF; break;
+        }
+        w[0][in] = l;
+        w[1][in] = r;
+        in++;
+    }
+    dvda_pcm_mix m = {};
+    m.in_channels = in;
+    m.out_channels = out_channels;
+    if (out_channels == 1)
+        for (uint32_t c = 0; c < in; c++)
+            w[0][c] += w[1][c];
+    if (flags & DVDA_MIX_UNITY) {
+        for (uint32_t o = 0; o < out_channels; o++)
+            for (uint32_t c = 0; c < in; c++)
+                m.coef[o][c] = (int32_t)(out_channels == 1 ? w[0][c] >> 1 : w[o][c]);
+    } else {
+        int64_t S = 0;
+        for (uint32_t o = 0; o < out_channels; o++) {
+            int64_t sum = 0;
+            for (uint32_t c = 0; c < in; c++)
+                sum += w[o][c];
+            S = sum > S ? sum : S;
+        }
+        // (S == 0: an LFE alone without the flag; nothing of it reaches the output)
+        for (uint32_t o = 0; o < out_channels; o++)
+            for (uint32_t c = 0; c < in; c++)
+                m.coef[o][c] = S ? (int32_t)((w[o][c] << 30) / S) : 0;
+    }
+    *out = m;
+    return DVDA_HIP_OK;
+}
+
+extern "C" int dvda_pcm_hip_mix_valid(const dvda_pcm_mix *m) { return m && mix::valid(*m) ? 1 : 0; }
+
+extern "C" int32_t dvda_pcm_hip_mix_value(const int32_t *x, const dvda_pcm_mix *m, uint32_t o, unsigned bits, int *clipped)
+{
+    if (!x || !m || !mix::valid(*m) || o >= m->out_channels || !mix::depth_ok(bits)) {
+        if (clipped)
+            *clipped = -1;
+        return 0;
+    }
+    uint32_t cl = 0;
+    const int32_t y = mix::value(x, *m, o, bits, &cl);
     if (clipped)
         *clipped = (int)cl;
     return y;

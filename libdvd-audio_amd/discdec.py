@@ -29,6 +29,7 @@ EXPORTS = [
     "dvda_hip_set_energy", "dvda_hip_reader_energy", "dvda_hip_set_requantize", "dvda_hip_reader_requantized",
     "dvda_hip_reader_source_bits", "dvda_hip_set_decimate", "dvda_hip_reader_decimated", "dvda_hip_reader_source_rate",
     "dvda_hip_set_resample", "dvda_hip_reader_resampled",
+    "dvda_hip_set_downmix", "dvda_hip_reader_downmixed", "dvda_hip_reader_source_channels",
     "dvda_hip_set_conceal", "dvda_hip_reader_concealed", "dvda_hip_open_track_reader_concealing",
 ]
 
@@ -114,6 +115,12 @@ def lib():
         L.dvda_hip_set_resample.argtypes = [ctypes.c_uint]
         L.dvda_hip_reader_resampled.restype = ctypes.c_int
         L.dvda_hip_reader_resampled.argtypes = [vp, ctypes.POINTER(hipdec.DecimReport)]
+        L.dvda_hip_set_downmix.restype = None
+        L.dvda_hip_set_downmix.argtypes = [ctypes.c_uint, ctypes.c_uint]
+        L.dvda_hip_reader_downmixed.restype = ctypes.c_int
+        L.dvda_hip_reader_downmixed.argtypes = [vp, ctypes.POINTER(hipdec.PcmMixReport)]
+        L.dvda_hip_reader_source_channels.restype = ctypes.c_uint
+        L.dvda_hip_reader_source_channels.argtypes = [vp]
         L.dvda_hip_reader_source_rate.restype = ctypes.c_uint
         L.dvda_hip_reader_source_rate.argtypes = [vp]
         L.dvda_hip_reader_energy.restype = ctypes.c_int
@@ -157,7 +164,7 @@ def layout(audio_ts, titleset=1):
 
 def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0, fused=False, pieces=False,
                presentation=0, digest=False, levels=False, conceal=None, energy=0, requant=None, decimate=0,
-               resample=0):
+               resample=0, downmix=0):
     """Decodes one track on the GPU.  Returns a dict: codec ("PCM"/"MLP"), bits, rate, channels,
     mask, status, and pcm = int32 [frames, channels] (interleaved, RIFF-WAVE order) read with
     dvda_read() in `chunk`-frame calls -- or, with wav=True, payload = the WAV data bytes packed
@@ -196,6 +203,13 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
     48 -> 44.1 kHz pass counted as hipdec.DecimReport.as_dict() gives it (None when the reader does not resample: the
     44.1 kHz family), info["resample_state"] = what dvda_hip_reader_resampled returned, info["resample_decimate"] = the
     report of the decimation in front of it (None: there was none), info["source_rate"] = the rate on the disc.
+    downmix=2, 1 or (out_channels, flags): the reader delivers a track of any other channel count mixed to that many
+    channels (dvda_hip_set_downmix: the default matrix of the track's channel assignment with `flags`, hipdec.MIX_*, on
+    the device, exact, clamped at the track's depth, IN FRONT of decimate=, resample=, requant= and every report;
+    whole-track readers only, not together with conceal=); info["channels"] and info["mask"] are then those of the mix
+    (0x3, mono 0x4).  info["downmix"] = what the pass counted as hipdec.PcmMixReport.as_dict() gives it (None when the
+    reader does not mix: the track has that many channels already), info["downmix_state"] = what
+    dvda_hip_reader_downmixed returned, info["source_channels"] = the channels on the disc.
     conceal=True: a damaged MLP track is concealed, not refused (dvda_hip_set_conceal): info["concealed"] = the spans as
     6-tuples (first_frame, frames, byte_off, byte_end, cause, flags) in track terms, and info["concealed_states"] = what
     dvda_hip_reader_concealed returned right after the open and at the end.  conceal=False says "off" explicitly; None
@@ -219,6 +233,8 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
             L.dvda_hip_set_requantize(int(requant[0]), int(requant[1]), int(requant[2]))
         L.dvda_hip_set_decimate(int(decimate))
         L.dvda_hip_set_resample(int(resample))
+        mx = downmix if isinstance(downmix, (tuple, list)) else (downmix, 0)
+        L.dvda_hip_set_downmix(int(mx[0]), int(mx[1]))
         try:
             r = L.dvda_hip_open_track_reader_concealing(k, device, 1 if (fused and wav) else 0, presentation,
                                                         -1 if conceal is None else int(bool(conceal))) if k else None
@@ -229,6 +245,7 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
             L.dvda_hip_set_requantize(0, 0, 0)
             L.dvda_hip_set_decimate(0)
             L.dvda_hip_set_resample(0)
+            L.dvda_hip_set_downmix(0, 0)
         if not r:
             raise RuntimeError("track %d/%d/%d cannot be opened for reading" % (titleset, title, track))
         ch = L.dvda_channel_count(r)
@@ -313,6 +330,12 @@ def read_track(audio_ts, titleset, title, track, chunk=4096, wav=False, device=0
             info["resample"] = rs_report.as_dict() if state == 1 else None
             info["resample_decimate"] = dc_report.as_dict() if L.dvda_hip_reader_decimated(r, ctypes.byref(dc_report)) == 1 else None
             info["source_rate"] = int(L.dvda_hip_reader_source_rate(r))
+        if mx[0]:
+            mx_report = hipdec.PcmMixReport()
+            state = L.dvda_hip_reader_downmixed(r, ctypes.byref(mx_report))
+            info["downmix_state"] = state
+            info["downmix"] = mx_report.as_dict() if state == 1 else None
+            info["source_channels"] = int(L.dvda_hip_reader_source_channels(r))
         if conceal:
             state = L.dvda_hip_reader_concealed(r, None, 0, ctypes.byref(n_spans))
             arr = (hipdec.ConcealSpan * max(int(n_spans.value), 1))()

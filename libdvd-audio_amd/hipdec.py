@@ -84,7 +84,9 @@ EXPORTS = ("dvda_mlp_hip_create", "dvda_mlp_hip_destroy", "dvda_mlp_hip_index", 
            "dvda_pcm_hip_decimate", "dvda_pcm_hip_decimate_workspace_words", "dvda_mlp_hip_pcm_decimate",
            "dvda_pcm_hip_decim_taps", "dvda_pcm_hip_decim_out_frames", "dvda_pcm_hip_decim_value",
            "dvda_pcm_hip_resample", "dvda_pcm_hip_resample_workspace_words", "dvda_mlp_hip_pcm_resample",
-           "dvda_pcm_hip_resample_taps", "dvda_pcm_hip_resample_out_frames", "dvda_pcm_hip_resample_value")
+           "dvda_pcm_hip_resample_taps", "dvda_pcm_hip_resample_out_frames", "dvda_pcm_hip_resample_value",
+           "dvda_pcm_hip_mix", "dvda_pcm_hip_mix_workspace_words", "dvda_mlp_hip_pcm_mix",
+           "dvda_pcm_hip_speaker_mask", "dvda_pcm_hip_mix_matrix", "dvda_pcm_hip_mix_valid", "dvda_pcm_hip_mix_value")
 
 CRC_TILE_BYTES = 16384      # DVDA_CRC_TILE_BYTES: the digest's tiles, aligned to the end of a stream's payload
 CRC_JOIN_TILES = 256        # DVDA_CRC_JOIN_TILES: tiles a join workgroup folds per turn of its loop
@@ -96,15 +98,24 @@ class _Record(ctypes.Structure):
 
     def as_dict(self):
         out = {}
-        for k, t in self._fields_:
+        for k, _ in self._fields_:
             if k != "reserved":
-                v = getattr(self, k)
-                out[k] = [int(e) for e in v] if issubclass(t, ctypes.Array) else int(v)
+                out[k] = _plain(getattr(self, k))
         return out
 
     @classmethod
     def from_dict(cls, d):
-        return cls(**{k: t(*d[k]) if issubclass(t, ctypes.Array) else d[k] for k, t in cls._fields_ if k != "reserved"})
+        return cls(**{k: _typed(t, d[k]) for k, t in cls._fields_ if k != "reserved"})
+
+
+def _plain(v):
+    """a field of a record -> int, or (nested) lists of int for an array"""
+    return [_plain(e) for e in v] if isinstance(v, ctypes.Array) else int(v)
+
+
+def _typed(t, v):
+    """... and back: the value of ctypes type t"""
+    return t(*[_typed(t._type_, e) for e in v]) if issubclass(t, ctypes.Array) else v
 
 
 class CrcDesc(ctypes.Structure):
@@ -175,6 +186,19 @@ class DecimPiece(ctypes.Structure):
 class DecimReport(_Record):
     """dvda_pcm_decim_report of include/dvda_mlp_hip.h"""
     _fields_ = [("frames_in", ctypes.c_uint64), ("frames_out", ctypes.c_uint64), ("clipped", ctypes.c_uint64 * 8)]
+
+
+MIX_NORMALIZED, MIX_UNITY, MIX_LFE = 0, 1, 2     # DVDA_MIX_*: how dvda_pcm_hip_mix_matrix scales, and whether the LFE takes part
+
+
+class PcmMix(_Record):
+    """dvda_pcm_mix of include/dvda_mlp_hip.h"""
+    _fields_ = [("in_channels", ctypes.c_uint32), ("out_channels", ctypes.c_uint32), ("coef", (ctypes.c_int32 * 8) * 8)]
+
+
+class PcmMixReport(_Record):
+    """dvda_pcm_mix_report of include/dvda_mlp_hip.h"""
+    _fields_ = [("frames", ctypes.c_uint64), ("clipped", ctypes.c_uint64 * 8)]
 
 
 ST_CONCEALED = 1 << 30          # DVDA_ST_CONCEALED: conceal mode, the stream was damaged (not in ST_BENIGN)
@@ -350,6 +374,17 @@ def lib():
         L.dvda_pcm_hip_resample_out_frames.argtypes = [u64, u64]
         L.dvda_pcm_hip_resample_value.restype = ctypes.c_int32
         L.dvda_pcm_hip_resample_value.argtypes = [vp, u32, ctypes.c_uint, ctypes.POINTER(ctypes.c_int)]
+        L.dvda_pcm_hip_mix_workspace_words.restype = ctypes.c_size_t
+        L.dvda_pcm_hip_mix_workspace_words.argtypes = [u32, u64]
+        L.dvda_pcm_hip_mix.argtypes = [vp, u32, vp, vp, u32, vp, vp, u32, ctypes.c_uint, u64, vp, vp, ctypes.c_size_t, vp]
+        L.dvda_mlp_hip_pcm_mix.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(PcmMix), ctypes.c_uint,
+                                           ctypes.POINTER(PcmMixReport), u32, vp]
+        L.dvda_pcm_hip_speaker_mask.restype = ctypes.c_uint
+        L.dvda_pcm_hip_speaker_mask.argtypes = [ctypes.c_uint]
+        L.dvda_pcm_hip_mix_matrix.argtypes = [ctypes.c_uint, u32, u32, ctypes.POINTER(PcmMix)]
+        L.dvda_pcm_hip_mix_valid.argtypes = [ctypes.POINTER(PcmMix)]
+        L.dvda_pcm_hip_mix_value.restype = ctypes.c_int32
+        L.dvda_pcm_hip_mix_value.argtypes = [vp, ctypes.POINTER(PcmMix), u32, ctypes.c_uint, ctypes.POINTER(ctypes.c_int)]
         _lib = L
     return _lib
 
@@ -598,6 +633,19 @@ class Context:
         stride = (ctypes.c_uint64 * max(n, 1))(*[int(v) for v in dst_stride][:n])
         return self._records("dvda_mlp_hip_pcm_resample", DecimReport, n, stream, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr,
                              bits, d_dst_ptr, layout_dst, off, stride)
+
+    def pcm_mix(self, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr, d_dst_ptr, d_mix_off_ptr, d_mix_stride_ptr, matrices, bits,
+                n=None, stream=0):
+        """dvda_mlp_hip_pcm_mix: the int32 PCM the last decode wrote, stream i mixed through matrices[i] (a PcmMix or its
+        dict) and clamped to `bits` into the device buffer at d_dst_ptr, in the context's layout: to the int32 word
+        d_mix_off[i] with the planar stride d_mix_stride[i] (device arrays of uint64, as d_out_off / d_out_stride are) ->
+        list of PcmMixReport.as_dict(); blocks.  HipError (EINVAL) when the context's layout is a WAV one."""
+        n = self.n_streams if n is None else n
+        if len(matrices) < n:
+            raise HipError("pcm_mix: %d matrices for %d streams" % (len(matrices), n))
+        mats = (PcmMix * max(n, 1))(*[_mix_record(m) for m in matrices[:n]])
+        return self._records("dvda_mlp_hip_pcm_mix", PcmMixReport, n, stream, d_pcm_ptr, d_out_off_ptr, d_out_stride_ptr,
+                             d_dst_ptr, d_mix_off_ptr, d_mix_stride_ptr, mats, bits)
 
     def decode_time(self):
         """mean device ms of a whole decode call (all passes); call before kernel_time(), which resets the ring"""
@@ -1090,6 +1138,114 @@ def pcm_resample_workspace_words(n, max_total_out_frames):
     """dvda_pcm_hip_resample_workspace_words: the uint32 words of workspace pcm_resample needs for n streams whose
     OUTPUT frames sum to at most max_total_out_frames; needs no GPU"""
     return int(lib().dvda_pcm_hip_resample_workspace_words(n, max_total_out_frames))
+
+
+def _mix_record(m):
+    """a PcmMix, or the dict PcmMix.as_dict() gives -> a PcmMix"""
+    return m if isinstance(m, PcmMix) else PcmMix.from_dict(m)
+
+
+def speaker_mask(assignment):
+    """dvda_pcm_hip_speaker_mask: the RIFF-WAVE speaker mask of DVD-Audio channel assignment 0..20, else 0; needs no GPU"""
+    return int(lib().dvda_pcm_hip_speaker_mask(assignment))
+
+
+def mix_matrix(mask, out_channels=2, flags=MIX_NORMALIZED):
+    """dvda_pcm_hip_mix_matrix: the default matrix of a buffer whose channel c is the c-th set bit of `mask`, to 1 or 2
+    channels -> PcmMix.as_dict(); host arithmetic, needs no GPU.  HipError (EINVAL) for a mask, a channel count or flags
+    the call does not take"""
+    rec = PcmMix()
+    _check(lib().dvda_pcm_hip_mix_matrix(mask, out_channels, flags, ctypes.byref(rec)), "dvda_pcm_hip_mix_matrix")
+    return rec.as_dict()
+
+
+def mix_valid(m):
+    """dvda_pcm_hip_mix_valid: whether the kernels take the matrix; needs no GPU"""
+    return bool(lib().dvda_pcm_hip_mix_valid(ctypes.byref(_mix_record(m))))
+
+
+def mix_value(x, m, o, bits):
+    """dvda_pcm_hip_mix_value: output channel o of the frame whose in_channels values are x -> (value, 1 when the clamp
+    changed it else 0); host arithmetic, needs no GPU.  HipError for an invalid matrix, channel or depth or another
+    number of values"""
+    rec = _mix_record(m)
+    v = np.ascontiguousarray(x, np.int32)
+    if v.shape != (int(rec.in_channels),):
+        raise HipError("dvda_pcm_hip_mix_value: %s values for %d channels" % (v.shape, rec.in_channels))
+    cl = ctypes.c_int(0)
+    y = lib().dvda_pcm_hip_mix_value(v.ctypes.data, ctypes.byref(rec), o, bits, ctypes.byref(cl))
+    if cl.value < 0:
+        raise HipError("dvda_pcm_hip_mix_value: invalid parameters (channel %r, bits %r)" % (o, bits))
+    return int(y), int(cl.value)
+
+
+def _mix_records(matrices):
+    """a list of matrices -> their dvda_pcm_mix records as a numpy array of bytes rows (one at least)"""
+    rec = np.zeros((max(len(matrices), 1), ctypes.sizeof(PcmMix)), np.uint8)
+    for i, m in enumerate(matrices):
+        rec[i] = np.frombuffer(bytes(_mix_record(m)), np.uint8)
+    return rec
+
+
+def mix_desc_out(desc_in, matrices):
+    """the output descriptors pcm_mix makes when none are passed: per stream the input's frames and the matrix's output
+    channels, the regions end to end with the stride = the frames, which serves either int32 layout -> (desc_out, words)"""
+    out, pos = [], 0
+    for (_, _, frames, ch), m in zip(desc_in, matrices):
+        rec = _mix_record(m)
+        och = int(rec.out_channels)
+        ok = 1 <= int(ch) <= 8 and int(frames) <= 1 << 40 and 1 <= och <= 8
+        f = int(frames) if ok else 0
+        out.append((pos, f, f, och))
+        pos += f * och if ok else 0
+    return out, max(pos, 1)
+
+
+def pcm_mix(d_in, layout_in, desc_in, matrices, bits, out=None, layout_out=None, desc_out=None, max_total_frames=None,
+            work=None):
+    """dvda_pcm_hip_mix over torch tensors: d_in an int32 tensor on the device holding the streams in layout_in
+    (PCM_PLANAR or PCM_INTERLEAVED), desc_in a list of (off, stride, frames, channels), matrices one PcmMix (or its dict)
+    per stream; every stream mixed through its matrix, the values clamped to `bits`.  out / layout_out / desc_out: where
+    the result goes -- default: the input's layout, the regions end to end in a fresh zeroed tensor (mix_desc_out).  ->
+    (d_out, desc_out, d_report): the output tensor, its descriptors and a uint8 device tensor [n, sizeof(PcmMixReport)]
+    (mix_list brings it to the host).  Only the kernels are asynchronous, on torch's current stream: like pcm_levels, this
+    helper builds the descriptors and matrices on the host, copies them to the device and allocates them, the results
+    and -- when none is passed -- the workspace."""
+    layout_out = layout_in if layout_out is None else layout_out
+    if len(matrices) != len(desc_in):
+        raise HipError("pcm_mix: %d matrices for %d streams" % (len(matrices), len(desc_in)))
+    words = None
+    if desc_out is None:
+        desc_out, words = mix_desc_out(desc_in, matrices)
+    if len(desc_out) != len(desc_in):
+        raise HipError("pcm_mix: %d output descriptors for %d streams" % (len(desc_out), len(desc_in)))
+    if max_total_frames is None:
+        max_total_frames = int(sum(int(f) for _, _, f, c in desc_in if 1 <= int(c) <= 8 and int(f) <= 1 << 40))
+    torch, n, d_desc_in, work, st = _report_args(d_in, desc_in, "the channel mix", max_total_frames, work,
+                                                 lib().dvda_pcm_hip_mix_workspace_words)
+    dev = d_in.device
+    if out is None:
+        if words is None:
+            words = max([int(o) + int(r) * int(c) for o, r, f, c in desc_out] + [1])
+        out = torch.zeros(words, dtype=torch.int32, device=dev)
+    d_desc_out = _to_device(_desc_records(desc_out), dev)
+    d_mix = _to_device(_mix_records(matrices), dev)
+    d_rep = _result_tensor(PcmMixReport, n, dev)
+    _check(lib().dvda_pcm_hip_mix(d_in.data_ptr(), layout_in, d_desc_in.data_ptr(), out.data_ptr(), layout_out,
+                                  d_desc_out.data_ptr(), d_mix.data_ptr(), n, bits, max_total_frames, d_rep.data_ptr(),
+                                  work.data_ptr(), work.numel(), st), "dvda_pcm_hip_mix")
+    return out, desc_out, d_rep[:n]
+
+
+def pcm_mix_workspace_words(n, max_total_frames):
+    """dvda_pcm_hip_mix_workspace_words: the uint32 words of workspace pcm_mix needs for n streams whose frames sum to at
+    most max_total_frames; needs no GPU"""
+    return int(lib().dvda_pcm_hip_mix_workspace_words(n, max_total_frames))
+
+
+def mix_list(d_report):
+    """pcm_mix's report tensor -> list of PcmMixReport.as_dict() on the host (waits)"""
+    return _record_list(PcmMixReport, d_report)
 
 
 def crc_list(d_crc, d_nbytes):
@@ -1655,6 +1811,74 @@ def decode_streams_resampled(streams, rate=RESAMPLE_RATE, device=0, layout=PCM_P
             pcm.append(np.stack([host[c * stride:c * stride + frames] for c in range(ch)]).astype(np.int32))
         else:
             pcm.append(np.ascontiguousarray(host[:frames * ch].reshape(frames, ch).T).astype(np.int32))
+    return pcm, list(infos), reports
+
+
+def decode_streams_downmixed(streams, out_channels=2, flags=MIX_NORMALIZED, matrices=None, device=0, layout=PCM_PLANAR,
+                             ctx=None, presentation=PRESENT_FULL):
+    """Decodes complete MLP byte streams and mixes each to out_channels (1 or 2) channels on the device (Context.pcm_mix),
+    clamped at its own depth: through matrices[i] where the caller passes one (a PcmMix or its dict; None: the default),
+    else through the default matrix of its channel assignment (mix_matrix(speaker_mask(assignment), out_channels,
+    flags)).  A stream that already has out_channels channels and no matrix of the caller's is handed out as it is, with
+    a report of None.  -> (pcm, infos, reports): pcm[i] int32 [out channels, frames], reports[i] = PcmMixReport.as_dict().
+    ValueError for a default matrix the kernels do not take (MIX_UNITY rows whose weights sum above 2^31) or an
+    assignment without a speaker mask: judged before anything is mixed.  A stream whose region the decode could not fill
+    (DVDA_ST_OVERFLOW) comes out empty with a report of zeros."""
+    if layout not in (PCM_PLANAR, PCM_INTERLEAVED) or out_channels not in (1, 2):
+        raise HipError("decode_streams_downmixed: EINVAL (an int32 layout, 1 or 2 channels)")
+    import torch
+    batch = Batch(streams, device)
+    with _call_context(ctx, batch, None, 0, layout, presentation) as (ctx, capacity):
+        regions, infos, _ = decode_batch(ctx, batch, layout, attempts=2, capacity=capacity, to_host=False)
+        n = len(infos)
+        frames, desc, depth = _decoded_lists(infos, regions)
+        mats = [None] * n
+        for i, inf in enumerate(infos):
+            if matrices is not None and matrices[i] is not None:
+                mats[i] = _mix_record(matrices[i])
+            elif int(regions.channels[i]) != out_channels:
+                mask = speaker_mask(int(inf.assignment))
+                if bin(mask).count("1") != int(regions.channels[i]):
+                    raise ValueError("decode_streams_downmixed: stream %d: assignment %d names no %d channels" %
+                                     (i, inf.assignment, regions.channels[i]))
+                mats[i] = _mix_record(mix_matrix(mask, out_channels, flags))
+                if not mix_valid(mats[i]):
+                    raise ValueError("decode_streams_downmixed: stream %d: the default matrix of assignment %d with flags %d "
+                                     "has a row above 2^31" % (i, inf.assignment, flags))
+        reports = [None] * n
+        idx_all = [i for i in range(n) if mats[i] is not None]
+        # only a stream handed out as it is is copied with all its channels; of a mixed one, the mix alone
+        pcm = [None] * n
+        for i in range(n):
+            if mats[i] is None:
+                words = region_words(regions.rows[i], regions.channels[i], layout)
+                part = regions.d_pcm[regions.out_off[i]:regions.out_off[i] + words].cpu().numpy()
+                pcm[i] = cut_regions(part, [0], [regions.rows[i]], [regions.channels[i]], [infos[i].pcm_frames], layout)[0]
+        if idx_all:
+            # the mixed regions end to end; a stream handed out as it is has none
+            off, pos = [0] * n, 0
+            for i in idx_all:
+                off[i] = pos
+                pos += frames[i] * int(mats[i].out_channels)
+            d_out = torch.zeros(max(pos, 1), dtype=torch.int32, device=regions.dev)
+            d_off = torch.from_numpy(np.array(off, np.int64)).to(regions.dev)
+            d_stride = torch.from_numpy(np.array(frames, np.int64)).to(regions.dev)
+            none = PcmMix(0, 0)
+            st = torch.cuda.current_stream(regions.dev).cuda_stream
+            for bits in sorted(set(depth[i] for i in idx_all)):
+                # one call per depth over the whole batch: a stream of another depth, or one handed out as it is, runs
+                # with a matrix of no channels and is not taken
+                call = [mats[i] if mats[i] is not None and depth[i] == bits else none for i in range(n)]
+                rep = ctx.pcm_mix(regions.d_pcm.data_ptr(), regions.d_out_off.data_ptr(), regions.d_stride.data_ptr(),
+                                  d_out.data_ptr(), d_off.data_ptr(), d_stride.data_ptr(), call, bits, n=n, stream=st)
+                for i in idx_all:
+                    if depth[i] == bits:
+                        reports[i] = rep[i]
+            host = d_out.cpu().numpy()
+            for i in idx_all:
+                och, f = int(mats[i].out_channels), frames[i] if reports[i]["frames"] else 0
+                part = host[off[i]:off[i] + f * och]
+                pcm[i] = (part.reshape(och, f) if layout == PCM_PLANAR else np.ascontiguousarray(part.reshape(f, och).T)).astype(np.int32)
     return pcm, list(infos), reports
 
 

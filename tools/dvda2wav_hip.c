@@ -64,6 +64,8 @@ static unsigned long long g_rq_seed;
 static unsigned g_rate;
 /* --resample: with -r 44100, a 48 / 96 / 192 kHz track is resampled to 44.1 kHz */
 static int g_resample;
+/* --downmix: the channels every track of another count is mixed to (0: its own), and the DVDA_MIX_* flags */
+static unsigned g_mix_ch, g_mix_flags;
 
 static int extract(DVDA_Title *title, unsigned track_num, const char *dir, int device, int fused_wav, int stereo,
                    int crc, int conceal, unsigned titleset_num)
@@ -90,6 +92,8 @@ static int extract(DVDA_Title *title, unsigned track_num, const char *dir, int d
        divided by 2 comes as it is), and where that did not give RATE the track is opened again, by 4 or as it is.  A
        track long enough to be read in windows is refused by 2: it is opened as it is to learn its rate, and fails only
        where it really needs a ratio */
+    /* --downmix: the reader mixes the track to one or two channels on the device, in front of all of that */
+    dvda_hip_set_downmix(g_mix_ch, g_mix_flags);
     dvda_hip_set_decimate(g_rate ? 2 : 0);
     DVDA_Track_Reader *r = dvda_hip_open_track_reader_with(track, device, fused_wav, stereo);
     if (g_rate && (!r || dvda_sample_rate(r) != g_rate)) {
@@ -128,6 +132,7 @@ static int extract(DVDA_Title *title, unsigned track_num, const char *dir, int d
                         windowed ? " and is read in windows" : "", g_rate);
         }
     }
+    dvda_hip_set_downmix(0, 0);
     if (!r) {
         fprintf(stderr, "*** Error: unable to open track %u for reading\n", track_num);
         dvda_close_track(track);
@@ -214,6 +219,20 @@ static int extract(DVDA_Title *title, unsigned track_num, const char *dir, int d
         } else {
             printf("DECIMATE %u %u %u %u %u none\n", titleset_num, title_number, track_number, dvda_hip_reader_source_rate(r),
                    rate);
+        }
+    }
+    if (ok && g_mix_ch) {
+        /* what the mix did to the track just written: the channels on the disc, the file's, values the clamp changed */
+        struct dvda_pcm_mix_report mx;
+        if (dvda_hip_reader_downmixed(r, &mx) == 1) {
+            unsigned long long clipped = 0;
+            for (int c = 0; c < 8; c++)
+                clipped += mx.clipped[c];
+            printf("DOWNMIX %u %u %u %u %u %llu\n", titleset_num, title_number, track_number,
+                   dvda_hip_reader_source_channels(r), dvda_channel_count(r), clipped);
+        } else {
+            printf("DOWNMIX %u %u %u %u %u none\n", titleset_num, title_number, track_number,
+                   dvda_hip_reader_source_channels(r), dvda_channel_count(r));
         }
     }
     if (ok && g_resample) {
@@ -338,6 +357,13 @@ static void usage(const char *prog)
            "                            with -b / --dither (the reduction follows the decimation).  Whole-track readers\n"
            "                            only: a track long enough to be read in windows fails where it would have to be\n"
            "                            decimated, and is written as it is where not.  Not together with -K\n"
+           "      --downmix[=mono][,lfe][,unity]  mix every track of another channel count to 2 channels (mono: 1) on the\n"
+           "                            GPU with the default matrix of its channel assignment, exact, clamped at the track's\n"
+           "                            depth, in front of -r, --resample and -b; lfe: the LFE takes part; unity: the fronts\n"
+           "                            at gain 1 (the default scales so that nothing clips).  One line per track on stdout:\n"
+           "                            DOWNMIX <titleset> <title> <track> <source channels> <file's channels> <values\n"
+           "                            clamped> (\"none\" for a track written as it is).  Whole-track readers only.  Not\n"
+           "                            together with -K\n"
            "      --resample            with -r 44100: a 48, 96 or 192 kHz track is brought to 44100 Hz too (decimated by 2 or\n"
            "                            4 where its rate asks for it, then resampled by 147 / 160 on the GPU, exact, clamped\n"
            "                            at the track's depth).  One line per track on stdout: RESAMPLE <titleset> <title>\n"
@@ -360,6 +386,7 @@ int main(int argc, char *argv[])
                                        {"bits", required_argument, 0, 'b'},     {"dither", required_argument, 0, 1001},
                                        {"seed", required_argument, 0, 1002},    {"rate", required_argument, 0, 'r'},
                                        {"resample", no_argument, 0, 1003},
+                                       {"downmix", optional_argument, 0, 1004},
                                        {0, 0, 0, 0}};
     const char *audio_ts = NULL, *dir = ".", *cdrom = NULL;
     unsigned titleset_num = 1, title_num = 0, track_num = 0;
@@ -399,6 +426,23 @@ int main(int argc, char *argv[])
         case 'r': g_rate = (unsigned)strtoul(optarg, NULL, 10); break;
         case 1002: g_rq_seed = strtoull(optarg, NULL, 0); break;
         case 1003: g_resample = 1; break;
+        case 1004:
+            g_mix_ch = 2;
+            for (char *tok = optarg ? strtok(optarg, ",") : NULL; tok; tok = strtok(NULL, ",")) {
+                if (!strcmp(tok, "mono"))
+                    g_mix_ch = 1;
+                else if (!strcmp(tok, "stereo"))
+                    g_mix_ch = 2;
+                else if (!strcmp(tok, "lfe"))
+                    g_mix_flags |= DVDA_MIX_LFE;
+                else if (!strcmp(tok, "unity"))
+                    g_mix_flags |= DVDA_MIX_UNITY;
+                else {
+                    fprintf(stderr, "*** Error: --downmix takes mono, lfe and unity, separated by commas\n");
+                    return 1;
+                }
+            }
+            break;
         case 'h': usage(argv[0]); return 0;
         default: return 1;
         }
@@ -413,6 +457,10 @@ int main(int argc, char *argv[])
     }
     if (g_rate && ((g_rate != 44100 && g_rate != 48000 && g_rate != 88200 && g_rate != 96000) || conceal)) {
         fprintf(stderr, "*** Error: -r takes 44100, 48000, 88200 or 96000, and not together with -K\n");
+        return 1;
+    }
+    if (g_mix_ch && conceal) {
+        fprintf(stderr, "*** Error: --downmix does not go together with -K\n");
         return 1;
     }
     if (g_resample && g_rate != 44100) {
