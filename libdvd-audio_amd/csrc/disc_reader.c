@@ -490,84 +490,88 @@ static void reports_join(struct pcm_reports *track, const struct pcm_reports *pi
     }
 }
 
-/* A whole track decimated where it lies on the device (dvda_hip_set_decimate): `*frames` frames of `ch` channels at
- * `bits` in `layout` (an int32 one) at *d_pcm, capacity *stride frames, go through dvda_pcm_hip_decimate as one whole
- * track (no piece) into a second buffer in the same layout, which takes the place of the first: *d_pcm, *stride and
- * *frames are then those of a track of ceil(frames / ratio) frames at the lower rate, and everything the reader does
- * from here on -- requantize, the reports, the packing step, dvda_read -- sees that track.  One block on the device holds
- * the two descriptors, the report and the workspace.  Blocks; the first buffer is freed.  1 = ok. */
-static int track_decimate(int32_t **d_pcm, uint32_t layout, unsigned bits, uint64_t *stride, uint64_t *frames, unsigned ch,
-                          unsigned ratio, dvda_pcm_decim_report *rep)
+/* What a writer is to track_write: its call on one stream -- where the PCM, the descriptors, the pass's extra record,
+ * its report and its workspace lie on the device -- with the pass's own parameter, and what it keeps in the block. */
+struct track_dev {
+    const int32_t *in;
+    int32_t *out;
+    uint32_t layout;
+    unsigned bits;
+    const dvda_pcm_crc_desc *desc_in, *desc_out;
+    const void *extra;
+    void *rep;
+    uint32_t *work;
+    size_t words;
+    uint64_t out_frames;
+};
+struct track_pass {
+    int (*call)(const struct track_dev *v, unsigned arg);
+    unsigned arg;                   /* the pass's parameter (the ratio) */
+    const void *extra;              /* a record the pass reads on the device (the matrix), extra_bytes of it; or none */
+    size_t extra_bytes;
+    void *rep;                      /* its report, rep_bytes of it, the output's frame count frames_at bytes into it */
+    size_t rep_bytes, frames_at;
+    size_t words;                   /* its workspace */
+};
+
+static int call_decimate(const struct track_dev *v, unsigned ratio)
 {
-    /* (ratio 0: the same steps around dvda_pcm_hip_resample, 48 kHz to 44.1 kHz: dvda_hip_set_resample) */
-    const uint64_t out_frames = ratio ? dvda_pcm_hip_decim_out_frames(0, *frames, ratio)
-                                      : dvda_pcm_hip_resample_out_frames(0, *frames);
+    return dvda_pcm_hip_decimate(v->in, v->layout, v->desc_in, v->out, v->layout, v->desc_out, NULL, 1, ratio, v->bits,
+                                 v->out_frames, v->rep, v->work, v->words, NULL);
+}
+
+static int call_resample(const struct track_dev *v, unsigned none)
+{
+    (void)none;
+    return dvda_pcm_hip_resample(v->in, v->layout, v->desc_in, v->out, v->layout, v->desc_out, NULL, 1, v->bits, v->out_frames,
+                                 v->rep, v->work, v->words, NULL);
+}
+
+static int call_mix(const struct track_dev *v, unsigned none)
+{
+    (void)none;
+    return dvda_pcm_hip_mix(v->in, v->layout, v->desc_in, v->out, v->layout, v->desc_out, v->extra, 1, v->bits, v->out_frames,
+                            v->rep, v->work, v->words, NULL);
+}
+
+/* A whole track through a writer where it lies on the device: `frames` frames of `ch` channels at `bits` in `layout` (an
+ * int32 one) at *d_pcm, capacity *stride frames, go as one whole track (no piece) through p->call into a second buffer in
+ * the same layout -- out_frames frames of out_ch channels, the stride padded to a multiple of 4 -- which takes the place
+ * of the first: *d_pcm and *stride are then those of the track the pass made, and everything the reader does from here on
+ * sees that track.  One block on the device holds the two descriptors, the pass's extra record, its report and its
+ * workspace.  The pass must report out_frames frames (no frames: no call, a report of zeros).  Blocks; the first buffer
+ * is freed.  1 = ok. */
+static int track_write(int32_t **d_pcm, uint32_t layout, unsigned bits, uint64_t *stride, uint64_t frames, unsigned ch,
+                       uint64_t out_frames, unsigned out_ch, const struct track_pass *p)
+{
     uint64_t out_stride = (out_frames + 3) & ~(uint64_t)3;
     if (out_stride == 0)
         out_stride = 4;
-    struct {
-        dvda_pcm_crc_desc in, out;
-        dvda_pcm_decim_report rep;
-    } blk = {{0, *stride, *frames, ch, 0}, {0, out_stride, out_frames, ch, 0}, {0, 0, {0}}};
-    const size_t words = ratio ? dvda_pcm_hip_decimate_workspace_words(1, out_frames)
-                               : dvda_pcm_hip_resample_workspace_words(1, out_frames);
-    int32_t *d_out = NULL;
-    uint8_t *d = NULL;
-    int ok = dev_alloc((void **)&d_out, (size_t)out_stride * ch * sizeof(int32_t));
-    if (ok && out_frames) {
-        ok = dev_block_open(&d, &blk, sizeof(blk), words * sizeof(uint32_t)) &&
-             (ratio ? dvda_pcm_hip_decimate(*d_pcm, layout, DEV_AT(d, blk, in), d_out, layout, DEV_AT(d, blk, out), NULL, 1,
-                                            ratio, bits, out_frames, DEV_AT(d, blk, rep), (uint32_t *)(d + sizeof(blk)), words,
-                                            NULL)
-                    : dvda_pcm_hip_resample(*d_pcm, layout, DEV_AT(d, blk, in), d_out, layout, DEV_AT(d, blk, out), NULL, 1,
-                                            bits, out_frames, DEV_AT(d, blk, rep), (uint32_t *)(d + sizeof(blk)), words,
-                                            NULL)) == DVDA_HIP_OK;
-        ok = dev_block_close(d, &blk, sizeof(blk), ok) && blk.rep.frames_out == out_frames;
-    }
-    if (!ok) {
-        (void)hipFree(d_out);
+    const dvda_pcm_crc_desc desc[2] = {{0, *stride, frames, ch, 0}, {0, out_stride, out_frames, out_ch, 0}};
+    /* the head: the descriptors | the extra record | the report (room for the largest of either) */
+    uint8_t head[sizeof(desc) + sizeof(dvda_pcm_mix) + sizeof(dvda_pcm_decim_report)];
+    const size_t rep_at = sizeof(desc) + p->extra_bytes, head_bytes = rep_at + p->rep_bytes;
+    if (head_bytes > sizeof(head))
         return 0;
-    }
-    (void)hipFree(*d_pcm);
-    *d_pcm = d_out;
-    *stride = out_stride;
-    *frames = out_frames;
-    *rep = blk.rep;
-    return 1;
-}
-
-/* A whole track mixed where it lies on the device (dvda_hip_set_downmix), by track_decimate's steps: `frames` frames of
- * *ch channels (the channels of `mask`, ascending) at `bits` in `layout` at *d_pcm, capacity *stride frames, go through
- * dvda_pcm_hip_mix with the default matrix of `mask` into a second buffer in the same layout, which takes the place of
- * the first: the reader is the track of out_ch channels from here on.  One block on the device holds the two descriptors,
- * the matrix, the report and the workspace.  Blocks; the first buffer is freed.  1 = ok. */
-static int track_mix(int32_t **d_pcm, uint32_t layout, unsigned bits, uint64_t *stride, uint64_t frames, unsigned *ch,
-                     unsigned mask, unsigned out_ch, unsigned flags, dvda_pcm_mix_report *rep)
-{
-    uint64_t out_stride = (frames + 3) & ~(uint64_t)3;
-    if (out_stride == 0)
-        out_stride = 4;
-    struct {
-        dvda_pcm_crc_desc in, out;
-        dvda_pcm_mix mix;
-        dvda_pcm_mix_report rep;
-    } blk;
-    memset(&blk, 0, sizeof(blk));
-    blk.in = (dvda_pcm_crc_desc){0, *stride, frames, *ch, 0};
-    blk.out = (dvda_pcm_crc_desc){0, out_stride, frames, out_ch, 0};
-    /* (a matrix the kernels would not take -- DVDA_MIX_UNITY rows above 2^31 -- or a mask of other channels: no reader) */
-    if (dvda_pcm_hip_mix_matrix(mask, out_ch, flags, &blk.mix) != DVDA_HIP_OK || !dvda_pcm_hip_mix_valid(&blk.mix) ||
-        blk.mix.in_channels != *ch)
-        return 0;
-    const size_t words = dvda_pcm_hip_mix_workspace_words(1, frames);
+    memset(head, 0, sizeof(head));
+    memcpy(head, desc, sizeof(desc));
+    if (p->extra_bytes)
+        memcpy(head + sizeof(desc), p->extra, p->extra_bytes);
     int32_t *d_out = NULL;
     uint8_t *d = NULL;
     int ok = dev_alloc((void **)&d_out, (size_t)out_stride * out_ch * sizeof(int32_t));
-    if (ok && frames) {
-        ok = dev_block_open(&d, &blk, sizeof(blk), words * sizeof(uint32_t)) &&
-             dvda_pcm_hip_mix(*d_pcm, layout, DEV_AT(d, blk, in), d_out, layout, DEV_AT(d, blk, out), DEV_AT(d, blk, mix), 1,
-                              bits, frames, DEV_AT(d, blk, rep), (uint32_t *)(d + sizeof(blk)), words, NULL) == DVDA_HIP_OK;
-        ok = dev_block_close(d, &blk, sizeof(blk), ok) && blk.rep.frames == frames;
+    if (ok && out_frames) {
+        uint64_t made = 0;
+        ok = dev_block_open(&d, head, head_bytes, p->words * sizeof(uint32_t));
+        if (ok) {
+            const struct track_dev v = {*d_pcm, d_out, layout, bits, (const dvda_pcm_crc_desc *)d,
+                                        (const dvda_pcm_crc_desc *)d + 1, d + sizeof(desc), d + rep_at,
+                                        (uint32_t *)(d + head_bytes), p->words, out_frames};
+            ok = p->call(&v, p->arg) == DVDA_HIP_OK;
+        }
+        ok = dev_block_close(d, head, head_bytes, ok);
+        memcpy(&made, head + rep_at + p->frames_at, sizeof(made));
+        ok = ok && made == out_frames;
     }
     if (!ok) {
         (void)hipFree(d_out);
@@ -576,8 +580,40 @@ static int track_mix(int32_t **d_pcm, uint32_t layout, unsigned bits, uint64_t *
     (void)hipFree(*d_pcm);
     *d_pcm = d_out;
     *stride = out_stride;
+    memcpy(p->rep, head + rep_at, p->rep_bytes);
+    return 1;
+}
+
+/* dvda_hip_set_decimate, and with ratio 0 dvda_hip_set_resample (48 kHz to 44.1 kHz): *frames is then the frame count of
+ * the track at the lower rate */
+static int track_decimate(int32_t **d_pcm, uint32_t layout, unsigned bits, uint64_t *stride, uint64_t *frames, unsigned ch,
+                          unsigned ratio, dvda_pcm_decim_report *rep)
+{
+    const uint64_t out_frames = ratio ? dvda_pcm_hip_decim_out_frames(0, *frames, ratio)
+                                      : dvda_pcm_hip_resample_out_frames(0, *frames);
+    const struct track_pass p = {ratio ? call_decimate : call_resample, ratio, NULL, 0, rep, sizeof(*rep),
+                                 offsetof(dvda_pcm_decim_report, frames_out),
+                                 ratio ? dvda_pcm_hip_decimate_workspace_words(1, out_frames)
+                                       : dvda_pcm_hip_resample_workspace_words(1, out_frames)};
+    if (!track_write(d_pcm, layout, bits, stride, *frames, ch, out_frames, ch, &p))
+        return 0;
+    *frames = out_frames;
+    return 1;
+}
+
+/* dvda_hip_set_downmix: the track's *ch channels (the channels of `mask`, ascending) through the default matrix of `mask`
+ * to out_ch channels; the reader is the track of out_ch channels from here on */
+static int track_mix(int32_t **d_pcm, uint32_t layout, unsigned bits, uint64_t *stride, uint64_t frames, unsigned *ch,
+                     unsigned mask, unsigned out_ch, unsigned flags, dvda_pcm_mix_report *rep)
+{
+    dvda_pcm_mix mix;
+    const struct track_pass p = {call_mix, 0, &mix, sizeof(mix), rep, sizeof(*rep), offsetof(dvda_pcm_mix_report, frames),
+                                 dvda_pcm_hip_mix_workspace_words(1, frames)};
+    /* (a matrix the kernels would not take -- DVDA_MIX_UNITY rows above 2^31 -- or a mask of other channels: no reader) */
+    if (dvda_pcm_hip_mix_matrix(mask, out_ch, flags, &mix) != DVDA_HIP_OK || !dvda_pcm_hip_mix_valid(&mix) ||
+        mix.in_channels != *ch || !track_write(d_pcm, layout, bits, stride, frames, *ch, frames, out_ch, &p))
+        return 0;
     *ch = out_ch;
-    *rep = blk.rep;
     return 1;
 }
 

@@ -16,14 +16,12 @@
 //          Sample i of a channel lies at word i + i / 16: lanes of the tap loop are 16 samples apart, 17 words
 //          in LDS, so their reads fall into different banks.
 //   taps   a work item is R = 16 / D consecutive output frames of one channel: R int64 accumulators, the window walked
-//          once, each LDS read feeding up to R multiply-adds (v_mad_i64_i32).  Items are dealt to the lanes across
+//          once, each LDS read feeding up to R multiply-adds (pcmw::mad).  Items are dealt to the lanes across
 //          channels, C / R per channel.
 //   out    planar: 16-byte stores where the plane allows them, else the values one by one; frame-major: dwords, a
 //          frame apart (the staged input is still being read, and a value stored is some hundred multiply-adds).
 //          Nothing outside the stream's output region is written.
-//   count  a thread counts the clamped values, 16 bits per channel in two 64-bit words (a tile has at most TILE per
-//          channel); per tile they are folded (pcmt::block_fold) into REC words that the join sums.  No atomics; every
-//          word a join reads was stored by this launch.
+//   count  the clamped values per channel, a record of REC words per tile, summed by the join (pcm_write.h).
 //
 // tests/decimate_model.py restates the arithmetic with Python integers and in numpy.
 #pragma once
@@ -35,19 +33,23 @@
 #include "../../include/dvda_mlp_hip.h"
 #include "pcm_decim_taps.h"
 #include "pcm_tiles.h"
+#include "pcm_write.h"
 
 namespace dcm {
 
 using pcmt::MAX_CHANNELS;
 using pcmt::THREADS;
 using pcmt::WAVES;
+using pcmw::depth_ok;
+using pcmw::finish;
+using pcmw::mad;
+using pcmw::MAX_FRAME0;
+using pcmw::REC;
 
 constexpr uint32_t TILE = DVDA_DCM_TILE_FRAMES;
 constexpr uint32_t TILE_BLOCKS = 4096;      // workgroups of k_dc_tiles at most: they stride over the tile list
-constexpr uint32_t REC = MAX_CHANNELS;      // words of a tile's record: the clamped values per channel
 constexpr uint32_t LDS_WORDS = 15616;       // of staged input (61 KiB: two workgroups per CU)
 constexpr uint32_t LANE_SPAN = 16;          // input samples between two lanes' windows: D * R
-constexpr uint64_t MAX_FRAME0 = 1ull << 62; // a piece that says it starts behind this is not taken
 static_assert(TILE == 1024 && TILE < (1u << 16), "a tile's counts fit 16 bits");
 
 __host__ __device__ constexpr uint32_t taps_of(uint32_t D) { return 96u * D - 1u; }
@@ -63,7 +65,6 @@ static_assert(MAX_CHANNELS * chan_words(2, 256) <= LDS_WORDS && MAX_CHANNELS * c
               "the smallest chunk of eight channels fits");
 
 __host__ __device__ __forceinline__ bool ratio_ok(uint32_t D) { return D == 2 || D == 4; }
-__host__ __device__ __forceinline__ bool depth_ok(uint32_t b) { return b == 16 || b == 20 || b == 24; }
 
 // output frames of the absolute frames [frame0, frame0 + own): the M with frame0 <= D M < frame0 + own
 __host__ __device__ __forceinline__ uint64_t out_frames(uint64_t frame0, uint64_t own, uint32_t D)
@@ -111,20 +112,11 @@ __host__ __device__ __forceinline__ void load_block(int32_t (&x)[BLOCK], const L
     (one(std::integral_constant<uint32_t, Is>()), ...);
 }
 
-// acc += h * x.  On the device the instruction is written out: from `acc += (int64_t)h * x` the compiler factors the
-// symmetric taps, h (x1 + x2), and multiplies that 33-bit sum by h in three instructions where two of these do it.
-// The statement pins the tap to an SGPR and clobbers vcc (the carry out nobody reads).  Its price is the compiler's to
-// set: the hazard recognizer puts an s_nop 0 behind nearly every one, and at D = 4 the distinct taps do not fit the scalar
-// file and are rematerialised with s_mov inside the loop.  tests/test_isa_budget_decimate.py holds every build to the
-// counts DESIGN.md section 17 records.
-__host__ __device__ __forceinline__ void mad(int64_t &acc, int32_t h, int32_t x)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_mad_i64_i32 %0, vcc, %1, %2, %0" : "+v"(acc) : "v"(x), "s"(h) : "vcc");
-#else
-    acc += (int64_t)h * (int64_t)x;
-#endif
-}
+// The multiply-adds are pcmw::mad, each tap a compile-time constant.  From `acc += (int64_t)h * x` the compiler factors
+// the symmetric taps, h (x1 + x2), and multiplies that 33-bit sum by h in three instructions where two of the written-out
+// one do it.  Its price is the compiler's to set: the hazard recognizer puts an s_nop 0 behind nearly every one, and at
+// D = 4 the distinct taps do not fit the scalar file and are rematerialised with s_mov inside the loop.
+// tests/test_isa_budget_decimate.py holds every build to the counts DESIGN.md section 17 records.
 
 // position J of the window, value x, into the accumulators of the outputs that have a non-zero tap there
 template <uint32_t D, uint32_t R, uint32_t J, uint32_t... Rs>
@@ -177,16 +169,6 @@ __host__ __device__ __forceinline__ void accumulate(int64_t (&acc)[R], const Loa
     load_block<D, R, 0>(first, load, std::make_integer_sequence<uint32_t, BLOCK>());
     DCM_SCHED_FENCE();
     blocks_from<D, R, 0>(acc, load, first);
-}
-
-// the one rounding and the clamp; *clipped += 1 when the clamp changed the value
-__host__ __device__ __forceinline__ int32_t finish(int64_t acc, uint32_t bits, uint32_t *clipped)
-{
-    const int64_t q = (acc + (1ll << 29)) >> 30;
-    const int64_t hi = (1ll << (bits - 1)) - 1, lo = -hi - 1;
-    const int64_t r = q < lo ? lo : q > hi ? hi : q;
-    *clipped += r != q ? 1u : 0u;
-    return (int32_t)r;
 }
 
 // THE value: the output frame whose window of 2 H + 1 input values is window[0 .. 2 H]
@@ -267,7 +249,7 @@ __global__ __launch_bounds__(THREADS, 2) void k_dc_tiles(const int32_t *__restri
         const int32_t *in_s = pcm + di.off;
         int32_t *out_s = out + dn.off;
         const bool out_16 = (reinterpret_cast<uintptr_t>(out_s) & 15u) == 0 && (ch == 1 || (dn.stride & 3u) == 0);
-        uint64_t cnt_lo = 0, cnt_hi = 0;
+        pcmw::ClipCount cnt;
         for (uint32_t k0 = 0; k0 < nm; k0 += C) {
             const uint32_t nmc = nm - k0 < C ? nm - k0 : C;                         // output frames of the chunk
             // region index of staged sample 0: H in front of the centre of the chunk's first output
@@ -351,9 +333,7 @@ __global__ __launch_bounds__(THREADS, 2) void k_dc_tiles(const int32_t *__restri
                     y[r] = finish(acc[r], bits, &one);
                     cl += o0 + r < nmc ? one : 0u;                      // (behind the stream's end: not an output)
                 }
-                const uint64_t add = (uint64_t)cl << (16u * (c & 3u));
-                cnt_lo += c < 4 ? add : 0ull;
-                cnt_hi += c < 4 ? 0ull : add;
+                cnt.add(c, cl);
                 const uint64_t m = m0 + k0 + o0;                        // the item's first output frame in the stream
                 if (OUT_PLANAR) {
                     int32_t *o = out_s + (uint64_t)c * dn.stride + m;
@@ -379,16 +359,7 @@ __global__ __launch_bounds__(THREADS, 2) void k_dc_tiles(const int32_t *__restri
             }
             __syncthreads();            // (s_buf has been read: the next chunk fills it)
         }
-        cnt_lo = pcmt::block_fold(cnt_lo, s_red, pcmt::FoldSum());
-        cnt_hi = pcmt::block_fold(cnt_hi, s_red, pcmt::FoldSum());
-        if (t == 0) {
-            uint32_t *o = rec + (uint64_t)b * REC;
-#pragma unroll
-            for (uint32_t c = 0; c < 4; c++) {
-                o[c] = (uint32_t)(cnt_lo >> (16u * c)) & 0xFFFFu;
-                o[4 + c] = (uint32_t)(cnt_hi >> (16u * c)) & 0xFFFFu;
-            }
-        }
+        cnt.store(rec + (uint64_t)b * REC, s_red);
     }
 }
 
@@ -404,25 +375,14 @@ __global__ __launch_bounds__(THREADS) void k_dc_join(const dvda_pcm_crc_desc *__
     const uint32_t s = blockIdx.x;
     if (s >= n)
         return;
-    Take tk = take(desc_in[s], desc_out[s], piece ? piece + s : nullptr, D);
+    const Take tk = take(desc_in[s], desc_out[s], piece ? piece + s : nullptr, D);
     const uint32_t first = base[s], n_t = tiles_of(tk.out);
-    if ((uint64_t)first + n_t > max_tiles)
-        tk.taken = false;
-    const uint32_t ch = tk.taken ? desc_in[s].channels : 0u, turns = tk.taken ? n_t : 0u;
-    const uint32_t *r0 = rec + (uint64_t)first * REC;
+    const bool taken = tk.taken && (uint64_t)first + n_t <= max_tiles;
     if (threadIdx.x == 0) {
-        out[s].frames_in = tk.taken ? tk.own : 0ull;
-        out[s].frames_out = tk.taken ? tk.out : 0ull;
+        out[s].frames_in = taken ? tk.own : 0ull;
+        out[s].frames_out = taken ? tk.out : 0ull;
     }
-    for (uint32_t c = 0; c < MAX_CHANNELS; c++) {
-        uint64_t sum = 0;
-        if (c < ch)
-            for (uint32_t i = threadIdx.x; i < turns; i += THREADS)
-                sum += r0[(uint64_t)i * REC + c];
-        sum = pcmt::block_fold(sum, s_red, pcmt::FoldSum());
-        if (threadIdx.x == 0)
-            out[s].clipped[c] = sum;
-    }
+    pcmw::join_clipped(rec, first, taken ? n_t : 0u, taken ? desc_in[s].channels : 0u, s_red, out[s].clipped);
 }
 
 } // namespace dcm

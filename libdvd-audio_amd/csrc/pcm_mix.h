@@ -6,7 +6,7 @@
 //
 //   value  acc = sum_c coef[o][c] x[c] in int64 (a valid row has sum |coef| <= 2^31: no int32 input overflows it), y =
 //          clamp((acc + 2^29) >> 30).  One text for the kernel and the host: mad() and finish(); value() is the two over
-//          one frame and dvda_pcm_hip_mix_value compiles it.
+//          one frame and dvda_pcm_hip_mix_value compiles it.  (Both are pcm_write.h's.)
 //   take   THE predicate of plan, tiles and join: the matrix valid, its channel counts those of the two descriptors, the
 //          output descriptor exactly the input's frames with room for them.  The matrices are device arrays, so it is
 //          the kernels that judge them.
@@ -28,9 +28,7 @@
 //          skipped by a wave-uniform branch that covers the lane's four frames.
 //   out    mirrors the input side: planes out as they lie, frame-major gathered from the planes into 16-byte groups.
 //          Nothing outside the stream's output region is written.
-//   count  a thread counts the clamped values, 16 bits per OUTPUT channel in two 64-bit words (a tile has at most TILE
-//          per channel); per tile they are folded (pcmt::block_fold) into REC words that the join sums per stream.  No
-//          atomics; every word a join reads was stored by this launch.
+//   count  the clamped values per OUTPUT channel, a record of REC words per tile, summed by the join (pcm_write.h).
 //
 // tests/mix_model.py restates the arithmetic with Python integers and in numpy.
 #pragma once
@@ -40,24 +38,27 @@
 #include "../../include/dvda_mlp_hip.h"
 #include "pcm_levels.h"
 #include "pcm_tiles.h"
+#include "pcm_write.h"
 
 namespace mix {
 
 using pcmt::MAX_CHANNELS;
 using pcmt::THREADS;
 using pcmt::WAVES;
+using pcmw::depth_ok;
+using pcmw::div_small;
+using pcmw::finish;
+using pcmw::mad;
+using pcmw::REC;
 
 constexpr uint32_t TILE = lvl::TILE;
 constexpr uint32_t TILE_BLOCKS = 2048;      // workgroups of k_mix_tiles at most: they stride over the tile list
-constexpr uint32_t REC = MAX_CHANNELS;      // words of a tile's record: the clamped values per OUTPUT channel
 constexpr uint32_t PER_LANE = 4;            // frames of a chunk a lane mixes
 constexpr uint32_t CHUNK = PER_LANE * THREADS;      // frames a workgroup holds at a time
 constexpr uint32_t PITCH = CHUNK + 4;       // words between the planes of a chunk in LDS
 constexpr uint32_t BATCH = 4;               // 16-byte loads a lane has in flight on the input side
 static_assert(TILE % CHUNK == 0 && TILE < (1u << 16), "a tile is whole chunks, its counts fit 16 bits");
 static_assert(CHUNK / 4 <= THREADS, "a plane of a chunk is at most one 16-byte group per lane");
-
-__host__ __device__ __forceinline__ bool depth_ok(uint32_t b) { return b == 16 || b == 20 || b == 24; }
 
 // the channel counts in range and every used row's sum of |coef| at most 2^31
 __host__ __device__ __forceinline__ bool valid(const dvda_pcm_mix &m)
@@ -76,29 +77,9 @@ __host__ __device__ __forceinline__ bool valid(const dvda_pcm_mix &m)
     return ok;
 }
 
-// acc += g * x.  On the device the instruction is written out, the coefficient in an SGPR: from `acc += (int64_t)g * x`
-// with a wave-uniform g the compiler extends g to 64 bits on the scalar side and multiplies in pieces (v_mad_u64_u32,
-// v_mul_lo_u32, adds), about three slow-class instructions where this is one.  (vcc: the carry out nobody reads.)
-__host__ __device__ __forceinline__ void mad(int64_t &acc, int32_t g, int32_t x)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_mad_i64_i32 %0, vcc, %1, %2, %0" : "+v"(acc) : "v"(x), "s"(g) : "vcc");
-#else
-    acc += (int64_t)g * (int64_t)x;
-#endif
-}
-
-// the one rounding and the clamp; *clipped += 1 when the clamp changed the value
-__host__ __device__ __forceinline__ int32_t finish(int64_t acc, uint32_t bits, uint32_t *clipped)
-{
-    const int64_t q = (acc + (1ll << 29)) >> 30;
-    const int64_t hi = (1ll << (bits - 1)) - 1, lo = -hi - 1;
-    const int64_t r = q < lo ? lo : q > hi ? hi : q;
-    *clipped += r != q ? 1u : 0u;
-    return (int32_t)r;
-}
-
-// THE value: output channel o of the frame whose in_channels values are x[]
+// THE value: output channel o of the frame whose in_channels values are x[].  (In the kernel the coefficient of
+// pcmw::mad is wave-uniform: from `acc += (int64_t)g * x` with such a g the compiler extends g to 64 bits on the scalar
+// side and multiplies in pieces -- v_mad_u64_u32, v_mul_lo_u32, adds.)
 __host__ __device__ __forceinline__ int32_t value(const int32_t *x, const dvda_pcm_mix &m, uint32_t o, uint32_t bits,
                                                   uint32_t *clipped)
 {
@@ -128,9 +109,6 @@ __global__ void k_mix_plan(const dvda_pcm_crc_desc *__restrict__ desc_in, const 
     if (i < n)
         cnt[i] = lvl::tiles_of(take(desc_in[i], desc_out[i], mat[i]));
 }
-
-// e / d for 0 < d <= 8 and e < 2^24, inv = 2^32 / d rounded up
-__device__ __forceinline__ uint32_t div_small(uint32_t e, uint32_t d, uint32_t inv) { return d == 1 ? e : __umulhi(e, inv); }
 
 // dwords of a run at `p` in front of its first 16-byte boundary (all n where it does not reach one)
 __device__ __forceinline__ uint32_t head_of(const void *p, uint32_t n)
@@ -184,12 +162,12 @@ __global__ __launch_bounds__(THREADS, 4) void k_mix_tiles(const int32_t *__restr
         if (ti >= lvl::tiles_of(frames))    // (counts that wrapped the scan: no tile of this stream, nothing is touched)
             continue;
         const uint32_t ich = di.channels, och = dn.channels;
-        const uint32_t inv_i = ich > 1 ? 0xFFFFFFFFu / ich + 1u : 0u, inv_o = och > 1 ? 0xFFFFFFFFu / och + 1u : 0u;
+        const uint32_t inv_i = pcmw::inv_of(ich), inv_o = pcmw::inv_of(och);
         const uint64_t f0 = (uint64_t)ti * TILE;
         const uint32_t nf = frames - f0 < TILE ? (uint32_t)(frames - f0) : TILE;
         const int32_t *in_s = pcm + di.off;
         int32_t *out_s = out + dn.off;
-        uint64_t cnt_lo = 0, cnt_hi = 0;
+        pcmw::ClipCount cnt;
         for (uint32_t k0 = 0; k0 < nf; k0 += CHUNK) {
             const uint32_t nfc = nf - k0 < CHUNK ? nf - k0 : CHUNK;     // frames of the chunk
             const uint64_t fc = f0 + k0;                                // the chunk's first frame in the stream
@@ -302,9 +280,7 @@ __global__ __launch_bounds__(THREADS, 4) void k_mix_tiles(const int32_t *__restr
                             s_buf[o * PITCH + t + j * THREADS] = finish(acc[j], bits, &one);
                             cl += t + j * THREADS < nfc ? one : 0u;     // (behind the chunk's end: not a value)
                         }
-                        const uint64_t add = (uint64_t)cl << (16u * (o & 3u));
-                        cnt_lo += o < 4 ? add : 0ull;
-                        cnt_hi += o < 4 ? 0ull : add;
+                        cnt.add(o, cl);
                     }
             }
             __syncthreads();
@@ -356,16 +332,7 @@ __global__ __launch_bounds__(THREADS, 4) void k_mix_tiles(const int32_t *__restr
             }
             __syncthreads();            // (s_buf has been read: the next chunk fills it)
         }
-        cnt_lo = pcmt::block_fold(cnt_lo, s_red, pcmt::FoldSum());
-        cnt_hi = pcmt::block_fold(cnt_hi, s_red, pcmt::FoldSum());
-        if (t == 0) {
-            uint32_t *o = rec + (uint64_t)b * REC;
-#pragma unroll
-            for (uint32_t c = 0; c < 4; c++) {
-                o[c] = (uint32_t)(cnt_lo >> (16u * c)) & 0xFFFFu;
-                o[4 + c] = (uint32_t)(cnt_hi >> (16u * c)) & 0xFFFFu;
-            }
-        }
+        cnt.store(rec + (uint64_t)b * REC, s_red);
     }
 }
 
@@ -385,19 +352,9 @@ __global__ __launch_bounds__(THREADS) void k_mix_join(const dvda_pcm_crc_desc *_
     const uint32_t first = base[s], n_t = lvl::tiles_of(frames);
     if ((uint64_t)first + n_t > max_tiles)
         frames = 0;
-    const uint32_t ch = frames ? desc_out[s].channels : 0u, turns = frames ? n_t : 0u;
-    const uint32_t *r0 = rec + (uint64_t)first * REC;
     if (threadIdx.x == 0)
         out[s].frames = frames;
-    for (uint32_t c = 0; c < MAX_CHANNELS; c++) {
-        uint64_t sum = 0;
-        if (c < ch)
-            for (uint32_t i = threadIdx.x; i < turns; i += THREADS)
-                sum += r0[(uint64_t)i * REC + c];
-        sum = pcmt::block_fold(sum, s_red, pcmt::FoldSum());
-        if (threadIdx.x == 0)
-            out[s].clipped[c] = sum;
-    }
+    pcmw::join_clipped(rec, first, frames ? n_t : 0u, frames ? desc_out[s].channels : 0u, s_red, out[s].clipped);
 }
 
 } // namespace mix

@@ -1,10 +1,12 @@
 // pcm_report_run.h -- host side of the eight passes over decoded PCM (pcm_digest.h, pcm_levels.h, pcm_compare.h, pcm_energy.h,
-// pcm_requant.h, pcm_decim.h, pcm_resample.h, pcm_mix.h): what a report is to the driver, the one driver of the flat tile list (pcm_tiles.h), the one
-// call that runs a report behind a decode on the context's buffers, and the host arithmetic that joins two pieces' results.
+// pcm_requant.h, pcm_decim.h, pcm_resample.h, pcm_mix.h): what a report is to the driver (the three writers with an
+// output buffer of their own on one base, WriterOut), the one driver of the flat tile list (pcm_tiles.h), the one call
+// that runs a report behind a decode on the context's buffers, and the host arithmetic that joins two pieces' results.
 #pragma once
 #include <string.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "mlp_ctx.h"
@@ -18,6 +20,16 @@
 #include "pcm_resample.h"
 
 static inline bool int32_layout(uint32_t layout) { return layout == DVDA_PCM_PLANAR || layout == DVDA_PCM_INTERLEAVED; }
+
+// the <IN_PLANAR, OUT_PLANAR> instance of a kernel template for two int32 layouts: pick(in, out) names the instance of
+// the two constants' values
+template <class Pick>
+static inline auto planar_instance(uint32_t layout_in, uint32_t layout_out, Pick pick)
+{
+    const bool pi = layout_in == DVDA_PCM_PLANAR, po = layout_out == DVDA_PCM_PLANAR;
+    return pi ? (po ? pick(std::true_type(), std::true_type()) : pick(std::true_type(), std::false_type()))
+              : (po ? pick(std::false_type(), std::true_type()) : pick(std::false_type(), std::false_type()));
+}
 
 // What a report behind a decode lays into the context's buffers (report_of_decode, below), as its stage() states it on
 // the host: the uint64 words it wants in d_rep_out -- its results first; none: nothing to run -- and what is uploaded
@@ -140,9 +152,7 @@ struct CmpReport {
     void tiles(dim3 grid, dim3 block, hipStream_t st, const int32_t *d_a, uint32_t layout, const dvda_pcm_crc_desc *d_desc,
                uint32_t n, unsigned bits, const uint32_t *base, uint32_t *rec, uint32_t max_tiles) const
     {
-        const bool pa = layout == DVDA_PCM_PLANAR, pb = layout_b == DVDA_PCM_PLANAR;
-        auto k = pa ? (pb ? cmp::k_cmp_tiles<true, true> : cmp::k_cmp_tiles<true, false>)
-                    : (pb ? cmp::k_cmp_tiles<false, true> : cmp::k_cmp_tiles<false, false>);
+        auto k = planar_instance(layout, layout_b, [](auto a, auto b) { return cmp::k_cmp_tiles<a.value, b.value>; });
         hipLaunchKernelGGL(k, grid, block, 0, st, d_a, d_desc, d_b, d_desc_b, n, (uint32_t)bits, base, rec, max_tiles);
     }
     void join(dim3 block, hipStream_t st, const dvda_pcm_crc_desc *d_desc, uint32_t n, unsigned, const uint32_t *base,
@@ -290,25 +300,24 @@ struct RqReport {
 };
 static_assert(sizeof(dvda_pcm_requant) == 24 && sizeof(dvda_pcm_requant_report) == 72, "the requantizer's structs");
 
-// The decimation: the input is what the driver calls the PCM; the output -- buffer, layout, descriptors -- the pieces
-// and the ratio travel here.  Its unit is OUTPUT frames; the driver's `bits` is the depth the values are clamped to.
-struct DcReport {
-    static constexpr uint32_t TILE = dcm::TILE, TILE_WORDS = dcm::REC, TILE_BLOCKS = dcm::TILE_BLOCKS;     // unit: output frames
-    dvda_pcm_decim_report *d_report;
+// What the writers that lay their output into a buffer of its own (decimate, resample, mix) share: the input is what
+// the driver calls the PCM; the output -- buffer, layout, descriptors -- and the results travel here, and behind a decode
+// where the output's regions lie.
+template <class Rep>
+struct WriterOut {
+    Rep *d_report;
     int32_t *d_out;
     uint32_t layout_out;
     const dvda_pcm_crc_desc *d_desc_out;
-    const dvda_pcm_decim_piece *d_piece;
-    uint32_t ratio;
     const uint64_t *host_off, *host_stride;     // (host) behind a decode: where the output's regions lie
 
-    // (an overflowed stream has no frames here: zeros reported, nothing written)
-    uint64_t units(const dvda_pcm_crc_desc &d, unsigned) const
-    {
-        return PCMT_NOT_TAKEN(d) ? 0 : dcm::out_frames(0, d.frames, ratio);
-    }
-    // the descriptors of both sides in one array: the input's [n], then the output's [n]
-    int stage(Descs &desc, uint32_t n, ReportStage *s) const
+    bool out_ok() const { return d_report && d_out && d_desc_out && int32_layout(layout_out); }
+    // the descriptors of both sides in one array: the input's [n], then the output's [n] -- the input's at the output's
+    // place, shape(o, i) making the frames and channels the output's.  d_rep_out: the reports | s->behind -- so a pass
+    // that lays words behind its reports (the mix's matrices) fills s->behind BEFORE it calls this, and `s` is the fresh
+    // one of this call (report_of_decode makes it): the words wanted are counted from what it holds here
+    template <class Shape>
+    int stage_out(Descs &desc, uint32_t n, ReportStage *s, Shape shape) const
     {
         desc.resize(2 * (size_t)n);
         for (uint32_t i = 0; i < n; i++) {
@@ -316,16 +325,34 @@ struct DcReport {
             o = desc[i];
             o.off = host_off[i];
             o.stride = host_stride[i];
-            o.frames = units(desc[i], 0);
+            shape(o, i);
         }
-        return s->want((size_t)n * (sizeof(dvda_pcm_decim_report) / 8));
+        return s->want((size_t)n * (sizeof(Rep) / 8) + s->behind.size());
     }
     void bind(uint64_t *d_out_, uint64_t *, const dvda_pcm_crc_desc *d_desc, uint32_t n)
     {
-        d_report = (dvda_pcm_decim_report *)d_out_;
+        d_report = (Rep *)d_out_;
         d_desc_out = d_desc + n;
     }
-    bool has_out() const { return d_report && d_out && d_desc_out && dcm::ratio_ok(ratio) && int32_layout(layout_out); }
+};
+
+// The decimation: the pieces and the ratio travel here.  Its unit is OUTPUT frames; the driver's `bits` is the depth the
+// values are clamped to.
+struct DcReport : WriterOut<dvda_pcm_decim_report> {
+    static constexpr uint32_t TILE = dcm::TILE, TILE_WORDS = dcm::REC, TILE_BLOCKS = dcm::TILE_BLOCKS;     // unit: output frames
+    const dvda_pcm_decim_piece *d_piece;
+    uint32_t ratio;
+
+    // (an overflowed stream has no frames here: zeros reported, nothing written)
+    uint64_t units(const dvda_pcm_crc_desc &d, unsigned) const
+    {
+        return PCMT_NOT_TAKEN(d) ? 0 : dcm::out_frames(0, d.frames, ratio);
+    }
+    int stage(Descs &desc, uint32_t n, ReportStage *s) const
+    {
+        return stage_out(desc, n, s, [&](dvda_pcm_crc_desc &o, uint32_t) { o.frames = units(o, 0); });
+    }
+    bool has_out() const { return out_ok() && dcm::ratio_ok(ratio); }
     static bool takes(uint32_t layout, unsigned bits) { return int32_layout(layout) && dcm::depth_ok(bits); }
 
     void plan(hipStream_t st, const dvda_pcm_crc_desc *d_desc, uint32_t n, unsigned, uint32_t *cnt) const
@@ -336,9 +363,7 @@ struct DcReport {
     void tiles_of(dim3 grid, dim3 block, hipStream_t st, const int32_t *d_pcm, uint32_t layout, const dvda_pcm_crc_desc *d_desc,
                   uint32_t n, unsigned bits, const uint32_t *base, uint32_t *rec, uint32_t max_tiles) const
     {
-        const bool pi = layout == DVDA_PCM_PLANAR, po = layout_out == DVDA_PCM_PLANAR;
-        auto k = pi ? (po ? dcm::k_dc_tiles<D, true, true> : dcm::k_dc_tiles<D, true, false>)
-                    : (po ? dcm::k_dc_tiles<D, false, true> : dcm::k_dc_tiles<D, false, false>);
+        auto k = planar_instance(layout, layout_out, [](auto i, auto o) { return dcm::k_dc_tiles<D, i.value, o.value>; });
         hipLaunchKernelGGL(k, grid, block, 0, st, d_pcm, d_desc, d_out, d_desc_out, d_piece, n, (uint32_t)bits, base, rec,
                            max_tiles);
     }
@@ -359,38 +384,18 @@ struct DcReport {
 };
 static_assert(sizeof(dvda_pcm_decim_piece) == 16 && sizeof(dvda_pcm_decim_report) == 80, "the decimator's structs");
 
-// The resampler, 48 kHz to 44.1 kHz: the decimator's shape without a ratio.  Its unit is OUTPUT frames; the driver's
-// `bits` is the depth the values are clamped to.
-struct RsReport {
+// The resampler, 48 kHz to 44.1 kHz: the decimator's shape without a ratio.
+struct RsReport : WriterOut<dvda_pcm_decim_report> {
     static constexpr uint32_t TILE = rsm::TILE, TILE_WORDS = rsm::REC, TILE_BLOCKS = rsm::TILE_BLOCKS;     // unit: output frames
-    dvda_pcm_decim_report *d_report;
-    int32_t *d_out;
-    uint32_t layout_out;
-    const dvda_pcm_crc_desc *d_desc_out;
     const dvda_pcm_decim_piece *d_piece;
-    const uint64_t *host_off, *host_stride;     // (host) behind a decode: where the output's regions lie
 
     // (an overflowed stream has no frames here: zeros reported, nothing written)
     uint64_t units(const dvda_pcm_crc_desc &d, unsigned) const { return PCMT_NOT_TAKEN(d) ? 0 : rsm::out_frames(0, d.frames); }
-    // the descriptors of both sides in one array: the input's [n], then the output's [n]
     int stage(Descs &desc, uint32_t n, ReportStage *s) const
     {
-        desc.resize(2 * (size_t)n);
-        for (uint32_t i = 0; i < n; i++) {
-            dvda_pcm_crc_desc &o = desc[n + i];
-            o = desc[i];
-            o.off = host_off[i];
-            o.stride = host_stride[i];
-            o.frames = units(desc[i], 0);
-        }
-        return s->want((size_t)n * (sizeof(dvda_pcm_decim_report) / 8));
+        return stage_out(desc, n, s, [&](dvda_pcm_crc_desc &o, uint32_t) { o.frames = units(o, 0); });
     }
-    void bind(uint64_t *d_out_, uint64_t *, const dvda_pcm_crc_desc *d_desc, uint32_t n)
-    {
-        d_report = (dvda_pcm_decim_report *)d_out_;
-        d_desc_out = d_desc + n;
-    }
-    bool has_out() const { return d_report && d_out && d_desc_out && int32_layout(layout_out); }
+    bool has_out() const { return out_ok(); }
     static bool takes(uint32_t layout, unsigned bits) { return int32_layout(layout) && rsm::depth_ok(bits); }
 
     void plan(hipStream_t st, const dvda_pcm_crc_desc *d_desc, uint32_t n, unsigned, uint32_t *cnt) const
@@ -400,9 +405,7 @@ struct RsReport {
     void tiles(dim3 grid, dim3 block, hipStream_t st, const int32_t *d_pcm, uint32_t layout, const dvda_pcm_crc_desc *d_desc,
                uint32_t n, unsigned bits, const uint32_t *base, uint32_t *rec, uint32_t max_tiles) const
     {
-        const bool pi = layout == DVDA_PCM_PLANAR, po = layout_out == DVDA_PCM_PLANAR;
-        auto k = pi ? (po ? rsm::k_rs_tiles<true, true> : rsm::k_rs_tiles<true, false>)
-                    : (po ? rsm::k_rs_tiles<false, true> : rsm::k_rs_tiles<false, false>);
+        auto k = planar_instance(layout, layout_out, [](auto i, auto o) { return rsm::k_rs_tiles<i.value, o.value>; });
         hipLaunchKernelGGL(k, grid, block, 0, st, d_pcm, d_desc, d_out, d_desc_out, d_piece, n, (uint32_t)bits, base, rec,
                            max_tiles);
     }
@@ -414,45 +417,28 @@ struct RsReport {
     }
 };
 
-// The channel mix: the input is what the driver calls the PCM; the output -- buffer, layout, descriptors -- and the
-// matrices (a device array, so the kernels judge them) travel here.  Its unit is frames; the driver's `bits` is the depth
-// the values are clamped to.
-struct MixReport {
+// The channel mix: the matrices (a device array, so the kernels judge them) travel here.  Its unit is frames; the
+// driver's `bits` is the depth the values are clamped to.
+struct MixReport : WriterOut<dvda_pcm_mix_report> {
     static constexpr uint32_t TILE = mix::TILE, TILE_WORDS = mix::REC, TILE_BLOCKS = mix::TILE_BLOCKS;     // unit: frames
-    dvda_pcm_mix_report *d_report;
-    int32_t *d_out;
-    uint32_t layout_out;
-    const dvda_pcm_crc_desc *d_desc_out;
     const dvda_pcm_mix *d_mix;
-    const uint64_t *host_off, *host_stride;     // (host) behind a decode: where the output's regions lie
-    const dvda_pcm_mix *host_mix;               // (host) ... and the streams' matrices
+    const dvda_pcm_mix *host_mix;               // (host) behind a decode: the streams' matrices
 
     // (an overflowed stream has no frames here: zeros reported, nothing written)
     uint64_t units(const dvda_pcm_crc_desc &d, unsigned) const { return PCMT_NOT_TAKEN(d) ? 0 : d.frames; }
-    // the descriptors of both sides in one array: the input's [n], then the output's [n], which say the matrix's output
-    // channels.  d_rep_out: the reports (9 words each) | the matrices (33 words each)
+    // the output's descriptors say the matrix's output channels; the matrices (33 words each) lie behind the reports
     int stage(Descs &desc, uint32_t n, ReportStage *s) const
     {
-        desc.resize(2 * (size_t)n);
-        for (uint32_t i = 0; i < n; i++) {
-            dvda_pcm_crc_desc &o = desc[n + i];
-            o = desc[i];
-            o.off = host_off[i];
-            o.stride = host_stride[i];
-            o.channels = host_mix[i].out_channels;
-        }
-        constexpr size_t W = sizeof(dvda_pcm_mix) / 8;
-        s->behind.resize(W * n);
+        s->behind.resize(sizeof(dvda_pcm_mix) / 8 * n);
         memcpy(s->behind.data(), host_mix, sizeof(dvda_pcm_mix) * (size_t)n);
-        return s->want((sizeof(dvda_pcm_mix_report) / 8 + W) * (size_t)n);
+        return stage_out(desc, n, s, [&](dvda_pcm_crc_desc &o, uint32_t i) { o.channels = host_mix[i].out_channels; });
     }
     void bind(uint64_t *d_out_, uint64_t *d_behind, const dvda_pcm_crc_desc *d_desc, uint32_t n)
     {
-        d_report = (dvda_pcm_mix_report *)d_out_;
-        d_desc_out = d_desc + n;
+        WriterOut::bind(d_out_, d_behind, d_desc, n);
         d_mix = (const dvda_pcm_mix *)d_behind;
     }
-    bool has_out() const { return d_report && d_out && d_desc_out && d_mix && int32_layout(layout_out); }
+    bool has_out() const { return out_ok() && d_mix; }
     static bool takes(uint32_t layout, unsigned bits) { return int32_layout(layout) && mix::depth_ok(bits); }
 
     void plan(hipStream_t st, const dvda_pcm_crc_desc *d_desc, uint32_t n, unsigned, uint32_t *cnt) const
@@ -462,9 +448,7 @@ struct MixReport {
     void tiles(dim3 grid, dim3 block, hipStream_t st, const int32_t *d_pcm, uint32_t layout, const dvda_pcm_crc_desc *d_desc,
                uint32_t n, unsigned bits, const uint32_t *base, uint32_t *rec, uint32_t max_tiles) const
     {
-        const bool pi = layout == DVDA_PCM_PLANAR, po = layout_out == DVDA_PCM_PLANAR;
-        auto k = pi ? (po ? mix::k_mix_tiles<true, true> : mix::k_mix_tiles<true, false>)
-                    : (po ? mix::k_mix_tiles<false, true> : mix::k_mix_tiles<false, false>);
+        auto k = planar_instance(layout, layout_out, [](auto i, auto o) { return mix::k_mix_tiles<i.value, o.value>; });
         hipLaunchKernelGGL(k, grid, block, 0, st, d_pcm, d_desc, d_out, d_desc_out, d_mix, n, (uint32_t)bits, base, rec,
                            max_tiles);
     }
@@ -540,23 +524,29 @@ static int report_run(const R &r, const int32_t *d_pcm, uint32_t layout, unsigne
     return DVDA_HIP_OK;
 }
 
+// n clamped to the batch of the context's last decode (0: nothing to do); ESTATE for a context that has not indexed
+static int report_clamp(const dvda_mlp_hip_ctx *c, uint32_t *n_io)
+{
+    if (!c->indexed)
+        return DVDA_HIP_ESTATE;
+    if (*n_io > c->n_streams)
+        *n_io = c->n_streams;
+    return DVDA_HIP_OK;
+}
+
 // The descriptors of the first n (clamped to the batch; 0: nothing to do) streams of the context's last decode, on the
 // host: frames and channels from what dvda_mlp_hip_stream_info says, off / stride from the caller's d_out_off /
 // d_out_stride, copied down.  Blocks.
 static int report_decode_descs(dvda_mlp_hip_ctx *c, const uint64_t *d_out_off, const uint64_t *d_out_stride, uint32_t *n_io,
                                void *stream_, std::vector<dvda_pcm_crc_desc> *desc_)
 {
-    if (!c->indexed)
-        return DVDA_HIP_ESTATE;
-    if (*n_io > c->n_streams)
-        *n_io = c->n_streams;
+    int rc = report_clamp(c, n_io);
     const uint32_t n = *n_io;
-    if (n == 0)
-        return DVDA_HIP_OK;
+    if (rc || n == 0)
+        return rc;
     // frames and channels as the caller is told them: conceal mode's composed record and the presentation included
     std::vector<dvda_mlp_stream_info> infos(n);
-    int rc = dvda_mlp_hip_stream_info(c, infos.data(), n, stream_);
-    if (rc)
+    if ((rc = dvda_mlp_hip_stream_info(c, infos.data(), n, stream_)) != 0)
         return rc;
     HIP_TRY(hipSetDevice(c->device));
     std::vector<uint64_t> off(n), stride(n);
@@ -618,6 +608,18 @@ static int report_down(void *stream_, void *host, const void *dev, size_t bytes,
         HIP_TRY(hipMemcpyAsync(host2, dev2, bytes2, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return DVDA_HIP_OK;
+}
+
+// What the *_value entry points do around their pass's value(): bad arguments (`ok` false) give 0 with *clipped = -1,
+// else value(&cl) with *clipped = whether the clamp changed it.  clipped may be NULL.
+template <class Value>
+static inline int32_t value_or_bad(bool ok, int *clipped, Value value)
+{
+    uint32_t cl = 0;
+    const int32_t y = ok ? value(&cl) : 0;
+    if (clipped)
+        *clipped = ok ? (int)cl : -1;
+    return y;
 }
 
 // ---- the digest
@@ -885,18 +887,11 @@ extern "C" int dvda_mlp_hip_pcm_requantize(dvda_mlp_hip_ctx *c, int32_t *d_pcm, 
 extern "C" int32_t dvda_pcm_hip_requant_value(int32_t v, uint64_t frame, uint32_t channel, const dvda_pcm_requant *params,
                                               int *clipped)
 {
-    if (!params || !rq::params_ok(*params)) {
-        if (clipped)
-            *clipped = -1;
-        return 0;
-    }
-    const rq::Par p = rq::par_of(*params);
-    const uint64_t z = p.mode == DVDA_RQ_TPDF && p.s ? rq::noise_word(p.seed, frame >> 2, channel) : 0;
-    uint32_t cl = 0;
-    const int32_t q = rq::value(v, p, rq::noise_field(z, (uint32_t)frame & 3u), &cl);
-    if (clipped)
-        *clipped = (int)cl;
-    return q;
+    return value_or_bad(params && rq::params_ok(*params), clipped, [&](uint32_t *cl) {
+        const rq::Par p = rq::par_of(*params);
+        const uint64_t z = p.mode == DVDA_RQ_TPDF && p.s ? rq::noise_word(p.seed, frame >> 2, channel) : 0;
+        return rq::value(v, p, rq::noise_field(z, (uint32_t)frame & 3u), cl);
+    });
 }
 
 // ---- the decimation
@@ -911,7 +906,7 @@ extern "C" int dvda_pcm_hip_decimate(const int32_t *d_in, uint32_t layout_in, co
                                      uint64_t max_total_out_frames, dvda_pcm_decim_report *d_report, uint32_t *d_work,
                                      size_t work_words, void *stream_)
 {
-    return report_run(DcReport{d_report, d_out, layout_out, d_desc_out, d_piece, ratio}, d_in, layout_in, bits, d_desc_in, n,
+    return report_run(DcReport{{d_report, d_out, layout_out, d_desc_out}, d_piece, ratio}, d_in, layout_in, bits, d_desc_in, n,
                       max_total_out_frames, d_work, work_words, stream_);
 }
 
@@ -923,7 +918,7 @@ extern "C" int dvda_mlp_hip_pcm_decimate(dvda_mlp_hip_ctx *c, const int32_t *d_p
     if (!c || !d_pcm || !d_out_off || !d_out_stride || !d_dst || !host_dst_off || !host_dst_stride || !host_report ||
         !dcm::ratio_ok(ratio) || !int32_layout(layout_dst) || !DcReport::takes(c->set.pcm_layout, bits))
         return DVDA_HIP_EINVAL;
-    DcReport r{nullptr, d_dst, layout_dst, nullptr, nullptr, ratio, host_dst_off, host_dst_stride};
+    DcReport r{{nullptr, d_dst, layout_dst, nullptr, host_dst_off, host_dst_stride}, nullptr, ratio};
     const int rc = report_of_decode(c, d_pcm, d_out_off, d_out_stride, bits, &n, stream_, &r);
     if (rc || n == 0)
         return rc;
@@ -944,16 +939,9 @@ extern "C" uint64_t dvda_pcm_hip_decim_out_frames(uint64_t frame0, uint64_t own,
 
 extern "C" int32_t dvda_pcm_hip_decim_value(const int32_t *window, uint32_t ratio, unsigned bits, int *clipped)
 {
-    if (!window || !dcm::ratio_ok(ratio) || !dcm::depth_ok(bits)) {
-        if (clipped)
-            *clipped = -1;
-        return 0;
-    }
-    uint32_t cl = 0;
-    const int32_t y = ratio == 2 ? dcm::value<2>(window, bits, &cl) : dcm::value<4>(window, bits, &cl);
-    if (clipped)
-        *clipped = (int)cl;
-    return y;
+    return value_or_bad(window && dcm::ratio_ok(ratio) && dcm::depth_ok(bits), clipped, [&](uint32_t *cl) {
+        return ratio == 2 ? dcm::value<2>(window, bits, cl) : dcm::value<4>(window, bits, cl);
+    });
 }
 
 // ---- the resampler
@@ -968,7 +956,7 @@ extern "C" int dvda_pcm_hip_resample(const int32_t *d_in, uint32_t layout_in, co
                                      uint64_t max_total_out_frames, dvda_pcm_decim_report *d_report, uint32_t *d_work,
                                      size_t work_words, void *stream_)
 {
-    return report_run(RsReport{d_report, d_out, layout_out, d_desc_out, d_piece}, d_in, layout_in, bits, d_desc_in, n,
+    return report_run(RsReport{{d_report, d_out, layout_out, d_desc_out}, d_piece}, d_in, layout_in, bits, d_desc_in, n,
                       max_total_out_frames, d_work, work_words, stream_);
 }
 
@@ -980,7 +968,7 @@ extern "C" int dvda_mlp_hip_pcm_resample(dvda_mlp_hip_ctx *c, const int32_t *d_p
     if (!c || !d_pcm || !d_out_off || !d_out_stride || !d_dst || !host_dst_off || !host_dst_stride || !host_report ||
         !int32_layout(layout_dst) || !RsReport::takes(c->set.pcm_layout, bits))
         return DVDA_HIP_EINVAL;
-    RsReport r{nullptr, d_dst, layout_dst, nullptr, nullptr, host_dst_off, host_dst_stride};
+    RsReport r{{nullptr, d_dst, layout_dst, nullptr, host_dst_off, host_dst_stride}};
     const int rc = report_of_decode(c, d_pcm, d_out_off, d_out_stride, bits, &n, stream_, &r);
     if (rc || n == 0)
         return rc;
@@ -1000,16 +988,8 @@ extern "C" uint64_t dvda_pcm_hip_resample_out_frames(uint64_t frame0, uint64_t o
 
 extern "C" int32_t dvda_pcm_hip_resample_value(const int32_t *window, uint32_t phase, unsigned bits, int *clipped)
 {
-    if (!window || phase >= rsm::PHASES || !rsm::depth_ok(bits)) {
-        if (clipped)
-            *clipped = -1;
-        return 0;
-    }
-    uint32_t cl = 0;
-    const int32_t y = rsm::value(window, phase, bits, &cl);
-    if (clipped)
-        *clipped = (int)cl;
-    return y;
+    return value_or_bad(window && phase < rsm::PHASES && rsm::depth_ok(bits), clipped,
+                        [&](uint32_t *cl) { return rsm::value(window, phase, bits, cl); });
 }
 
 // ---- the channel mix
@@ -1023,7 +1003,7 @@ extern "C" int dvda_pcm_hip_mix(const int32_t *d_in, uint32_t layout_in, const d
                                 uint32_t n, unsigned bits, uint64_t max_total_frames, dvda_pcm_mix_report *d_report,
                                 uint32_t *d_work, size_t work_words, void *stream_)
 {
-    return report_run(MixReport{d_report, d_out, layout_out, d_desc_out, d_mix}, d_in, layout_in, bits, d_desc_in, n,
+    return report_run(MixReport{{d_report, d_out, layout_out, d_desc_out}, d_mix}, d_in, layout_in, bits, d_desc_in, n,
                       max_total_frames, d_work, work_words, stream_);
 }
 
@@ -1035,19 +1015,16 @@ extern "C" int dvda_mlp_hip_pcm_mix(dvda_mlp_hip_ctx *c, const int32_t *d_pcm, c
     if (!c || !d_pcm || !d_out_off || !d_out_stride || !d_out || !d_mix_off || !d_mix_stride || !host_mix || !host_report ||
         !MixReport::takes(c->set.pcm_layout, bits))
         return DVDA_HIP_EINVAL;
-    if (!c->indexed)
-        return DVDA_HIP_ESTATE;
-    if (n > c->n_streams)
-        n = c->n_streams;
-    if (n == 0)
-        return DVDA_HIP_OK;
+    int rc = report_clamp(c, &n);
+    if (rc || n == 0)
+        return rc;
     // where the output's regions lie, on the host: the stage writes them into the output's descriptors
     std::vector<uint64_t> off(n), stride(n);
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipMemcpy(off.data(), d_mix_off, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(stride.data(), d_mix_stride, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    MixReport r{nullptr, d_out, c->set.pcm_layout, nullptr, nullptr, off.data(), stride.data(), host_mix};
-    const int rc = report_of_decode(c, d_pcm, d_out_off, d_out_stride, bits, &n, stream_, &r);
+    MixReport r{{nullptr, d_out, c->set.pcm_layout, nullptr, off.data(), stride.data()}, nullptr, host_mix};
+    rc = report_of_decode(c, d_pcm, d_out_off, d_out_stride, bits, &n, stream_, &r);
     if (rc || n == 0)
         return rc;
     return report_down(stream_, host_report, r.d_report, (size_t)n * sizeof(dvda_pcm_mix_report));
@@ -1124,14 +1101,6 @@ extern "C" int dvda_pcm_hip_mix_valid(const dvda_pcm_mix *m) { return m && mix::
 
 extern "C" int32_t dvda_pcm_hip_mix_value(const int32_t *x, const dvda_pcm_mix *m, uint32_t o, unsigned bits, int *clipped)
 {
-    if (!x || !m || !mix::valid(*m) || o >= m->out_channels || !mix::depth_ok(bits)) {
-        if (clipped)
-            *clipped = -1;
-        return 0;
-    }
-    uint32_t cl = 0;
-    const int32_t y = mix::value(x, *m, o, bits, &cl);
-    if (clipped)
-        *clipped = (int)cl;
-    return y;
+    return value_or_bad(x && m && mix::valid(*m) && o < m->out_channels && mix::depth_ok(bits), clipped,
+                        [&](uint32_t *cl) { return mix::value(x, *m, o, bits, cl); });
 }

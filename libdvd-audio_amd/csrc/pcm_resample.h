@@ -24,9 +24,8 @@
 //          twice.  255 is odd: the lanes of the tap loop, one pair apart, read 64 different banks.  Only frames inside
 //          `frames` are read (dwords: the pass is bound by its multiply-adds, 96 per value, not by its loads).
 //   out    dwords, straight from the registers; nothing outside the stream's output region is written.
-//   count  a thread counts the clamped values, 16 bits per channel in two 64-bit words (a tile has at most TILE per
-//          channel); per tile they are folded (pcmt::block_fold) into REC words that the join sums.  No atomics; every
-//          word a join reads was stored by this launch.
+//   count  the clamped values per channel, a record of REC words per tile, summed by the join: pcm_write.h's record,
+//          packed and stored here as pcmw::ClipCount does it (written out: see there).
 //
 // tests/resample_model.py restates the arithmetic with Python integers and in numpy.
 #pragma once
@@ -36,30 +35,33 @@
 #include "../../include/dvda_mlp_hip.h"
 #include "pcm_resample_taps.h"
 #include "pcm_tiles.h"
+#include "pcm_write.h"
 
 namespace rsm {
 
 using pcmt::MAX_CHANNELS;
 using pcmt::THREADS;
 using pcmt::WAVES;
+using pcmw::depth_ok;
+using pcmw::div_small;
+using pcmw::finish;
+using pcmw::mad;
+using pcmw::MAX_FRAME0;
+using pcmw::REC;
 
 constexpr uint32_t UP = PHASES, DOWN = 160; // out = in * UP / DOWN
 constexpr uint32_t FRONT = 47;              // input frames of a window in front of frame q
 constexpr uint32_t TILE = DVDA_RSM_TILE_FRAMES;
 constexpr uint32_t TILE_BLOCKS = 4096;      // workgroups of k_rs_tiles at most: they stride over the tile list
-constexpr uint32_t REC = MAX_CHANNELS;      // words of a tile's record: the clamped values per channel
 constexpr uint32_t PAIRS = 64;              // (block, channel) pairs of a chunk: the lanes of a wave
 constexpr uint32_t R = 3;                   // consecutive outputs of a work item
 constexpr uint32_t GROUPS = UP / R;         // work items of a pair
 constexpr uint32_t SPAN = DOWN + TAPS - 1;  // input frames a block's windows cover
 constexpr uint32_t WINDOW = TAPS + 2 * (R - 1);     // window positions of a work item
 constexpr uint32_t LDS_WORDS = PAIRS * SPAN + 2;    // (the last pair's last item reads two words behind its span, times 0)
-constexpr uint64_t MAX_FRAME0 = 1ull << 62; // a piece that says it starts behind this is not taken
 static_assert(TILE == PAIRS * UP && TILE < (1u << 16), "a tile is 64 blocks and its counts fit 16 bits");
 // (an item's last output starts at most DOWN - 1 into the span, and at least R - 1 behind its first)
 static_assert(GROUPS * R == UP && (SPAN & 1u) == 1 && DOWN - R + WINDOW <= SPAN + 2, "groups tile a block; odd LDS stride");
-
-__host__ __device__ __forceinline__ bool depth_ok(uint32_t b) { return b == 16 || b == 20 || b == 24; }
 
 // ceil(147 a / 160) without the product
 __host__ __device__ __forceinline__ uint64_t first_out(uint64_t a)
@@ -100,17 +102,8 @@ __host__ __device__ __forceinline__ uint32_t phase_of(uint32_t s) { return DOWN 
 // the row of output k of a work item: its window starts `shift` positions behind position k, 0 <= shift <= k
 __host__ __device__ __forceinline__ const int32_t *row_of(uint32_t phase, uint32_t shift) { return PAD.v[phase] + (R - 1 - shift); }
 
-// acc += g * x.  On the device the instruction is written out, the tap in an SGPR: from `acc += (int64_t)g * x` with a
-// wave-uniform g the compiler extends the tap to 64 bits on the scalar side and multiplies in pieces (v_mad_u64_u32,
-// v_mul_lo_u32, adds), about three slow-class instructions where this is one.  (vcc: the carry out nobody reads.)
-__host__ __device__ __forceinline__ void mad(int64_t &acc, int32_t g, int32_t x)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_mad_i64_i32 %0, vcc, %1, %2, %0" : "+v"(acc) : "v"(x), "s"(g) : "vcc");
-#else
-    acc += (int64_t)g * (int64_t)x;
-#endif
-}
+// The multiply-adds are pcmw::mad, the tap wave-uniform in an SGPR: from `acc += (int64_t)g * x` with such a g the
+// compiler extends the tap to 64 bits on the scalar side and multiplies in pieces (v_mad_u64_u32, v_mul_lo_u32, adds).
 
 // A block is BLOCK window positions: its values (LDS) and its taps (scalar loads) are asked for while the block in front
 // of it is multiplied.  The scheduler is held to that order, and the wave waits for the block it is about to multiply
@@ -197,16 +190,6 @@ __host__ __device__ __forceinline__ void accumulate(int64_t (&acc)[N], const int
     blocks_from<N, 0>(acc, row, load, first);
 }
 
-// the one rounding and the clamp; *clipped += 1 when the clamp changed the value
-__host__ __device__ __forceinline__ int32_t finish(int64_t acc, uint32_t bits, uint32_t *clipped)
-{
-    const int64_t q = (acc + (1ll << 29)) >> 30;
-    const int64_t hi = (1ll << (bits - 1)) - 1, lo = -hi - 1;
-    const int64_t r = q < lo ? lo : q > hi ? hi : q;
-    *clipped += r != q ? 1u : 0u;
-    return (int32_t)r;
-}
-
 // THE value: the output frame of phase `phase` whose window of 96 input values is window[0 .. 95]
 __host__ __device__ __forceinline__ int32_t value(const int32_t *window, uint32_t phase, uint32_t bits, uint32_t *clipped)
 {
@@ -249,9 +232,6 @@ __host__ __device__ __forceinline__ Take take(const dvda_pcm_crc_desc &in, const
 
 __host__ __device__ __forceinline__ uint32_t tiles_of(uint64_t out) { return (uint32_t)((out + TILE - 1) / TILE); }
 
-// e / d for 0 < d <= 8 and e < 2^24
-__device__ __forceinline__ uint32_t div_small(uint32_t e, uint32_t d, uint32_t inv) { return d == 1 ? e : __umulhi(e, inv); }
-
 // ---- step 1: tiles per stream
 __global__ void k_rs_plan(const dvda_pcm_crc_desc *__restrict__ desc_in, const dvda_pcm_crc_desc *__restrict__ desc_out,
                           const dvda_pcm_decim_piece *__restrict__ piece, uint32_t n, uint32_t *__restrict__ cnt)
@@ -284,7 +264,7 @@ __global__ __launch_bounds__(THREADS, 2) void k_rs_tiles(const int32_t *__restri
         const uint32_t ti = b - base[s];
         if (ti >= tiles_of(tk.out))         // (counts that wrapped the scan: no tile of this stream, nothing is touched)
             continue;
-        const uint32_t ch = di.channels, inv = ch > 1 ? 0xFFFFFFFFu / ch + 1u : 0u;
+        const uint32_t ch = di.channels, inv = pcmw::inv_of(ch);
         const uint64_t m0 = (uint64_t)ti * TILE;                                    // the tile's first output frame
         const uint32_t nm = tk.out - m0 < TILE ? (uint32_t)(tk.out - m0) : TILE;    // ... and how many it has
         const uint32_t tile_blocks = (nm + UP - 1) / UP;
@@ -396,25 +376,14 @@ __global__ __launch_bounds__(THREADS) void k_rs_join(const dvda_pcm_crc_desc *__
     const uint32_t s = blockIdx.x;
     if (s >= n)
         return;
-    Take tk = take(desc_in[s], desc_out[s], piece ? piece + s : nullptr);
+    const Take tk = take(desc_in[s], desc_out[s], piece ? piece + s : nullptr);
     const uint32_t first = base[s], n_t = tiles_of(tk.out);
-    if ((uint64_t)first + n_t > max_tiles)
-        tk.taken = false;
-    const uint32_t ch = tk.taken ? desc_in[s].channels : 0u, turns = tk.taken ? n_t : 0u;
-    const uint32_t *r0 = rec + (uint64_t)first * REC;
+    const bool taken = tk.taken && (uint64_t)first + n_t <= max_tiles;
     if (threadIdx.x == 0) {
-        out[s].frames_in = tk.taken ? tk.own : 0ull;
-        out[s].frames_out = tk.taken ? tk.out : 0ull;
+        out[s].frames_in = taken ? tk.own : 0ull;
+        out[s].frames_out = taken ? tk.out : 0ull;
     }
-    for (uint32_t c = 0; c < MAX_CHANNELS; c++) {
-        uint64_t sum = 0;
-        if (c < ch)
-            for (uint32_t i = threadIdx.x; i < turns; i += THREADS)
-                sum += r0[(uint64_t)i * REC + c];
-        sum = pcmt::block_fold(sum, s_red, pcmt::FoldSum());
-        if (threadIdx.x == 0)
-            out[s].clipped[c] = sum;
-    }
+    pcmw::join_clipped(rec, first, taken ? n_t : 0u, taken ? desc_in[s].channels : 0u, s_red, out[s].clipped);
 }
 
 } // namespace rsm

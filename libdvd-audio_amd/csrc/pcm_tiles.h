@@ -1,6 +1,8 @@
 // pcm_tiles.h -- what the reports of decoded PCM (pcm_digest.h, pcm_levels.h, pcm_compare.h, pcm_energy.h, pcm_requant.h, pcm_decim.h, pcm_resample.h, pcm_mix.h) share on the device: a descriptor per
 // stream, a flat list of tiles over all streams (tiles per stream -> exclusive scan `base` -> one workgroup per tile ->
 // one workgroup per stream joins its tiles), workgroups of WAVES waves.  The host side of the list: pcm_report_run.h.
+// What only the writers share (decimate, resample, mix): pcm_write.h -- the written-out multiply-add,
+// the rounding and the clamp, the depth test, the small division, the packed count of clamped values and the joins' sum.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

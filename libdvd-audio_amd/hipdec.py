@@ -950,15 +950,21 @@ def requant_list(d_report):
     return _record_list(RequantReport, d_report)
 
 
+def _value_call(name, invalid, *args):
+    """what the *_value wrappers have in common: lib().<name>(*args, &clipped) -> (value, clipped); HipError naming
+    `invalid` where the call says its parameters are (clipped < 0)"""
+    cl = ctypes.c_int(0)
+    y = getattr(lib(), name)(*args, ctypes.byref(cl))
+    if cl.value < 0:
+        raise HipError("%s: invalid parameters %s" % (name, invalid))
+    return int(y), int(cl.value)
+
+
 def requant_value(v, frame, channel, bits_in, bits_out, mode=RQ_TPDF, seed=0):
     """dvda_pcm_hip_requant_value: the word-length reduction of one value at absolute frame `frame` of channel `channel`
     -> (value, 1 when the clamp changed it else 0); host arithmetic, needs no GPU.  HipError for invalid parameters"""
     par = Requant(bits_in, bits_out, mode, 0, seed)
-    cl = ctypes.c_int(0)
-    q = lib().dvda_pcm_hip_requant_value(int(v), frame, channel, ctypes.byref(par), ctypes.byref(cl))
-    if cl.value < 0:
-        raise HipError("dvda_pcm_hip_requant_value: invalid parameters %r" % (par.as_dict(),))
-    return int(q), int(cl.value)
+    return _value_call("dvda_pcm_hip_requant_value", "%r" % (par.as_dict(),), int(v), frame, channel, ctypes.byref(par))
 
 
 def decim_taps(ratio):
@@ -983,11 +989,7 @@ def decim_value(window, ratio, bits):
     w = np.ascontiguousarray(window, np.int32)
     if ratio not in (2, 4) or w.shape != (96 * ratio - 1,):
         raise HipError("dvda_pcm_hip_decim_value: a window of %s values for ratio %r" % (w.shape, ratio))
-    cl = ctypes.c_int(0)
-    y = lib().dvda_pcm_hip_decim_value(w.ctypes.data, ratio, bits, ctypes.byref(cl))
-    if cl.value < 0:
-        raise HipError("dvda_pcm_hip_decim_value: invalid parameters (ratio %r, bits %r)" % (ratio, bits))
-    return int(y), int(cl.value)
+    return _value_call("dvda_pcm_hip_decim_value", "(ratio %r, bits %r)" % (ratio, bits), w.ctypes.data, ratio, bits)
 
 
 def _piece_records(pieces):
@@ -998,18 +1000,59 @@ def _piece_records(pieces):
     return rec
 
 
+def _end_to_end(desc_in, frames_and_channels):
+    """the output descriptors a writer makes when none are passed: stream i of `frames` frames and `ch` channels gives
+    frames_and_channels(i, frames, ch, ok) = (its output frames, its output channels), ok saying whether a pass takes the
+    input descriptor at all (where not, it asks the library nothing and gives no frames); the regions end to end with the
+    stride = the frames, which serves either int32 layout -> (desc_out, words)"""
+    out, pos = [], 0
+    for i, (_, _, frames, ch) in enumerate(desc_in):
+        f, c = frames_and_channels(i, int(frames), int(ch), 1 <= int(ch) <= 8 and int(frames) <= 1 << 40)
+        out.append((pos, f, f, c))
+        pos += f * c
+    return out, max(pos, 1)
+
+
+def _writer_call(name, cname, what, cls, d_in, layout_in, desc_in, extra, params, out, layout_out, desc_out, default_desc,
+                 bound_in, max_total, work):
+    """What pcm_decimate, pcm_resample and pcm_mix (`name`) do around their entry point `cname` and its
+    <cname>_workspace_words: the defaults of layout_out and desc_out (default_desc() -> (desc_out, words)), the bound (the
+    frames the pass takes of desc_in where bound_in, else of desc_out), _report_args, the zeroed output, the device copies
+    of desc_out and of extra() (the pieces' or matrices' records; None: none), room for n records of cls, and the call:
+    (d_in, layout_in, desc_in, out, layout_out, desc_out, extra, n, *params, bound, report, work, words, stream).
+    -> (d_out, desc_out, d_report)"""
+    layout_out = layout_in if layout_out is None else layout_out
+    words = None
+    if desc_out is None:
+        desc_out, words = default_desc()
+    if len(desc_out) != len(desc_in):
+        raise HipError("%s: %d output descriptors for %d streams" % (name, len(desc_out), len(desc_in)))
+    if max_total is None:
+        bound = desc_in if bound_in else desc_out
+        max_total = int(sum(int(f) for _, _, f, c in bound if 1 <= int(c) <= 8 and int(f) <= 1 << 40))
+    torch, n, d_desc_in, work, st = _report_args(d_in, desc_in, what, max_total, work, getattr(lib(), cname + "_workspace_words"))
+    dev = d_in.device
+    if out is None:
+        if words is None:
+            words = max([int(o) + int(r) * int(c) for o, r, f, c in desc_out] + [1])
+        out = torch.zeros(words, dtype=torch.int32, device=dev)
+    d_desc_out = _to_device(_desc_records(desc_out), dev)
+    d_extra = None if extra is None else _to_device(extra(), dev)
+    d_rep = _result_tensor(cls, n, dev)
+    _check(getattr(lib(), cname)(d_in.data_ptr(), layout_in, d_desc_in.data_ptr(), out.data_ptr(), layout_out,
+                                 d_desc_out.data_ptr(), None if d_extra is None else d_extra.data_ptr(), n, *params, max_total,
+                                 d_rep.data_ptr(), work.data_ptr(), work.numel(), st), cname)
+    return out, desc_out, d_rep[:n]
+
+
 def decim_desc_out(desc_in, ratio, pieces=None):
     """the output descriptors pcm_decimate makes when none are passed: per stream its output frames (0 for a stream the
     pass does not take), the input's channels, the regions end to end with the stride = the frames, which serves either
     int32 layout -> (desc_out, words)"""
-    out, pos = [], 0
-    for i, (_, _, frames, ch) in enumerate(desc_in):
+    def shape(i, frames, ch, ok):
         frame0, before, after = pieces[i] if pieces is not None else (0, 0, 0)
-        ok = 1 <= int(ch) <= 8 and int(frames) <= 1 << 40 and before + after <= int(frames)
-        f = decim_out_frames(frame0, int(frames) - before - after, ratio) if ok else 0
-        out.append((pos, f, f, int(ch)))
-        pos += f * int(ch) if ok else 0
-    return out, max(pos, 1)
+        return (decim_out_frames(frame0, frames - before - after, ratio) if ok and before + after <= frames else 0), ch
+    return _end_to_end(desc_in, shape)
 
 
 def pcm_decimate(d_in, layout_in, desc_in, ratio, bits, pieces=None, out=None, layout_out=None, desc_out=None,
@@ -1022,31 +1065,11 @@ def pcm_decimate(d_in, layout_in, desc_in, ratio, bits, pieces=None, out=None, l
     descriptors and a uint8 device tensor [n, sizeof(DecimReport)] (decim_list brings it to the host).  Only the kernels
     are asynchronous, on torch's current stream: like pcm_levels, this helper builds the descriptors on the host, copies
     them to the device and allocates them, the results and -- when none is passed -- the workspace."""
-    layout_out = layout_in if layout_out is None else layout_out
     if pieces is not None and len(pieces) != len(desc_in):
         raise HipError("pcm_decimate: %d pieces for %d streams" % (len(pieces), len(desc_in)))
-    words = None
-    if desc_out is None:
-        desc_out, words = decim_desc_out(desc_in, ratio, pieces)
-    if len(desc_out) != len(desc_in):
-        raise HipError("pcm_decimate: %d output descriptors for %d streams" % (len(desc_out), len(desc_in)))
-    if max_total_out_frames is None:
-        max_total_out_frames = int(sum(int(f) for _, _, f, c in desc_out if 1 <= int(c) <= 8 and int(f) <= 1 << 40))
-    torch, n, d_desc_in, work, st = _report_args(d_in, desc_in, "the decimation", max_total_out_frames, work,
-                                                 lib().dvda_pcm_hip_decimate_workspace_words)
-    dev = d_in.device
-    if out is None:
-        if words is None:
-            words = max([int(o) + int(r) * int(c) for o, r, f, c in desc_out] + [1])
-        out = torch.zeros(words, dtype=torch.int32, device=dev)
-    d_desc_out = _to_device(_desc_records(desc_out), dev)
-    d_piece = None if pieces is None else _to_device(_piece_records(pieces), dev)
-    d_rep = _result_tensor(DecimReport, n, dev)
-    _check(lib().dvda_pcm_hip_decimate(d_in.data_ptr(), layout_in, d_desc_in.data_ptr(), out.data_ptr(), layout_out,
-                                       d_desc_out.data_ptr(), None if d_piece is None else d_piece.data_ptr(), n, ratio,
-                                       bits, max_total_out_frames, d_rep.data_ptr(), work.data_ptr(), work.numel(), st),
-           "dvda_pcm_hip_decimate")
-    return out, desc_out, d_rep[:n]
+    return _writer_call("pcm_decimate", "dvda_pcm_hip_decimate", "the decimation", DecimReport, d_in, layout_in, desc_in,
+                        None if pieces is None else lambda: _piece_records(pieces), (ratio, bits), out, layout_out, desc_out,
+                        lambda: decim_desc_out(desc_in, ratio, pieces), False, max_total_out_frames, work)
 
 
 def pcm_decimate_workspace_words(n, max_total_out_frames):
@@ -1079,23 +1102,15 @@ def resample_value(window, phase, bits):
     w = np.ascontiguousarray(window, np.int32)
     if w.shape != (RSM_TAPS,):
         raise HipError("dvda_pcm_hip_resample_value: a window of %s values" % (w.shape,))
-    cl = ctypes.c_int(0)
-    y = lib().dvda_pcm_hip_resample_value(w.ctypes.data, phase, bits, ctypes.byref(cl))
-    if cl.value < 0:
-        raise HipError("dvda_pcm_hip_resample_value: invalid parameters (phase %r, bits %r)" % (phase, bits))
-    return int(y), int(cl.value)
+    return _value_call("dvda_pcm_hip_resample_value", "(phase %r, bits %r)" % (phase, bits), w.ctypes.data, phase, bits)
 
 
 def resample_desc_out(desc_in, pieces=None):
     """the output descriptors pcm_resample makes when none are passed, as decim_desc_out -> (desc_out, words)"""
-    out, pos = [], 0
-    for i, (_, _, frames, ch) in enumerate(desc_in):
+    def shape(i, frames, ch, ok):
         frame0, before, after = pieces[i] if pieces is not None else (0, 0, 0)
-        ok = 1 <= int(ch) <= 8 and int(frames) <= 1 << 40 and before + after <= int(frames)
-        f = resample_out_frames(frame0, int(frames) - before - after) if ok else 0
-        out.append((pos, f, f, int(ch)))
-        pos += f * int(ch) if ok else 0
-    return out, max(pos, 1)
+        return (resample_out_frames(frame0, frames - before - after) if ok and before + after <= frames else 0), ch
+    return _end_to_end(desc_in, shape)
 
 
 def pcm_resample(d_in, layout_in, desc_in, bits, pieces=None, out=None, layout_out=None, desc_out=None,
@@ -1107,31 +1122,11 @@ def pcm_resample(d_in, layout_in, desc_in, bits, pieces=None, out=None, layout_o
     regions end to end in a fresh zeroed tensor (resample_desc_out).  -> (d_out, desc_out, d_report): the output tensor,
     its descriptors and a uint8 device tensor [n, sizeof(DecimReport)] (decim_list brings it to the host).  Only the
     kernels are asynchronous, on torch's current stream."""
-    layout_out = layout_in if layout_out is None else layout_out
     if pieces is not None and len(pieces) != len(desc_in):
         raise HipError("pcm_resample: %d pieces for %d streams" % (len(pieces), len(desc_in)))
-    words = None
-    if desc_out is None:
-        desc_out, words = resample_desc_out(desc_in, pieces)
-    if len(desc_out) != len(desc_in):
-        raise HipError("pcm_resample: %d output descriptors for %d streams" % (len(desc_out), len(desc_in)))
-    if max_total_out_frames is None:
-        max_total_out_frames = int(sum(int(f) for _, _, f, c in desc_out if 1 <= int(c) <= 8 and int(f) <= 1 << 40))
-    torch, n, d_desc_in, work, st = _report_args(d_in, desc_in, "the resampler", max_total_out_frames, work,
-                                                 lib().dvda_pcm_hip_resample_workspace_words)
-    dev = d_in.device
-    if out is None:
-        if words is None:
-            words = max([int(o) + int(r) * int(c) for o, r, f, c in desc_out] + [1])
-        out = torch.zeros(words, dtype=torch.int32, device=dev)
-    d_desc_out = _to_device(_desc_records(desc_out), dev)
-    d_piece = None if pieces is None else _to_device(_piece_records(pieces), dev)
-    d_rep = _result_tensor(DecimReport, n, dev)
-    _check(lib().dvda_pcm_hip_resample(d_in.data_ptr(), layout_in, d_desc_in.data_ptr(), out.data_ptr(), layout_out,
-                                       d_desc_out.data_ptr(), None if d_piece is None else d_piece.data_ptr(), n, bits,
-                                       max_total_out_frames, d_rep.data_ptr(), work.data_ptr(), work.numel(), st),
-           "dvda_pcm_hip_resample")
-    return out, desc_out, d_rep[:n]
+    return _writer_call("pcm_resample", "dvda_pcm_hip_resample", "the resampler", DecimReport, d_in, layout_in, desc_in,
+                        None if pieces is None else lambda: _piece_records(pieces), (bits,), out, layout_out, desc_out,
+                        lambda: resample_desc_out(desc_in, pieces), False, max_total_out_frames, work)
 
 
 def pcm_resample_workspace_words(n, max_total_out_frames):
@@ -1172,11 +1167,7 @@ def mix_value(x, m, o, bits):
     v = np.ascontiguousarray(x, np.int32)
     if v.shape != (int(rec.in_channels),):
         raise HipError("dvda_pcm_hip_mix_value: %s values for %d channels" % (v.shape, rec.in_channels))
-    cl = ctypes.c_int(0)
-    y = lib().dvda_pcm_hip_mix_value(v.ctypes.data, ctypes.byref(rec), o, bits, ctypes.byref(cl))
-    if cl.value < 0:
-        raise HipError("dvda_pcm_hip_mix_value: invalid parameters (channel %r, bits %r)" % (o, bits))
-    return int(y), int(cl.value)
+    return _value_call("dvda_pcm_hip_mix_value", "(channel %r, bits %r)" % (o, bits), v.ctypes.data, ctypes.byref(rec), o, bits)
 
 
 def _mix_records(matrices):
@@ -1190,15 +1181,8 @@ def _mix_records(matrices):
 def mix_desc_out(desc_in, matrices):
     """the output descriptors pcm_mix makes when none are passed: per stream the input's frames and the matrix's output
     channels, the regions end to end with the stride = the frames, which serves either int32 layout -> (desc_out, words)"""
-    out, pos = [], 0
-    for (_, _, frames, ch), m in zip(desc_in, matrices):
-        rec = _mix_record(m)
-        och = int(rec.out_channels)
-        ok = 1 <= int(ch) <= 8 and int(frames) <= 1 << 40 and 1 <= och <= 8
-        f = int(frames) if ok else 0
-        out.append((pos, f, f, och))
-        pos += f * och if ok else 0
-    return out, max(pos, 1)
+    och = [int(_mix_record(m).out_channels) for m in matrices]
+    return _end_to_end(desc_in[:len(och)], lambda i, frames, ch, ok: (frames if ok and 1 <= och[i] <= 8 else 0, och[i]))
 
 
 def pcm_mix(d_in, layout_in, desc_in, matrices, bits, out=None, layout_out=None, desc_out=None, max_total_frames=None,
@@ -1211,30 +1195,11 @@ def pcm_mix(d_in, layout_in, desc_in, matrices, bits, out=None, layout_out=None,
     (mix_list brings it to the host).  Only the kernels are asynchronous, on torch's current stream: like pcm_levels, this
     helper builds the descriptors and matrices on the host, copies them to the device and allocates them, the results
     and -- when none is passed -- the workspace."""
-    layout_out = layout_in if layout_out is None else layout_out
     if len(matrices) != len(desc_in):
         raise HipError("pcm_mix: %d matrices for %d streams" % (len(matrices), len(desc_in)))
-    words = None
-    if desc_out is None:
-        desc_out, words = mix_desc_out(desc_in, matrices)
-    if len(desc_out) != len(desc_in):
-        raise HipError("pcm_mix: %d output descriptors for %d streams" % (len(desc_out), len(desc_in)))
-    if max_total_frames is None:
-        max_total_frames = int(sum(int(f) for _, _, f, c in desc_in if 1 <= int(c) <= 8 and int(f) <= 1 << 40))
-    torch, n, d_desc_in, work, st = _report_args(d_in, desc_in, "the channel mix", max_total_frames, work,
-                                                 lib().dvda_pcm_hip_mix_workspace_words)
-    dev = d_in.device
-    if out is None:
-        if words is None:
-            words = max([int(o) + int(r) * int(c) for o, r, f, c in desc_out] + [1])
-        out = torch.zeros(words, dtype=torch.int32, device=dev)
-    d_desc_out = _to_device(_desc_records(desc_out), dev)
-    d_mix = _to_device(_mix_records(matrices), dev)
-    d_rep = _result_tensor(PcmMixReport, n, dev)
-    _check(lib().dvda_pcm_hip_mix(d_in.data_ptr(), layout_in, d_desc_in.data_ptr(), out.data_ptr(), layout_out,
-                                  d_desc_out.data_ptr(), d_mix.data_ptr(), n, bits, max_total_frames, d_rep.data_ptr(),
-                                  work.data_ptr(), work.numel(), st), "dvda_pcm_hip_mix")
-    return out, desc_out, d_rep[:n]
+    return _writer_call("pcm_mix", "dvda_pcm_hip_mix", "the channel mix", PcmMixReport, d_in, layout_in, desc_in,
+                        lambda: _mix_records(matrices), (bits,), out, layout_out, desc_out,
+                        lambda: mix_desc_out(desc_in, matrices), True, max_total_frames, work)
 
 
 def pcm_mix_workspace_words(n, max_total_frames):
@@ -1801,16 +1766,8 @@ def decode_streams_resampled(streams, rate=RESAMPLE_RATE, device=0, layout=PCM_P
             cur[i] = (d_out, do)
             reports[i]["resample"] = rep
     pcm = []
-    for i in range(n):
-        buf, (off, stride, frames, ch) = cur[i]
-        if frames == 0 or ch == 0:
-            pcm.append(np.zeros((int(ch), 0), np.int32))
-            continue
-        host = buf[off:off + max(stride, frames) * ch].cpu().numpy()
-        if layout == PCM_PLANAR:
-            pcm.append(np.stack([host[c * stride:c * stride + frames] for c in range(ch)]).astype(np.int32))
-        else:
-            pcm.append(np.ascontiguousarray(host[:frames * ch].reshape(frames, ch).T).astype(np.int32))
+    for buf, (off, stride, frames, ch) in cur:      # (one cut per stream: the streams lie in up to three buffers)
+        pcm.append(cut_regions(buf[off:off + stride * ch].cpu().numpy(), [0], [stride], [ch], [frames], layout)[0])
     return pcm, list(infos), reports
 
 
@@ -1875,10 +1832,11 @@ def decode_streams_downmixed(streams, out_channels=2, flags=MIX_NORMALIZED, matr
                     if depth[i] == bits:
                         reports[i] = rep[i]
             host = d_out.cpu().numpy()
-            for i in idx_all:
-                och, f = int(mats[i].out_channels), frames[i] if reports[i]["frames"] else 0
-                part = host[off[i]:off[i] + f * och]
-                pcm[i] = (part.reshape(och, f) if layout == PCM_PLANAR else np.ascontiguousarray(part.reshape(f, och).T)).astype(np.int32)
+            cut = cut_regions(host, [off[i] for i in idx_all], [frames[i] for i in idx_all],
+                              [int(mats[i].out_channels) for i in idx_all],
+                              [frames[i] if reports[i]["frames"] else 0 for i in idx_all], layout)
+            for i, part in zip(idx_all, cut):
+                pcm[i] = part
     return pcm, list(infos), reports
 
 
